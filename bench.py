@@ -19,12 +19,22 @@ Images shard over ranks (weak scaling, no collective in the forward); per step O
 per-rank pooled embeddings / image scores.  `ranks_seen` is torch.distributed's world size, `per_rank_images_per_s`
 each rank's own rate; `value` is all images of all ranks over the slowest rank's time.
 
-The JSON line carries `roofline` for the dominant kernel (the c_fc GEMM, timed with HIP events on the launch stream
-inside the timed region), `parity_vs_north_star` (where the timed arithmetic mode stands against BASELINE.json's
-tolerance, from the committed GPU test record), `<mode>_companion` for the other arithmetic modes on the same workload
-(fp32 = exact, the reference's type; fp16x2 = split fp16 on the 16-bit MFMAs, inside the tolerance; fp16 = fastest,
-outside it on taps and maps) and, at N=1, `cpu_baseline`: the CPU oracle (a port of the reference's math in stock torch CPU ops) timed on the
-host cores at the reference's 4-thread cap and on all cores, batch 1 and 2, median of 3.
+A plain run sets up, warms up, times the `--steps` steps and prints the JSON line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, plus the run's configuration).  Everything
+else is measured only with `--full`: the line then also carries `roofline` for the dominant kernel (the c_fc GEMM, timed
+with HIP events on the launch stream inside the timed region), `parity_vs_north_star` (where the timed arithmetic mode
+stands against BASELINE.json's tolerance, measured in the run), the per-kernel-class breakdown of one extra step, the
+other workload's rate, the pinned-host input feed, `<mode>_companion` for the other arithmetic modes on the same
+workload (fp32 = exact, the reference's type; fp16x2 = split fp16 on the 16-bit MFMAs, inside the tolerance; fp16 =
+fastest, outside it on taps and maps), the text side and, at N=1, `cpu_baseline`: the CPU oracle (a port of the
+reference's math in stock torch CPU ops) timed on the host cores at the reference's 4-thread cap and on all cores, batch 1
+and 2, median of 3.
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step (rank 0) as DIR/<name>.npy, float32
+(float64 stays float64): tower = `pooled` (all ranks' rows) and `tap6` ... `tap24`; full = `anomaly_map` and
+`image_score`.  An array of more than 2**21 elements is written as a fixed sample of 2**21 elements at sorted flat
+indices drawn from a CPU generator seeded by crc32(<name>), so two builds run with the same arguments are compared value
+for value (inputs and weights are seeded too); at most 64 MB in all.
 
 `--rehearse-cpu` is a control-flow rehearsal for the CPU test of the launcher (gloo, no GPU, no kernels): it times a
 stand-in step and labels its output as such; it never produces a valid metric line.
@@ -74,11 +84,50 @@ def parse_args(argv=None):
                     help="resident: the batch stays in HBM (the metric's definition).  pinned: every step computes on a "
                          "batch that was copied from pinned host memory on a side stream while the previous step ran "
                          "(two device buffers, one event each way; reference test_last.py:70-71 feeds from a DataLoader)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: roofline, in-run parity, kernel breakdown, "
+                         "other workload, input feed, other arithmetic modes, text side, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, seeded sample of large "
+                         "arrays, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary measurements")
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="control-flow rehearsal on CPU/gloo with a stand-in step (launcher test); not a measurement")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 21            # elements per dumped array; larger arrays are sampled
+DUMP_LIMIT = 64 << 20            # bytes in all
+
+
+def dump_outputs(outdir, named, torch):
+    """Write each tensor of `named` (name -> tensor) as outdir/<name>.npy in float32 (float64 kept).  A tensor of more
+    than DUMP_SAMPLE elements is reduced to DUMP_SAMPLE elements at sorted flat indices drawn from a CPU generator seeded
+    by crc32(name): the same name always selects the same elements."""
+    import zlib
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {}
+    for name, t in named.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator()
+            g.manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        flat = flat.cpu()
+        flat = flat.double() if flat.dtype == torch.float64 else flat.float()
+        arrays[name] = flat.numpy() if flat.numel() != t.numel() else flat.reshape(t.shape).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return total
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -307,24 +356,35 @@ def run_rank(args):
             sync()
 
     fc_ms = []
+    roofline = lib is not None and args.full
     with torch.no_grad():
         for _ in range(args.warmup):
             step()
         fence()
         cap = 24 * args.steps + 8
-        if lib is not None:
+        if roofline:
             _lib.check(lib.aaclip_profile_begin(1 << 4, cap), "profile_begin")   # time every c_fc GEMM launch
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last = step()
         fence()
         dt_own = time.perf_counter() - t0
-        if lib is not None:
+        if roofline:
             ms = (C.c_float * cap)()
             tg = (C.c_int * cap)()
             n = lib.aaclip_profile_end(ms, tg, cap)
             fc_ms = [ms[i] for i in range(n)]
         rows_gathered = int(gathered[0].shape[0]) if torch.is_tensor(gathered[0]) else None
+        if args.dump_outputs and rank == 0:
+            # what a caller of the timed path received in the last timed step, taken before anything else runs
+            if rehearse:
+                named = {"rehearsal_rows": gathered[0]}
+            elif args.workload == "tower":
+                named = {"pooled": gathered[0], **{f"tap{k}": t for k, t in zip((6, 12, 18, 24), last)}}
+            else:
+                named = {"anomaly_map": last, "image_score": gathered[0]}
+            nbytes = dump_outputs(args.dump_outputs, named, torch)
+            print(f"[bench] wrote {len(named)} arrays ({nbytes} bytes) to {args.dump_outputs}", file=sys.stderr)
 
         # max over ranks (the timed region ends when the slowest rank ends) + every rank's own time
         times = torch.tensor([dt_own], device=dev, dtype=torch.float64)
@@ -337,7 +397,7 @@ def run_rank(args):
         dt = max(per_rank_dt)
 
         extra = {}
-        if not args.no_extra and not rehearse:
+        if args.full and not args.no_extra and not rehearse:
             # (every rank runs these untimed steps: step() ends in the all-gather, a collective all ranks must enter)
             # per-kernel-class breakdown of one extra (untimed) step
             cap2 = 8 * 24 + 16
@@ -412,7 +472,7 @@ def run_rank(args):
         # parity of the timed model, measured now (rank 0; the other ranks wait in the barrier below, so that no rank tears
         # the process group down while rank 0 still works)
         parity = None
-        if rank == 0 and not rehearse:
+        if args.full and rank == 0 and not rehearse:
             try:
                 parity = parity_in_run(clip, model, args.precision, args.clip_weights, dev, torch)
             except Exception as e:   # noqa: BLE001
@@ -465,6 +525,16 @@ def run_rank(args):
             result["note"] = (f"{n_gpus} ranks share {devices} visible device(s) (gloo rehearsal): the sum is not a "
                               "multi-GPU throughput")
         if not rehearse:
+            result.update({
+                "whole_path_tflops": round(value * gflop_img / 1e3, 1),
+                "whole_path_frac_of_mfma_peak": round(value * gflop_img / 1e3 / (peak * n_gpus), 4),
+                # share of the fp16 MFMA pipe's time the path keeps busy = algorithmic fraction x the mode's MFMA time
+                # multiple (fp16x2: GEMMs 82 % of the flops at 2.0 -- 1.5 with fp16-exact weights --, attention 18 % at 1.5)
+                "whole_path_mfma_time_frac": round(value * gflop_img / 1e3 / (peak * n_gpus) * (
+                    ((0.82 * (1.5 if args.clip_weights == "fp16" else 2.0) + 0.18 * 1.5) if args.precision == "fp16x2"
+                     else 1.0)), 4),
+            })
+        if not rehearse and args.full:
             fc_flop = 2.0 * (B * cfg.tokens) * cfg.vision.mlp * cfg.vision.width   # per launch
             fc_avg = sum(fc_ms) / max(1, len(fc_ms))
             achieved = fc_flop / (fc_avg * 1e-3) / 1e12 if fc_avg > 0 else 0.0
@@ -474,13 +544,6 @@ def run_rank(args):
                          3 if args.clip_weights == "fp16" else 4)}.get(
                              args.precision, f"gemm16_256x_kernel<{tname}, EPI_BIAS_GELU>")
             result.update({
-                "whole_path_tflops": round(value * gflop_img / 1e3, 1),
-                "whole_path_frac_of_mfma_peak": round(value * gflop_img / 1e3 / (peak * n_gpus), 4),
-                # share of the fp16 MFMA pipe's time the path keeps busy = algorithmic fraction x the mode's MFMA time
-                # multiple (fp16x2: GEMMs 82 % of the flops at 2.0 -- 1.5 with fp16-exact weights --, attention 18 % at 1.5)
-                "whole_path_mfma_time_frac": round(value * gflop_img / 1e3 / (peak * n_gpus) * (
-                    ((0.82 * (1.5 if args.clip_weights == "fp16" else 2.0) + 0.18 * 1.5) if args.precision == "fp16x2"
-                     else 1.0)), 4),
                 "roofline": {
                     "kernel": kname + f" (mlp.c_fc, M={B}*1370, N=4096, K=1024)",
                     "bound": "mfma",
@@ -497,13 +560,13 @@ def run_rank(args):
                 "parity_vs_north_star": parity,
             })
         result.update(extra)
-        if n_gpus == 1 and not args.no_extra and not rehearse:
+        if n_gpus == 1 and args.full and not args.no_extra and not rehearse:
             try:    # the text side (reported separately, never part of images/s)
                 result["text_anchors"] = text_anchors_leg(model, lib, dev, torch, cfg, args.precision,
                                                           not args.no_cpu_baseline)
             except Exception as e:   # noqa: BLE001
                 result["text_anchors"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if n_gpus == 1 and not args.no_cpu_baseline and not rehearse:
+        if n_gpus == 1 and args.full and not args.no_cpu_baseline and not rehearse:
             try:
                 result["cpu_baseline"] = cpu_baseline(cfg, args.workload)
             except Exception as e:   # noqa: BLE001

@@ -33,7 +33,7 @@ for K in ${KERNELS:-attn out_proj c_fc}; do
 done
 # plain per-kernel timing of one default bench step set (kernel trace + stats), summarised to csv
 rm -rf $OUT/prof_$TAG
-rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o $TAG -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $OUT/prof_$TAG.json 2> $OUT/prof_$TAG.log
+rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o $TAG -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $OUT/prof_$TAG.json 2> $OUT/prof_$TAG.log
 python3 tools/rocpd_summary.py stats $(find $OUT/prof_$TAG -name '*_results.db' | head -1) $OUT/${TAG}_bench_kernel_stats.csv
 rm -rf $OUT/prof_$TAG
 cat $OUT/prof_$TAG.json
