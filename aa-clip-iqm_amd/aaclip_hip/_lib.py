@@ -13,12 +13,13 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AACLIP_LIB") or os.path.join(_HERE, "libaaclip_hip.so")   # AACLIP_LIB: experiment builds
 MEASURE_LIB_PATH = os.path.join(_HERE, "libaaclip_hip_measure.so")   # `make measure`: A/B variants, ablations, stamps
-ABI_VERSION = 5   # include/aaclip.h AACLIP_ABI_VERSION this binding was written against
+ABI_VERSION = 6   # include/aaclip.h AACLIP_ABI_VERSION this binding was written against
 
 F32, F16, BF16, F16X2 = 0, 1, 2, 3   # F16X2: split fp16 (hi + lo pairs), include/aaclip.h
 EXACT16_QKV, EXACT16_OUT, EXACT16_FC, EXACT16_PROJ, EXACT16_ADAPTER = 1, 2, 4, 8, 16
 ACT_NONE, ACT_LEAKY, ACT_RELU = 0, 1, 2
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_ACT_F32 = 0, 1, 2, 3
+SEG_LOSS_FOCAL, SEG_LOSS_DICE0, SEG_LOSS_DICE1, SEG_LOSS_ALL = 1, 2, 4, 7
 
 _vp, _i, _l, _f, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 
@@ -52,6 +53,11 @@ SIGNATURES = {
     "aaclip_det_head": (_i, [_vp, _vp, _vp, _vp, _i, _vp] + [_i] * 5 + [_vp, _sz, _vp]),
     "aaclip_anomaly_map": (_i, [C.POINTER(_vp), _i, _vp, _l, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "aaclip_similarity_map_train": (_i, [_vp, _vp, _l, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "aaclip_similarity_map_train_backward_workspace_bytes": (_sz, [_i, _i, _i]),
+    "aaclip_similarity_map_train_backward": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "aaclip_seg_loss_workspace_bytes": (_sz, [_i]),
+    "aaclip_seg_loss": (_i, [_vp, _l, _l, _vp, _i, _vp, _vp, _i, _l, _vp, _sz, _vp]),
+    "aaclip_seg_loss_backward": (_i, [_vp, _l, _l, _vp, _i, _vp, _vp, _vp, _i, _l, _vp]),
     "aaclip_text_embed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "aaclip_resample_ksize": (_i, [_i, _i]),
     "aaclip_resample_table": (_i, [_i, _i, _vp, _vp]),

@@ -536,6 +536,79 @@ def similarity_map_train(seg: torch.Tensor, text_feature: torch.Tensor, img_size
     return out
 
 
+def similarity_map_train_backward(seg: torch.Tensor, text_feature: torch.Tensor, preds: torch.Tensor,
+                                  d_preds: torch.Tensor, need_seg: bool = False, need_anchors: bool = True):
+    """Backward of similarity_map_train: (d seg [B,P,E] or None, d text_feature (its shape) or None)."""
+    lib = _lib.load()
+    seg = _f32c(seg)
+    require_gpu(seg, "similarity_map_train_backward")
+    B, P, E = seg.shape
+    g = int(round(P ** 0.5))
+    tf = _f32c(text_feature).to(seg.device)
+    if tf.shape not in ((E, 2), (B, E, 2)):
+        raise ValueError(f"text feature must be [{E}, 2] or [{B}, {E}, 2], got {tuple(tf.shape)}")
+    stride = 0 if tf.dim() == 2 else E * 2
+    S = preds.shape[-1]
+    preds, d_preds = _f32c(preds), _f32c(d_preds)
+    if preds.shape != (B, 2, S, S) or d_preds.shape != preds.shape:
+        raise ValueError("preds / d_preds must be [B, 2, S, S]")
+    d_seg = torch.empty_like(seg) if need_seg else None
+    d_tf = torch.empty_like(tf) if need_anchors else None
+    ws = Workspace.get(seg.device, lib.aaclip_similarity_map_train_backward_workspace_bytes(B, g, S))
+    _lib.check(lib.aaclip_similarity_map_train_backward(seg.data_ptr(), tf.data_ptr(), stride, preds.data_ptr(),
+                                                        d_preds.data_ptr(), _ptr(d_tf), _ptr(d_seg), B, g, E, S,
+                                                        ws.data_ptr(), ws.numel(), _stream(seg.device)),
+               "similarity_map_train_backward")
+    return d_seg, d_tf
+
+
+def _seg_loss_layout(preds: torch.Tensor, mask: torch.Tensor):
+    """preds [B,2,S,S] (or [B,S,S] / [B,P] for a single channel) + mask with B*P elements -> (B, P, img_stride,
+    chan_stride, fp32 contiguous mask)."""
+    if preds.dim() == 4:
+        if preds.shape[1] != 2:
+            raise ValueError("seg loss: preds must have 2 channels")
+        B, P = preds.shape[0], preds.shape[2] * preds.shape[3]
+        istr, cstr = 2 * P, P
+    else:
+        B, P = preds.shape[0], preds[0].numel()
+        istr, cstr = P, 0
+    m = _f32c(mask).to(preds.device)
+    if m.numel() != B * P:
+        raise ValueError(f"seg loss: mask has {m.numel()} elements, preds need {B * P} (one value per pixel)")
+    return B, P, istr, cstr, m
+
+
+def seg_loss(preds: torch.Tensor, mask: torch.Tensor, terms: int = _lib.SEG_LOSS_ALL):
+    """reference forward_utils.py:223-227 (and its FocalLoss / BinaryDiceLoss) -> (loss [4] = {total, focal, dice0,
+    dice1}, coef [B,4] for seg_loss_backward)."""
+    lib = _lib.load()
+    preds = _f32c(preds)
+    require_gpu(preds, "seg_loss")
+    B, P, istr, cstr, m = _seg_loss_layout(preds, mask)
+    loss = torch.empty(4, dtype=torch.float32, device=preds.device)
+    coef = torch.empty(B, 4, dtype=torch.float32, device=preds.device)
+    ws = Workspace.get(preds.device, lib.aaclip_seg_loss_workspace_bytes(B))
+    _lib.check(lib.aaclip_seg_loss(preds.data_ptr(), istr, cstr, m.data_ptr(), int(terms), loss.data_ptr(),
+                                   coef.data_ptr(), B, P, ws.data_ptr(), ws.numel(), _stream(preds.device)), "seg_loss")
+    return loss, coef
+
+
+def seg_loss_backward(preds: torch.Tensor, mask: torch.Tensor, coef: torch.Tensor, d_loss: torch.Tensor,
+                      terms: int = _lib.SEG_LOSS_ALL) -> torch.Tensor:
+    """d preds (preds' shape; zeros in a channel no term reads) from d loss [4]."""
+    lib = _lib.load()
+    preds = _f32c(preds)
+    require_gpu(preds, "seg_loss_backward")
+    B, P, istr, cstr, m = _seg_loss_layout(preds, mask)
+    d = torch.zeros_like(preds) if terms != _lib.SEG_LOSS_ALL else torch.empty_like(preds)
+    dl = _f32c(d_loss).to(preds.device).reshape(4)
+    _lib.check(lib.aaclip_seg_loss_backward(preds.data_ptr(), istr, cstr, m.data_ptr(), int(terms), coef.data_ptr(),
+                                            dl.data_ptr(), d.data_ptr(), B, P, _stream(preds.device)),
+               "seg_loss_backward")
+    return d
+
+
 # ------------------------------------------------------------------------------------------------
 # image pre-processing (reference dataset/__init__.py:150-161), Pillow-exact on the GPU
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)

@@ -700,6 +700,51 @@ int aaclip_similarity_map_train(const float* seg, const float* anchors, long anc
   return finish("similarity_map_train");
 }
 
+size_t aaclip_similarity_map_train_backward_workspace_bytes(int B, int g, int S) {
+  if (B <= 0 || g <= 0 || S <= 0) return 0;
+  return simmap_bwd_ws_bytes(B, g, S);
+}
+
+int aaclip_similarity_map_train_backward(const float* seg, const float* anchors, long anchor_bstride,
+                                         const float* preds, const float* d_preds, float* d_anchors, float* d_seg,
+                                         int B, int g, int E, int S, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(seg && anchors && preds && d_preds && ws, "similarity_map_train_backward: null pointer");
+  REQUIRE(B > 0 && B <= 65535 && g >= 1 && g <= 40 && S >= 1 && S <= SIMMAP_BWD_MAX_S,
+          "similarity_map_train_backward: bad shape (grid <= 40, size <= 2048)");
+  REQUIRE(anchor_bstride == 0 || anchor_bstride == 2L * E, "similarity_map_train_backward: anchor stride 0 or 2E");
+  const char* m = row_width_check(E);
+  if (m) return fail(-1, m);
+  REQUIRE(ws_bytes >= simmap_bwd_ws_bytes(B, g, S), "similarity_map_train_backward: workspace too small");
+  launch_similarity_map_train_bwd(seg, anchors, anchor_bstride, preds, d_preds, d_anchors, d_seg, B, g, E, S, ws,
+                                  (hipStream_t)stream);
+  return finish("similarity_map_train_backward");
+}
+
+size_t aaclip_seg_loss_workspace_bytes(int B) { return B > 0 ? seg_loss_ws_bytes(B) : 0; }
+
+int aaclip_seg_loss(const float* preds, long img_stride, long chan_stride, const float* mask, int terms, float* loss,
+                    float* coef, int B, long P, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(preds && mask && loss && coef && ws, "seg_loss: null pointer");
+  REQUIRE(B > 0 && B <= 65535 && P > 0, "seg_loss: bad shape");
+  REQUIRE(terms > 0 && terms <= 7, "seg_loss: terms is a non-empty mask of AACLIP_SEG_LOSS_*");
+  REQUIRE(img_stride >= 0 && chan_stride >= 0, "seg_loss: negative stride");
+  REQUIRE(ws_bytes >= seg_loss_ws_bytes(B), "seg_loss: workspace too small");
+  launch_seg_loss(preds, img_stride, chan_stride, mask, terms, loss, coef, B, P, ws, (hipStream_t)stream);
+  return finish("seg_loss");
+}
+
+int aaclip_seg_loss_backward(const float* preds, long img_stride, long chan_stride, const float* mask, int terms,
+                             const float* coef, const float* d_loss, float* d_preds, int B, long P, void* stream) {
+  REQUIRE(preds && mask && coef && d_loss && d_preds, "seg_loss_backward: null pointer");
+  REQUIRE(B > 0 && B <= 65535 && P > 0, "seg_loss_backward: bad shape");
+  REQUIRE(terms > 0 && terms <= 7, "seg_loss_backward: terms is a non-empty mask of AACLIP_SEG_LOSS_*");
+  REQUIRE(img_stride >= 0 && chan_stride >= 0, "seg_loss_backward: negative stride");
+  REQUIRE(chan_stride != 0 || !((terms & SEG_LOSS_FOCAL) || ((terms & SEG_LOSS_DICE0) && (terms & SEG_LOSS_DICE1))),
+          "seg_loss_backward: both channels are written, they cannot share storage (chan_stride 0)");
+  launch_seg_loss_grad(preds, img_stride, chan_stride, mask, terms, coef, d_loss, d_preds, B, P, (hipStream_t)stream);
+  return finish("seg_loss_backward");
+}
+
 int aaclip_resample_ksize(int in_size, int out_size) {
   if (in_size < 1 || out_size < 1) return fail(-1, "resample_ksize: sizes must be positive");
   return resample_ksize(in_size, out_size);

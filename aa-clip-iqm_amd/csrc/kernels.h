@@ -137,6 +137,26 @@ void launch_iqm_scores(const float* seg, const float* q, float* grid, int B, int
 void launch_iqm_upsample(const float* grids, const float* base, float* out, int B, int g, int S, int NL, float w_base,
                          float w_iqm, hipStream_t s);
 
+// ---- train_loss.hip : segmentation loss (focal + dice) with its gradient, train-mode similarity map backward
+enum { SEG_LOSS_FOCAL = 1, SEG_LOSS_DICE0 = 2, SEG_LOSS_DICE1 = 4 };   // = AACLIP_SEG_LOSS_* (include/aaclip.h)
+constexpr int SEG_LOSS_CHUNKS = 64;   // pixel chunks per image of the first pass
+constexpr int SEG_LOSS_NSUM = 6;      // per-chunk sums
+constexpr int SIMMAP_BWD_MAX_S = 2048;
+inline size_t seg_loss_part_bytes(int B) {
+  return ((size_t)B * SEG_LOSS_CHUNKS * SEG_LOSS_NSUM * 4 + 255) & ~(size_t)255;
+}
+inline size_t seg_loss_ws_bytes(int B) { return seg_loss_part_bytes(B) + (size_t)B * 3 * 8; }
+inline size_t simmap_bwd_t_floats(int B, int g, int S) { return (size_t)B * S * g; }
+inline size_t simmap_bwd_ws_bytes(int B, int g, int S) { return (simmap_bwd_t_floats(B, g, S) + (size_t)B * g * g) * 4; }
+// preds: image b, channel c, pixel i at preds[b * img_stride + c * chan_stride + i]; mask [B, P]; coef [B, 4]
+void launch_seg_loss(const float* preds, long img_stride, long chan_stride, const float* mask, int terms, float* loss,
+                     float* coef, int B, long P, void* ws, hipStream_t s);
+void launch_seg_loss_grad(const float* preds, long img_stride, long chan_stride, const float* mask, int terms,
+                          const float* coef, const float* d_loss, float* d_preds, int B, long P, hipStream_t s);
+void launch_similarity_map_train_bwd(const float* seg, const float* anchors, long anchor_bstride, const float* preds,
+                                     const float* d_preds, float* d_anchors, float* d_seg, int B, int g, int E, int S,
+                                     void* ws, hipStream_t s);
+
 // ---- preprocess.hip : 8-bit bicubic resize + ToTensor + Normalize (Pillow-exact)
 int resample_ksize(int in_size, int out_size);
 void resample_table(int in_size, int out_size, int32_t* bounds, int32_t* coefs);   // host buffers

@@ -6,7 +6,7 @@ from typing import Sequence
 
 import torch
 
-from aaclip_hip import engine
+from aaclip_hip import _lib, autograd, engine
 from dataset.constants import CLASS_NAMES, DOMAINS, PROMPTS, REAL_NAMES  # noqa: F401  (DOMAINS: re-exported like the reference)
 from model.tokenizer import tokenize
 
@@ -69,7 +69,43 @@ def calculate_similarity_map(patch_features, epoch_text_feature, img_size, test=
         assert epoch_text_feature.shape[-1] == 2
         sigma, ksize = (1.0, 7) if domain == "Industrial" else (1.5, 9)
         return engine.anomaly_map([patch_features], epoch_text_feature, img_size, ksize, sigma).unsqueeze(1)
+    if torch.is_grad_enabled() and (patch_features.requires_grad or epoch_text_feature.requires_grad):
+        return autograd.similarity_map_train(patch_features, epoch_text_feature, img_size)   # same forward kernels
     return engine.similarity_map_train(patch_features, epoch_text_feature, img_size)
+
+
+# ------------------------------------------------------------------------------------------------
+# training criterion (reference forward_utils.py:21-108,223-227): one HIP loss kernel pair, differentiable in preds
+class FocalLoss(torch.nn.Module):
+    """The reference's FocalLoss as train.py uses it (apply_nonlin None, alpha None = 1, gamma 2, smooth 1e-5,
+    size_average): mean over pixels of -(1 - pt)^2 log pt on 2-channel probabilities [B,2,S,S] and a 0/1 mask."""
+
+    def __init__(self, apply_nonlin=None, alpha=None, gamma=2, balance_index=0, smooth=1e-5, size_average=True):
+        super().__init__()
+        if apply_nonlin is not None or alpha is not None or gamma != 2 or smooth != 1e-5 or not size_average:
+            raise NotImplementedError("FocalLoss: the HIP kernel implements the configuration calculate_seg_loss uses "
+                                      "(apply_nonlin=None, alpha=None, gamma=2, smooth=1e-5, size_average=True)")
+        self.gamma, self.smooth = gamma, smooth
+
+    def forward(self, logit, target):
+        return autograd.seg_loss(logit, target, _lib.SEG_LOSS_FOCAL)[1]
+
+
+class BinaryDiceLoss(torch.nn.Module):
+    """1 - mean over images of (2 sum(x t) + 1) / (sum x + sum t + 1), x and t [N, ...]."""
+
+    def forward(self, input, targets):
+        return autograd.seg_loss(input.reshape(input.shape[0], -1), targets, _lib.SEG_LOSS_DICE1)[3]
+
+
+focal_loss = FocalLoss()
+dice_loss = BinaryDiceLoss()
+
+
+def calculate_seg_loss(patch_preds, mask):
+    """focal(preds, mask) + dice(preds[:, 0], 1 - mask) + dice(preds[:, 1], mask) in one kernel pair (reference
+    forward_utils.py:223-227); preds [B,2,S,S] probabilities, mask [B,1,S,S] or [B,S,S] of 0 / 1."""
+    return autograd.seg_loss(patch_preds, mask, _lib.SEG_LOSS_ALL)[0]
 
 
 def calculate_anomaly_map(patch_features: Sequence[torch.Tensor], epoch_text_feature, img_size, domain="Industrial"):

@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define AACLIP_ABI_VERSION 5   /* 5: + aaclip_tap_head_keep_rows, aaclip_cross_rows_levels (additions only) */
+#define AACLIP_ABI_VERSION 6   /* 6: + the training-loss entry points (seg loss, similarity map backward; additions only) */
 
 enum { AACLIP_F32 = 0, AACLIP_F16 = 1, AACLIP_BF16 = 2, AACLIP_F16X2 = 3 };
 enum { AACLIP_ACT_NONE = 0, AACLIP_ACT_LEAKY = 1, AACLIP_ACT_RELU = 2 };
@@ -199,6 +199,38 @@ int aaclip_anomaly_map(const float* const* seg, int NL, const float* anchors, lo
  * (reference forward_utils.py:199-203,211-215). */
 int aaclip_similarity_map_train(const float* seg, const float* anchors, long anchor_bstride, float* out, int B, int g,
                                 int E, int S, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- Training: the loss side of the text-adapter stage (reference train.py:38-114, SURVEY.md 8 / VERDICT.md #5).
+ * Every reduction runs in a fixed order (no float atomics): repeated calls give bit-identical results. */
+
+/* Backward of aaclip_similarity_map_train.  preds = its output [B,2,S,S], d_preds = d loss / d preds (same shape):
+ * softmax backward per pixel, the transpose of the align-corners bilinear upsample (a gather over each coarse cell's
+ * support window), x100, then
+ *   d_anchors[b, e, c] = sum_p seg[b, p, e] dS[b, p, c]   ([B, E, 2]; anchor_bstride 0: one [E, 2] pair, summed over b)
+ *   d_seg[b, p, e]     = sum_c dS[b, p, c] anchors[b, e, c]
+ * Either output may be NULL.  g <= 40, S <= 2048, E a supported row width. */
+size_t aaclip_similarity_map_train_backward_workspace_bytes(int B, int g, int S);
+int aaclip_similarity_map_train_backward(const float* seg, const float* anchors, long anchor_bstride,
+                                         const float* preds, const float* d_preds, float* d_anchors, float* d_seg,
+                                         int B, int g, int E, int S, void* ws, size_t ws_bytes, void* stream);
+
+/* Segmentation loss, reference forward_utils.py:21-108,223-227 (calculate_seg_loss = FocalLoss + BinaryDiceLoss on
+ * channel 0 against 1 - mask + BinaryDiceLoss on channel 1 against mask):
+ *   focal = mean over B*P pixels of -(1 - pt)^2 log pt,  pt = sum_c clamp(onehot_c, 1e-5, 1 - 1e-5) p_c + 1e-5
+ *           (gamma 2, alpha 1; the class of a pixel is its mask value truncated: masks hold 0 / 1)
+ *   dice0 = 1 - mean_b (2 sum p0 (1 - m) + 1) / (sum p0 + sum (1 - m) + 1),  dice1 likewise with p1 and m.
+ * preds: channel c of image b at preds + b * img_stride + c * chan_stride (P pixels; [B,2,S,S]: P, 2P, P), mask
+ * [B, P] fp32.  terms: the AACLIP_SEG_LOSS_* that are computed (the others read 0).  loss (out, device) [4] =
+ * {focal + dice0 + dice1, focal, dice0, dice1}; coef (out) [B, 4]: per-image dice coefficients the backward reads.
+ * Two passes: per (image, pixel chunk) sums, then a one-block pass over the chunks in order (double). */
+enum { AACLIP_SEG_LOSS_FOCAL = 1, AACLIP_SEG_LOSS_DICE0 = 2, AACLIP_SEG_LOSS_DICE1 = 4, AACLIP_SEG_LOSS_ALL = 7 };
+size_t aaclip_seg_loss_workspace_bytes(int B);
+int aaclip_seg_loss(const float* preds, long img_stride, long chan_stride, const float* mask, int terms, float* loss,
+                    float* coef, int B, long P, void* ws, size_t ws_bytes, void* stream);
+/* d_preds (same layout as preds) from d_loss (device [4], the gradient of the loss vector) and the forward's coef.
+ * A channel that no computed term reads is not written, so chan_stride 0 is allowed for the single dice terms. */
+int aaclip_seg_loss_backward(const float* preds, long img_stride, long chan_stride, const float* mask, int terms,
+                             const float* coef, const float* d_loss, float* d_preds, int B, long P, void* stream);
 
 /* Image pre-processing in front of the patch embed: Pillow's 8-bit BICUBIC resize to S x S,
  * ToTensor (v/255) and Normalize((v - mean)/std), bit-exact.  Replaces the reference's
