@@ -12,8 +12,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AACLIP_LIB") or os.path.join(_HERE, "libaaclip_hip.so")   # AACLIP_LIB: experiment builds
-MEASURE_LIB_PATH = os.path.join(_HERE, "libaaclip_hip_measure.so")   # `make measure`: A/B variants, ablations, stamps
-ABI_VERSION = 6   # include/aaclip.h AACLIP_ABI_VERSION this binding was written against
+ABI_VERSION = 7   # include/aaclip.h AACLIP_ABI_VERSION this binding was written against
 
 F32, F16, BF16, F16X2 = 0, 1, 2, 3   # F16X2: split fp16 (hi + lo pairs), include/aaclip.h
 EXACT16_QKV, EXACT16_OUT, EXACT16_FC, EXACT16_PROJ, EXACT16_ADAPTER = 1, 2, 4, 8, 16
@@ -41,7 +40,6 @@ class BlockWeights(C.Structure):
 SIGNATURES = {
     "aaclip_version": (_i, []),
     "aaclip_last_error": (C.c_char_p, []),
-    "aaclip_is_measurement_build": (_i, []),
     "aaclip_workspace_bytes": (_sz, [_i, _l, _i, _i, _i]),
     "aaclip_patch_embed": (_i, [_vp] * 7 + [_i] * 6 + [_vp, _sz, _vp]),
     "aaclip_block": (_i, [_vp, C.POINTER(BlockWeights), _f] + [_i] * 7 + [_vp, _sz, _vp]),
@@ -81,7 +79,6 @@ SIGNATURES = {
     "aaclip_drop_cls_rows": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "aaclip_iqm_map": (_i, [C.POINTER(_vp), _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _sz, _vp]),
     "aaclip_set_gemm_variant": (_i, [_i]),
-    "aaclip_debug_gemm_stamps": (_i, [C.POINTER(C.c_double), _i]),
     "aaclip_profile_begin": (_i, [C.c_uint, _i]),
     "aaclip_profile_end": (_i, [C.POINTER(C.c_float), C.POINTER(C.c_int), _i]),
 }

@@ -105,58 +105,13 @@ int aaclip_set_gemm_variant(int v) {
   REQUIRE(v >= 0 && (v >> 18) == 0, "set_gemm_variant: unknown bits");
   // Validate everything before changing anything: a rejected call leaves the selection as it was.
   const int gv = v & 0xFF, av = (v >> 8) & 0xFF;
-#ifdef AACLIP_MEASURE
-  REQUIRE((gv <= 60 || gv == 70 || (gv >= 80 && gv <= 82)) && (av <= 3 || av == 6), "set_gemm_variant: no such kernel variant");
-#else
   REQUIRE((gv <= 1 || (gv >= 80 && gv <= 82)) && av <= 1,
-          "set_gemm_variant: libaaclip_hip.so only has GEMM variants 0/1/80/81/82 and attention variants 0/1; A/B variants, "
-          "timing ablations (wrong results) and stamp builds live in libaaclip_hip_measure.so (make measure)");
-#endif
+          "set_gemm_variant: no such kernel variant (GEMM variants are 0/1/80/81/82, attention variants 0/1)");
   set_gemm_variant(gv);
   set_attn_variant(av);   // bits 8..15: attention kernel selection
   g_ln_fold = ((v >> 17) & 1) ? 0 : 1;
   set_tail_peel((v >> 16) & 1);  // bit 16: peel the partial last round to the 128-tile kernel (measured: -1.6 %, off by default)
   return 0;
-}
-
-int aaclip_debug_gemm_stamps(double* out3, int nwaves) {
-#ifdef AACLIP_MEASURE
-  REQUIRE(out3, "debug_gemm_stamps: null pointer");
-  if (nwaves == -2) {   // walking kernel's compact epilogue (-DX_WALK_STAMP): 8 sums, reset on read
-    read_gemm_estamps(out3);
-    return 0;
-  }
-  if (nwaves < 0) {   // persistent kernel: 8 values (cycles per tile of 7 segments, tile count)
-    read_gemm_zstamps(out3);
-    return 0;
-  }
-  read_gemm_stamps(out3, nwaves);
-  return 0;
-#else
-  (void)out3; (void)nwaves;
-  return fail(-1, "debug_gemm_stamps: stamp kernels are part of libaaclip_hip_measure.so only (make measure)");
-#endif
-}
-
-#ifdef AACLIP_MEASURE
-// measurement library only (not declared in include/aaclip.h): how often the long-sequence attention kernel took each
-// of its tile paths since the last reset -- out[0] tile 0, out[1] fast passes, out[2] exact redos
-extern "C" int aaclip_measure_attn_passes(unsigned long long* out4, int reset) {
-  read_attn_passes(out4, reset);
-  return 0;
-}
-extern "C" int aaclip_measure_attn_stamps(unsigned long long* out9, int reset) {
-  read_attn_stamps(out9, reset);
-  return 0;
-}
-#endif
-
-int aaclip_is_measurement_build(void) {
-#ifdef AACLIP_MEASURE
-  return 1;
-#else
-  return 0;
-#endif
 }
 
 int aaclip_version(void) { return AACLIP_ABI_VERSION; }

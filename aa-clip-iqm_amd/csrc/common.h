@@ -188,6 +188,16 @@ AACLIP_DEV void glds16(const void* gsrc, void* lds_base) {
   __builtin_amdgcn_global_load_lds((gbl_void*)gsrc, (lds_void*)lds_base, 16, 0, 0);
 }
 
+// A pointer that hipcc can PROVE wave-uniform (a buffer descriptor built from it then lives in SGPRs; otherwise every
+// buffer instruction that uses it is wrapped in a waterfall loop).  The halves go through unsigned: readfirstlane
+// returns int, and OR-ing a negative low half into the 64-bit value sign-extends it (a base of 0xffff... whenever bit 31
+// of the address is set).
+template <typename P> AACLIP_DEV P* uniform_ptr(P* ptr) {
+  const unsigned long long a = (unsigned long long)ptr;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+  return (P*)(((unsigned long long)hi << 32) | lo);
+}
+
 AACLIP_DEV void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // XCD-aware bijective remap of a 1-D workgroup id (guide T1): workgroups that

@@ -401,23 +401,22 @@ const char* gemm_check(int dtype, int epi, const GemmParams& p) {
 static int g_tail_peel = 0;  // measured: not a win (the 128-tile kernel is too slow for the peeled rows)
 void set_tail_peel(int v) { g_tail_peel = v; }
 // 0 automatic, 1 force the 128-tile kernel, 80 / 81 / 82 force the 8-wave 256 x 256 kernel (one tile per workgroup) / the
-// 4-wave 256 x 128 half-tile kernel / the walking 8-wave kernel (all bit-identical); more in the measurement library only
+// 4-wave 256 x 128 half-tile kernel / the walking 8-wave kernel (all bit-identical)
 static int g_gemm_variant = 0;
-// launch_gemm256t kernel id: 14 = 8 waves, 256 x 256 tile; 15 = 4 waves, 256 x 128 half tile, two workgroups per CU.
+// GEMM256_TILE = 8 waves, 256 x 256 tile; GEMM256_HALF_TILE = 4 waves, 256 x 128 half tile, two workgroups per CU.
 // Measured (profiles/r04_gemm_half_tile_ab.txt): the half tile's K loop is 6-12 % slower (12 instead of 8 DMA
 // pieces per 64 MFMAs on a loop that is bound by exactly that); the overlap of one workgroup's epilogue with the other's K
 // loop wins it back only on isolated epilogue-heavy 16-bit products (out_proj +9...12 %, seg / det projections +10 %) and
 // not inside the tower, where the same products carry the LayerNorm-folding epilogue (tower: 917 vs 923 images/s with
 // them on the half tile, 878 with every product on it); split operands lose 2-8 % on every shape.  So the automatic
 // choice is the 8-wave kernel everywhere and the half tile stays selectable (variant 81).
-// 16 = the 8-wave kernel WALKING its tiles (one workgroup per CU; the next tile's first K tile is fetched under the
-// epilogue of the current one; split operands only, launch_gemm256t falls back to 14 for the others): bit-identical,
+// GEMM256_WALK = the 8-wave kernel WALKING its tiles (one workgroup per CU; the next tile's first K tile is fetched under
+// the epilogue of the current one; split operands only, launch_gemm256t runs GEMM256_TILE for the others): bit-identical,
 // tower +0.5 % (profiles/r04_gemm_walk_ab.txt).  Automatic for split operands; 80 forces the one-tile-per-workgroup form.
-static int big_kernel_id(int dtype, const GemmParams& p) {
-  (void)p;
-  if (g_gemm_variant == 81) return 15;
-  if (g_gemm_variant == 80) return 14;
-  return (dtype == AACLIP_F16X2 || g_gemm_variant == 82) ? 16 : 14;
+static Gemm256Form big_kernel_form(int dtype) {
+  if (g_gemm_variant == 81) return GEMM256_HALF_TILE;
+  if (g_gemm_variant == 80) return GEMM256_TILE;
+  return (dtype == AACLIP_F16X2 || g_gemm_variant == 82) ? GEMM256_WALK : GEMM256_TILE;
 }
 
 static thread_local const char* g_launch_err = nullptr;
@@ -438,46 +437,16 @@ bool gemm256_applicable(int dtype, const GemmParams& p) {
 }
 
 bool set_gemm_variant(int v) {
-#ifdef AACLIP_MEASURE
-  // 2..5 = 256-tile kernels on 32x32x16 MFMAs (gemm256.hip), 6..60 = the 16x16x32 family incl. timing ablations and
-  // the stamp build (gemm256t.hip), 70 = persistent tiles (gemm256z.hip)
-  const bool ok = v >= 0 && (v <= 60 || v == 70 || v == 80 || v == 81 || v == 82);
-#else
   const bool ok = v == 0 || v == 1 || v == 80 || v == 81 || v == 82;
-#endif
   if (ok) g_gemm_variant = v;
   return ok;
-}
-
-static void launch_gemm_big(int dtype, int epi, const GemmParams& p, hipStream_t s) {
-#ifdef AACLIP_MEASURE
-  if (g_gemm_variant == 70) {   // persistent tiles (gemm256z.hip); falls through when K/64 is odd or < 4
-    if (launch_gemm256z(dtype, epi, p, s)) return;
-    launch_gemm256t(dtype, epi, p, s, 14);
-    return;
-  }
-  if (g_gemm_variant >= 6 && g_gemm_variant <= 60) {
-    // 16x16x32 MFMA shape; 6 plain, 7 overlapped LDS reads, 8/9/10 staggered with 0/1/2 DMA issues in the load
-    // segment, 11..17 timing ablations / stamps of 10 (fp32-out epilogue only), 18 staggered + in-cluster reads,
-    // 19 = 10 with buffer_load ... lds, 20 = the default
-    launch_gemm256t(dtype, epi, p, s, g_gemm_variant - 6);
-    return;
-  }
-  if (g_gemm_variant >= 2 && g_gemm_variant < 80) {
-    // 32x32x16 kernels: 2 DMA at the phase start, 3 DMA between the MFMAs, 4/5 timing ablations
-    launch_gemm256(dtype, epi, p, s, g_gemm_variant == 2 ? 0 : g_gemm_variant - 2);
-    return;
-  }
-#endif
-  launch_gemm256t(dtype, epi, p, s, big_kernel_id(dtype, p));
 }
 
 // True when launch_gemm will run one of the 16x16x32 256-tile kernels (gemm256t.hip) on the whole problem:
 // those are the kernels whose epilogue implements the LayerNorm-folding options of GemmParams.
 bool gemm_routes_to_256t(int dtype, const GemmParams& p) {
   if (dtype == AACLIP_F32 || dtype == AACLIP_F16X2 || !gemm256_applicable(dtype, p) || p.M < 4096) return false;
-  if (!(g_gemm_variant == 0 || g_gemm_variant >= 80 || (g_gemm_variant >= 6 && g_gemm_variant <= 60))) return false;   // 2..70: measurement library
-  if (g_tail_peel) return false;
+  if (g_gemm_variant == 1 || g_tail_peel) return false;
   return true;
 }
 
@@ -488,7 +457,7 @@ bool gemm_split_routes_to_256t(const GemmParams& p) { return g_gemm_variant != 1
 void launch_gemm(int dtype, int epi, const GemmParams& p, hipStream_t s) {
   if (dtype == AACLIP_F16X2) {   // split fp16: the default 256-tile kernel from M = 4096 rows, else the 128-tile kernel
     if (gemm_split_routes_to_256t(p)) {
-      launch_gemm256t(dtype, epi, p, s, big_kernel_id(dtype, p));
+      launch_gemm256t(dtype, epi, p, s, big_kernel_form(dtype));
       return;
     }
     if (p.out_qk8) { set_launch_error("gemm: out_qk8 needs the 256-tile kernel"); return; }
@@ -497,9 +466,8 @@ void launch_gemm(int dtype, int epi, const GemmParams& p, hipStream_t s) {
     else launch16s<4>(epi, p, g, s);
     return;
   }
-  // variants: 0 automatic (256-tile kernels from M = 4096 rows), 1 the 128-tile kernel, >= 2 (measurement library) 256-tile
-  // kernels at any M
-  if (g_gemm_variant != 1 && gemm256_applicable(dtype, p) && ((g_gemm_variant >= 2 && g_gemm_variant < 80) || p.M >= 4096)) {
+  // variants: 1 the 128-tile kernel; otherwise the 256-tile kernels from M = 4096 rows
+  if (g_gemm_variant != 1 && gemm256_applicable(dtype, p) && p.M >= 4096) {
     // Tail peeling: 256x256 tiles run one per CU in rounds of 256.  When the last round would be
     // less than 60 % full, the rows of that partial round go to the 128-tile kernel instead (two
     // workgroups per CU, finer granularity); both kernels produce bit-identical results.
@@ -516,14 +484,14 @@ void launch_gemm(int dtype, int epi, const GemmParams& p, hipStream_t s) {
         b.A = (const char*)p.A + rows_full * p.lda * es;
         b.out = (char*)p.out + rows_full * p.ldc * os;
         b.M = p.M - (int)rows_full;
-        launch_gemm_big(dtype, epi, a, s);
+        launch_gemm256t(dtype, epi, a, s, big_kernel_form(dtype));
         const int t128 = ((b.M + 127) / 128) * (b.N / 128);
         if (dtype == AACLIP_F16) launch16<f16>(epi, b, dim3(t128), s);
         else launch16<bf16>(epi, b, dim3(t128), s);
         return;
       }
     }
-    launch_gemm_big(dtype, epi, p, s);
+    launch_gemm256t(dtype, epi, p, s, big_kernel_form(dtype));
     return;
   }
   const int tiles = ((p.M + 127) / 128) * (p.N / 128);

@@ -40,12 +40,14 @@ struct GemmParams {
 const char* gemm_check(int dtype, int epi, const GemmParams& p);
 void launch_gemm(int dtype, int epi, const GemmParams& p, hipStream_t s);
 bool gemm256_applicable(int dtype, const GemmParams& p);
-// 256-tile kernels on 16x16x32 MFMAs.  kernel_id: 14 = the default two-fragment-set kernel (falls back to 13 when
-// K/64 is odd), 13 = its one-set predecessor; every other id exists only in the measurement library.  A (kernel_id,
-// epilogue) pair without a kernel launches NOTHING and records a launch error (launch_error()).
-void launch_gemm256t(int dtype, int epi, const GemmParams& p, hipStream_t s, int kernel_id);
-// Kernel selection for A/B runs.  The product library knows GEMM variants 0 (automatic) and 1 (128-tile kernel) and
-// attention variants 0 and 1 (128-query kernel); both return false for anything else and leave the selection alone.
+// 256-tile kernels on 16x16x32 MFMAs (gemm256t.hip), bit-identical to one another: the 8-wave 256 x 256 kernel, the
+// 4-wave 256 x 128 half tile, and the 8-wave kernel walking its tiles (split operands only; plain operands run the
+// 256 x 256 form).  Plain operands with an odd K-tile count run the one-set 8-wave kernel whatever form is asked for.
+// An epilogue without a kernel launches NOTHING and records a launch error (take_launch_error()).
+enum Gemm256Form { GEMM256_TILE, GEMM256_HALF_TILE, GEMM256_WALK };
+void launch_gemm256t(int dtype, int epi, const GemmParams& p, hipStream_t s, Gemm256Form form);
+// Kernel selection for A/B runs: GEMM variants 0 (automatic), 1 (128-tile kernel) and 80 / 81 / 82 (gemm.hip), attention
+// variants 0 and 1 (128-query kernel); both return false for anything else and leave the selection alone.
 bool set_gemm_variant(int v);
 bool set_attn_variant(int v);
 void set_tail_peel(int v);
@@ -53,17 +55,6 @@ void set_tail_peel(int v);
 // reports and clears it, so the entry point returns rc < 0 instead of running something else.
 void set_launch_error(const char* msg);
 const char* take_launch_error();
-#ifdef AACLIP_MEASURE
-// Measurement library only (libaaclip_hip_measure.so, `make measure`): A/B variants, timing ablations that compute
-// WRONG results, and s_memtime stamp builds.  None of this is compiled into libaaclip_hip.so.
-void launch_gemm256(int dtype, int epi, const GemmParams& p, hipStream_t s, int pipelined);
-void read_gemm_zstamps(double* out8);   // -DZ_STAMP builds only, zeros otherwise
-bool launch_gemm256z(int dtype, int epi, const GemmParams& p, hipStream_t s);   // persistent tiles; false = not applicable
-void read_gemm_stamps(double* out3, int nwaves);
-void read_gemm_estamps(double* out8);   // -DX_WALK_STAMP builds of the measurement library only, zeros otherwise
-void read_attn_passes(unsigned long long* out4, int reset);
-void read_attn_stamps(unsigned long long* out9, int reset);   // -DATTN_STAMP builds: cycles per tile-loop segment   // attn16x2 tile passes: [0] tile 0, [1] fast, [2] exact redo
-#endif
 
 // fused softmax(q k^T) v over packed qkv [B*L, 3*H*64] (q pre-scaled) -> ctx [B*L, H*64]
 // log2q != 0: q is pre-multiplied by log2(e) as well (16-bit kernels only)

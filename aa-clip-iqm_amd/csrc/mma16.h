@@ -1,5 +1,5 @@
 // v_mfma_f32_16x16x32 wrapper and the LDS tile addressing shared by the 256x256 GEMM kernels
-// (gemm256t.hip, gemm256z.hip).
+// (gemm256t.hip).
 #pragma once
 #include "common.h"
 

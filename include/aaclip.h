@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define AACLIP_ABI_VERSION 6   /* 6: + the training-loss entry points (seg loss, similarity map backward; additions only) */
+#define AACLIP_ABI_VERSION 7   /* 7: the entry points of the removed measurement build are gone */
 
 enum { AACLIP_F32 = 0, AACLIP_F16 = 1, AACLIP_BF16 = 2, AACLIP_F16X2 = 3 };
 enum { AACLIP_ACT_NONE = 0, AACLIP_ACT_LEAKY = 1, AACLIP_ACT_RELU = 2 };
@@ -64,9 +64,6 @@ enum { AACLIP_EPI_BIAS = 0, AACLIP_EPI_BIAS_GELU = 1, AACLIP_EPI_BIAS_RESID = 2,
 
 int aaclip_version(void);            /* AACLIP_ABI_VERSION the library was built from; bind only if it matches */
 const char* aaclip_last_error(void);
-/* 0 for libaaclip_hip.so.  1 for libaaclip_hip_measure.so, the separate build (`make measure`) that adds A/B kernel
- * variants, timing ablations that compute WRONG results and s_memtime stamp kernels: never bind a product to it. */
-int aaclip_is_measurement_build(void);
 
 /* Scratch needed by any call below for `rows` token rows of width D, MLP width F,
  * embed width E (pass the largest you will use). */
@@ -274,21 +271,13 @@ int aaclip_profile_end(float* ms, int* tags, int max_n);
  * bits 0..7   GEMM: 1 = always the 128x128-tile kernel; 80 / 81 / 82 = where the automatic choice is a 256-row-tile
  *             kernel, always the 8-wave 256x256 one with one tile per workgroup / the 4-wave 256x128 half-tile one /
  *             the 8-wave one walking its tiles (split operands; one workgroup per CU) -- bit-identical results; 0
- *             picks the fastest.  Measurement library only: 2..5 = 256-tile kernels on
- *             32x32x16 MFMAs; 6..60 = the 16x16x32 family (20 = the default kernel, others: lock-step /
- *             in-cluster-read variants, timing ablations and the stamp build); 70 = persistent tiles (gemm256z.hip)
- * bits 8..15  attention: 1 = always the 128-query kernel; measurement library only: 2 = software-pipelined kernel
+ *             picks the fastest.
+ * bits 8..15  attention: 1 = always the 128-query kernel
  * bit 16      peel the partial last round of 256-tile GEMMs to the 128-tile kernel (off by default: -1.6 %)
  * bit 17      turn the LayerNorm folding of aaclip_block(s) off
- * Every selectable kernel of libaaclip_hip.so computes the same function.  A value that names a variant the loaded
- * library does not contain is rejected (rc < 0) and leaves the selection unchanged; inside the measurement library a
- * (variant, epilogue) pair without a kernel makes the affected call return rc < 0 instead of running a substitute. */
+ * Every selectable kernel computes the same function.  Any other value is rejected (rc < 0) and leaves the selection
+ * unchanged. */
 int aaclip_set_gemm_variant(int v);
-
-/* Diagnostics of stamp builds (tools/gemm_stamps.py, tools/gemm_zstamps.py): nwaves >= 0 -> 6 averaged s_memtime
- * segment sums of GEMM variant 17; nwaves < 0 -> 8 values of the persistent kernel built with -DZ_STAMP (zeros in
- * a normal build).  `out` is HOST memory.  rc < 0 in libaaclip_hip.so (measurement library only). */
-int aaclip_debug_gemm_stamps(double* out, int nwaves);
 
 /* Building blocks, exported for unit parity tests and for callers that fuse differently. */
 int aaclip_layernorm(const float* x, const float* w, const float* b, void* out, int out_dtype, long rows, int D,

@@ -18,16 +18,22 @@ def _header_abi_version():
     return int(re.search(r"#define\s+AACLIP_ABI_VERSION\s+(\d+)", header).group(1))
 
 
-def test_library_exports_every_declared_symbol():
+# entry points of the measurement build that ABI 7 removed: the library must not export them any more
+_REMOVED_SYMBOLS = ("aaclip_is_measurement_build", "aaclip_debug_gemm_stamps", "aaclip_measure_attn_passes",
+                    "aaclip_measure_attn_stamps")
+
+
+def test_library_exports_every_header_symbol():
     lib = _lib.load()
     assert lib.aaclip_version() == _header_abi_version() == _lib.ABI_VERSION
-    assert lib.aaclip_is_measurement_build() == 0      # the product library carries no ablation / stamp kernels
     header = open(os.path.join(REPO, "include", "aaclip.h")).read()
     declared = set(re.findall(r"\b(aaclip_[a-z_0-9]+)\s*\(", header))
     declared.discard("aaclip_block_weights")
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
     for name in declared:
         assert getattr(lib, name) is not None
+    for name in _REMOVED_SYMBOLS:
+        assert name not in declared and not hasattr(lib, name), name
 
 
 def test_graft_entry_build_runs():
@@ -84,45 +90,22 @@ def test_short_or_old_block_struct_is_rejected():
     assert rc < 0 and b"struct_bytes" in lib.aaclip_last_error()
 
 
-def test_product_library_refuses_measurement_variants():
-    """Timing ablations (wrong results), A/B variants and stamp kernels are not in libaaclip_hip.so: selecting one is
-    an error and leaves the selection unchanged; no environment variable selects kernels any more."""
+def test_set_gemm_variant_refuses_unknown_words():
+    """The words of the former A/B variants, timing ablations (wrong results) and stamp kernels select nothing: each is
+    an error that names the accepted words; no environment variable selects kernels any more."""
     lib = _lib.load()
-    for v in (2, 5, 11, 17, 20, 46, 70, 2 << 8, 1 << 18, -1):
+    for v in (2, 5, 11, 17, 20, 46, 70, 2 << 8):
         assert lib.aaclip_set_gemm_variant(v) < 0, v
-    assert b"measure" in lib.aaclip_last_error() or b"unknown" in lib.aaclip_last_error()
+        assert b"no such kernel variant" in lib.aaclip_last_error(), v
+    for v in (1 << 18, -1):
+        assert lib.aaclip_set_gemm_variant(v) < 0, v
+        assert b"unknown" in lib.aaclip_last_error(), v
     for v in (1, 1 << 8, 1 << 16, 1 << 17, 0):
         assert lib.aaclip_set_gemm_variant(v) == 0, v
-    assert lib.aaclip_debug_gemm_stamps(None, 4) < 0
+    for name in _REMOVED_SYMBOLS:
+        assert not hasattr(lib, name), name
     src = open(os.path.join(REPO, "aa-clip-iqm_amd", "aaclip_hip", "_lib.py")).read()
     assert "AACLIP_GEMM_VARIANT" not in src
-
-
-def test_measurement_library_has_no_substitute_kernels():
-    """Regression for the round-1 GPU fault: an fp32-storing timing ablation was launched for a
-    product whose output buffer is 16-bit and overran it.  The ablations now live in libaaclip_hip_measure.so only,
-    exist for the fp32-output epilogue only, and any other (variant, epilogue) pair returns rc < 0 WITHOUT launching
-    (so this runs on a CPU box with made-up pointers)."""
-    if not os.path.exists(_lib.MEASURE_LIB_PATH):
-        pytest.skip("measurement library not built (make -C aa-clip-iqm_amd/csrc measure)")
-    m = ctypes.CDLL(_lib.MEASURE_LIB_PATH)
-    m.aaclip_last_error.restype = ctypes.c_char_p
-    res, args = _lib.SIGNATURES["aaclip_gemm"]
-    m.aaclip_gemm.restype, m.aaclip_gemm.argtypes = res, args
-    assert m.aaclip_is_measurement_build() == 1 and m.aaclip_version() == _lib.ABI_VERSION
-    M, N, K = 8192, 1024, 1024
-    for variant in (4, 5, 11, 12, 13, 14, 15, 16, 17, 46):      # 32x32x16 ablations, 16x16x32 ablations + stamp build
-        assert m.aaclip_set_gemm_variant(variant) == 0
-        for epi in (_lib.EPI_BIAS, _lib.EPI_BIAS_GELU, _lib.EPI_BIAS_RESID):
-            rc = m.aaclip_gemm(_lib.F16, epi, 0x7f0000001000, K, 0x7f0000002000, 0x7f0000003000, 0x7f0000004000, N,
-                               M, N, K, 0, 0, 1.0, None)
-            assert rc < 0 and b"fp32-output epilogue only" in m.aaclip_last_error(), (variant, epi)
-    assert m.aaclip_set_gemm_variant(61) < 0
-    for av in (4, 5, 7):                                         # attention variants: 0-3 and 6 exist
-        assert m.aaclip_set_gemm_variant(av << 8) < 0, av
-    for av in (3, 6, 0):
-        assert m.aaclip_set_gemm_variant(av << 8) == 0, av
-    assert m.aaclip_set_gemm_variant(0) == 0
 
 
 def test_workspace_bytes_monotone():

@@ -1,19 +1,18 @@
 #!/usr/bin/env python3
-"""A/B attention kernel variants of the measurement library in ONE process (interleaved rounds, same data), with the
-maximum difference of their outputs.  usage: python tools/attn_ab.py --variants 0,6 [--L 1370] [--batch 64] [--data zeros]
-Variants: 0 product kernel (attn16x2), 1 128-query kernel, 2 attn16p, 3 8-wave attn16x2, 6 unit-pipelined experiment (attn16u)."""
+"""A/B attention kernel variants in ONE process (interleaved rounds, same data), with the maximum difference of their
+outputs.  usage: python tools/attn_ab.py --variants 0,1 [--L 1370] [--batch 64] [--data zeros]
+Variants: 0 long-sequence kernel (attn16x2), 1 128-query kernel.  AACLIP_LIB selects an experiment build."""
 import argparse, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "aa-clip-iqm_amd"))
 import torch
-os.environ.setdefault("AACLIP_LIB", os.path.join(REPO, "aa-clip-iqm_amd", "aaclip_hip", "libaaclip_hip_measure.so"))
 from aaclip_hip import _lib
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--L", type=int, default=1370)
 ap.add_argument("--H", type=int, default=16)
-ap.add_argument("--variants", default="0,6")
+ap.add_argument("--variants", default="0,1")
 ap.add_argument("--scale", type=float, default=0.5)
 ap.add_argument("--data", default="randn", choices=["randn", "zeros", "const"], help="operand values: the chip is power-limited, so the bits that toggle set the clock")
 a = ap.parse_args()

@@ -5,13 +5,12 @@ import argparse, os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "aa-clip-iqm_amd"))
 import torch
-os.environ.setdefault("AACLIP_LIB", os.path.join(REPO, "aa-clip-iqm_amd", "aaclip_hip", "libaaclip_hip_measure.so"))   # A/B variants live in the measurement library (make measure)
 from aaclip_hip import _lib
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--rounds", type=int, default=5)
-ap.add_argument("--variants", default="1,2")
+ap.add_argument("--variants", default="0,1", help="aaclip_set_gemm_variant words (0/1/80/81/82)")
 ap.add_argument("--dtype", default="f16")
 ap.add_argument("--only", default="")
 ap.add_argument("--m", type=int, default=0, help="override the row count (default batch*1370)")
@@ -29,9 +28,10 @@ shapes = [("qkv", _lib.EPI_BIAS, 3072, 1024), ("out_proj", _lib.EPI_BIAS_RESID, 
           ("k256_n4096", _lib.EPI_ACT_F32, 4096, 256)]
 if a.only:
     shapes = [s for s in shapes if s[0] in a.only.split(",")]
-if any(v in (4, 5, 11, 12, 13, 14, 15, 16, 46) for v in [int(v) for v in a.variants.split(",")]):
-    shapes = [s for s in shapes if s[1] == _lib.EPI_ACT_F32]   # timing ablations exist for the fp32-out epilogue only
 variants = [int(v) for v in a.variants.split(",")]
+for v in variants:
+    if lib.aaclip_set_gemm_variant(v) != 0:
+        raise SystemExit(f"variant {v} refused: {lib.aaclip_last_error().decode()}")
 st = torch.cuda.current_stream().cuda_stream
 res = {}
 for name, epi, N, K in shapes:
