@@ -316,19 +316,7 @@ def run_block(x: torch.Tensor, block, B: int, L: int, heads: int, code: int, cau
     """In place on x [B*L, D]: reference model/transformer.py:239-258 (+ adapter.py:163-170).
     A block flagged by VisionTransformer.DAPM_replace (`block.surgery`) runs the V-V attention over
     the batch axis (reference transformer.py:102-152 as executed, include/aaclip.h AACLIP_ATTN_VV_BATCH)."""
-    if getattr(block, "surgery", False):
-        if causal:
-            raise ValueError("the V-V attention block takes no mask")
-        causal = ATTN_VV_BATCH
-    require_gpu(x, "block")
-    lib = _lib.load()
-    D = x.shape[1]
-    F = block.mlp.c_fc.weight.shape[0]
-    w, refs = pack_block(block, code, adapter_weight)
-    ws = Workspace.for_rows(x.device, code, B * L, D, F, 0)
-    _lib.check(lib.aaclip_block(x.data_ptr(), C.byref(w), float(mix), B, L, D, heads, F, int(causal), code,
-                                ws.data_ptr(), ws.numel(), _stream(x.device)), "block")
-    del refs
+    run_blocks(x, [block], B, L, heads, code, causal=causal, adapter_weights=[adapter_weight], mix=mix)
 
 
 def run_blocks(x: torch.Tensor, blocks: Sequence, B: int, L: int, heads: int, code: int, causal: bool = False,

@@ -1,6 +1,7 @@
 // C ABI of libaaclip_hip.so (declared in include/aaclip.h): argument checks,
 // workspace carving and kernel sequencing.  No allocation, no synchronisation:
 // every entry point only enqueues kernels on the caller's stream.
+#include <assert.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -19,6 +20,10 @@ static int fail(int code, const char* msg) {
 #define REQUIRE(cond, msg) \
   do {                     \
     if (!(cond)) return fail(-1, msg); \
+  } while (0)
+#define REQUIRE_ROW_WIDTH(D) \
+  do {                       \
+    if (const char* m_ = row_width_check(D)) return fail(-1, m_); \
   } while (0)
 
 static int finish(const char* what) {
@@ -62,12 +67,20 @@ struct ProfScope {
 static inline size_t esize(int dtype) { return (dtype == AACLIP_F32 || dtype == AACLIP_F16X2) ? 4 : 2; }
 static inline int split_w(int dtype) { return dtype == AACLIP_F16X2 ? 2 : 1; }   // row stride factor of split rows
 static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-// aux region of the workspace: 16-bit copy of the residual rows, per-row partial sums [rows][D/64][2], (a, b) pairs
-static inline size_t aux_bytes(size_t es, long rows, int D) {
-  return up256((size_t)rows * D * es) + up256((size_t)rows * (D / 64 + 1) * 2 * 4) + up256((size_t)rows * 2 * 4);
-}
 static inline bool dtype_ok(int d) { return d == AACLIP_F32 || d == AACLIP_F16 || d == AACLIP_BF16 || d == AACLIP_F16X2; }
 static inline bool plain_dtype_ok(int d) { return d == AACLIP_F32 || d == AACLIP_F16 || d == AACLIP_BF16; }
+// shape limits shared by the map entry points (anomaly_map.hip, iqm.hip, train_loss.hip)
+static inline bool map_shape_ok(int B, int g, int S) { return B > 0 && B <= 65535 && g >= 1 && g <= 40 && S >= 1; }
+
+// out[M, ldc] = A[M, lda] . W[N, K]^T (+ bias): the fields every product sets; every other field is zero (= off) and
+// the call site sets the ones its epilogue needs
+static GemmParams gemm_params(const void* A, long lda, const void* W, const float* bias, void* out, long ldc, int M,
+                              int N, int K) {
+  GemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.A = A; p.lda = lda; p.W = W; p.bias = bias; p.out = out; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
+  return p;
+}
 
 extern "C" {
 
@@ -117,21 +130,26 @@ int aaclip_set_gemm_variant(int v) {
 int aaclip_version(void) { return AACLIP_ABI_VERSION; }
 const char* aaclip_last_error(void) { return g_err; }
 
-// workspace layout: [narrow: rows*max(D,640)*es] [big] [rows floats] [aux: LayerNorm folding] + slack
-struct WsLayout { size_t big_off, rowf_off, aux_off, total; };
+// The block / head workspace, byte offsets from its start (narrow starts at 0).  This is the only place that knows it:
+//   [narrow: rows*max(D,640)*es] [big: rows * max(3D, F) in the compute dtype, or D / E floats]
+//   [reserved: rows floats, read by nothing] [aux, LayerNorm folding: x16 | partials | rowab] + 4096 slack
+// x16: 16-bit copy of the residual rows; partials: per-row partial sums [rows][D/64][2]; rowab: per-row (a, b) pairs
+struct WsLayout { size_t narrow_bytes, big, big_bytes, reserved, x16, partials, rowab, total; };
 static WsLayout ws_layout(int dtype, long rows, int D, int F, int E) {
   const size_t es = esize(dtype);
   size_t wide = (size_t)rows * (size_t)(3 * D > F ? 3 * D : F) * es;
   size_t f32d = (size_t)rows * D * 4;
   size_t f32e = (size_t)rows * (E > 0 ? E : 1) * 4;
-  size_t big = wide > f32d ? wide : f32d;
-  if (f32e > big) big = f32e;
-  size_t narrow = (size_t)rows * (D > 640 ? D : 640) * es;
   WsLayout l;
-  l.big_off = up256(narrow);
-  l.rowf_off = l.big_off + up256(big);
-  l.aux_off = l.rowf_off + up256((size_t)rows * 4);
-  l.total = l.aux_off + aux_bytes(es, rows, D) + 4096;
+  l.narrow_bytes = up256((size_t)rows * (D > 640 ? D : 640) * es);
+  l.big = l.narrow_bytes;
+  l.big_bytes = wide > f32d ? wide : f32d;
+  if (f32e > l.big_bytes) l.big_bytes = f32e;
+  l.reserved = l.big + up256(l.big_bytes);
+  l.x16 = l.reserved + up256((size_t)rows * 4);
+  l.partials = l.x16 + up256((size_t)rows * D * es);
+  l.rowab = l.partials + up256((size_t)rows * (D / 64 + 1) * 2 * 4);
+  l.total = l.rowab + up256((size_t)rows * 2 * 4) + 4096;
   return l;
 }
 
@@ -142,8 +160,7 @@ int aaclip_layernorm(const float* x, const float* w, const float* b, void* out, 
   REQUIRE(x && w && b && out, "layernorm: null pointer");
   REQUIRE(dtype_ok(out_dtype), "layernorm: bad dtype");
   REQUIRE(rows > 0, "layernorm: rows must be positive");
-  const char* m = row_width_check(D);
-  if (m) return fail(-1, m);
+  REQUIRE_ROW_WIDTH(D);
   launch_layernorm(out_dtype, x, w, b, out, rows, D, eps, (hipStream_t)stream);
   return finish("layernorm");
 }
@@ -152,9 +169,7 @@ int aaclip_gemm(int dtype, int epi, const void* A, long lda, const void* W, cons
                 int M, int N, int K, int act, int scale_cols, float scale, void* stream) {
   REQUIRE(dtype_ok(dtype), "gemm: bad dtype");
   REQUIRE(epi >= AACLIP_EPI_BIAS && epi <= AACLIP_EPI_ACT_F32, "gemm: bad epilogue");
-  GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = A; p.lda = lda; p.W = W; p.M = M; p.N = N; p.K = K; p.bias = bias; p.out = out; p.ldc = ldc;
+  GemmParams p = gemm_params(A, lda, W, bias, out, ldc, M, N, K);
   p.scale_cols = scale_cols; p.scale = scale; p.act = act;
   const char* m = gemm_check(dtype, epi, p);
   if (m) return fail(-1, m);
@@ -162,32 +177,31 @@ int aaclip_gemm(int dtype, int epi, const void* A, long lda, const void* W, cons
   return finish("gemm");
 }
 
-int aaclip_attention(int dtype, const void* qkv, void* ctx, int B, int L, int H, int causal, void* stream) {
-  REQUIRE(dtype_ok(dtype), "attention: bad dtype");
+// aaclip_attention / aaclip_attention_log2q behind their own dtype rules
+static int attention_entry(int dtype, const void* qkv, void* ctx, int B, int L, int H, int causal, int log2q,
+                           void* stream) {
   REQUIRE(qkv && ctx, "attention: null pointer");
   REQUIRE(B > 0 && L > 0 && H > 0, "attention: empty problem");
   REQUIRE(B <= 65535 && H <= 65535, "attention: grid limit");
   REQUIRE((long)L * 3 * 64 * H * 4 < (1L << 31), "attention: L * 3 * 64 * H * 4 must stay below 2^31 (32-bit row offsets)");
   REQUIRE((long)((L + 255) / 256) * H * B < (1L << 30), "attention: too many workgroups");
-  launch_attention(dtype, qkv, ctx, B, L, H, causal, 0, (hipStream_t)stream);
+  launch_attention(dtype, qkv, ctx, B, L, H, causal, log2q, (hipStream_t)stream);
   return finish("attention");
+}
+
+int aaclip_attention(int dtype, const void* qkv, void* ctx, int B, int L, int H, int causal, void* stream) {
+  REQUIRE(dtype_ok(dtype), "attention: bad dtype");
+  return attention_entry(dtype, qkv, ctx, B, L, H, causal, 0, stream);
 }
 
 int aaclip_attention_log2q(int dtype, const void* qkv, void* ctx, int B, int L, int H, int causal, void* stream) {
   REQUIRE(dtype == AACLIP_F16 || dtype == AACLIP_BF16 || dtype == AACLIP_F16X2, "attention_log2q: 16-bit dtypes only");
-  REQUIRE(qkv && ctx, "attention: null pointer");
-  REQUIRE(B > 0 && L > 0 && H > 0, "attention: empty problem");
-  REQUIRE(B <= 65535 && H <= 65535, "attention: grid limit");
-  REQUIRE((long)L * 3 * 64 * H * 4 < (1L << 31), "attention: L * 3 * 64 * H * 4 must stay below 2^31 (32-bit row offsets)");
-  REQUIRE((long)((L + 255) / 256) * H * B < (1L << 30), "attention: too many workgroups");
-  launch_attention(dtype, qkv, ctx, B, L, H, causal, 1, (hipStream_t)stream);
-  return finish("attention");
+  return attention_entry(dtype, qkv, ctx, B, L, H, causal, 1, stream);
 }
 
 int aaclip_adapter_mix(float* x, const float* a, long rows, int D, float weight, void* stream) {
   REQUIRE(x && a && rows > 0, "adapter_mix: bad arguments");
-  const char* m = row_width_check(D);
-  if (m) return fail(-1, m);
+  REQUIRE_ROW_WIDTH(D);
   launch_adapter_mix(x, a, rows, D, weight, (hipStream_t)stream);
   return finish("adapter_mix");
 }
@@ -289,9 +303,8 @@ int aaclip_iqm_map(const float* const* seg, int NL, const float* queries, const 
                    int E, int S, float w_base, float w_iqm, void* ws, size_t ws_bytes, void* stream) {
   REQUIRE(seg && queries && out && ws, "iqm_map: null pointer");
   REQUIRE(NL >= 1 && NL <= 4, "iqm_map: 1..4 levels");
-  REQUIRE(B > 0 && B <= 65535 && g >= 1 && g <= 40 && S >= 1, "iqm_map: bad shape (grid <= 40)");
-  const char* m = row_width_check(E);
-  if (m) return fail(-1, m);
+  REQUIRE(map_shape_ok(B, g, S), "iqm_map: bad shape (grid <= 40)");
+  REQUIRE_ROW_WIDTH(E);
   const int P = g * g;
   REQUIRE(ws_bytes >= (size_t)NL * B * P * 4, "iqm_map: workspace too small");
   hipStream_t s = (hipStream_t)stream;
@@ -310,19 +323,16 @@ int aaclip_patch_embed(const float* img, const void* conv_w, const float* cls, c
   REQUIRE(dtype_ok(dtype), "patch_embed: bad dtype");
   REQUIRE(img && conv_w && cls && pos && ln_pre_w && ln_pre_b && x && ws, "patch_embed: null pointer");
   REQUIRE(B > 0 && ps > 0 && H >= ps && W >= ps, "patch_embed: bad image shape");
-  const char* m = row_width_check(D);
-  if (m) return fail(-1, m);
+  REQUIRE_ROW_WIDTH(D);
   const int g = H / ps, gw = W / ps, P = g * gw, L = P + 1;
   const int K = 3 * ps * ps, Kpad = (K + 63) / 64 * 64;
   REQUIRE(Kpad <= 640, "patch_embed: 3*ps*ps must be <= 640");
   REQUIRE(ws_bytes >= (size_t)B * P * Kpad * esize(dtype), "patch_embed: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   launch_im2col(dtype, img, ws, B, 3, H, W, ps, Kpad, s);
-  GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = ws; p.lda = split_w(dtype) * Kpad; p.W = conv_w; p.M = B * P; p.N = D; p.K = Kpad; p.out = x; p.ldc = D;
+  GemmParams p = gemm_params(ws, split_w(dtype) * Kpad, conv_w, nullptr, x, D, B * P, D, Kpad);
   p.pos = pos; p.P = P; p.L = L;
-  m = gemm_check(dtype, EPI_PATCH, p);
+  const char* m = gemm_check(dtype, EPI_PATCH, p);
   if (m) return fail(-1, m);
   launch_gemm(dtype, EPI_PATCH, p, s);
   launch_cls_rows(x, cls, pos, B, L, D, s);
@@ -337,7 +347,7 @@ int aaclip_patch_embed(const float* img, const void* conv_w, const float* cls, c
 // x_in != x: the block READS the stream from x_in (left untouched) and continues it in x -- the first residual
 // update (out_proj) takes its residual from x_in and writes x.
 static int block_impl(const float* x_in, float* x, const aaclip_block_weights* w, float mix, int B, int L, int D, int H,
-                      int F, int attn_mode, int dtype, void* ws, size_t ws_bytes, hipStream_t s, bool aux_in,
+                      int F, int attn_mode, int dtype, void* ws, const WsLayout& l, hipStream_t s, bool aux_in,
                       bool want_out, bool* aux_out) {
   *aux_out = false;
   REQUIRE(w->ln1_w && w->ln1_b && w->qkv_w && w->qkv_b && w->out_w && w->out_b && w->ln2_w && w->ln2_b && w->fc_w &&
@@ -346,32 +356,31 @@ static int block_impl(const float* x_in, float* x, const aaclip_block_weights* w
   const long rows = (long)B * L;
   const size_t es = esize(dtype);
   char* narrow = (char*)ws;
-  char* big = narrow + up256((size_t)rows * (D > 640 ? D : 640) * es);
-  char* aux = (char*)ws + ws_layout(dtype, rows, D, F, 0).aux_off;
-  char* x16 = aux;
-  float* partials = (float*)(aux + up256((size_t)rows * D * es));
-  float* rowab = (float*)((char*)partials + up256((size_t)rows * (D / 64 + 1) * 2 * 4));
+  char* big = narrow + l.big;
+  char* x16 = narrow + l.x16;
+  float* partials = (float*)(narrow + l.partials);
+  float* rowab = (float*)(narrow + l.rowab);
   const int M = (int)rows;
   const bool folding = g_ln_fold && (dtype == AACLIP_F16 || dtype == AACLIP_BF16);
   const int sw = split_w(dtype);                    // split fp16 rows are [hi | lo]: twice the row stride
   const unsigned ex = dtype == AACLIP_F16X2 ? w->exact16 : 0u;   // weights whose lo half is all zero
 
-  GemmParams p;
   // ---- x += out_proj(attn(ln_1 x))
-  memset(&p, 0, sizeof(p));
   // 16-bit path: fold log2(e) into the q scale (one rounding) so the attention kernel works in log2 units
   const int log2q = dtype != AACLIP_F32;
   const float qscale = log2q ? 0.125f * 1.4426950408889634f : 0.125f;
+  const int qkv_exact = ex & AACLIP_EXACT16_QKV;
   const char* ctx = narrow;
   if (attn_mode == AACLIP_ATTN_VV_BATCH) {
-    { ProfScope ps(0, s); launch_layernorm(dtype, x_in, w->ln1_w, w->ln1_b, narrow, rows, D, 1e-5f, s, !(ex & AACLIP_EXACT16_QKV)); }
-    // only the value third of in_proj is needed; v lives behind the packed q|k|v buffer inside `big`
+    { ProfScope ps(0, s); launch_layernorm(dtype, x_in, w->ln1_w, w->ln1_b, narrow, rows, D, 1e-5f, s, !qkv_exact); }
+    // only the value third of in_proj is needed; v lives behind the packed q|k|v buffer inside `big`, which holds
+    // rows * max(3D, F) elements: blocks_core()'s F >= 4*D check is what makes room for it
+    assert((size_t)rows * 4 * D * es <= l.big_bytes);
     char* vbuf = big + (size_t)rows * 3 * D * es;
-    p.A = narrow; p.lda = sw * D; p.M = M; p.N = D; p.K = D;
-    p.w_exact16 = ex & AACLIP_EXACT16_QKV;
     // rows 2D.. of the packed weight; a split8 weight row holds 4 (3: exact in fp16) bytes per element
-    p.W = (const char*)w->qkv_w + (size_t)2 * D * D * (dtype == AACLIP_F16X2 ? (p.w_exact16 ? 3 : 4) : es);
-    p.bias = w->qkv_b + 2 * D; p.out = vbuf; p.ldc = sw * D;
+    const char* v_w = (const char*)w->qkv_w + (size_t)2 * D * D * (dtype == AACLIP_F16X2 ? (qkv_exact ? 3 : 4) : es);
+    GemmParams p = gemm_params(narrow, sw * D, v_w, w->qkv_b + 2 * D, vbuf, sw * D, M, D, D);
+    p.w_exact16 = qkv_exact;
     { ProfScope ps(1, s); launch_gemm(dtype, EPI_BIAS, p, s); }
     {
       ProfScope ps(2, s);
@@ -381,14 +390,14 @@ static int block_impl(const float* x_in, float* x, const aaclip_block_weights* w
     }
     ctx = vbuf;
   } else {
-    p.A = narrow; p.lda = sw * D; p.W = w->qkv_w; p.M = M; p.N = 3 * D; p.K = D; p.bias = w->qkv_b; p.out = big;
-    p.ldc = sw * 3 * D; p.scale_cols = D; p.scale = qscale; p.w_exact16 = ex & AACLIP_EXACT16_QKV;
+    GemmParams p = gemm_params(narrow, sw * D, w->qkv_w, w->qkv_b, big, sw * 3 * D, M, 3 * D, D);
+    p.scale_cols = D; p.scale = qscale; p.w_exact16 = qkv_exact;
     if (aux_in && folding && w->qkv_w_fold && w->qkv_fold_s && w->qkv_fold_b && gemm_routes_to_256t(dtype, p)) {
       // ln_1 folded into the QKV product (include/aaclip.h, aaclip_block_weights)
       p.A = x16; p.W = w->qkv_w_fold; p.bias = w->qkv_fold_b; p.row_ab = rowab; p.col_s = w->qkv_fold_s;
     } else {
       ProfScope ps(0, s);
-      launch_layernorm(dtype, x_in, w->ln1_w, w->ln1_b, narrow, rows, D, 1e-5f, s, !(ex & AACLIP_EXACT16_QKV));
+      launch_layernorm(dtype, x_in, w->ln1_w, w->ln1_b, narrow, rows, D, 1e-5f, s, !qkv_exact);
     }
     // split fp16, long rows, 256-tile QKV kernel: q and k leave the epilogue as fp16 + e4m3 records and the attention
     // kernel runs its two correction products on the e4m3 MFMA (attention.hip, QK8)
@@ -401,16 +410,13 @@ static int block_impl(const float* x_in, float* x, const aaclip_block_weights* w
     { ProfScope ps(1, s); launch_gemm(dtype, EPI_BIAS, p, s); }
     { ProfScope ps(2, s); launch_attention(dtype, big, narrow, B, L, H, attn_mode == AACLIP_ATTN_CAUSAL, log2q, s, !(ex & AACLIP_EXACT16_OUT), qk8); }
   }
-  memset(&p, 0, sizeof(p));
-  p.A = ctx; p.lda = sw * D; p.W = w->out_w; p.M = M; p.N = D; p.K = D; p.bias = w->out_b; p.out = x; p.ldc = D;
+  GemmParams p = gemm_params(ctx, sw * D, w->out_w, w->out_b, x, D, M, D, D);
   p.w_exact16 = ex & AACLIP_EXACT16_OUT;
   if (x_in != x) p.resid = x_in;
   // ln_2 folded into c_fc: only where both products run on the kernels whose epilogue implements it;
   // everywhere else the ln_2 pass runs as before
-  GemmParams fc;
-  memset(&fc, 0, sizeof(fc));
-  fc.lda = sw * D; fc.M = M; fc.N = F; fc.K = D; fc.out = big; fc.ldc = sw * F;
-  fc.A = narrow; fc.W = w->fc_w; fc.bias = w->fc_b; fc.w_exact16 = ex & AACLIP_EXACT16_FC;
+  GemmParams fc = gemm_params(narrow, sw * D, w->fc_w, w->fc_b, big, sw * F, M, F, D);
+  fc.w_exact16 = ex & AACLIP_EXACT16_FC;
   fc.out_no_hi8 = (ex & AACLIP_EXACT16_PROJ) ? 1 : 0;   // c_proj is the only reader of the GELU rows
   const bool fold2 = folding && w->fc_w_fold && w->fc_fold_s && w->fc_fold_b && gemm_routes_to_256t(dtype, p) &&
                      gemm_routes_to_256t(dtype, fc);
@@ -429,8 +435,7 @@ static int block_impl(const float* x_in, float* x, const aaclip_block_weights* w
     launch_layernorm(dtype, x, w->ln2_w, w->ln2_b, narrow, rows, D, 1e-5f, s, !(ex & AACLIP_EXACT16_FC));
   }
   { ProfScope ps(4, s); launch_gemm(dtype, EPI_BIAS_GELU, fc, s); }
-  memset(&p, 0, sizeof(p));
-  p.A = big; p.lda = sw * F; p.W = w->proj_w; p.M = M; p.N = D; p.K = F; p.bias = w->proj_b; p.out = x; p.ldc = D;
+  p = gemm_params(big, sw * F, w->proj_w, w->proj_b, x, D, M, D, F);
   p.w_exact16 = ex & AACLIP_EXACT16_PROJ;
   // the c_proj epilogue can also emit the new rows in 16 bits: input of the adapter product, or (with their
   // row sums) of the next block's folded ln_1
@@ -458,8 +463,8 @@ static int block_impl(const float* x_in, float* x, const aaclip_block_weights* w
       launch_cast_rows(dtype, x, narrow, rows * D, s);
       a_in = narrow;
     }
-    memset(&p, 0, sizeof(p));
-    p.A = a_in; p.lda = sw * D; p.W = w->adapter_w; p.M = M; p.N = D; p.K = D; p.out = big; p.ldc = D; p.act = 1;
+    p = gemm_params(a_in, sw * D, w->adapter_w, nullptr, big, D, M, D, D);
+    p.act = 1;
     p.w_exact16 = ex & AACLIP_EXACT16_ADAPTER;
     launch_gemm(dtype, EPI_ACT_F32, p, s);
     if (folding && want_out) {
@@ -494,19 +499,17 @@ static int blocks_core(const float* x_in, float* const* x_out, float* x_all, con
   REQUIRE(dtype_ok(dtype), "block: bad dtype");
   REQUIRE(attn_mode >= AACLIP_ATTN_FULL && attn_mode <= AACLIP_ATTN_VV_BATCH, "block: attn_mode must be 0, 1 or 2");
   REQUIRE(attn_mode != AACLIP_ATTN_VV_BATCH || F >= 4 * D, "block: V-V attention needs F >= 4*D workspace columns");
-  REQUIRE(x && w && ws, "block: null pointer");
-  REQUIRE(n_blocks >= 1, "block: n_blocks must be positive");
+  REQUIRE(x && ws, "block: null pointer");
   REQUIRE(B > 0 && L > 0, "block: empty batch");
   REQUIRE(D == 64 * H, "block: D must equal 64*H (head dim 64)");
   REQUIRE((long)L * 3 * D * 4 < (1L << 31) && (long)B * 3 * D * 4 < (1L << 31),
           "block: sequence too long for the attention kernel's 32-bit row offsets");
-  REQUIRE(F % 128 == 0 && F % 64 == 0, "block: F must be a multiple of 128");
-  const char* m = row_width_check(D);
-  if (m) return fail(-1, m);
-  REQUIRE(D % 128 == 0, "block: D must be a multiple of 128");
+  REQUIRE(F % 128 == 0, "block: F must be a multiple of 128");
+  REQUIRE_ROW_WIDTH(D);   // every accepted width is a multiple of 128, which the 128-tile GEMMs need
   const long rows = (long)B * L;
   REQUIRE(rows < (1L << 31) / 4, "block: too many rows");
-  REQUIRE(ws_bytes >= aaclip_workspace_bytes(dtype, rows, D, F, 0), "block: workspace too small");
+  const WsLayout l = ws_layout(dtype, rows, D, F, 0);
+  REQUIRE(ws_bytes >= l.total, "block: workspace too small");
   if (x_out)
     for (int i = 0; i < n_blocks; ++i) REQUIRE(x_out[i], "block: null output buffer");
   bool aux = false;
@@ -514,7 +517,7 @@ static int blocks_core(const float* x_in, float* const* x_out, float* x_all, con
   for (int i = 0; i < n_blocks; ++i) {
     bool produced = false;
     float* dst = x_out ? x_out[i] : x_all;
-    int rc = block_impl(src, dst, w + i, mix, B, L, D, H, F, attn_mode, dtype, ws, ws_bytes, (hipStream_t)stream, aux,
+    int rc = block_impl(src, dst, w + i, mix, B, L, D, H, F, attn_mode, dtype, ws, l, (hipStream_t)stream, aux,
                         i + 1 < n_blocks, &produced);
     if (rc) return rc;
     aux = produced;
@@ -542,49 +545,47 @@ int aaclip_block(float* x, const aaclip_block_weights* w, float mix, int B, int 
 }
 
 static int head_common(const float* x, const float* ln_w, const float* ln_b, int B, int L, int D, int E, int dtype,
-                       void* ws, size_t ws_bytes, char** narrow, char** big, char** rowf) {
+                       void* ws, size_t ws_bytes, WsLayout* l) {
   REQUIRE(dtype_ok(dtype), "head: bad dtype");
   REQUIRE(x && ln_w && ln_b && ws, "head: null pointer");
   REQUIRE(B > 0 && L > 1, "head: bad shape");
-  const char* m = row_width_check(D);
-  if (m) return fail(-1, m);
-  m = row_width_check(E);
-  if (m) return fail(-1, m);
+  REQUIRE_ROW_WIDTH(D);
+  REQUIRE_ROW_WIDTH(E);
   REQUIRE(E % 128 == 0, "head: E must be a multiple of 128");
-  const long rows = (long)B * L;
-  REQUIRE(ws_bytes >= aaclip_workspace_bytes(dtype, rows, D, 0, E), "head: workspace too small");
-  *narrow = (char*)ws;
-  *big = *narrow + up256((size_t)rows * (D > 640 ? D : 640) * esize(dtype));
-  size_t wide = (size_t)rows * (size_t)(3 * D) * esize(dtype);
-  size_t f32d = (size_t)rows * D * 4, f32e = (size_t)rows * E * 4;
-  size_t bigsz = wide > f32d ? wide : f32d;
-  if (f32e > bigsz) bigsz = f32e;
-  *rowf = *big + up256(bigsz);
+  *l = ws_layout(dtype, (long)B * L, D, 0, E);
+  REQUIRE(ws_bytes >= l->total, "head: workspace too small");
   return 0;
+}
+
+// The det product of a head: the LayerNorm'ed rows `ln` -> big -> the mean over each image's patch rows.  narrow is
+// the mean's scratch; where `ln` is narrow itself, it is free once the GEMM has run.
+static void det_tail(const void* ln, const void* det_w, int act, float* det_out, int B, int L, int D, int E, int dtype,
+                     void* ws, const WsLayout& l, hipStream_t s) {
+  float* big = (float*)((char*)ws + l.big);
+  GemmParams p = gemm_params(ln, split_w(dtype) * D, det_w, nullptr, big, E, (int)((long)B * L), E, D);
+  p.act = act;
+  launch_gemm(dtype, EPI_ACT_F32, p, s);
+  launch_det_mean(big, (float*)ws, l.narrow_bytes / 4, det_out, B, L, 1, E, s);
 }
 
 static int tap_head_impl(const float* x, const float* ln_post_w, const float* ln_post_b, const void* proj_w, int act,
                          float* seg_out, const void* det_w, float* det_out, void* ln_rows_out, int B, int L, int D, int E,
                          int dtype, void* ws, size_t ws_bytes, void* stream) {
-  char *narrow, *big, *rowf;
-  int rc = head_common(x, ln_post_w, ln_post_b, B, L, D, E, dtype, ws, ws_bytes, &narrow, &big, &rowf);
+  WsLayout l;
+  int rc = head_common(x, ln_post_w, ln_post_b, B, L, D, E, dtype, ws, ws_bytes, &l);
   if (rc) return rc;
   REQUIRE(proj_w && seg_out, "tap_head: null pointer");
   REQUIRE(!det_w || det_out, "tap_head: det_out missing");
   hipStream_t s = (hipStream_t)stream;
   const long rows = (long)B * L;
-  char* ln = ln_rows_out ? (char*)ln_rows_out : narrow;   // the LayerNorm'ed rows, kept for the caller if asked
+  float* big = (float*)((char*)ws + l.big);
+  void* ln = ln_rows_out ? ln_rows_out : ws;   // the LayerNorm'ed rows: in narrow, or kept for the caller if asked
   launch_layernorm(dtype, x, ln_post_w, ln_post_b, ln, rows, D, 1e-5f, s);
-  GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = ln; p.lda = split_w(dtype) * D; p.W = proj_w; p.M = (int)rows; p.N = E; p.K = D; p.out = big; p.ldc = E; p.act = act;
+  GemmParams p = gemm_params(ln, split_w(dtype) * D, proj_w, nullptr, big, E, (int)rows, E, D);
+  p.act = act;
   launch_gemm(dtype, EPI_ACT_F32, p, s);
-  launch_normalize_rows((const float*)big, seg_out, B, L, 1, E, s);
-  if (det_w) {
-    p.W = det_w;
-    launch_gemm(dtype, EPI_ACT_F32, p, s);
-    launch_det_mean((const float*)big, (float*)narrow, (size_t)(big - narrow) / 4, det_out, B, L, 1, E, s);   // narrow is free after the GEMM
-  }
+  launch_normalize_rows(big, seg_out, B, L, 1, E, s);
+  if (det_w) det_tail(ln, det_w, act, det_out, B, L, D, E, dtype, ws, l, s);
   return finish("tap_head");
 }
 
@@ -605,18 +606,13 @@ int aaclip_tap_head_keep_rows(const float* x, const float* ln_post_w, const floa
 
 int aaclip_det_head(const float* x, const float* ln_post_w, const float* ln_post_b, const void* det_w, int act,
                     float* det_out, int B, int L, int D, int E, int dtype, void* ws, size_t ws_bytes, void* stream) {
-  char *narrow, *big, *rowf;
-  int rc = head_common(x, ln_post_w, ln_post_b, B, L, D, E, dtype, ws, ws_bytes, &narrow, &big, &rowf);
+  WsLayout l;
+  int rc = head_common(x, ln_post_w, ln_post_b, B, L, D, E, dtype, ws, ws_bytes, &l);
   if (rc) return rc;
   REQUIRE(det_w && det_out, "det_head: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  const long rows = (long)B * L;
-  launch_layernorm(dtype, x, ln_post_w, ln_post_b, narrow, rows, D, 1e-5f, s);
-  GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = narrow; p.lda = split_w(dtype) * D; p.W = det_w; p.M = (int)rows; p.N = E; p.K = D; p.out = big; p.ldc = E; p.act = act;
-  launch_gemm(dtype, EPI_ACT_F32, p, s);
-  launch_det_mean((const float*)big, (float*)narrow, (size_t)(big - narrow) / 4, det_out, B, L, 1, E, s);
+  launch_layernorm(dtype, x, ln_post_w, ln_post_b, ws, (long)B * L, D, 1e-5f, s);   // into narrow
+  det_tail(ws, det_w, act, det_out, B, L, D, E, dtype, ws, l, s);
   return finish("det_head");
 }
 
@@ -624,11 +620,10 @@ int aaclip_anomaly_map(const float* const* seg, int NL, const float* anchors, lo
                        int g, int E, int S, int ksize, float sigma, void* ws, size_t ws_bytes, void* stream) {
   REQUIRE(seg && anchors && out && ws, "anomaly_map: null pointer");
   REQUIRE(NL >= 1 && NL <= 4, "anomaly_map: 1..4 levels");
-  REQUIRE(B > 0 && B <= 65535 && g >= 1 && g <= 40 && S >= 1, "anomaly_map: bad shape (grid <= 40)");
+  REQUIRE(map_shape_ok(B, g, S), "anomaly_map: bad shape (grid <= 40)");
   REQUIRE(ksize >= 1 && ksize <= 15 && ksize / 2 < g, "anomaly_map: kernel size must be 1..15 and < 2*grid");
   REQUIRE(sigma > 0.f, "anomaly_map: sigma must be positive");
-  const char* m = row_width_check(E);
-  if (m) return fail(-1, m);
+  REQUIRE_ROW_WIDTH(E);
   const int P = g * g;
   REQUIRE(ws_bytes >= (size_t)NL * B * P * 4, "anomaly_map: workspace too small");
   hipStream_t s = (hipStream_t)stream;
@@ -644,9 +639,8 @@ int aaclip_anomaly_map(const float* const* seg, int NL, const float* anchors, lo
 int aaclip_similarity_map_train(const float* seg, const float* anchors, long anchor_bstride, float* out, int B, int g,
                                 int E, int S, void* ws, size_t ws_bytes, void* stream) {
   REQUIRE(seg && anchors && out && ws, "similarity_map_train: null pointer");
-  REQUIRE(B > 0 && B <= 65535 && g >= 1 && g <= 40 && S >= 1, "similarity_map_train: bad shape (grid <= 40)");
-  const char* m = row_width_check(E);
-  if (m) return fail(-1, m);
+  REQUIRE(map_shape_ok(B, g, S), "similarity_map_train: bad shape (grid <= 40)");
+  REQUIRE_ROW_WIDTH(E);
   const int P = g * g;
   REQUIRE(ws_bytes >= (size_t)2 * B * P * 4, "similarity_map_train: workspace too small");
   hipStream_t s = (hipStream_t)stream;
@@ -664,11 +658,10 @@ int aaclip_similarity_map_train_backward(const float* seg, const float* anchors,
                                          const float* preds, const float* d_preds, float* d_anchors, float* d_seg,
                                          int B, int g, int E, int S, void* ws, size_t ws_bytes, void* stream) {
   REQUIRE(seg && anchors && preds && d_preds && ws, "similarity_map_train_backward: null pointer");
-  REQUIRE(B > 0 && B <= 65535 && g >= 1 && g <= 40 && S >= 1 && S <= SIMMAP_BWD_MAX_S,
+  REQUIRE(map_shape_ok(B, g, S) && S <= SIMMAP_BWD_MAX_S,
           "similarity_map_train_backward: bad shape (grid <= 40, size <= 2048)");
   REQUIRE(anchor_bstride == 0 || anchor_bstride == 2L * E, "similarity_map_train_backward: anchor stride 0 or 2E");
-  const char* m = row_width_check(E);
-  if (m) return fail(-1, m);
+  REQUIRE_ROW_WIDTH(E);
   REQUIRE(ws_bytes >= simmap_bwd_ws_bytes(B, g, S), "similarity_map_train_backward: workspace too small");
   launch_similarity_map_train_bwd(seg, anchors, anchor_bstride, preds, d_preds, d_anchors, d_seg, B, g, E, S, ws,
                                   (hipStream_t)stream);
@@ -754,8 +747,7 @@ int aaclip_row_head(const float* x, const int32_t* tokens, const float* ln_w, co
   REQUIRE(x && ln_w && ln_b && proj_w && out && ws, "row_head: null pointer");
   REQUIRE(mode == 1 || tokens, "row_head: tokens required for EOT mode");
   REQUIRE(n > 0 && T > 0, "row_head: bad shape");
-  const char* m = row_width_check(D);
-  if (m) return fail(-1, m);
+  REQUIRE_ROW_WIDTH(D);
   REQUIRE(E % 128 == 0, "row_head: E must be a multiple of 128");
   const size_t es = esize(dtype);
   const long rows = (long)n * T;
@@ -766,9 +758,8 @@ int aaclip_row_head(const float* x, const int32_t* tokens, const float* ln_w, co
   char* picked = ln_out + up256((size_t)rows * D * es);
   launch_layernorm(dtype, x, ln_w, ln_b, ln_out, rows, D, 1e-5f, s);
   launch_gather_rows(dtype, ln_out, picked, tokens, n, T, D, mode, s);
-  GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = picked; p.lda = split_w(dtype) * D; p.W = proj_w; p.M = n; p.N = E; p.K = D; p.out = out; p.ldc = E; p.act = act;
+  GemmParams p = gemm_params(picked, split_w(dtype) * D, proj_w, nullptr, out, E, n, E, D);
+  p.act = act;
   const char* gm = gemm_check(dtype, EPI_ACT_F32, p);
   if (gm) return fail(-1, gm);
   launch_gemm(dtype, EPI_ACT_F32, p, s);

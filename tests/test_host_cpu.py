@@ -117,6 +117,25 @@ def test_workspace_bytes_monotone():
     assert a >= 1370 * (1024 * 2 + 4096 * 2)
 
 
+def test_workspace_bytes_pinned():
+    """Sizes of the block / head workspace [narrow][big][rows floats][aux: x16 | partials | rowab] + slack, recorded
+    from the library before its host code was reduced to one copy of the layout.  The kernels write every region, so
+    a layout formula edited in one place only must show up here: (dtype, rows, D, F, E) -> bytes."""
+    lib = _lib.load()
+    pinned = {
+        (_lib.F16, 1370, 1024, 4096, 768): 17041664,
+        (_lib.F16X2, 4 * 1370, 1024, 4096, 0): 135492096,
+        (_lib.F32, 1370, 1024, 0, 768): 28264704,
+        (_lib.BF16, 257, 768, 3072, 768): 2403072,
+        (_lib.F16, 64 * 1370, 1024, 4096, 768): 1090392576,
+        (_lib.F16X2, 50, 256, 512, 128): 339712,
+        (_lib.F32, 1, 256, 1024, 0): 12544,
+        (_lib.F16, 4 * 1370, 768, 0, 768): 42726656,
+    }
+    for args, want in pinned.items():
+        assert lib.aaclip_workspace_bytes(*args) == want, args
+
+
 def test_argument_errors_cross_the_abi_as_codes():
     lib = _lib.load()
     rc = lib.aaclip_layernorm(None, None, None, None, _lib.F32, 4, 1024, 1e-5, None)
