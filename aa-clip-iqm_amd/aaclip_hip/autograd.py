@@ -1,5 +1,6 @@
 """torch.autograd.Functions over the training entry points of libaaclip_hip.so (include/aaclip.h, "Training"): the
-train-mode similarity map (reference forward_utils.py:196-216, test=False) and the segmentation loss (:21-108,223-227).
+train-mode similarity map (reference forward_utils.py:196-216, test=False), the segmentation loss (:21-108,223-227) and
+the adapted text tower (reference model/adapter.py:273-304), whose backward fills the text_adapter gradients.
 Forward and backward are HIP kernels; these classes only carry tensors between them.  The saved tensors live in
 ctx.save_for_backward, so they are freed with the graph (after backward(), or when the output is dropped)."""
 from __future__ import annotations
@@ -51,6 +52,79 @@ class SegLoss(torch.autograd.Function):
             return None, None, None
         d = engine.seg_loss_backward(preds, mask, coef, d_loss, ctx.terms)
         return d.to(preds.dtype), None, None
+
+
+class TextTower(torch.autograd.Function):
+    """AdaptedCLIP.encode_text with a backward for the text_adapter weights (CLIP's own parameters are frozen: they are
+    not inputs of this Function and receive no gradient).
+
+    forward(model, tokens, *text_adapter weights): the same kernels as the no-grad path, bit-identical embeddings; the
+    tower runs as ONE aaclip_blocks_taps call that leaves the stream after every block in its own buffer.  Those
+    layers x n*T x D fp32 values are all that is saved (ctx.save_for_backward: freed with the graph); the backward
+    recomputes a block's internals from its input in fp32, whatever precision the forward ran in.  When only the last
+    adapter (the EOT projection) requires grad, no block is revisited and only the n EOT rows are kept.
+    The backward stops at the first block whose adapter requires grad (the token embedding is frozen)."""
+
+    @staticmethod
+    def forward(ctx, model, tokens, *weights):
+        code = model._code()
+        c = model.clipmodel
+        until = model.text_adapt_until
+        x0, tk = engine.text_embed(tokens, c.token_embedding.weight, c.positional_embedding)
+        n, T = tk.shape
+        blocks = list(c.transformer.resblocks)
+        aws = [weights[i] if i < until else None for i in range(len(blocks))]
+        need = [i for i in range(min(until, len(blocks))) if ctx.needs_input_grad[2 + i]]
+        ctx.first = need[0] if need else None
+        ctx.model, ctx.n, ctx.T = model, n, T
+        if ctx.first is None:
+            engine.run_blocks(x0, blocks, n, T, c.transformer.heads, code, causal=True, adapter_weights=aws, mix=model.t_w)
+            out = engine.row_head(x0, tk, c.ln_final, weights[until], "plain", True, n, T, 0, code)
+            eot = tk.argmax(dim=-1)
+            ctx.save_for_backward(x0.view(n, T, -1)[torch.arange(n, device=x0.device), eot].contiguous(), tk, *weights)
+            return out
+        streams = torch.empty(len(blocks), n * T, x0.shape[1], dtype=torch.float32, device=x0.device)
+        engine.run_blocks(x0, blocks, n, T, c.transformer.heads, code, causal=True, adapter_weights=aws, mix=model.t_w,
+                          x_outs=[streams[i] for i in range(len(blocks))])
+        out = engine.row_head(streams[-1], tk, c.ln_final, weights[until], "plain", True, n, T, 0, code)
+        ctx.save_for_backward(streams, tk, *weights)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        saved, tk, *weights = ctx.saved_tensors
+        model, n, T = ctx.model, ctx.n, ctx.T
+        c = model.clipmodel
+        until = model.text_adapt_until
+        heads = c.transformer.heads
+        grads = [None] * len(weights)
+        d_out = d_out.contiguous().float()
+        if ctx.first is None:
+            # the n EOT rows as n one-row sequences: LayerNorm and the projection see rows, not sequences
+            _, d_w = engine.row_head_backward(saved, None, c.ln_final, weights[until], _lib.ACT_LEAKY, d_out, n, 1, 1,
+                                              need_input_grad=False)
+            grads[until] = d_w.to(weights[until].dtype)
+            return (None, None, *grads)
+        blocks = list(c.transformer.resblocks)
+        d_x, d_w = engine.row_head_backward(saved[-1], tk, c.ln_final, weights[until], _lib.ACT_LEAKY, d_out, n, T, 0)
+        if ctx.needs_input_grad[2 + until]:
+            grads[until] = d_w.to(weights[until].dtype)
+        for i in range(len(blocks) - 1, ctx.first - 1, -1):
+            if i > 0:
+                x_in = saved[i - 1]
+            else:   # the tower's input is not kept: token + positional embedding again
+                x_in, _ = engine.text_embed(tk, c.token_embedding.weight, c.positional_embedding)
+            aw = weights[i] if i < until else None
+            _, d_aw = engine.block_backward(x_in, blocks[i], n, T, heads, d_x, causal=True, adapter_weight=aw,
+                                            mix=model.t_w, need_input_grad=i > ctx.first, in_place=True)
+            if aw is not None and ctx.needs_input_grad[2 + i]:
+                grads[i] = d_aw.to(aw.dtype)
+        return (None, None, *grads)
+
+
+def encode_text(model, tokens):
+    """model.encode_text(tokens) with a graph: see TextTower."""
+    return TextTower.apply(model, tokens, *[m.weight for m in model.text_adapter])
 
 
 def similarity_map_train(seg, text_feature, img_size):

@@ -598,6 +598,120 @@ def seg_loss_backward(preds: torch.Tensor, mask: torch.Tensor, coef: torch.Tenso
 
 
 # ------------------------------------------------------------------------------------------------
+# backward of the adapted text tower (include/aaclip.h, "backward of the adapted text tower"): fp32, thin wrappers
+def text_backward_workspace(dev: torch.device, rows: int, D: int, F: int) -> torch.Tensor:
+    return Workspace.get(dev, _lib.load().aaclip_text_backward_workspace_bytes(int(rows), int(D), int(F)))
+
+
+def gemm_wgrad(dz: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """dw[o, i] = sum_r dz[r, o] u[r, i] for fp32 dz [rows, O], u [rows, I] -> fp32 [O, I] (aaclip_gemm_wgrad)."""
+    require_gpu(dz, "gemm_wgrad")
+    dz, u = _f32c(dz), _f32c(u)
+    rows, O = dz.shape
+    I = u.shape[1]
+    dw = torch.empty(O, I, dtype=torch.float32, device=dz.device)
+    ws = text_backward_workspace(dz.device, rows, I, 0)
+    _lib.check(_lib.load().aaclip_gemm_wgrad(dz.data_ptr(), O, u.data_ptr(), I, dw.data_ptr(), rows, O, I, ws.data_ptr(),
+                                             ws.numel(), _stream(dz.device)), "gemm_wgrad")
+    return dw
+
+
+def attention_backward(qkv: torch.Tensor, d_ctx: torch.Tensor, B: int, L: int, heads: int, causal: bool,
+                       dq_scale: float = 1.0) -> torch.Tensor:
+    """packed fp32 q|k|v rows [B*L, 3*H*64] (q pre-scaled) + d ctx [B*L, H*64] -> d qkv (aaclip_attention_backward)."""
+    require_gpu(qkv, "attention_backward")
+    qkv, d_ctx = _f32c(qkv), _f32c(d_ctx)
+    out = torch.empty_like(qkv)
+    _lib.check(_lib.load().aaclip_attention_backward(qkv.data_ptr(), d_ctx.data_ptr(), out.data_ptr(), B, L, heads,
+                                                     int(causal), float(dq_scale), _stream(qkv.device)),
+               "attention_backward")
+    return out
+
+
+def layernorm_backward(x: torch.Tensor, weight: torch.Tensor, d_y: torch.Tensor, d_resid: Optional[torch.Tensor] = None,
+                       eps: float = 1e-5) -> torch.Tensor:
+    """LayerNorm input gradient of fp32 rows [rows, D] (+ d_resid)."""
+    require_gpu(x, "layernorm_backward")
+    x, d_y, w = _f32c(x), _f32c(d_y), _f32c(weight)
+    r = _f32c(d_resid) if d_resid is not None else None
+    D = x.shape[-1]
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().aaclip_layernorm_backward(x.data_ptr(), w.data_ptr(), d_y.data_ptr(), _ptr(r), out.data_ptr(),
+                                                     x.numel() // D, D, float(eps), _stream(x.device)),
+               "layernorm_backward")
+    return out
+
+
+def adapter_mix_backward(u: torch.Tensor, z: torch.Tensor, d_y: torch.Tensor, weight: float):
+    """-> (d z, direct d u) of y = weight * a |u| / |a| + (1 - weight) * u, a = LeakyReLU(z); fp32 rows [rows, D]."""
+    require_gpu(u, "adapter_mix_backward")
+    u, z, d_y = _f32c(u), _f32c(z), _f32c(d_y)
+    D = u.shape[-1]
+    d_z, d_u = torch.empty_like(u), torch.empty_like(u)
+    _lib.check(_lib.load().aaclip_adapter_mix_backward(u.data_ptr(), z.data_ptr(), d_y.data_ptr(), d_z.data_ptr(),
+                                                       d_u.data_ptr(), u.numel() // D, D, float(weight),
+                                                       _stream(u.device)), "adapter_mix_backward")
+    return d_z, d_u
+
+
+def pack_block_transposed(block, adapter_weight: Optional[torch.Tensor]) -> Tuple[BlockWeights, list]:
+    """The `wt` argument of aaclip_block_backward: fp32 transposes [in, out] of the block's matrix weights."""
+    refs: list = []
+    w = BlockWeights()
+    w.qkv_w = _keep(refs, CACHE.get(block.attn.in_proj_weight, F32, "transpose"))
+    w.out_w = _keep(refs, CACHE.get(block.attn.out_proj.weight, F32, "transpose"))
+    w.fc_w = _keep(refs, CACHE.get(block.mlp.c_fc.weight, F32, "transpose"))
+    w.proj_w = _keep(refs, CACHE.get(block.mlp.c_proj.weight, F32, "transpose"))
+    if adapter_weight is not None:
+        w.adapter_w = _keep(refs, CACHE.get(adapter_weight, F32, "transpose"))
+    return w, refs
+
+
+def block_backward(x_in: torch.Tensor, block, B: int, L: int, heads: int, d_out: torch.Tensor, causal: bool = False,
+                   adapter_weight: Optional[torch.Tensor] = None, mix: float = 0.0, need_input_grad: bool = True,
+                   in_place: bool = False):
+    """Backward of one block from its input x_in [B*L, D] (aaclip_block_backward) -> (d x_in or None, d adapter weight
+    [D, D] or None).  in_place: d x_in overwrites d_out."""
+    require_gpu(x_in, "block_backward")
+    lib = _lib.load()
+    if x_in.dtype != torch.float32 or not x_in.is_contiguous() or d_out.dtype != torch.float32 or not d_out.is_contiguous():
+        raise ValueError("block_backward: x_in and d_out must be contiguous fp32")
+    D = x_in.shape[1]
+    F = block.mlp.c_fc.weight.shape[0]
+    w, refs = pack_block(block, F32, adapter_weight)
+    wt, refs_t = pack_block_transposed(block, adapter_weight) if need_input_grad else (BlockWeights(), [])
+    d_in = (d_out if in_place else torch.empty_like(d_out)) if need_input_grad else None
+    d_aw = torch.empty(D, D, dtype=torch.float32, device=x_in.device) if adapter_weight is not None else None
+    ws = text_backward_workspace(x_in.device, B * L, D, F)
+    _lib.check(lib.aaclip_block_backward(x_in.data_ptr(), C.byref(w), C.byref(wt), float(mix), B, L, D, heads, F,
+                                         ATTN_CAUSAL if causal else ATTN_FULL, d_out.data_ptr(), _ptr(d_in), _ptr(d_aw),
+                                         ws.data_ptr(), ws.numel(), _stream(x_in.device)), "block_backward")
+    del refs, refs_t
+    return d_in, d_aw
+
+
+def row_head_backward(x: torch.Tensor, tokens: Optional[torch.Tensor], ln, proj: torch.Tensor, act: int, d_out: torch.Tensor,
+                      n: int, T: int, mode: int, need_input_grad: bool = True):
+    """Backward of row_head(kind='plain', code fp32) -> (d x [n*T, D] or None, d proj [E, D])."""
+    require_gpu(x, "row_head_backward")
+    lib = _lib.load()
+    x, d_out = _f32c(x), _f32c(d_out)
+    D = x.shape[1]
+    pw = CACHE.get(proj, F32)
+    pwt = CACHE.get(proj, F32, "transpose") if need_input_grad else None
+    E = pw.shape[0]
+    lw, lb = _f32c(ln.weight), _f32c(ln.bias)
+    tk = tokens.to(device=x.device, dtype=torch.int32).contiguous() if tokens is not None else None
+    d_x = torch.empty(n * T, D, dtype=torch.float32, device=x.device) if need_input_grad else None
+    d_w = torch.empty(E, D, dtype=torch.float32, device=x.device)
+    ws = text_backward_workspace(x.device, n * T, D, 0)
+    _lib.check(lib.aaclip_row_head_backward(x.data_ptr(), _ptr(tk), lw.data_ptr(), lb.data_ptr(), pw.data_ptr(), _ptr(pwt),
+                                            int(act), d_out.data_ptr(), _ptr(d_x), d_w.data_ptr(), n, T, D, E, mode,
+                                            ws.data_ptr(), ws.numel(), _stream(x.device)), "row_head_backward")
+    return d_x, d_w
+
+
+# ------------------------------------------------------------------------------------------------
 # image pre-processing (reference dataset/__init__.py:150-161), Pillow-exact on the GPU
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)

@@ -21,6 +21,13 @@ static int fail(int code, const char* msg) {
   do {                     \
     if (!(cond)) return fail(-1, msg); \
   } while (0)
+// fp32 rows are moved as 16-byte vectors: every pointer named must be 16-byte aligned (NULL passes)
+#define REQUIRE_ALIGNED16(what, ...)                                            \
+  do {                                                                          \
+    const void* ptrs_[] = {__VA_ARGS__};                                        \
+    for (const void* p_ : ptrs_)                                                \
+      if ((uintptr_t)p_ & 15) return fail(-1, what ": pointers must be 16-byte aligned"); \
+  } while (0)
 #define REQUIRE_ROW_WIDTH(D) \
   do {                       \
     if (const char* m_ = row_width_check(D)) return fail(-1, m_); \
@@ -691,6 +698,198 @@ int aaclip_seg_loss_backward(const float* preds, long img_stride, long chan_stri
           "seg_loss_backward: both channels are written, they cannot share storage (chan_stride 0)");
   launch_seg_loss_grad(preds, img_stride, chan_stride, mask, terms, coef, d_loss, d_preds, B, P, (hipStream_t)stream);
   return finish("seg_loss_backward");
+}
+
+// ---- Training: backward of the adapted text tower (text_backward.hip).  fp32, fixed-order reductions.
+
+// The block-backward workspace, byte offsets from its start.  The recomputed internals of one block (h: a LayerNorm
+// output, qkv, ctx, x1: the stream after the attention half, f: the c_fc pre-activation, g: GELU(f) and later its
+// gradient, x2: the adapter's input, z: the adapter pre-activation and later its gradient), the gradients in flight (dx,
+// dqkv, tmp) and the chunk partials of the weight-gradient GEMM (sized for the largest split, whatever `rows` is, so
+// that the total grows with rows).
+struct TbLayout { size_t h, qkv, ctx, x1, f, g, x2, z, dx, dqkv, tmp, wg, total; };
+static TbLayout tb_layout(long rows, int D, int F) {
+  const size_t rd = up256((size_t)rows * D * 4), r3 = up256((size_t)rows * 3 * D * 4), rf = up256((size_t)rows * F * 4);
+  TbLayout l;
+  l.h = 0;
+  l.qkv = l.h + rd;
+  l.ctx = l.qkv + r3;
+  l.x1 = l.ctx + rd;
+  l.f = l.x1 + rd;
+  l.g = l.f + rf;
+  l.x2 = l.g + rf;
+  l.z = l.x2 + rd;
+  l.dx = l.z + rd;
+  l.dqkv = l.dx + rd;
+  l.tmp = l.dqkv + r3;
+  l.wg = l.tmp + rd;
+  l.total = l.wg + up256((size_t)WGRAD_MAX_CHUNKS * 1024 * D * 4) + 4096;
+  return l;
+}
+
+size_t aaclip_text_backward_workspace_bytes(long rows, int D, int F) {
+  if (rows <= 0 || D <= 0 || F < 0) return 0;
+  return tb_layout(rows, D, F).total;
+}
+
+int aaclip_gemm_wgrad(const float* dz, long ldz, const float* u, long ldu, float* dw, long rows, int O, int I, void* ws,
+                      size_t ws_bytes, void* stream) {
+  REQUIRE(dz && u && dw, "gemm_wgrad: null pointer");
+  REQUIRE(rows > 0 && rows < (1L << 31), "gemm_wgrad: rows must be positive (and below 2^31)");
+  REQUIRE(O > 0 && I > 0 && O % 128 == 0 && I % 128 == 0, "gemm_wgrad: both weight dimensions must be multiples of 128");
+  REQUIRE(O <= 1024, "gemm_wgrad: at most 1024 output features (O <= 1024)");
+  REQUIRE(ldz >= O && ldu >= I && ldz % 4 == 0 && ldu % 4 == 0, "gemm_wgrad: row strides must be multiples of 4 and cover the rows");
+  REQUIRE((((uintptr_t)dz | (uintptr_t)u | (uintptr_t)dw) & 15) == 0, "gemm_wgrad: pointers must be 16-byte aligned");
+  const size_t need = wgrad_ws_bytes(rows, O, I);
+  REQUIRE(need == 0 || (ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0), "gemm_wgrad: workspace too small");
+  launch_wgrad(dz, ldz, u, ldu, dw, rows, O, I, ws, (hipStream_t)stream);
+  return finish("gemm_wgrad");
+}
+
+int aaclip_attention_backward(const float* qkv, const float* d_ctx, float* d_qkv, int B, int L, int H, int causal,
+                              float dq_scale, void* stream) {
+  REQUIRE(qkv && d_ctx && d_qkv, "attention_backward: null pointer");
+  if (const char* m = attention_backward_check(B, L, H)) return fail(-1, m);
+  REQUIRE_ALIGNED16("attention_backward", qkv, d_ctx, d_qkv);
+  launch_attention_backward(qkv, d_ctx, d_qkv, B, L, H, causal != 0, dq_scale, (hipStream_t)stream);
+  return finish("attention_backward");
+}
+
+int aaclip_layernorm_backward(const float* x, const float* w, const float* d_y, const float* d_resid, float* d_x,
+                              long rows, int D, float eps, void* stream) {
+  REQUIRE(x && w && d_y && d_x, "layernorm_backward: null pointer");
+  REQUIRE(rows > 0, "layernorm_backward: rows must be positive");
+  REQUIRE_ROW_WIDTH(D);
+  REQUIRE_ALIGNED16("layernorm_backward", x, w, d_y, d_resid, d_x);
+  launch_layernorm_backward(x, w, d_y, d_resid, d_x, nullptr, rows, D, eps, (hipStream_t)stream);
+  return finish("layernorm_backward");
+}
+
+int aaclip_adapter_mix_backward(const float* u, const float* z, const float* d_y, float* d_z, float* d_u, long rows,
+                                int D, float weight, void* stream) {
+  REQUIRE(u && z && d_y && d_z && d_u, "adapter_mix_backward: null pointer");
+  REQUIRE(rows > 0, "adapter_mix_backward: rows must be positive");
+  REQUIRE_ROW_WIDTH(D);
+  REQUIRE_ALIGNED16("adapter_mix_backward", u, z, d_y, d_z, d_u);
+  launch_adapter_mix_backward(u, z, d_y, d_z, d_u, rows, D, weight, (hipStream_t)stream);
+  return finish("adapter_mix_backward");
+}
+
+int aaclip_block_backward(const float* x_in, const aaclip_block_weights* w, const aaclip_block_weights* wt, float mix,
+                          int B, int L, int D, int H, int F, int attn_mode, const float* d_out, float* d_in,
+                          float* d_adapter_w, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(x_in && w && wt && d_out && ws, "block_backward: null pointer");
+  REQUIRE(w->struct_bytes == sizeof(aaclip_block_weights) && wt->struct_bytes == sizeof(aaclip_block_weights),
+          "block_backward: aaclip_block_weights.struct_bytes does not match this library");
+  REQUIRE(attn_mode == AACLIP_ATTN_FULL || attn_mode == AACLIP_ATTN_CAUSAL,
+          "block_backward: attn_mode must be AACLIP_ATTN_FULL or AACLIP_ATTN_CAUSAL");
+  REQUIRE(B > 0 && L > 0, "block_backward: empty batch");
+  REQUIRE(D == 64 * H, "block_backward: D must equal 64*H (head dim 64)");
+  REQUIRE_ROW_WIDTH(D);
+  REQUIRE(F > 0 && F % 128 == 0, "block_backward: F must be a multiple of 128");
+  if (const char* m = attention_backward_check(B, L, H)) return fail(-1, m);
+  const long rows = (long)B * L;
+  REQUIRE(rows < (1L << 31) / 4, "block_backward: too many rows");
+  REQUIRE(w->ln1_w && w->ln1_b && w->qkv_w && w->qkv_b && w->out_w && w->out_b && w->ln2_w && w->ln2_b && w->fc_w &&
+              w->fc_b && w->proj_w && w->proj_b,
+          "block_backward: null weight pointer");
+  const bool adapter = w->adapter_w != nullptr;
+  REQUIRE(adapter || d_in, "block_backward: nothing to compute (no adapter and d_in is NULL)");
+  REQUIRE(!adapter || d_adapter_w, "block_backward: d_adapter_w is required for a block with an adapter");
+  REQUIRE(!d_in || (wt->qkv_w && wt->out_w && wt->fc_w && wt->proj_w && (!adapter || wt->adapter_w)),
+          "block_backward: null transposed weight pointer");
+  const TbLayout l = tb_layout(rows, D, F);
+  REQUIRE(ws_bytes >= l.total, "block_backward: workspace too small");
+  REQUIRE_ALIGNED16("block_backward", x_in, d_out, d_in, d_adapter_w, ws, w->ln1_w, w->ln2_w, w->adapter_w);
+  hipStream_t s = (hipStream_t)stream;
+  char* base = (char*)ws;
+  float *h = (float*)(base + l.h), *qkv = (float*)(base + l.qkv), *ctx = (float*)(base + l.ctx);
+  float *x1 = (float*)(base + l.x1), *f = (float*)(base + l.f), *g = (float*)(base + l.g), *x2 = (float*)(base + l.x2);
+  float *z = (float*)(base + l.z), *dx = (float*)(base + l.dx), *dqkv = (float*)(base + l.dqkv);
+  float* tmp = (float*)(base + l.tmp);
+  const int M = (int)rows;
+  const int causal = attn_mode == AACLIP_ATTN_CAUSAL;
+  const float qscale = 0.125f;
+  // ---- the block's internals again, in fp32, from its input (aaclip_block's arithmetic)
+  launch_layernorm(AACLIP_F32, x_in, w->ln1_w, w->ln1_b, h, rows, D, 1e-5f, s);
+  GemmParams p = gemm_params(h, D, w->qkv_w, w->qkv_b, qkv, 3 * D, M, 3 * D, D);
+  p.scale_cols = D; p.scale = qscale;
+  launch_gemm(AACLIP_F32, EPI_BIAS, p, s);
+  launch_attention(AACLIP_F32, qkv, ctx, B, L, H, causal, 0, s);
+  p = gemm_params(ctx, D, w->out_w, w->out_b, x1, D, M, D, D);
+  p.resid = x_in;
+  launch_gemm(AACLIP_F32, EPI_BIAS_RESID, p, s);
+  launch_layernorm(AACLIP_F32, x1, w->ln2_w, w->ln2_b, h, rows, D, 1e-5f, s);
+  p = gemm_params(h, D, w->fc_w, w->fc_b, f, F, M, F, D);
+  launch_gemm(AACLIP_F32, EPI_BIAS, p, s);
+  const float* dy = d_out;   // gradient of the stream after the MLP half
+  if (adapter) {
+    launch_gelu_forward(f, g, rows * F, s);
+    p = gemm_params(g, F, w->proj_w, w->proj_b, x2, D, M, D, F);
+    p.resid = x1;
+    launch_gemm(AACLIP_F32, EPI_BIAS_RESID, p, s);
+    p = gemm_params(x2, D, w->adapter_w, nullptr, z, D, M, D, D);
+    launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+    launch_adapter_mix_backward(x2, z, d_out, z, dx, rows, D, mix, s);   // z <- dz, dx <- the direct d x2
+    launch_wgrad(z, D, x2, D, d_adapter_w, rows, D, D, base + l.wg, s);
+    if (!d_in) return finish("block_backward");
+    p = gemm_params(z, D, wt->adapter_w, nullptr, tmp, D, M, D, D);
+    launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+    launch_add_rows(dx, tmp, dx, rows * D, s);
+    dy = dx;
+  }
+  // ---- x2 = x1 + c_proj(gelu(f)),  f = c_fc(ln_2 x1)
+  p = gemm_params(dy, D, wt->proj_w, nullptr, g, F, M, F, D);
+  launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+  launch_gelu_backward(f, g, g, rows * F, s);
+  p = gemm_params(g, F, wt->fc_w, nullptr, tmp, D, M, D, F);
+  launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+  launch_layernorm_backward(x1, w->ln2_w, tmp, dy, dx, nullptr, rows, D, 1e-5f, s);   // dx <- d x1
+  // ---- x1 = x_in + out_proj(attention(qkv)),  qkv = in_proj(ln_1 x_in), q scaled
+  p = gemm_params(dx, D, wt->out_w, nullptr, tmp, D, M, D, D);
+  launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+  launch_attention_backward(qkv, tmp, dqkv, B, L, H, causal, qscale, s);
+  p = gemm_params(dqkv, 3 * D, wt->qkv_w, nullptr, tmp, D, M, D, 3 * D);
+  launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+  launch_layernorm_backward(x_in, w->ln1_w, tmp, dx, d_in, nullptr, rows, D, 1e-5f, s);
+  return finish("block_backward");
+}
+
+int aaclip_row_head_backward(const float* x, const int32_t* tokens, const float* ln_w, const float* ln_b,
+                             const float* proj_w, const float* proj_wt, int act, const float* d_out, float* d_x,
+                             float* d_proj_w, int n, int T, int D, int E, int mode, void* ws, size_t ws_bytes,
+                             void* stream) {
+  REQUIRE(x && ln_w && ln_b && proj_w && d_out && d_proj_w && ws, "row_head_backward: null pointer");
+  REQUIRE(mode == 0 || mode == 1, "row_head_backward: mode must be 0 (EOT row) or 1 (row 0)");
+  REQUIRE(mode == 1 || tokens, "row_head_backward: tokens required for EOT mode");
+  REQUIRE(!d_x || proj_wt, "row_head_backward: the transposed projection is required for d_x");
+  REQUIRE(n > 0 && T > 0 && (long)n * T < (1L << 31) / 4, "row_head_backward: bad shape");
+  REQUIRE(act >= AACLIP_ACT_NONE && act <= AACLIP_ACT_RELU, "row_head_backward: bad activation");
+  REQUIRE_ROW_WIDTH(D);
+  REQUIRE(E > 0 && E % 128 == 0 && E <= 1024, "row_head_backward: E must be a multiple of 128, <= 1024");
+  const size_t o_idx = 0, o_xg = o_idx + up256((size_t)n * 4), o_ln = o_xg + up256((size_t)n * D * 4);
+  const size_t o_z = o_ln + up256((size_t)n * D * 4), o_dp = o_z + up256((size_t)n * E * 4);
+  const size_t o_wg = o_dp + up256((size_t)n * D * 4);
+  REQUIRE(ws_bytes >= o_wg + wgrad_ws_bytes(n, E, D), "row_head_backward: workspace too small");
+  REQUIRE_ALIGNED16("row_head_backward", x, ln_w, d_out, d_x, d_proj_w, ws);
+  hipStream_t s = (hipStream_t)stream;
+  char* base = (char*)ws;
+  int* idx = (int*)(base + o_idx);
+  float *xg = (float*)(base + o_xg), *ln = (float*)(base + o_ln), *z = (float*)(base + o_z), *dp = (float*)(base + o_dp);
+  launch_pick_rows(x, xg, idx, tokens, n, T, D, mode, s);
+  launch_layernorm(AACLIP_F32, xg, ln_w, ln_b, ln, n, D, 1e-5f, s);
+  GemmParams p = gemm_params(ln, D, proj_w, nullptr, z, E, n, E, D);
+  launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+  launch_act_backward(z, d_out, z, (long)n * E, act, s);   // z <- dz
+  launch_wgrad(z, E, ln, D, d_proj_w, n, E, D, base + o_wg, s);
+  if (d_x) {
+    // a true scatter: the n picked rows are distinct, every other row of the stream gradient is zero
+    if (hipMemsetAsync(d_x, 0, (size_t)n * T * D * 4, s) != hipSuccess) return fail(-2, "row_head_backward: memset failed");
+    p = gemm_params(z, E, proj_wt, nullptr, dp, D, n, D, E);
+    launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+    launch_layernorm_backward(xg, ln_w, dp, nullptr, d_x, idx, n, D, 1e-5f, s);
+  }
+  return finish("row_head_backward");
 }
 
 int aaclip_resample_ksize(int in_size, int out_size) {

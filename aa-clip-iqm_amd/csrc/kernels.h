@@ -148,6 +148,29 @@ void launch_similarity_map_train_bwd(const float* seg, const float* anchors, lon
                                      const float* d_preds, float* d_anchors, float* d_seg, int B, int g, int E, int S,
                                      void* ws, hipStream_t s);
 
+// ---- text_backward.hip : backward of the adapted text tower (fp32, fixed-order reductions)
+constexpr int ATTN_BWD_MAX_L = 128;
+constexpr int WGRAD_MAX_CHUNKS = 16;
+// dw[O, I] = sum_r dz[r, o] u[r, i]; O, I multiples of 128, ldz / ldu multiples of 4; ws >= wgrad_ws_bytes
+size_t wgrad_ws_bytes(long rows, int O, int I);
+void launch_wgrad(const float* dz, long ldz, const float* u, long ldu, float* dw, long rows, int O, int I, void* ws,
+                  hipStream_t s);
+const char* attention_backward_check(int B, int L, int H);
+// qkv [B*L, 3*H*64] (q pre-scaled), dctx [B*L, H*64] -> dqkv [B*L, 3*H*64]; the dq columns are multiplied by dq_scale
+void launch_attention_backward(const float* qkv, const float* dctx, float* dqkv, int B, int L, int H, int causal,
+                               float dq_scale, hipStream_t s);
+// dx[out_rows ? out_rows[r] : r] = LayerNorm input gradient of row r (+ add, read at the output row)
+void launch_layernorm_backward(const float* x, const float* w, const float* dy, const float* add, float* dx,
+                               const int* out_rows, long rows, int D, float eps, hipStream_t s);
+void launch_adapter_mix_backward(const float* u, const float* z, const float* dy, float* dz, float* du, long rows, int D,
+                                 float weight, hipStream_t s);
+void launch_gelu_forward(const float* f, float* out, long n, hipStream_t s);
+void launch_gelu_backward(const float* f, const float* dg, float* df, long n, hipStream_t s);
+void launch_act_backward(const float* z, const float* dy, float* dz, long n, int act, hipStream_t s);
+void launch_add_rows(const float* a, const float* b, float* out, long n, hipStream_t s);
+void launch_pick_rows(const float* x, float* dst, int* idx, const int32_t* tokens, int n, int T, int D, int mode,
+                      hipStream_t s);
+
 // ---- preprocess.hip : 8-bit bicubic resize + ToTensor + Normalize (Pillow-exact)
 int resample_ksize(int in_size, int out_size);
 void resample_table(int in_size, int out_size, int32_t* bounds, int32_t* coefs);   // host buffers

@@ -16,7 +16,7 @@ from typing import List
 import torch
 from torch import nn
 
-from aaclip_hip import engine
+from aaclip_hip import autograd, engine
 
 from aaclip_hip._lib import ACT_LEAKY, ACT_RELU, EPI_ACT_F32, EPI_BIAS
 
@@ -209,6 +209,10 @@ class AdaptedCLIP(nn.Module):
     def encode_text(self, text, adapt_text=True):
         if not adapt_text:
             return self.clipmodel.encode_text(text)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.text_adapter.parameters()):
+            # training (reference train.py:62-68): same kernels and bits, plus a graph whose backward fills the
+            # text_adapter gradients through the HIP backward kernels
+            return autograd.encode_text(self, text)
         code = self._code()
         c = self.clipmodel
         x, tk = engine.text_embed(text, c.token_embedding.weight, c.positional_embedding)

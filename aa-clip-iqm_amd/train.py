@@ -1,0 +1,73 @@
+"""Stage 1 of training: fit the text adapters against frozen V-V ("surgery") patch features of CLIP, on the HIP path end
+to end -- encode_text forward and backward (aaclip_hip.autograd.TextTower), the train-mode similarity map and the
+segmentation loss with their backward kernels.  Behaviour follows reference train.py:57-113.
+
+Not here: the training-time datasets, main() and stage 2 (the image adapters).
+`train_text_adapter` is fed by any iterable of {"image", "mask", "class_name"} batches.
+"""
+from __future__ import annotations
+
+import logging
+import os
+
+import torch
+from torch import nn
+
+import forward_utils as FU
+
+CHECKPOINT_NAME = "text_adapter.pth"
+
+
+def _unit(t: torch.Tensor) -> torch.Tensor:
+    return t / t.norm(dim=-1, keepdim=True)
+
+
+@torch.no_grad()
+def stage1_patch_features(adapted_model, clip_surgery, image, levels=(6, 12, 18, 24)):
+    """The frozen image side, one [B, P, E] tensor per tap level: the surgery model's tapped patch rows through ln_post
+    and visual.proj as unit vectors, each shifted by the unit CLS embedding of the unmodified CLIP (not renormalised)."""
+    visual = clip_surgery.visual
+    taps = clip_surgery.encode_image(image, list(levels))[1]
+    cls = _unit(adapted_model.clipmodel.encode_image(image, [])[0]).unsqueeze(1)
+    return [_unit(visual.ln_post(tap[:, 1:, :]) @ visual.proj) + cls for tap in taps]
+
+
+def batch_anchors(adapted_model, dataset_name, class_names, device):
+    """[B, E, 2] anchor pairs of a batch; every distinct class is encoded once, with a graph down to the adapters."""
+    per_class = {c: FU.get_adapted_single_class_text_embedding(adapted_model, dataset_name, c, device)
+                 for c in set(class_names)}
+    return torch.stack([per_class[c] for c in class_names])
+
+
+def level_loss(features, anchors, mask, img_size, text_norm_weight):
+    """Seg loss of one tap level plus text_norm_weight x (mean over the batch of <normal, abnormal>) squared."""
+    seg = FU.calculate_seg_loss(FU.calculate_similarity_map(features, anchors, img_size), mask)
+    overlap = (anchors[..., 0] * anchors[..., 1]).sum(dim=1).mean()
+    return seg + text_norm_weight * overlap ** 2
+
+
+def train_text_adapter(adapted_model: nn.Module, clip_surgery: nn.Module, text_norm_weight: float, train_loader,
+                       optimizer: torch.optim.Optimizer, device: str, start_epoch: int, save_path: str, text_epoch: int,
+                       dataset_name: str, img_size: int, logger: logging.Logger, levels=(6, 12, 18, 24)):
+    """Same arguments as the reference's function (plus `levels`, which it hard-codes) and the same checkpoint after
+    every epoch: {"epoch", "text_adapter", "text_optimizer"} in <save_path>/text_adapter.pth."""
+    for epoch in range(start_epoch, text_epoch):
+        logger.info(f"training text epoch {epoch}:")
+        step_losses = []
+        for batch in train_loader:
+            mask = batch["mask"].to(device)
+            anchors = batch_anchors(adapted_model, dataset_name, batch["class_name"], device)
+            features = stage1_patch_features(adapted_model, clip_surgery, batch["image"].to(device), levels)
+            # The reference overwrites its loss variable at every tap level, so what it back-propagates is the LAST
+            # level's loss alone; the earlier levels are evaluated and discarded.  Kept as executed, quirk included.
+            for level_features in features:
+                loss = level_loss(level_features, anchors, mask, img_size, text_norm_weight)
+            optimizer.zero_grad()
+            loss.backward()
+            optimizer.step()
+            step_losses.append(loss.item())
+        logger.info(f"loss: {sum(step_losses) / len(step_losses)}")
+        os.makedirs(save_path, exist_ok=True)
+        torch.save({"epoch": epoch + 1, "text_adapter": adapted_model.text_adapter.state_dict(),
+                    "text_optimizer": optimizer.state_dict()}, os.path.join(save_path, CHECKPOINT_NAME))
+    return adapted_model

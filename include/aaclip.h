@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define AACLIP_ABI_VERSION 7   /* 7: the entry points of the removed measurement build are gone */
+#define AACLIP_ABI_VERSION 8   /* 8: backward of the adapted text tower (aaclip_block_backward and its building blocks) */
 
 enum { AACLIP_F32 = 0, AACLIP_F16 = 1, AACLIP_BF16 = 2, AACLIP_F16X2 = 3 };
 enum { AACLIP_ACT_NONE = 0, AACLIP_ACT_LEAKY = 1, AACLIP_ACT_RELU = 2 };
@@ -228,6 +228,62 @@ int aaclip_seg_loss(const float* preds, long img_stride, long chan_stride, const
  * A channel that no computed term reads is not written, so chan_stride 0 is allowed for the single dice terms. */
 int aaclip_seg_loss_backward(const float* preds, long img_stride, long chan_stride, const float* mask, int terms,
                              const float* coef, const float* d_loss, float* d_preds, int B, long P, void* stream);
+
+/* ---- Training: backward of the adapted text tower (reference model/adapter.py:273-304 under train.py:62-68,97-100).
+ * Everything below is fp32 whatever dtype the forward ran in (the reference trains in fp32), uses no float atomics and
+ * sums in a fixed order: repeated calls give bit-identical results.  Only the text_adapter weights receive gradients;
+ * CLIP's own parameters are frozen, so no bias, LayerNorm-parameter or CLIP weight gradient is formed.
+ * Workspace: every entry point below that takes one accepts aaclip_text_backward_workspace_bytes(rows, D, F) bytes,
+ * rows = the token rows it is given and D = the width of those rows (aaclip_gemm_wgrad: D = I, its input features, and
+ * F = 0; aaclip_row_head_backward: rows = n*T, F = 0).  Monotonic in rows.
+ * Alignment: fp32 rows move as 16-byte vectors, so every fp32 pointer passed below (and the workspace) must be 16-byte
+ * aligned; a misaligned pointer is rejected (rc < 0). */
+size_t aaclip_text_backward_workspace_bytes(long rows, int D, int F);
+
+/* Weight gradient of y = u W^T over an arbitrary number of rows: dw[o, i] = sum_r dz[r, o] u[r, i] on the exact-fp32
+ * MFMA.  dz [rows, ldz >= O], u [rows, ldu >= I], dw [O, I] (overwritten); O and I multiples of 128, O <= 1024, strides multiples
+ * of 4, pointers 16-byte aligned.  The rows are split into at most 16 chunks whose partial products a second pass adds
+ * in order. */
+int aaclip_gemm_wgrad(const float* dz, long ldz, const float* u, long ldu, float* dw, long rows, int O, int I, void* ws,
+                      size_t ws_bytes, void* stream);
+
+/* Backward of aaclip_attention(AACLIP_F32): from the packed q|k|v rows [B*L, 3*H*64] (q pre-scaled, as the forward
+ * takes it) and d_ctx [B*L, H*64] to d_qkv [B*L, 3*H*64]; the dq columns are multiplied by dq_scale (pass the q scale to
+ * get the gradient of the unscaled projection, 1 otherwise).  Probabilities are recomputed on chip.  Head dim 64,
+ * causal != 0 = the text tower's mask, every L <= 128; anything else is rejected before a launch. */
+int aaclip_attention_backward(const float* qkv, const float* d_ctx, float* d_qkv, int B, int L, int H, int causal,
+                              float dq_scale, void* stream);
+
+/* LayerNorm input gradient (weight and bias are frozen): d_x = d_resid + dLN(x; w)^T d_y, d_resid may be NULL; d_x may
+ * alias d_y or d_resid. */
+int aaclip_layernorm_backward(const float* x, const float* w, const float* d_y, const float* d_resid, float* d_x,
+                              long rows, int D, float eps, void* stream);
+
+/* Backward of the adapter mix y = weight * a |u| / |a| + (1 - weight) * u with a = LeakyReLU(z), z = u Wa^T
+ * (aaclip_adapter_mix; both norms are functions of the inputs): d_z for the weight gradient (and for d_z Wa, the part of
+ * d u that runs through the product) and the direct d_u.  d_z may alias z, d_u may alias d_y. */
+int aaclip_adapter_mix_backward(const float* u, const float* z, const float* d_y, float* d_z, float* d_u, long rows,
+                                int D, float weight, void* stream);
+
+/* Backward of one aaclip_block (AACLIP_ATTN_FULL or AACLIP_ATTN_CAUSAL, L <= 128) from its INPUT x_in [B*L, D]: the
+ * block's internals are recomputed in fp32, nothing else needs to be kept from the forward.  w: the block's weights as
+ * AACLIP_F32; wt: a second struct whose matrix fields (qkv_w, out_w, fc_w, proj_w, adapter_w) hold the TRANSPOSED fp32
+ * weights [in_features, out_features] -- the input-gradient products are aaclip_gemm(AACLIP_F32) calls on them; its
+ * other fields are ignored, and it is not read when d_in is NULL.  d_out [B*L, D]: gradient of the block's output.
+ * d_in (out): gradient of x_in; may alias d_out; NULL = not wanted (then only the adapter's weight gradient is formed).
+ * d_adapter_w (out) [D, D] fp32, overwritten; required when w->adapter_w is set, ignored otherwise. */
+int aaclip_block_backward(const float* x_in, const aaclip_block_weights* w, const aaclip_block_weights* wt, float mix,
+                          int B, int L, int D, int H, int F, int attn_mode, const float* d_out, float* d_in,
+                          float* d_adapter_w, void* ws, size_t ws_bytes, void* stream);
+
+/* Backward of aaclip_row_head(AACLIP_F32): x, tokens, ln_w, ln_b, act, mode as there; proj_w [E, D] and its transpose
+ * proj_wt [D, E] in fp32 (proj_wt may be NULL when d_x is); d_out [n, E].  d_proj_w (out) [E, D], overwritten.  d_x
+ * (out, may be NULL) [n*T, D]: zero except the n picked rows, which receive the LayerNorm input gradient -- a scatter of
+ * n distinct rows.  E a multiple of 128, <= 1024. */
+int aaclip_row_head_backward(const float* x, const int32_t* tokens, const float* ln_w, const float* ln_b,
+                             const float* proj_w, const float* proj_wt, int act, const float* d_out, float* d_x,
+                             float* d_proj_w, int n, int T, int D, int E, int mode, void* ws, size_t ws_bytes,
+                             void* stream);
 
 /* Image pre-processing in front of the patch embed: Pillow's 8-bit BICUBIC resize to S x S,
  * ToTensor (v/255) and Normalize((v - mean)/std), bit-exact.  Replaces the reference's
