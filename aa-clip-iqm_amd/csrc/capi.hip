@@ -336,11 +336,11 @@ int aaclip_patch_embed(const float* img, const void* conv_w, const float* cls, c
   REQUIRE(Kpad <= 640, "patch_embed: 3*ps*ps must be <= 640");
   REQUIRE(ws_bytes >= (size_t)B * P * Kpad * esize(dtype), "patch_embed: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  launch_im2col(dtype, img, ws, B, 3, H, W, ps, Kpad, s);
   GemmParams p = gemm_params(ws, split_w(dtype) * Kpad, conv_w, nullptr, x, D, B * P, D, Kpad);
   p.pos = pos; p.P = P; p.L = L;
-  const char* m = gemm_check(dtype, EPI_PATCH, p);
+  const char* m = gemm_check(dtype, EPI_PATCH, p);   // before the first launch: a rejected call enqueues nothing
   if (m) return fail(-1, m);
+  launch_im2col(dtype, img, ws, B, 3, H, W, ps, Kpad, s);
   launch_gemm(dtype, EPI_PATCH, p, s);
   launch_cls_rows(x, cls, pos, B, L, D, s);
   launch_layernorm(AACLIP_F32, x, ln_pre_w, ln_pre_b, x, (long)B * L, D, 1e-5f, s);
@@ -955,12 +955,12 @@ int aaclip_row_head(const float* x, const int32_t* tokens, const float* ln_w, co
   hipStream_t s = (hipStream_t)stream;
   char* ln_out = (char*)ws;
   char* picked = ln_out + up256((size_t)rows * D * es);
-  launch_layernorm(dtype, x, ln_w, ln_b, ln_out, rows, D, 1e-5f, s);
-  launch_gather_rows(dtype, ln_out, picked, tokens, n, T, D, mode, s);
   GemmParams p = gemm_params(picked, split_w(dtype) * D, proj_w, nullptr, out, E, n, E, D);
   p.act = act;
   const char* gm = gemm_check(dtype, EPI_ACT_F32, p);
   if (gm) return fail(-1, gm);
+  launch_layernorm(dtype, x, ln_w, ln_b, ln_out, rows, D, 1e-5f, s);
+  launch_gather_rows(dtype, ln_out, picked, tokens, n, T, D, mode, s);
   launch_gemm(dtype, EPI_ACT_F32, p, s);
   return finish("row_head");
 }

@@ -115,7 +115,9 @@ enum { AACLIP_EXACT16_QKV = 1, AACLIP_EXACT16_OUT = 2, AACLIP_EXACT16_FC = 4, AA
  * Replaces reference model/adapter.py:139-156 (== model/transformer.py:507-526).
  * img [B,3,H,W] fp32 NCHW; conv_w = conv1.weight reshaped [D, 3*ps*ps] and zero
  * padded to [D, Kpad], Kpad = round_up(3*ps*ps, 64), dtype; pos [L, D];
- * x (out) [B*L, D] fp32 with L = (H/ps)*(W/ps)+1. */
+ * x (out) [B*L, D] fp32 with L = (H/ps)*(W/ps)+1 (pixels behind the last whole patch are not read).  The unfolded
+ * patch rows in the workspace are zero padded to Kpad by the library itself.  Kpad <= 640; AACLIP_F16X2 needs Kpad to
+ * be a multiple of 128.  A rejected call (rc < 0) launches nothing. */
 int aaclip_patch_embed(const float* img, const void* conv_w, const float* cls, const float* pos,
                        const float* ln_pre_w, const float* ln_pre_b, float* x, int B, int H, int W, int ps, int D,
                        int dtype, void* ws, size_t ws_bytes, void* stream);
@@ -301,7 +303,8 @@ int aaclip_preprocess(const uint8_t* src, int B, int Hs, int Ws, int S, const in
                       const int32_t* vbounds, const int32_t* vcoefs, const float* lut, float* out, void* stream);
 
 /* Text embedding: x[i*T+t] = token_embedding[tokens[i,t]] + positional_embedding[t].
- * Replaces reference model/adapter.py:277-281 (model/model.py:192-194). */
+ * Replaces reference model/adapter.py:277-281 (model/model.py:192-194).  Token ids outside [0, vocab) are CLAMPED
+ * to 0 / vocab - 1 (the reference's nn.Embedding raises instead); D a multiple of 4. */
 int aaclip_text_embed(const int32_t* tokens, const float* table, const float* pos, float* x, int n, int T, int D,
                       int vocab, void* stream);
 
