@@ -12,7 +12,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AACLIP_LIB") or os.path.join(_HERE, "libaaclip_hip.so")   # AACLIP_LIB: experiment builds
-ABI_VERSION = 8   # include/aaclip.h AACLIP_ABI_VERSION this binding was written against
+ABI_VERSION = 9   # include/aaclip.h AACLIP_ABI_VERSION this binding was written against
 
 F32, F16, BF16, F16X2 = 0, 1, 2, 3   # F16X2: split fp16 (hi + lo pairs), include/aaclip.h
 EXACT16_QKV, EXACT16_OUT, EXACT16_FC, EXACT16_PROJ, EXACT16_ADAPTER = 1, 2, 4, 8, 16
@@ -59,10 +59,15 @@ SIGNATURES = {
     "aaclip_text_backward_workspace_bytes": (_sz, [_l, _i, _i]),
     "aaclip_gemm_wgrad": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _vp, _sz, _vp]),
     "aaclip_attention_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "aaclip_attention_backward_long_workspace_bytes": (_sz, [_i, _i, _i]),
+    "aaclip_attention_backward_long": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "aaclip_layernorm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _f, _vp]),
     "aaclip_adapter_mix_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _f, _vp]),
     "aaclip_block_backward": (_i, [_vp, C.POINTER(BlockWeights), C.POINTER(BlockWeights), _f] + [_i] * 6
                               + [_vp, _vp, _vp, _vp, _sz, _vp]),
+    "aaclip_block_backward_long_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "aaclip_block_backward_long": (_i, [_vp, C.POINTER(BlockWeights), C.POINTER(BlockWeights), _f] + [_i] * 6
+                                   + [_vp, _vp, _vp, _vp, _sz, _vp]),
     "aaclip_row_head_backward": (_i, [_vp] * 6 + [_i, _vp, _vp, _vp] + [_i] * 5 + [_vp, _sz, _vp]),
     "aaclip_text_embed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "aaclip_resample_ksize": (_i, [_i, _i]),

@@ -1,6 +1,7 @@
 """torch.autograd.Functions over the training entry points of libaaclip_hip.so (include/aaclip.h, "Training"): the
 train-mode similarity map (reference forward_utils.py:196-216, test=False), the segmentation loss (:21-108,223-227) and
-the adapted text tower (reference model/adapter.py:273-304), whose backward fills the text_adapter gradients.
+the adapted text tower (reference model/adapter.py:273-304), whose backward fills the text_adapter gradients, and the
+visual tower up to its tap streams (model/adapter.py:137-170), whose backward fills the layer-adapter gradients.
 Forward and backward are HIP kernels; these classes only carry tensors between them.  The saved tensors live in
 ctx.save_for_backward, so they are freed with the graph (after backward(), or when the output is dropped)."""
 from __future__ import annotations
@@ -120,6 +121,84 @@ class TextTower(torch.autograd.Function):
             if aw is not None and ctx.needs_input_grad[2 + i]:
                 grads[i] = d_aw.to(aw.dtype)
         return (None, None, *grads)
+
+
+class VisualTaps(torch.autograd.Function):
+    """The adapted visual tower up to its tap streams, with a backward for image_adapter["layer_adapters"] (CLIP's own
+    parameters are frozen: they are not inputs of this Function and receive no gradient).
+
+    forward(model, image, *layer-adapter weights) -> one stream [B, L, D] (CLS row included) per tapped level, in
+    ascending order: engine.patch_embed, then the blocks up to the last tapped level as ONE aaclip_blocks_taps call
+    that leaves the stream after every block in its own buffer -- the kernels of the no-grad path, so the taps are
+    bit-identical to what AdaptedCLIP.forward feeds its heads.  Saved (ctx.save_for_backward: freed with the graph):
+    the inputs of the blocks the backward revisits, i.e. the patch-embed output and the per-block streams from the
+    first trainable adapter's block on, and nothing else.  The backward runs in fp32 whatever precision the forward
+    ran in: from the last tapped level down it adds d_tap into the running stream gradient at every tapped level and
+    calls engine.block_backward(in_place=True), which recomputes the block from its input; it stops at the first block
+    whose adapter requires grad (the patch embedding is frozen).  Blocks above the last tapped level are never run.
+    When no layer adapter requires grad nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, model, image, *weights):
+        code = model._code()
+        v = model.image_encoder
+        until = model.image_adapt_until
+        all_blocks = list(v.transformer.resblocks)
+        levels = [lv for lv in range(1, len(all_blocks) + 1) if lv in model.levels]
+        if not levels:
+            raise ValueError("visual_taps: model.levels names no block of the visual tower")
+        blocks = all_blocks[:levels[-1]]
+        if any(getattr(b, "surgery", False) for b in blocks):
+            raise ValueError("visual_taps: the V-V attention blocks (DAPM_replace) have no backward")
+        x0, B, L = engine.patch_embed(image, v, code)
+        aws = [weights[i] if i < until else None for i in range(len(blocks))]
+        outs = [torch.empty_like(x0) for _ in blocks]
+        engine.run_blocks(x0, blocks, B, L, v.transformer.heads, code, causal=False, adapter_weights=aws, mix=model.i_w,
+                          x_outs=outs)
+        need = [i for i in range(min(until, len(blocks))) if ctx.needs_input_grad[2 + i]]
+        ctx.first = need[0] if need else None
+        ctx.model, ctx.B, ctx.L, ctx.levels = model, B, L, levels
+        if ctx.first is not None:
+            ins = [x0] + outs[:-1]          # ins[i]: the input of block i
+            ctx.save_for_backward(*ins[ctx.first:], *weights)
+        return tuple(outs[lv - 1].view(B, L, -1) for lv in levels)
+
+    @staticmethod
+    def backward(ctx, *d_taps):
+        model, B, L, levels = ctx.model, ctx.B, ctx.L, ctx.levels
+        if ctx.first is None:
+            return (None, None, *([None] * (len(ctx.needs_input_grad) - 2)))
+        n_in = levels[-1] - ctx.first
+        ins, weights = ctx.saved_tensors[:n_in], ctx.saved_tensors[n_in:]
+        grads = [None] * len(weights)
+        v = model.image_encoder
+        blocks = list(v.transformer.resblocks)
+        until = model.image_adapt_until
+        d_x = None
+        for i in range(levels[-1] - 1, ctx.first - 1, -1):
+            if (i + 1) in levels:
+                d_tap = d_taps[levels.index(i + 1)]
+                if d_tap is not None:
+                    d_tap = d_tap.reshape(B * L, -1).float()
+                    d_x = d_tap.clone(memory_format=torch.contiguous_format) if d_x is None else d_x.add_(d_tap)
+            if d_x is None:      # no gradient has entered the stream yet: this block's share is zero
+                continue
+            aw = weights[i] if i < until else None
+            _, d_aw = engine.block_backward(ins[i - ctx.first], blocks[i], B, L, v.transformer.heads, d_x, causal=False,
+                                            adapter_weight=aw, mix=model.i_w, need_input_grad=i > ctx.first,
+                                            in_place=True)
+            if aw is not None and ctx.needs_input_grad[2 + i]:
+                grads[i] = d_aw.to(aw.dtype)
+        return (None, None, *grads)
+
+
+def visual_taps(model, image):
+    """The tap streams of AdaptedCLIP's visual tower, [B, L, D] each (CLS row included), one per entry of model.levels
+    in ascending order, carrying a graph to model.image_adapter["layer_adapters"][i].weight: see VisualTaps.
+    AdaptedCLIP.forward itself is unchanged and carries no graph; until the tap and det heads have backward kernels,
+    a training step composes them from torch ops on the streams returned here (drop the CLS row, ln_post, seg_proj,
+    normalise), as the tests do."""
+    return list(VisualTaps.apply(model, image, *[m.weight for m in model.image_adapter["layer_adapters"]]))
 
 
 def encode_text(model, tokens):

@@ -616,14 +616,31 @@ def gemm_wgrad(dz: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     return dw
 
 
+ATTN_BWD_SHORT_MAX_L = 128   # csrc/kernels.h ATTN_BWD_MAX_L: the longest row of aaclip_attention_backward
+
+
+def _long_rows(L: int, long_rows: Optional[bool]) -> bool:
+    """Which backward entry serves rows of length L: None = the short one up to 128 tokens (unchanged bits for the text
+    tower), the tiled *_long one above; True forces the tiled kernels at any L."""
+    return L > ATTN_BWD_SHORT_MAX_L if long_rows is None else bool(long_rows)
+
+
 def attention_backward(qkv: torch.Tensor, d_ctx: torch.Tensor, B: int, L: int, heads: int, causal: bool,
-                       dq_scale: float = 1.0) -> torch.Tensor:
-    """packed fp32 q|k|v rows [B*L, 3*H*64] (q pre-scaled) + d ctx [B*L, H*64] -> d qkv (aaclip_attention_backward)."""
+                       dq_scale: float = 1.0, long_rows: Optional[bool] = None) -> torch.Tensor:
+    """packed fp32 q|k|v rows [B*L, 3*H*64] (q pre-scaled) + d ctx [B*L, H*64] -> d qkv: aaclip_attention_backward for
+    L <= 128, aaclip_attention_backward_long above (long_rows: see _long_rows)."""
     require_gpu(qkv, "attention_backward")
     qkv, d_ctx = _f32c(qkv), _f32c(d_ctx)
     out = torch.empty_like(qkv)
-    _lib.check(_lib.load().aaclip_attention_backward(qkv.data_ptr(), d_ctx.data_ptr(), out.data_ptr(), B, L, heads,
-                                                     int(causal), float(dq_scale), _stream(qkv.device)),
+    lib = _lib.load()
+    if _long_rows(L, long_rows):
+        ws = Workspace.get(qkv.device, lib.aaclip_attention_backward_long_workspace_bytes(int(B), int(L), int(heads)))
+        _lib.check(lib.aaclip_attention_backward_long(qkv.data_ptr(), d_ctx.data_ptr(), out.data_ptr(), B, L, heads,
+                                                      int(causal), float(dq_scale), ws.data_ptr(), ws.numel(),
+                                                      _stream(qkv.device)), "attention_backward_long")
+        return out
+    _lib.check(lib.aaclip_attention_backward(qkv.data_ptr(), d_ctx.data_ptr(), out.data_ptr(), B, L, heads,
+                                             int(causal), float(dq_scale), _stream(qkv.device)),
                "attention_backward")
     return out
 
@@ -669,9 +686,10 @@ def pack_block_transposed(block, adapter_weight: Optional[torch.Tensor]) -> Tupl
 
 def block_backward(x_in: torch.Tensor, block, B: int, L: int, heads: int, d_out: torch.Tensor, causal: bool = False,
                    adapter_weight: Optional[torch.Tensor] = None, mix: float = 0.0, need_input_grad: bool = True,
-                   in_place: bool = False):
-    """Backward of one block from its input x_in [B*L, D] (aaclip_block_backward) -> (d x_in or None, d adapter weight
-    [D, D] or None).  in_place: d x_in overwrites d_out."""
+                   in_place: bool = False, long_rows: Optional[bool] = None):
+    """Backward of one block from its input x_in [B*L, D] -> (d x_in or None, d adapter weight [D, D] or None):
+    aaclip_block_backward for L <= 128, aaclip_block_backward_long above (long_rows: see _long_rows).
+    in_place: d x_in overwrites d_out."""
     require_gpu(x_in, "block_backward")
     lib = _lib.load()
     if x_in.dtype != torch.float32 or not x_in.is_contiguous() or d_out.dtype != torch.float32 or not d_out.is_contiguous():
@@ -682,10 +700,15 @@ def block_backward(x_in: torch.Tensor, block, B: int, L: int, heads: int, d_out:
     wt, refs_t = pack_block_transposed(block, adapter_weight) if need_input_grad else (BlockWeights(), [])
     d_in = (d_out if in_place else torch.empty_like(d_out)) if need_input_grad else None
     d_aw = torch.empty(D, D, dtype=torch.float32, device=x_in.device) if adapter_weight is not None else None
-    ws = text_backward_workspace(x_in.device, B * L, D, F)
-    _lib.check(lib.aaclip_block_backward(x_in.data_ptr(), C.byref(w), C.byref(wt), float(mix), B, L, D, heads, F,
-                                         ATTN_CAUSAL if causal else ATTN_FULL, d_out.data_ptr(), _ptr(d_in), _ptr(d_aw),
-                                         ws.data_ptr(), ws.numel(), _stream(x_in.device)), "block_backward")
+    if _long_rows(L, long_rows):
+        ws = Workspace.get(x_in.device, lib.aaclip_block_backward_long_workspace_bytes(int(B), int(L), int(D), int(F)))
+        entry = lib.aaclip_block_backward_long
+    else:
+        ws = text_backward_workspace(x_in.device, B * L, D, F)
+        entry = lib.aaclip_block_backward
+    _lib.check(entry(x_in.data_ptr(), C.byref(w), C.byref(wt), float(mix), B, L, D, heads, F,
+                     ATTN_CAUSAL if causal else ATTN_FULL, d_out.data_ptr(), _ptr(d_in), _ptr(d_aw),
+                     ws.data_ptr(), ws.numel(), _stream(x_in.device)), "block_backward")
     del refs, refs_t
     return d_in, d_aw
 

@@ -755,6 +755,20 @@ int aaclip_attention_backward(const float* qkv, const float* d_ctx, float* d_qkv
   return finish("attention_backward");
 }
 
+size_t aaclip_attention_backward_long_workspace_bytes(int B, int L, int H) {
+  return attention_backward_long_ws_bytes(B, L, H);
+}
+
+int aaclip_attention_backward_long(const float* qkv, const float* d_ctx, float* d_qkv, int B, int L, int H, int causal,
+                                   float dq_scale, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(qkv && d_ctx && d_qkv && ws, "attention_backward_long: null pointer");
+  if (const char* m = attention_backward_long_check(B, L, H)) return fail(-1, m);
+  REQUIRE_ALIGNED16("attention_backward_long", qkv, d_ctx, d_qkv, ws);
+  REQUIRE(ws_bytes >= attention_backward_long_ws_bytes(B, L, H), "attention_backward_long: workspace too small");
+  launch_attention_backward_long(qkv, d_ctx, d_qkv, B, L, H, causal != 0, dq_scale, ws, (hipStream_t)stream);
+  return finish("attention_backward_long");
+}
+
 int aaclip_layernorm_backward(const float* x, const float* w, const float* d_y, const float* d_resid, float* d_x,
                               long rows, int D, float eps, void* stream) {
   REQUIRE(x && w && d_y && d_x, "layernorm_backward: null pointer");
@@ -775,9 +789,12 @@ int aaclip_adapter_mix_backward(const float* u, const float* z, const float* d_y
   return finish("adapter_mix_backward");
 }
 
-int aaclip_block_backward(const float* x_in, const aaclip_block_weights* w, const aaclip_block_weights* wt, float mix,
-                          int B, int L, int D, int H, int F, int attn_mode, const float* d_out, float* d_in,
-                          float* d_adapter_w, void* ws, size_t ws_bytes, void* stream) {
+// The body of aaclip_block_backward and aaclip_block_backward_long: they differ in the length check, in the workspace
+// (the long form appends the attention statistics to the text-backward layout) and in which attention backward runs.
+static int block_backward_body(bool long_rows, const float* x_in, const aaclip_block_weights* w,
+                               const aaclip_block_weights* wt, float mix, int B, int L, int D, int H, int F, int attn_mode,
+                               const float* d_out, float* d_in, float* d_adapter_w, void* ws, size_t ws_bytes,
+                               void* stream) {
   REQUIRE(x_in && w && wt && d_out && ws, "block_backward: null pointer");
   REQUIRE(w->struct_bytes == sizeof(aaclip_block_weights) && wt->struct_bytes == sizeof(aaclip_block_weights),
           "block_backward: aaclip_block_weights.struct_bytes does not match this library");
@@ -787,7 +804,8 @@ int aaclip_block_backward(const float* x_in, const aaclip_block_weights* w, cons
   REQUIRE(D == 64 * H, "block_backward: D must equal 64*H (head dim 64)");
   REQUIRE_ROW_WIDTH(D);
   REQUIRE(F > 0 && F % 128 == 0, "block_backward: F must be a multiple of 128");
-  if (const char* m = attention_backward_check(B, L, H)) return fail(-1, m);
+  if (const char* m = long_rows ? attention_backward_long_check(B, L, H) : attention_backward_check(B, L, H))
+    return fail(-1, m);
   const long rows = (long)B * L;
   REQUIRE(rows < (1L << 31) / 4, "block_backward: too many rows");
   REQUIRE(w->ln1_w && w->ln1_b && w->qkv_w && w->qkv_b && w->out_w && w->out_b && w->ln2_w && w->ln2_b && w->fc_w &&
@@ -799,7 +817,8 @@ int aaclip_block_backward(const float* x_in, const aaclip_block_weights* w, cons
   REQUIRE(!d_in || (wt->qkv_w && wt->out_w && wt->fc_w && wt->proj_w && (!adapter || wt->adapter_w)),
           "block_backward: null transposed weight pointer");
   const TbLayout l = tb_layout(rows, D, F);
-  REQUIRE(ws_bytes >= l.total, "block_backward: workspace too small");
+  REQUIRE(ws_bytes >= l.total + (long_rows ? attention_backward_long_ws_bytes(B, L, H) : 0),
+          "block_backward: workspace too small");
   REQUIRE_ALIGNED16("block_backward", x_in, d_out, d_in, d_adapter_w, ws, w->ln1_w, w->ln2_w, w->adapter_w);
   hipStream_t s = (hipStream_t)stream;
   char* base = (char*)ws;
@@ -848,11 +867,31 @@ int aaclip_block_backward(const float* x_in, const aaclip_block_weights* w, cons
   // ---- x1 = x_in + out_proj(attention(qkv)),  qkv = in_proj(ln_1 x_in), q scaled
   p = gemm_params(dx, D, wt->out_w, nullptr, tmp, D, M, D, D);
   launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
-  launch_attention_backward(qkv, tmp, dqkv, B, L, H, causal, qscale, s);
+  if (long_rows) launch_attention_backward_long(qkv, tmp, dqkv, B, L, H, causal, qscale, base + l.total, s);
+  else launch_attention_backward(qkv, tmp, dqkv, B, L, H, causal, qscale, s);
   p = gemm_params(dqkv, 3 * D, wt->qkv_w, nullptr, tmp, D, M, D, 3 * D);
   launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
   launch_layernorm_backward(x_in, w->ln1_w, tmp, dx, d_in, nullptr, rows, D, 1e-5f, s);
   return finish("block_backward");
+}
+
+int aaclip_block_backward(const float* x_in, const aaclip_block_weights* w, const aaclip_block_weights* wt, float mix,
+                          int B, int L, int D, int H, int F, int attn_mode, const float* d_out, float* d_in,
+                          float* d_adapter_w, void* ws, size_t ws_bytes, void* stream) {
+  return block_backward_body(false, x_in, w, wt, mix, B, L, D, H, F, attn_mode, d_out, d_in, d_adapter_w, ws, ws_bytes,
+                             stream);
+}
+
+size_t aaclip_block_backward_long_workspace_bytes(int B, int L, int D, int F) {
+  if (B <= 0 || L <= 0 || D <= 0 || F < 0) return 0;
+  return tb_layout((long)B * L, D, F).total + attention_backward_long_ws_bytes(B, L, (D + 63) / 64);
+}
+
+int aaclip_block_backward_long(const float* x_in, const aaclip_block_weights* w, const aaclip_block_weights* wt,
+                               float mix, int B, int L, int D, int H, int F, int attn_mode, const float* d_out,
+                               float* d_in, float* d_adapter_w, void* ws, size_t ws_bytes, void* stream) {
+  return block_backward_body(true, x_in, w, wt, mix, B, L, D, H, F, attn_mode, d_out, d_in, d_adapter_w, ws, ws_bytes,
+                             stream);
 }
 
 int aaclip_row_head_backward(const float* x, const int32_t* tokens, const float* ln_w, const float* ln_b,

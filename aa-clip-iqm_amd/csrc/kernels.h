@@ -159,6 +159,11 @@ const char* attention_backward_check(int B, int L, int H);
 // qkv [B*L, 3*H*64] (q pre-scaled), dctx [B*L, H*64] -> dqkv [B*L, 3*H*64]; the dq columns are multiplied by dq_scale
 void launch_attention_backward(const float* qkv, const float* dctx, float* dqkv, int B, int L, int H, int causal,
                                float dq_scale, hipStream_t s);
+// attention_backward.hip: the same for any L, tiled on the fp32 MFMA; ws holds the 3*B*H*L row statistics
+const char* attention_backward_long_check(int B, int L, int H);
+size_t attention_backward_long_ws_bytes(int B, int L, int H);
+void launch_attention_backward_long(const float* qkv, const float* dctx, float* dqkv, int B, int L, int H, int causal,
+                                    float dq_scale, void* ws, hipStream_t s);
 // dx[out_rows ? out_rows[r] : r] = LayerNorm input gradient of row r (+ add, read at the output row)
 void launch_layernorm_backward(const float* x, const float* w, const float* dy, const float* add, float* dx,
                                const int* out_rows, long rows, int D, float eps, hipStream_t s);

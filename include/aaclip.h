@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define AACLIP_ABI_VERSION 8   /* 8: backward of the adapted text tower (aaclip_block_backward and its building blocks) */
+#define AACLIP_ABI_VERSION 9   /* 9: attention and block backward for rows of any length (the *_long entry points) */
 
 enum { AACLIP_F32 = 0, AACLIP_F16 = 1, AACLIP_BF16 = 2, AACLIP_F16X2 = 3 };
 enum { AACLIP_ACT_NONE = 0, AACLIP_ACT_LEAKY = 1, AACLIP_ACT_RELU = 2 };
@@ -256,6 +256,18 @@ int aaclip_gemm_wgrad(const float* dz, long ldz, const float* u, long ldu, float
 int aaclip_attention_backward(const float* qkv, const float* d_ctx, float* d_qkv, int B, int L, int H, int causal,
                               float dq_scale, void* stream);
 
+/* The same gradients for ANY L >= 1 (the visual tower's 1370 rows), in three tiled passes on the exact-fp32 MFMA: row
+ * statistics (maximum, 1 / sum, delta; 3*B*H*L floats in the workspace), then dk | dv, then dq.  Nothing of size L x L
+ * reaches memory; no atomics, every output element is summed by one wave in a fixed order.  Layouts, dq_scale and the
+ * alignment rule as above (the workspace is 16-byte aligned too).  ws_bytes >=
+ * aaclip_attention_backward_long_workspace_bytes(B, L, H), which is 0 for an empty problem and monotonic in each
+ * argument.  Null pointers, empty problems, B or H above 65535, misaligned pointers and a short workspace are rejected
+ * before a launch.  aaclip_attention_backward is unchanged: its arithmetic differs (VALU chains), so the two agree to
+ * rounding, not bit for bit. */
+size_t aaclip_attention_backward_long_workspace_bytes(int B, int L, int H);
+int aaclip_attention_backward_long(const float* qkv, const float* d_ctx, float* d_qkv, int B, int L, int H, int causal,
+                                   float dq_scale, void* ws, size_t ws_bytes, void* stream);
+
 /* LayerNorm input gradient (weight and bias are frozen): d_x = d_resid + dLN(x; w)^T d_y, d_resid may be NULL; d_x may
  * alias d_y or d_resid. */
 int aaclip_layernorm_backward(const float* x, const float* w, const float* d_y, const float* d_resid, float* d_x,
@@ -277,6 +289,15 @@ int aaclip_adapter_mix_backward(const float* u, const float* z, const float* d_y
 int aaclip_block_backward(const float* x_in, const aaclip_block_weights* w, const aaclip_block_weights* wt, float mix,
                           int B, int L, int D, int H, int F, int attn_mode, const float* d_out, float* d_in,
                           float* d_adapter_w, void* ws, size_t ws_bytes, void* stream);
+
+/* aaclip_block_backward without the limit on L (the visual tower: L = 1370, D = 1024, F = 4096): the same walk with
+ * aaclip_attention_backward_long in the attention step, every other launch identical.  Same arguments; ws_bytes >=
+ * aaclip_block_backward_long_workspace_bytes(B, L, D, F) = the text-backward layout for B*L rows plus the attention
+ * statistics (0 for an empty problem).  Error messages carry the "block_backward:" prefix of the short form. */
+size_t aaclip_block_backward_long_workspace_bytes(int B, int L, int D, int F);
+int aaclip_block_backward_long(const float* x_in, const aaclip_block_weights* w, const aaclip_block_weights* wt,
+                               float mix, int B, int L, int D, int H, int F, int attn_mode, const float* d_out,
+                               float* d_in, float* d_adapter_w, void* ws, size_t ws_bytes, void* stream);
 
 /* Backward of aaclip_row_head(AACLIP_F32): x, tokens, ln_w, ln_b, act, mode as there; proj_w [E, D] and its transpose
  * proj_wt [D, E] in fp32 (proj_wt may be NULL when d_x is); d_out [n, E].  d_proj_w (out) [E, D], overwritten.  d_x
