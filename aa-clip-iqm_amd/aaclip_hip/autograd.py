@@ -1,7 +1,8 @@
 """torch.autograd.Functions over the training entry points of libaaclip_hip.so (include/aaclip.h, "Training"): the
 train-mode similarity map (reference forward_utils.py:196-216, test=False), the segmentation loss (:21-108,223-227) and
-the adapted text tower (reference model/adapter.py:273-304), whose backward fills the text_adapter gradients, and the
-visual tower up to its tap streams (model/adapter.py:137-170), whose backward fills the layer-adapter gradients.
+the adapted text tower (reference model/adapter.py:273-304), whose backward fills the text_adapter gradients, the
+visual tower up to its tap streams (model/adapter.py:137-170), whose backward fills the layer-adapter gradients, and
+the tap and det heads behind them (:171-184), whose backward fills the seg_proj / det_proj gradients.
 Forward and backward are HIP kernels; these classes only carry tensors between them.  The saved tensors live in
 ctx.save_for_backward, so they are freed with the graph (after backward(), or when the output is dropped)."""
 from __future__ import annotations
@@ -192,13 +193,66 @@ class VisualTaps(torch.autograd.Function):
         return (None, None, *grads)
 
 
+class TapHead(torch.autograd.Function):
+    """One tap head of AdaptedCLIP.forward (reference model/adapter.py:171-184) with a backward for its projections and
+    for the tap stream: ln_post and CLIP's other parameters are frozen, they are not inputs and receive no gradient.
+
+    forward(model, tap [B, L, D], seg_proj weight, det_proj weight or None) -> seg [B, L-1, E], or (seg, det [B, E])
+    with a det weight: exactly engine.tap_head at the model's precision, so the outputs do not depend on whether
+    gradients are on.  Saved: the tap (the VisualTaps output itself, no copy) and the weights.  The backward is
+    engine.tap_head_backward, fp32 whatever precision the forward ran in, recomputing the head from the tap; an output
+    the loss does not read contributes nothing (its part is skipped), and a tap without a graph skips the
+    input-gradient products."""
+
+    @staticmethod
+    def forward(ctx, model, tap, proj_weight, det_weight):
+        B, L, D = tap.shape
+        seg, det = engine.tap_head(tap.reshape(B * L, D), model.image_encoder.ln_post, proj_weight, model.relu, B, L,
+                                   model._code(), det_weight=det_weight)
+        ctx.model = model
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(tap, proj_weight, det_weight)
+        return seg if det is None else (seg, det)
+
+    @staticmethod
+    def backward(ctx, d_seg, d_det=None):
+        tap, pw, dw = ctx.saved_tensors
+        _, need_x, need_p, need_d = ctx.needs_input_grad
+        if (d_seg is None and d_det is None) or not (need_x or need_p or need_d):
+            return None, None, None, None
+        model = ctx.model
+        d_x, d_pw, d_dw = engine.tap_head_backward(
+            tap, model.image_encoder.ln_post, pw, _lib.ACT_LEAKY if model.relu else _lib.ACT_NONE, d_seg,
+            det_weight=dw if d_det is not None else None, d_det=d_det, need_input_grad=need_x)
+        return (None, d_x.view_as(tap).to(tap.dtype) if need_x else None,
+                d_pw.to(pw.dtype) if need_p and d_pw is not None else None,
+                d_dw.to(dw.dtype) if need_d and d_dw is not None else None)
+
+
 def visual_taps(model, image):
     """The tap streams of AdaptedCLIP's visual tower, [B, L, D] each (CLS row included), one per entry of model.levels
     in ascending order, carrying a graph to model.image_adapter["layer_adapters"][i].weight: see VisualTaps.
-    AdaptedCLIP.forward itself is unchanged and carries no graph; until the tap and det heads have backward kernels,
-    a training step composes them from torch ops on the streams returned here (drop the CLS row, ln_post, seg_proj,
-    normalise), as the tests do."""
+    AdaptedCLIP.forward itself is unchanged and carries no graph; visual_heads puts the tap and det heads behind these
+    streams with their HIP backward (TapHead), so a training step needs no torch-op composition of the heads."""
     return list(VisualTaps.apply(model, image, *[m.weight for m in model.image_adapter["layer_adapters"]]))
+
+
+def visual_heads(model, image):
+    """AdaptedCLIP.forward(image)[:2] with a graph -> (seg_tokens: one [B, L-1, E] tensor of unit rows per tap level,
+    det_token [B, E]): visual_taps, then one TapHead per level with the det head on the last one, paired as the forward
+    pairs them and bit-identical to it.  The graph reaches image_adapter["layer_adapters"][i].weight, ["seg_proj"][k]
+    and ["det_proj"], whichever of them require grad.  Not built: the IQM branch's backward (the forward's third
+    output)."""
+    seg_proj = model.image_adapter["seg_proj"]
+    det_weight = model.image_adapter["det_proj"].weight
+    seg_tokens, det_token = [], None
+    for k, tap in enumerate(visual_taps(model, image)):
+        if k == len(model.levels) - 1:
+            seg, det_token = TapHead.apply(model, tap, seg_proj[k].weight, det_weight)
+        else:
+            seg = TapHead.apply(model, tap, seg_proj[k].weight, None)
+        seg_tokens.append(seg)
+    return seg_tokens, det_token
 
 
 def encode_text(model, tokens):

@@ -734,6 +734,43 @@ def row_head_backward(x: torch.Tensor, tokens: Optional[torch.Tensor], ln, proj:
     return d_x, d_w
 
 
+def tap_head_backward(x: torch.Tensor, ln_post, proj_weight: Optional[torch.Tensor], act: int,
+                      d_seg: Optional[torch.Tensor], det_weight: Optional[torch.Tensor] = None,
+                      d_det: Optional[torch.Tensor] = None, need_input_grad: bool = True):
+    """Backward of tap_head(code fp32) from the tap stream x [B, L, D] or [B*L, D] with d_seg [B, L-1, E] and / or
+    d_det [B, E] -> (d x [B*L, D] or None, d proj [E, D] or None, d det [E, D] or None): aaclip_tap_head_backward.
+    d_seg None: the det head alone.  need_input_grad False: the weight gradients alone, no transposed weight is read."""
+    require_gpu(x, "tap_head_backward")
+    lib = _lib.load()
+    if d_seg is None and d_det is None:
+        raise ValueError("tap_head_backward: d_seg and d_det are both None")
+    if (d_det is None) != (det_weight is None):
+        raise ValueError("tap_head_backward: det_weight and d_det go together")
+    B = d_seg.shape[0] if d_seg is not None else d_det.shape[0]
+    D = x.shape[-1]
+    L = x.numel() // D // B
+    x = _f32c(x).reshape(B * L, D)
+    lw, lb = _f32c(ln_post.weight), _f32c(ln_post.bias)
+    dev = x.device
+    seg, det = d_seg is not None, d_det is not None
+    E = proj_weight.shape[0] if seg else det_weight.shape[0]
+    d_seg = _f32c(d_seg) if seg else None
+    d_det = _f32c(d_det) if det else None
+    pw = CACHE.get(proj_weight, F32) if seg else None
+    pwt = CACHE.get(proj_weight, F32, "transpose") if seg and need_input_grad else None
+    dw = CACHE.get(det_weight, F32) if det else None
+    dwt = CACHE.get(det_weight, F32, "transpose") if det and need_input_grad else None
+    d_x = torch.empty(B * L, D, dtype=torch.float32, device=dev) if need_input_grad else None
+    d_pw = torch.empty(E, D, dtype=torch.float32, device=dev) if seg else None
+    d_dw = torch.empty(E, D, dtype=torch.float32, device=dev) if det else None
+    ws = Workspace.get(dev, lib.aaclip_tap_head_backward_workspace_bytes(int(B), int(L), int(D), int(E)))
+    _lib.check(lib.aaclip_tap_head_backward(x.data_ptr(), lw.data_ptr(), lb.data_ptr(), _ptr(pw), _ptr(pwt), int(act),
+                                            _ptr(d_seg), _ptr(dw), _ptr(dwt), _ptr(d_det), _ptr(d_x), _ptr(d_pw),
+                                            _ptr(d_dw), B, L, D, E, ws.data_ptr(), ws.numel(), _stream(dev)),
+               "tap_head_backward")
+    return d_x, d_pw, d_dw
+
+
 # ------------------------------------------------------------------------------------------------
 # image pre-processing (reference dataset/__init__.py:150-161), Pillow-exact on the GPU
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)

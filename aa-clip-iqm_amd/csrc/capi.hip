@@ -931,6 +931,75 @@ int aaclip_row_head_backward(const float* x, const int32_t* tokens, const float*
   return finish("row_head_backward");
 }
 
+// The tap-head-backward workspace, byte offsets from its start: the LayerNorm'ed rows, the projection rows (z, then dz;
+// the seg and the det part take turns), the two parts' d_ln and the chunk partials of the weight-gradient GEMM (sized
+// for the largest split, whatever the row count is, so that the total grows with it).
+struct ThLayout { size_t ln, z, dln, dln2, wg, total; };
+static ThLayout th_layout(long rows, int D, int E) {
+  const size_t rd = up256((size_t)rows * D * 4), re = up256((size_t)rows * E * 4);
+  ThLayout l;
+  l.ln = 0;
+  l.z = l.ln + rd;
+  l.dln = l.z + re;
+  l.dln2 = l.dln + rd;
+  l.wg = l.dln2 + rd;
+  l.total = l.wg + up256((size_t)WGRAD_MAX_CHUNKS * E * D * 4);
+  return l;
+}
+
+size_t aaclip_tap_head_backward_workspace_bytes(int B, int L, int D, int E) {
+  if (B <= 0 || L <= 0 || D <= 0 || E <= 0) return 0;
+  return th_layout((long)B * L, D, E).total;
+}
+
+int aaclip_tap_head_backward(const float* x, const float* ln_post_w, const float* ln_post_b, const float* proj_w,
+                             const float* proj_wt, int act, const float* d_seg, const float* det_w, const float* det_wt,
+                             const float* d_det, float* d_x, float* d_proj_w, float* d_det_w, int B, int L, int D, int E,
+                             void* ws, size_t ws_bytes, void* stream) {
+  const bool seg = d_seg != nullptr, det = d_det != nullptr;
+  REQUIRE(x && ln_post_w && ln_post_b && ws, "tap_head_backward: null pointer");
+  REQUIRE(seg || det, "tap_head_backward: nothing to compute (d_seg and d_det are both NULL)");
+  REQUIRE(!seg || (proj_w && d_proj_w), "tap_head_backward: null pointer (proj_w and d_proj_w go with d_seg)");
+  REQUIRE((det_w != nullptr) == det && (d_det_w != nullptr) == det && (det || !det_wt),
+          "tap_head_backward: det_w, d_det and d_det_w are given together or not at all");
+  REQUIRE(!d_x || ((!seg || proj_wt) && (!det || det_wt)),
+          "tap_head_backward: the transposed projections are required for d_x");
+  REQUIRE(B > 0 && L > 1, "tap_head_backward: bad shape (B > 0, L > 1)");
+  REQUIRE_ROW_WIDTH(D);
+  REQUIRE_ROW_WIDTH(E);
+  REQUIRE(E % 128 == 0, "tap_head_backward: E must be a multiple of 128");
+  REQUIRE(act >= AACLIP_ACT_NONE && act <= AACLIP_ACT_RELU, "tap_head_backward: bad activation");
+  const long rows = (long)B * L;
+  REQUIRE(rows < (1L << 31) / 4, "tap_head_backward: too many rows");
+  REQUIRE_ALIGNED16("tap_head_backward", x, ln_post_w, ln_post_b, proj_w, proj_wt, d_seg, det_w, det_wt, d_det, d_x,
+                    d_proj_w, d_det_w, ws);
+  const ThLayout l = th_layout(rows, D, E);
+  REQUIRE(ws_bytes >= l.total, "tap_head_backward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  char* base = (char*)ws;
+  float *ln = (float*)(base + l.ln), *z = (float*)(base + l.z), *dln = (float*)(base + l.dln);
+  const int M = (int)rows;
+  launch_layernorm(AACLIP_F32, x, ln_post_w, ln_post_b, ln, rows, D, 1e-5f, s);
+  // one projection: z = ln W^T again, z <- dz, dW = dz^T ln, and (for d_x) d_ln = dz W into `out`
+  auto part = [&](const float* w, const float* wt, const float* d, int is_det, float* dw, float* out) {
+    GemmParams p = gemm_params(ln, D, w, nullptr, z, E, M, E, D);
+    launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+    launch_head_normalize_backward(z, d, B, L, E, act, is_det, s);
+    launch_wgrad(z, E, ln, D, dw, rows, E, D, base + l.wg, s);
+    if (d_x) {
+      p = gemm_params(z, E, wt, nullptr, out, D, M, D, E);
+      launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+    }
+  };
+  if (seg) part(proj_w, proj_wt, d_seg, 0, d_proj_w, dln);
+  if (det) part(det_w, det_wt, d_det, 1, d_det_w, seg ? (float*)(base + l.dln2) : dln);
+  if (d_x) {
+    if (seg && det) launch_add_rows(dln, (const float*)(base + l.dln2), dln, rows * D, s);
+    launch_layernorm_backward(x, ln_post_w, dln, nullptr, d_x, nullptr, rows, D, 1e-5f, s);
+  }
+  return finish("tap_head_backward");
+}
+
 int aaclip_resample_ksize(int in_size, int out_size) {
   if (in_size < 1 || out_size < 1) return fail(-1, "resample_ksize: sizes must be positive");
   return resample_ksize(in_size, out_size);

@@ -173,6 +173,9 @@ void launch_gelu_forward(const float* f, float* out, long n, hipStream_t s);
 void launch_gelu_backward(const float* f, const float* dg, float* df, long n, hipStream_t s);
 void launch_act_backward(const float* z, const float* dy, float* dz, long n, int act, hipStream_t s);
 void launch_add_rows(const float* a, const float* b, float* out, long n, hipStream_t s);
+// in place on z [B*L, E] (pre-activation rows of a tap / det head): z <- dz of y = normalize(act(z)); det == 0: d is
+// d_seg [B, L-1, E]; det != 0: d is d_det [B, E], the gradient of the mean over the patch rows.  CLS rows <- 0.
+void launch_head_normalize_backward(float* z, const float* d, int B, int L, int E, int act, int det, hipStream_t s);
 void launch_pick_rows(const float* x, float* dst, int* idx, const int32_t* tokens, int n, int T, int D, int mode,
                       hipStream_t s);
 

@@ -9,6 +9,8 @@
 //   ln_bwd_kernel                        LayerNorm input gradient (gamma, beta frozen), wave per row
 //   adapter_mix_bwd_kernel               backward of y = w a |u| / |a| + (1 - w) u, a = LeakyReLU(z), wave per row
 //   gelu / gelu_bwd / act_bwd / gather   element-wise helpers of the block and row-head backward
+//   head_norm_bwd_kernel                 backward of activation + F.normalize (+ patch mean) of the tap / det head, wave
+//                                        per row
 #include "common.h"
 #include "kernels.h"
 
@@ -445,6 +447,73 @@ void launch_act_backward(const float* z, const float* dy, float* dz, long n, int
 }
 void launch_add_rows(const float* a, const float* b, float* out, long n, hipStream_t s) {
   hipLaunchKernelGGL(ew_kernel<3>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, a, b, out, n / 4, 0);
+}
+
+// Backward of the tail of the tap / det head (rowops.hip: normalize_rows_kernel, det_partial_kernel), in place on the
+// projection rows z [B*L, E] (pre-activation).  Forward: a = act(z), n = max(|a|, 1e-12), y = a / n.  Backward:
+//   dz = act'(z) (g - y <y, g>) / n      (a row below the clamp has a constant n: dz = act'(z) g / n)
+// det == 0: g = row (b, t - 1) of d [B, L-1, E], the gradient of the unit patch rows.  det != 0: d is [B, E], the
+// gradient of the mean over an image's L - 1 unit rows, so every patch row of image b takes g = d[b] / (L - 1).
+// The CLS row (t = 0) of every image reaches neither output: dz = 0, so the products behind run over all B*L rows.
+// Wave per row, the row in registers, like adapter_mix_bwd_kernel.
+template <int NCH>
+__global__ __launch_bounds__(256) void head_norm_bwd_kernel(float* z, const float* __restrict__ d, long rows, int L,
+                                                            int act, int det) {
+  constexpr int E = NCH * 256;
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long b = row / L;
+  const int t = (int)(row - b * L);
+  float* zp = z + row * E;
+  if (t == 0) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) *(f32x4*)(zp + (c * 64 + lane) * 4) = zero;
+    return;
+  }
+  f32x4 zv[NCH], gv[NCH];
+  load_row4<NCH>(zp, lane, zv);
+  load_row4<NCH>(det ? d + b * E : d + (b * (L - 1) + (t - 1)) * E, lane, gv);
+  const float gs = det ? 1.0f / (float)(L - 1) : 1.0f;
+  float q = 0.f, dot = 0.f;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float x = zv[c][e];
+      const float a = act == 1 ? leaky(x) : act == 2 ? fmaxf(x, 0.f) : x;
+      gv[c][e] *= gs;
+      q = fmaf(a, a, q);
+      dot = fmaf(a, gv[c][e], dot);
+    }
+  const float nrm = sqrtf(wave_sum(q));
+  const float inv = 1.0f / fmaxf(nrm, 1e-12f);
+  const float ag = wave_sum(dot);
+  const float yg = nrm > 1e-12f ? ag * inv : 0.f;   // <y, g>
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float x = zv[c][e];
+      const float a = act == 1 ? leaky(x) : act == 2 ? fmaxf(x, 0.f) : x;
+      const float k = act == 1 ? (x >= 0.f ? 1.0f : 0.01f) : act == 2 ? (x > 0.f ? 1.0f : 0.f) : 1.0f;
+      o[e] = k * ((gv[c][e] - (a * inv) * yg) * inv);
+    }
+    *(f32x4*)(zp + (c * 64 + lane) * 4) = o;
+  }
+}
+
+void launch_head_normalize_backward(float* z, const float* d, int B, int L, int E, int act, int det, hipStream_t s) {
+  const long rows = (long)B * L;
+  dim3 g((unsigned)((rows + 3) / 4));
+  switch (E / 256) {
+    case 1: hipLaunchKernelGGL(head_norm_bwd_kernel<1>, g, dim3(256), 0, s, z, d, rows, L, act, det); break;
+    case 2: hipLaunchKernelGGL(head_norm_bwd_kernel<2>, g, dim3(256), 0, s, z, d, rows, L, act, det); break;
+    case 3: hipLaunchKernelGGL(head_norm_bwd_kernel<3>, g, dim3(256), 0, s, z, d, rows, L, act, det); break;
+    case 4: hipLaunchKernelGGL(head_norm_bwd_kernel<4>, g, dim3(256), 0, s, z, d, rows, L, act, det); break;
+  }
 }
 
 // Row pick of the row head (gather_rows_kernel's rule: the first maximum of the token ids, or row 0): copies the picked

@@ -2,8 +2,11 @@
 to end -- encode_text forward and backward (aaclip_hip.autograd.TextTower), the train-mode similarity map and the
 segmentation loss with their backward kernels.  Behaviour follows reference train.py:57-113.
 
-Not here: the training-time datasets, main() and stage 2 (the image adapters).
-`train_text_adapter` is fed by any iterable of {"image", "mask", "class_name"} batches.
+Of stage 2 (the image adapters) only `stage2_text_loss` is here: the forward with a graph
+(aaclip_hip.autograd.visual_heads) and the part of the loss that does not involve the IQM branch.
+
+Not here: the training-time datasets, main(), the IQM terms of the stage-2 loss and
+train_image_adapter.  `train_text_adapter` is fed by any iterable of {"image", "mask", "class_name"} batches.
 """
 from __future__ import annotations
 
@@ -14,8 +17,13 @@ import torch
 from torch import nn
 
 import forward_utils as FU
+from aaclip_hip import autograd
 
 CHECKPOINT_NAME = "text_adapter.pth"
+# reference train.py:131-132,156,163: the weight of the text-anchor maps against the IQM maps, and the two halvings
+TEXT_WEIGHT = 0.6
+CLS_LOSS_SCALE = 0.5
+SEG_LOSS_SCALE = 0.5
 
 
 def _unit(t: torch.Tensor) -> torch.Tensor:
@@ -71,3 +79,22 @@ def train_text_adapter(adapted_model: nn.Module, clip_surgery: nn.Module, text_n
         torch.save({"epoch": epoch + 1, "text_adapter": adapted_model.text_adapter.state_dict(),
                     "text_optimizer": optimizer.state_dict()}, os.path.join(save_path, CHECKPOINT_NAME))
     return adapted_model
+
+
+def stage2_text_loss(adapted_model, image, mask, label, anchors, img_size):
+    """The stage-2 loss without its IQM terms (reference train.py:152-163), with a graph to the image adapters:
+        CLS_LOSS_SCALE * cross_entropy((det.unsqueeze(1) @ anchors)[:, 0], label)
+        + sum over the tap levels of TEXT_WEIGHT * SEG_LOSS_SCALE * seg_loss(similarity_map(seg, anchors), mask)
+    image [B, 3, S, S], mask [B, 1, S, S] of 0 / 1, label [B] int64, anchors [B, E, 2] (the batch's text embeddings).
+    The forward (autograd.visual_heads), the maps and the segmentation loss run on the HIP kernels, forward and backward;
+    the [B, 2] matmul and cross-entropy of the classification term are host-side torch ops, like
+    forward_utils.image_score.
+    Not built: the IQM terms of the loss (train.py:165-212: the branch has no backward) and train_image_adapter (the
+    epoch loop, clipping, scheduler and checkpoint around this loss)."""
+    seg_tokens, det = autograd.visual_heads(adapted_model, image)
+    cls_preds = torch.matmul(det.unsqueeze(1), anchors)[:, 0]
+    loss = CLS_LOSS_SCALE * nn.functional.cross_entropy(cls_preds, label)
+    for seg in seg_tokens:
+        preds = FU.calculate_similarity_map(seg, anchors, img_size)
+        loss = loss + TEXT_WEIGHT * SEG_LOSS_SCALE * FU.calculate_seg_loss(preds, mask)
+    return loss

@@ -308,6 +308,30 @@ int aaclip_row_head_backward(const float* x, const int32_t* tokens, const float*
                              float* d_proj_w, int n, int T, int D, int E, int mode, void* ws, size_t ws_bytes,
                              void* stream);
 
+/* ---- Training: backward of the tap and det heads (reference model/adapter.py:171-184 under train.py:150-163), the
+ * first step of stage 2 behind the loss.  Same rules as the text-tower backward above: fp32 whatever dtype the forward
+ * ran in, no float atomics, fixed summation order (repeated calls give bit-identical results), every fp32 pointer and
+ * the workspace 16-byte aligned, every check before the first launch.
+ *
+ * Backward of aaclip_tap_head(AACLIP_F32) from the tap stream x [B*L, D] (CLS row included): ln_post(x), the projection
+ * rows and their norms are recomputed, nothing is kept from the forward.  proj_w [E, D] and its transpose proj_wt [D, E];
+ * d_seg [B, L-1, E]: gradient of the unit patch rows.  det_w / det_wt / d_det [B, E] / d_det_w: the det head of the same
+ * stream (aaclip_tap_head's det_w) -- det_w, d_det and d_det_w are given together or all NULL (det_wt NULL too).  d_seg may
+ * be NULL when the det part is present (proj_w, proj_wt and d_proj_w are then ignored): that is the backward of
+ * aaclip_det_head.  One of the two parts must be present.
+ * d_proj_w (out) [E, D] and d_det_w (out) [E, D] are overwritten.  d_x (out) [B*L, D], overwritten, CLS rows exactly
+ * zero; may be NULL when only the projections train -- then proj_wt / det_wt may be NULL too and no input-gradient
+ * product runs.  Otherwise the transpose of every part that is present is required.
+ * D, E supported row widths (256, 512, 768, 1024), L > 1, B*L < 2^29, act one of AACLIP_ACT_*.
+ * ws_bytes >= aaclip_tap_head_backward_workspace_bytes(B, L, D, E): 0 for an empty problem, monotonic in each
+ * argument.  Errors carry the "tap_head_backward:" prefix.
+ * Not built: the backward of the IQM branch (aaclip_tap_head_keep_rows' rows feed it) -- see DESIGN.md section 7. */
+size_t aaclip_tap_head_backward_workspace_bytes(int B, int L, int D, int E);
+int aaclip_tap_head_backward(const float* x, const float* ln_post_w, const float* ln_post_b, const float* proj_w,
+                             const float* proj_wt, int act, const float* d_seg, const float* det_w, const float* det_wt,
+                             const float* d_det, float* d_x, float* d_proj_w, float* d_det_w, int B, int L, int D, int E,
+                             void* ws, size_t ws_bytes, void* stream);
+
 /* Image pre-processing in front of the patch embed: Pillow's 8-bit BICUBIC resize to S x S,
  * ToTensor (v/255) and Normalize((v - mean)/std), bit-exact.  Replaces the reference's
  * dataset transform (reference dataset/__init__.py:150-161 and :62-71: transforms.Resize(
