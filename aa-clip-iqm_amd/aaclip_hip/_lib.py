@@ -53,6 +53,9 @@ SIGNATURES = {
     "aaclip_similarity_map_train": (_i, [_vp, _vp, _l, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "aaclip_similarity_map_train_backward_workspace_bytes": (_sz, [_i, _i, _i]),
     "aaclip_similarity_map_train_backward": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "aaclip_iqm_map_train": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "aaclip_iqm_map_train_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "aaclip_iqm_map_train_backward": (_i, [_vp] * 6 + [_i] * 4 + [_vp, _sz, _vp]),
     "aaclip_seg_loss_workspace_bytes": (_sz, [_i]),
     "aaclip_seg_loss": (_i, [_vp, _l, _l, _vp, _i, _vp, _vp, _i, _l, _vp, _sz, _vp]),
     "aaclip_seg_loss_backward": (_i, [_vp, _l, _l, _vp, _i, _vp, _vp, _vp, _i, _l, _vp]),

@@ -2,7 +2,9 @@
 train-mode similarity map (reference forward_utils.py:196-216, test=False), the segmentation loss (:21-108,223-227) and
 the adapted text tower (reference model/adapter.py:273-304), whose backward fills the text_adapter gradients, the
 visual tower up to its tap streams (model/adapter.py:137-170), whose backward fills the layer-adapter gradients, and
-the tap and det heads behind them (:171-184), whose backward fills the seg_proj / det_proj gradients.
+the tap and det heads behind them (:171-184), whose backward fills the seg_proj / det_proj gradients, and the IQM map term of
+the stage-2 loss (reference train.py:173-209: the two-channel half-pixel upsample of sigmoid(cos - cos)), whose backward
+reaches the seg tokens and the two final queries.
 Forward and backward are HIP kernels; these classes only carry tensors between them.  The saved tensors live in
 ctx.save_for_backward, so they are freed with the graph (after backward(), or when the output is dropped)."""
 from __future__ import annotations
@@ -54,6 +56,32 @@ class SegLoss(torch.autograd.Function):
             return None, None, None
         d = engine.seg_loss_backward(preds, mask, coef, d_loss, ctx.terms)
         return d.to(preds.dtype), None, None
+
+
+class IqmMapTrain(torch.autograd.Function):
+    """seg tokens [B,P,E] x final queries [B,2,E] (row 0 normal, row 1 abnormal) -> [B,2,S,S]: channel 1 the half-pixel
+    bilinear upsample of p = sigmoid(cos(f, q_abnormal) - cos(f, q_normal)), channel 0 that of 1 - p.  The forward is
+    engine.iqm_map_train, so the output does not depend on whether gradients are on; seg, the queries and the patch
+    grid p are saved.  The backward computes only the gradients needs_input_grad asks for."""
+
+    @staticmethod
+    def forward(ctx, seg, queries, img_size):
+        out, grid = engine.iqm_map_train(seg, queries, int(img_size))
+        ctx.save_for_backward(seg, queries, grid)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        seg, q, grid = ctx.saved_tensors
+        need_seg, need_q = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_seg or need_q):
+            return None, None, None
+        d_seg, d_q = engine.iqm_map_train_backward(seg, q, grid, d_out, need_seg=need_seg, need_queries=need_q)
+        if d_seg is not None:
+            d_seg = d_seg.to(seg.dtype)
+        if d_q is not None:
+            d_q = d_q.to(q.dtype)
+        return d_seg, d_q, None
 
 
 class TextTower(torch.autograd.Function):
@@ -242,7 +270,7 @@ def visual_heads(model, image):
     det_token [B, E]): visual_taps, then one TapHead per level with the det head on the last one, paired as the forward
     pairs them and bit-identical to it.  The graph reaches image_adapter["layer_adapters"][i].weight, ["seg_proj"][k]
     and ["det_proj"], whichever of them require grad.  Not built: the IQM branch's backward (the forward's third
-    output)."""
+    output); iqm_map_train hands it d_queries."""
     seg_proj = model.image_adapter["seg_proj"]
     det_weight = model.image_adapter["det_proj"].weight
     seg_tokens, det_token = [], None
@@ -262,6 +290,12 @@ def encode_text(model, tokens):
 
 def similarity_map_train(seg, text_feature, img_size):
     return SimilarityMapTrain.apply(seg, text_feature, img_size)
+
+
+def iqm_map_train(seg, queries, img_size):
+    """The IQM map of one tap level for the stage-2 loss, [B, 2, S, S], with a graph to seg and to the queries: see
+    IqmMapTrain."""
+    return IqmMapTrain.apply(seg, queries, img_size)
 
 
 def seg_loss(preds, mask, terms: int = _lib.SEG_LOSS_ALL):

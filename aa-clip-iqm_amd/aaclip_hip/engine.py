@@ -550,6 +550,53 @@ def similarity_map_train_backward(seg: torch.Tensor, text_feature: torch.Tensor,
     return d_seg, d_tf
 
 
+def _iqm_train_shapes(seg: torch.Tensor, queries: torch.Tensor, what: str):
+    require_gpu(seg, what)
+    B, P, E = seg.shape
+    g = int(round(P ** 0.5))
+    if g * g != P:
+        raise AssertionError(f"L={P} is not a perfect square")         # reference train.py:196
+    if queries.shape != (B, 2, E):
+        raise ValueError(f"{what}: queries must be [{B}, 2, {E}] (normal, abnormal), got {tuple(queries.shape)}")
+    return B, P, E, g
+
+
+def iqm_map_train(seg: torch.Tensor, queries: torch.Tensor, img_size: int):
+    """reference train.py:173-209, one tap level -> (out [B, 2, S, S] = the half-pixel bilinear upsample of (1 - p, p),
+    grid [B, P] = p = sigmoid(cos(f, q_abnormal) - cos(f, q_normal)), which the backward reads)."""
+    lib = _lib.load()
+    seg = _f32c(seg)
+    B, P, E, g = _iqm_train_shapes(seg, queries, "iqm_map_train")
+    q = _f32c(queries).to(seg.device)
+    S = int(img_size)
+    out = torch.empty(B, 2, S, S, dtype=torch.float32, device=seg.device)
+    grid = torch.empty(B, P, dtype=torch.float32, device=seg.device)
+    _lib.check(lib.aaclip_iqm_map_train(seg.data_ptr(), q.data_ptr(), grid.data_ptr(), out.data_ptr(), B, g, E, S,
+                                        _stream(seg.device)), "iqm_map_train")
+    return out, grid
+
+
+def iqm_map_train_backward(seg: torch.Tensor, queries: torch.Tensor, grid: torch.Tensor, d_preds: torch.Tensor,
+                           need_seg: bool = True, need_queries: bool = True):
+    """Backward of iqm_map_train: (d seg [B, P, E] or None, d queries [B, 2, E] or None)."""
+    lib = _lib.load()
+    seg = _f32c(seg)
+    B, P, E, g = _iqm_train_shapes(seg, queries, "iqm_map_train_backward")
+    if not (need_seg or need_queries):
+        raise ValueError("iqm_map_train_backward: nothing to compute")
+    q, grid, d_preds = _f32c(queries).to(seg.device), _f32c(grid), _f32c(d_preds)
+    S = d_preds.shape[-1]
+    if d_preds.shape != (B, 2, S, S) or grid.shape != (B, P):
+        raise ValueError("iqm_map_train_backward: d_preds must be [B, 2, S, S] and grid [B, P]")
+    d_seg = torch.empty_like(seg) if need_seg else None
+    d_q = torch.empty_like(q) if need_queries else None
+    ws = Workspace.get(seg.device, lib.aaclip_iqm_map_train_backward_workspace_bytes(B, g, E, S))
+    _lib.check(lib.aaclip_iqm_map_train_backward(seg.data_ptr(), q.data_ptr(), grid.data_ptr(), d_preds.data_ptr(),
+                                                 _ptr(d_seg), _ptr(d_q), B, g, E, S, ws.data_ptr(), ws.numel(),
+                                                 _stream(seg.device)), "iqm_map_train_backward")
+    return d_seg, d_q
+
+
 def _seg_loss_layout(preds: torch.Tensor, mask: torch.Tensor):
     """preds [B,2,S,S] (or [B,S,S] / [B,P] for a single channel) + mask with B*P elements -> (B, P, img_stride,
     chan_stride, fp32 contiguous mask)."""

@@ -675,6 +675,46 @@ int aaclip_similarity_map_train_backward(const float* seg, const float* anchors,
   return finish("similarity_map_train_backward");
 }
 
+// the checks aaclip_iqm_map_train and its backward share (the workspace size, the backward's last check, is its own)
+static int iqm_map_train_checks(const char* shape_msg, const char* align_msg, int B, int g, int E, int S,
+                                const void* const (&ptrs)[7]) {
+  REQUIRE(map_shape_ok(B, g, S) && S <= SIMMAP_BWD_MAX_S, shape_msg);
+  REQUIRE_ROW_WIDTH(E);
+  for (const void* p : ptrs)
+    if ((uintptr_t)p & 15) return fail(-1, align_msg);
+  return 0;
+}
+
+int aaclip_iqm_map_train(const float* seg, const float* queries, float* grid_out, float* out, int B, int g, int E, int S,
+                         void* stream) {
+  REQUIRE(seg && queries && grid_out && out, "iqm_map_train: null pointer");
+  const void* const ptrs[7] = {seg, queries, grid_out, out, nullptr, nullptr, nullptr};
+  if (int rc = iqm_map_train_checks("iqm_map_train: bad shape (grid <= 40, size <= 2048)",
+                                    "iqm_map_train: pointers must be 16-byte aligned", B, g, E, S, ptrs))
+    return rc;
+  launch_iqm_map_train(seg, queries, grid_out, out, B, g, E, S, (hipStream_t)stream);
+  return finish("iqm_map_train");
+}
+
+size_t aaclip_iqm_map_train_backward_workspace_bytes(int B, int g, int E, int S) {
+  if (B <= 0 || g <= 0 || E <= 0 || S <= 0) return 0;
+  return iqm_map_train_bwd_ws_bytes(B, g, E, S);
+}
+
+int aaclip_iqm_map_train_backward(const float* seg, const float* queries, const float* grid, const float* d_preds,
+                                  float* d_seg, float* d_queries, int B, int g, int E, int S, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  REQUIRE(seg && queries && grid && d_preds && ws, "iqm_map_train_backward: null pointer");
+  REQUIRE(d_seg || d_queries, "iqm_map_train_backward: nothing to compute (both outputs are null)");
+  const void* const ptrs[7] = {seg, queries, grid, d_preds, d_seg, d_queries, ws};
+  if (int rc = iqm_map_train_checks("iqm_map_train_backward: bad shape (grid <= 40, size <= 2048)",
+                                    "iqm_map_train_backward: pointers must be 16-byte aligned", B, g, E, S, ptrs))
+    return rc;
+  REQUIRE(ws_bytes >= iqm_map_train_bwd_ws_bytes(B, g, E, S), "iqm_map_train_backward: workspace too small");
+  launch_iqm_map_train_bwd(seg, queries, grid, d_preds, d_seg, d_queries, B, g, E, S, ws, (hipStream_t)stream);
+  return finish("iqm_map_train_backward");
+}
+
 size_t aaclip_seg_loss_workspace_bytes(int B) { return B > 0 ? seg_loss_ws_bytes(B) : 0; }
 
 int aaclip_seg_loss(const float* preds, long img_stride, long chan_stride, const float* mask, int terms, float* loss,

@@ -148,6 +148,19 @@ void launch_similarity_map_train_bwd(const float* seg, const float* anchors, lon
                                      const float* d_preds, float* d_anchors, float* d_seg, int B, int g, int E, int S,
                                      void* ws, hipStream_t s);
 
+// ---- iqm_loss.hip : the IQM map term of the stage-2 loss, one tap level per call (half-pixel upsample of (1 - p, p))
+constexpr int IQ_QCHUNKS = 32;   // patch chunks of the query-gradient sum: E / 256 * 32 * B workgroups
+// chunk sums [B, IQ_QCHUNKS, 2, E] | T [B, S, g] | dz [B, P] | per-row scalars [B, P, 4] | [B, IQ_QCHUNKS, 2]
+inline size_t iqm_map_train_bwd_ws_bytes(int B, int g, int E, int S) {
+  return ((size_t)B * S * g + (size_t)B * g * g * 5 + (size_t)B * IQ_QCHUNKS * 2 * ((size_t)E + 1)) * 4;
+}
+// grid (out) [B, g*g] = launch_iqm_scores' values; out [B, 2, S, S]
+void launch_iqm_map_train(const float* seg, const float* q, float* grid, float* out, int B, int g, int E, int S,
+                          hipStream_t s);
+// d_seg [B, g*g, E] and d_q [B, 2, E]: either may be null
+void launch_iqm_map_train_bwd(const float* seg, const float* q, const float* grid, const float* d_preds, float* d_seg,
+                              float* d_q, int B, int g, int E, int S, void* ws, hipStream_t s);
+
 // ---- text_backward.hip : backward of the adapted text tower (fp32, fixed-order reductions)
 constexpr int ATTN_BWD_MAX_L = 128;
 constexpr int WGRAD_MAX_CHUNKS = 16;

@@ -2,11 +2,14 @@
 to end -- encode_text forward and backward (aaclip_hip.autograd.TextTower), the train-mode similarity map and the
 segmentation loss with their backward kernels.  Behaviour follows reference train.py:57-113.
 
-Of stage 2 (the image adapters) only `stage2_text_loss` is here: the forward with a graph
-(aaclip_hip.autograd.visual_heads) and the part of the loss that does not involve the IQM branch.
+Of stage 2 (the image adapters) the loss is here: `stage2_text_loss`, the forward with a graph
+(aaclip_hip.autograd.visual_heads) and the part of the loss that does not involve the IQM branch, and `stage2_loss`,
+which adds the IQM map terms (aaclip_hip.autograd.iqm_map_train) for given final queries, with their gradient to the seg
+tokens and to those queries.
 
-Not here: the training-time datasets, main(), the IQM terms of the stage-2 loss and
-train_image_adapter.  `train_text_adapter` is fed by any iterable of {"image", "mask", "class_name"} batches.
+Not here: the training-time datasets, main(), the IQM branch's own backward (from the queries'
+gradient to the branch's parameters and the tap streams) and train_image_adapter.  `train_text_adapter` is fed by any
+iterable of {"image", "mask", "class_name"} batches.
 """
 from __future__ import annotations
 
@@ -22,6 +25,7 @@ from aaclip_hip import autograd
 CHECKPOINT_NAME = "text_adapter.pth"
 # reference train.py:131-132,156,163: the weight of the text-anchor maps against the IQM maps, and the two halvings
 TEXT_WEIGHT = 0.6
+IQM_WEIGHT = 0.4
 CLS_LOSS_SCALE = 0.5
 SEG_LOSS_SCALE = 0.5
 
@@ -89,12 +93,45 @@ def stage2_text_loss(adapted_model, image, mask, label, anchors, img_size):
     The forward (autograd.visual_heads), the maps and the segmentation loss run on the HIP kernels, forward and backward;
     the [B, 2] matmul and cross-entropy of the classification term are host-side torch ops, like
     forward_utils.image_score.
-    Not built: the IQM terms of the loss (train.py:165-212: the branch has no backward) and train_image_adapter (the
-    epoch loop, clipping, scheduler and checkpoint around this loss)."""
+    The IQM terms of the loss (train.py:165-212) are added by stage2_loss.  Not built: train_image_adapter (the epoch
+    loop, clipping, scheduler and checkpoint around this loss)."""
+    return _stage2_text_terms(adapted_model, image, mask, label, anchors, img_size)[0]
+
+
+def _stage2_text_terms(adapted_model, image, mask, label, anchors, img_size):
+    """-> (the loss of stage2_text_loss, the seg tokens it was computed from)"""
     seg_tokens, det = autograd.visual_heads(adapted_model, image)
     cls_preds = torch.matmul(det.unsqueeze(1), anchors)[:, 0]
     loss = CLS_LOSS_SCALE * nn.functional.cross_entropy(cls_preds, label)
     for seg in seg_tokens:
         preds = FU.calculate_similarity_map(seg, anchors, img_size)
         loss = loss + TEXT_WEIGHT * SEG_LOSS_SCALE * FU.calculate_seg_loss(preds, mask)
+    return loss, seg_tokens
+
+
+def iqm_map_loss(seg, iqm_queries, mask, img_size):
+    """One tap level's IQM term (reference train.py:185-212): IQM_WEIGHT * SEG_LOSS_SCALE * seg_loss of the two-channel
+    half-pixel upsample of (1 - p, p), p = sigmoid(cos(seg, q_abnormal) - cos(seg, q_normal))."""
+    preds = autograd.iqm_map_train(seg, iqm_queries, img_size)
+    return IQM_WEIGHT * SEG_LOSS_SCALE * FU.calculate_seg_loss(preds, mask)
+
+
+def stage2_loss(adapted_model, image, mask, label, anchors, img_size, iqm_queries):
+    """The stage-2 loss (reference train.py:152-212): stage2_text_loss plus, per tap level,
+        IQM_WEIGHT * SEG_LOSS_SCALE * seg_loss(iqm_map_train(seg, iqm_queries, img_size), mask)
+    iqm_queries [B, 2, E]: the IQM branch's final queries, row 0 normal and row 1 abnormal.  Any tensor of that shape
+    serves; if it requires grad it receives its gradient (the input of the branch's backward), and the seg tokens pass
+    theirs on to seg_proj and the layer adapters.  Until the branch has a backward the queries of a training step are
+    model(image, text_embeddings=anchors)[2].last_hidden_state, which carries no graph: the branch's parameters do not
+    train yet.
+    A query width other than the seg tokens' raises ValueError: the reference draws a fresh random nn.Linear at every
+    step there (train.py:175-179), which cannot be reproduced.
+    Not built: the IQM branch's own backward and train_image_adapter."""
+    E = adapted_model.image_adapter["seg_proj"][0].weight.shape[0]
+    if iqm_queries.dim() != 3 or iqm_queries.shape[1] != 2 or iqm_queries.shape[-1] != E:
+        raise ValueError(f"stage2_loss: iqm_queries must be [B, 2, {E}] (the seg tokens' width), got "
+                         f"{tuple(iqm_queries.shape)}")
+    loss, seg_tokens = _stage2_text_terms(adapted_model, image, mask, label, anchors, img_size)
+    for seg in seg_tokens:
+        loss = loss + iqm_map_loss(seg, iqm_queries, mask, img_size)
     return loss

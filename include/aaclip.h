@@ -213,6 +213,32 @@ int aaclip_similarity_map_train_backward(const float* seg, const float* anchors,
                                          const float* preds, const float* d_preds, float* d_anchors, float* d_seg,
                                          int B, int g, int E, int S, void* ws, size_t ws_bytes, void* stream);
 
+/* The IQM map term of the stage-2 loss (reference train.py:173-212), one tap level per call.
+ *   p[b, i]      = sigmoid(cos(seg[b, i], queries[b, 1]) - cos(seg[b, i], queries[b, 0]))     (row 0 normal, 1 abnormal)
+ *   out[b, 1]    = half-pixel (align_corners=False) bilinear upsample of p to S x S: bit-identical to aaclip_iqm_map
+ *                  with this one level, w_iqm = 1 and no base
+ *   out[b, 0]    = the same interpolation of the values 1 - p (the reference interpolates the concatenated pair)
+ * seg [B, g*g, E], queries [B, 2, E], grid_out [B, g*g] (= p, kept for the backward), out [B, 2, S, S]; all fp32 and
+ * 16-byte aligned.  g <= 40, S <= 2048, E a supported row width.
+ * cos is F.cosine_similarity's x.y / sqrt(max(|x|^2 |y|^2, 1e-16)). */
+int aaclip_iqm_map_train(const float* seg, const float* queries, float* grid_out, float* out, int B, int g, int E, int S,
+                         void* stream);
+/* Its backward: d_preds [B, 2, S, S] -> d_seg [B, g*g, E] and d_queries [B, 2, E]; either may be NULL, not both.
+ *   dU = d_preds[:, 1] - d_preds[:, 0]; the transpose of the half-pixel upsample as a gather over each coarse cell's
+ *   support window (coarse index 0 collects every fine index whose source clamps to 0, the last one both terms);
+ *   dz = p (1 - p) dgrid;
+ *   d_seg[b, i]     = dz_i [(q1 / (|f||q1|) - c1 f / |f|^2) - (q0 / (|f||q0|) - c0 f / |f|^2)]
+ *   d_queries[b, 1] = sum_i (dz_i / |f_i|) f_i / |q1| - (sum_i dz_i c1_i) q1 / |q1|^2, row 0 likewise with q0, c0 and
+ *                     the opposite sign; the sum over i in 32 chunks, reduced in chunk order.
+ * Degenerate rows: the gradient is that of the function the forward computes.  Where |f|^2 |q|^2 <= 1e-16 the clamp is
+ * active and the denominator is a constant 1e-8: only the x.y term is differentiated, the c f / |f|^2 and c q / |q|^2
+ * terms are absent (torch clamps the two norms separately there and differs).  Every output stays finite.
+ * The same checks as the forward, all before the first launch; the workspace size is the last one. */
+size_t aaclip_iqm_map_train_backward_workspace_bytes(int B, int g, int E, int S);
+int aaclip_iqm_map_train_backward(const float* seg, const float* queries, const float* grid, const float* d_preds,
+                                  float* d_seg, float* d_queries, int B, int g, int E, int S, void* ws, size_t ws_bytes,
+                                  void* stream);
+
 /* Segmentation loss, reference forward_utils.py:21-108,223-227 (calculate_seg_loss = FocalLoss + BinaryDiceLoss on
  * channel 0 against 1 - mask + BinaryDiceLoss on channel 1 against mask):
  *   focal = mean over B*P pixels of -(1 - pt)^2 log pt,  pt = sum_c clamp(onehot_c, 1e-5, 1 - 1e-5) p_c + 1e-5
