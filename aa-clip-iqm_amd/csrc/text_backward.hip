@@ -353,6 +353,8 @@ void launch_layernorm_backward(const float* x, const float* w, const float* dy, 
 // With c = w <dy, a> (the gradient of s):
 //   du = (1 - w) dy + c / (|a| |u|) u          (direct part: the path through z = u Wa^T is the caller's GEMM)
 //   da = w s dy - c |u| / |a|^3 a,   dz = da * LeakyReLU'(z)
+// LeakyReLU'(z) is 1 for z > 0 and 0.01 for z <= 0: the kink itself (z = +0 or -0) takes the negative side's slope, as
+// the backward of torch's leaky_relu does.
 // dz may alias z, du may alias dy.
 template <int NCH>
 __global__ __launch_bounds__(256) void adapter_mix_bwd_kernel(const float* u, const float* z, const float* dy, float* dz,
@@ -386,7 +388,7 @@ __global__ __launch_bounds__(256) void adapter_mix_bwd_kernel(const float* u, co
     for (int e = 0; e < 4; ++e) {
       const float zz = zv[c][e];
       const float da = k_dy * gv[c][e] - k_a * leaky(zz);
-      odz[e] = zz >= 0.f ? da : 0.01f * da;
+      odz[e] = zz > 0.f ? da : 0.01f * da;
       odu[e] = (1.0f - weight) * gv[c][e] + k_u * uv[c][e];
     }
     *(f32x4*)(dz + row * D + col) = odz;
@@ -408,7 +410,8 @@ void launch_adapter_mix_backward(const float* u, const float* z, const float* dy
 // ------------------------------------------------------------------------------------------------ element-wise
 // mode 0: out = gelu_erf(f)                       (the c_proj input, recomputed from the c_fc pre-activation)
 // mode 1: out = g * gelu_erf'(f), gelu' = Phi(f) + f phi(f)
-// mode 2: out = g * act'(f)  (act 0 identity, 1 LeakyReLU(0.01), 2 ReLU)
+// mode 2: out = g * act'(f)  (act 0 identity, 1 LeakyReLU(0.01), 2 ReLU; at f = 0 both take the slope of the negative
+//         side, 0.01 and 0, like torch)
 // mode 3: out = f + g
 template <int MODE>
 __global__ __launch_bounds__(256) void ew_kernel(const float* f, const float* g, float* out, long n4, int act) {
@@ -427,7 +430,7 @@ __global__ __launch_bounds__(256) void ew_kernel(const float* f, const float* g,
       const float pdf = 0.39894228040143267794f * expf(-0.5f * x * x);
       o[e] = gv[e] * (cdf + x * pdf);
     } else if (MODE == 2) {
-      const float d = act == 1 ? (x >= 0.f ? 1.0f : 0.01f) : act == 2 ? (x > 0.f ? 1.0f : 0.f) : 1.0f;
+      const float d = act == 1 ? (x > 0.f ? 1.0f : 0.01f) : act == 2 ? (x > 0.f ? 1.0f : 0.f) : 1.0f;
       o[e] = gv[e] * d;
     } else {
       o[e] = x + gv[e];
@@ -452,6 +455,7 @@ void launch_add_rows(const float* a, const float* b, float* out, long n, hipStre
 // Backward of the tail of the tap / det head (rowops.hip: normalize_rows_kernel, det_partial_kernel), in place on the
 // projection rows z [B*L, E] (pre-activation).  Forward: a = act(z), n = max(|a|, 1e-12), y = a / n.  Backward:
 //   dz = act'(z) (g - y <y, g>) / n      (a row below the clamp has a constant n: dz = act'(z) g / n)
+// act'(0) is the slope of the negative side (LeakyReLU 0.01, ReLU 0), like torch.
 // det == 0: g = row (b, t - 1) of d [B, L-1, E], the gradient of the unit patch rows.  det != 0: d is [B, E], the
 // gradient of the mean over an image's L - 1 unit rows, so every patch row of image b takes g = d[b] / (L - 1).
 // The CLS row (t = 0) of every image reaches neither output: dz = 0, so the products behind run over all B*L rows.
@@ -498,7 +502,7 @@ __global__ __launch_bounds__(256) void head_norm_bwd_kernel(float* z, const floa
     for (int e = 0; e < 4; ++e) {
       const float x = zv[c][e];
       const float a = act == 1 ? leaky(x) : act == 2 ? fmaxf(x, 0.f) : x;
-      const float k = act == 1 ? (x >= 0.f ? 1.0f : 0.01f) : act == 2 ? (x > 0.f ? 1.0f : 0.f) : 1.0f;
+      const float k = act == 1 ? (x > 0.f ? 1.0f : 0.01f) : act == 2 ? (x > 0.f ? 1.0f : 0.f) : 1.0f;
       o[e] = k * ((gv[c][e] - (a * inv) * yg) * inv);
     }
     *(f32x4*)(zp + (c * 64 + lane) * 4) = o;

@@ -301,7 +301,9 @@ int aaclip_layernorm_backward(const float* x, const float* w, const float* d_y, 
 
 /* Backward of the adapter mix y = weight * a |u| / |a| + (1 - weight) * u with a = LeakyReLU(z), z = u Wa^T
  * (aaclip_adapter_mix; both norms are functions of the inputs): d_z for the weight gradient (and for d_z Wa, the part of
- * d u that runs through the product) and the direct d_u.  d_z may alias z, d_u may alias d_y. */
+ * d u that runs through the product) and the direct d_u.  d_z may alias z, d_u may alias d_y.  LeakyReLU's derivative is
+ * 1 for z > 0 and 0.01 for z <= 0 here and in every backward below: the kink itself takes the negative side's slope,
+ * like the backward of torch's leaky_relu (AACLIP_ACT_RELU: 0 at 0). */
 int aaclip_adapter_mix_backward(const float* u, const float* z, const float* d_y, float* d_z, float* d_u, long rows,
                                 int D, float weight, void* stream);
 
