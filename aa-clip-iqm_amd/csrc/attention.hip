@@ -1255,15 +1255,14 @@ void launch_attention(int dtype, const void* qkv, void* ctx, int B, int L, int H
     const long totl = (long)nqt * H * B;
     const int per_xcd = (int)((totl + 7) / 8), tot = (int)totl;
     dim3 g((unsigned)(per_xcd * 8));
-#define ATTN_LAUNCH_S(LQ, VLO) hipLaunchKernelGGL((attn16s_kernel<LQ, VLO>), g, dim3(256), 0, s, (const f16*)qkv, (f16*)ctx, L, H, causal, nqt, tot, per_xcd, hi8)
-    if (qk8) {        // block path, long rows: [q k v hi | q8 | k8] records, correction products on the e4m3 MFMA
-      hipLaunchKernelGGL((attn16s_kernel<true, false, true>), g, dim3(256), 0, s, (const f16*)qkv, (f16*)ctx, L, H, causal, nqt, tot, per_xcd, hi8);
-    } else if (L >= 512) {   // long rows: v's lo half is not read (see attn16s_kernel)
-      if (log2q) ATTN_LAUNCH_S(true, false); else ATTN_LAUNCH_S(false, false);
-    } else {
-      if (log2q) ATTN_LAUNCH_S(true, true); else ATTN_LAUNCH_S(false, true);
-    }
-#undef ATTN_LAUNCH_S
+    // lng: long rows (L >= 512), v's lo half is not read (see attn16s_kernel); q8: block path, long rows:
+    // [q k v hi | q8 | k8] records, correction products on the e4m3 MFMA
+    auto run = [&](auto lq, auto lng, auto q8) {
+      hipLaunchKernelGGL((attn16s_kernel<decltype(lq)::value, !decltype(lng)::value, decltype(q8)::value>), g, dim3(256), 0, s,
+                         (const f16*)qkv, (f16*)ctx, L, H, causal, nqt, tot, per_xcd, hi8);
+    };
+    if (qk8) run(std::true_type{}, std::true_type{}, std::true_type{});
+    else dispatch_bool(L >= 512, [&](auto lng) { dispatch_bool(log2q, [&](auto lq) { run(lq, lng, std::false_type{}); }); });
   } else if (dtype == AACLIP_F32 && L >= 64 && g_attn_variant != 1) {   // fp32 MFMA kernel (32 queries per wave)
     dim3 g((L + 127) / 128, H, B);
     hipLaunchKernelGGL(attn32m_kernel, g, dim3(256), 0, s, (const float*)qkv, (float*)ctx, L, H, causal);
@@ -1278,19 +1277,20 @@ void launch_attention(int dtype, const void* qkv, void* ctx, int B, int L, int H
     const int per_xcd = (int)((total + 7) / 8);
     dim3 g((unsigned)(per_xcd * 8)), blk(256);
     const int tot = (int)total;
-#define ATTN_LAUNCH(TT, LQ) hipLaunchKernelGGL((attn16x2_kernel<TT, LQ>), g, blk, 0, s, (const TT*)qkv, (TT*)ctx, L, H, causal, nqt, tot, per_xcd)
-    if (dtype == AACLIP_F16) { if (log2q) ATTN_LAUNCH(f16, true); else ATTN_LAUNCH(f16, false); }
-    else { if (log2q) ATTN_LAUNCH(bf16, true); else ATTN_LAUNCH(bf16, false); }
-#undef ATTN_LAUNCH
+    dispatch_bool(dtype == AACLIP_F16, [&](auto half) {
+      using T = std::conditional_t<decltype(half)::value, f16, bf16>;
+      dispatch_bool(log2q, [&](auto lq) {
+        hipLaunchKernelGGL((attn16x2_kernel<T, decltype(lq)::value>), g, blk, 0, s, (const T*)qkv, (T*)ctx, L, H, causal, nqt, tot, per_xcd);
+      });
+    });
   } else {
     dim3 g((L + 127) / 128, H, B);
-    if (dtype == AACLIP_F16) {
-      if (log2q) hipLaunchKernelGGL((attn16_kernel<f16, true>), g, dim3(256), 0, s, (const f16*)qkv, (f16*)ctx, L, H, causal);
-      else hipLaunchKernelGGL((attn16_kernel<f16, false>), g, dim3(256), 0, s, (const f16*)qkv, (f16*)ctx, L, H, causal);
-    } else {
-      if (log2q) hipLaunchKernelGGL((attn16_kernel<bf16, true>), g, dim3(256), 0, s, (const bf16*)qkv, (bf16*)ctx, L, H, causal);
-      else hipLaunchKernelGGL((attn16_kernel<bf16, false>), g, dim3(256), 0, s, (const bf16*)qkv, (bf16*)ctx, L, H, causal);
-    }
+    dispatch_bool(dtype == AACLIP_F16, [&](auto half) {
+      using T = std::conditional_t<decltype(half)::value, f16, bf16>;
+      dispatch_bool(log2q, [&](auto lq) {
+        hipLaunchKernelGGL((attn16_kernel<T, decltype(lq)::value>), g, dim3(256), 0, s, (const T*)qkv, (T*)ctx, L, H, causal);
+      });
+    });
   }
 }
 

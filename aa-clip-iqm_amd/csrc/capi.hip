@@ -122,7 +122,7 @@ int aaclip_profile_end(float* ms, int* tags, int max_n) {
 }
 
 int aaclip_set_gemm_variant(int v) {
-  REQUIRE(v >= 0 && (v >> 18) == 0, "set_gemm_variant: unknown bits");
+  REQUIRE(v >= 0 && (v >> 18) == 0 && !(v & (1 << 16)), "set_gemm_variant: unknown bits");
   // Validate everything before changing anything: a rejected call leaves the selection as it was.
   const int gv = v & 0xFF, av = (v >> 8) & 0xFF;
   REQUIRE((gv <= 1 || (gv >= 80 && gv <= 82)) && av <= 1,
@@ -130,7 +130,6 @@ int aaclip_set_gemm_variant(int v) {
   set_gemm_variant(gv);
   set_attn_variant(av);   // bits 8..15: attention kernel selection
   g_ln_fold = ((v >> 17) & 1) ? 0 : 1;
-  set_tail_peel((v >> 16) & 1);  // bit 16: peel the partial last round to the 128-tile kernel (measured: -1.6 %, off by default)
   return 0;
 }
 

@@ -258,13 +258,7 @@ __global__ __launch_bounds__(256) void gemm32_kernel(GemmParams p) {
 
 template <typename T>
 static void launch16(int epi, const GemmParams& p, dim3 g, hipStream_t s) {
-  switch (epi) {
-    case EPI_BIAS: hipLaunchKernelGGL((gemm16_kernel<T, EPI_BIAS>), g, dim3(256), 0, s, p); break;
-    case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm16_kernel<T, EPI_BIAS_GELU>), g, dim3(256), 0, s, p); break;
-    case EPI_BIAS_RESID: hipLaunchKernelGGL((gemm16_kernel<T, EPI_BIAS_RESID>), g, dim3(256), 0, s, p); break;
-    case EPI_ACT_F32: hipLaunchKernelGGL((gemm16_kernel<T, EPI_ACT_F32>), g, dim3(256), 0, s, p); break;
-    case EPI_PATCH: hipLaunchKernelGGL((gemm16_kernel<T, EPI_PATCH>), g, dim3(256), 0, s, p); break;
-  }
+  dispatch_epi(epi, [&](auto e) { hipLaunchKernelGGL((gemm16_kernel<T, decltype(e)::value>), g, dim3(256), 0, s, p); });
 }
 
 // ------------------------------------------------------------------ split fp16 (AACLIP_F16X2), small M
@@ -370,13 +364,7 @@ __global__ __launch_bounds__(256, 2) void gemm16s_kernel(GemmParams p) {
 
 template <int NP>
 static void launch16s(int epi, const GemmParams& p, dim3 g, hipStream_t s) {
-  switch (epi) {
-    case EPI_BIAS: hipLaunchKernelGGL((gemm16s_kernel<EPI_BIAS, NP>), g, dim3(256), 0, s, p); break;
-    case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm16s_kernel<EPI_BIAS_GELU, NP>), g, dim3(256), 0, s, p); break;
-    case EPI_BIAS_RESID: hipLaunchKernelGGL((gemm16s_kernel<EPI_BIAS_RESID, NP>), g, dim3(256), 0, s, p); break;
-    case EPI_ACT_F32: hipLaunchKernelGGL((gemm16s_kernel<EPI_ACT_F32, NP>), g, dim3(256), 0, s, p); break;
-    case EPI_PATCH: hipLaunchKernelGGL((gemm16s_kernel<EPI_PATCH, NP>), g, dim3(256), 0, s, p); break;
-  }
+  dispatch_epi(epi, [&](auto e) { hipLaunchKernelGGL((gemm16s_kernel<decltype(e)::value, NP>), g, dim3(256), 0, s, p); });
 }
 
 const char* gemm_check(int dtype, int epi, const GemmParams& p) {
@@ -398,8 +386,6 @@ const char* gemm_check(int dtype, int epi, const GemmParams& p) {
   return nullptr;
 }
 
-static int g_tail_peel = 0;  // measured: not a win (the 128-tile kernel is too slow for the peeled rows)
-void set_tail_peel(int v) { g_tail_peel = v; }
 // 0 automatic, 1 force the 128-tile kernel, 80 / 81 / 82 force the 8-wave 256 x 256 kernel (one tile per workgroup) / the
 // 4-wave 256 x 128 half-tile kernel / the walking 8-wave kernel (all bit-identical)
 static int g_gemm_variant = 0;
@@ -446,8 +432,7 @@ bool set_gemm_variant(int v) {
 // those are the kernels whose epilogue implements the LayerNorm-folding options of GemmParams.
 bool gemm_routes_to_256t(int dtype, const GemmParams& p) {
   if (dtype == AACLIP_F32 || dtype == AACLIP_F16X2 || !gemm256_applicable(dtype, p) || p.M < 4096) return false;
-  if (g_gemm_variant == 1 || g_tail_peel) return false;
-  return true;
+  return g_gemm_variant != 1;
 }
 
 // split fp16: true when launch_gemm will run the 256-tile kernel -- the one whose EPI_BIAS epilogue can write the
@@ -455,12 +440,16 @@ bool gemm_routes_to_256t(int dtype, const GemmParams& p) {
 bool gemm_split_routes_to_256t(const GemmParams& p) { return g_gemm_variant != 1 && split256_applicable(p) && p.M >= 4096; }
 
 void launch_gemm(int dtype, int epi, const GemmParams& p, hipStream_t s) {
+  // the attention kernel's e4m3 records (GemmParams::out_qk8) are written by one epilogue only
+  if (p.out_qk8 && !(epi == EPI_BIAS && dtype == AACLIP_F16X2 && gemm_split_routes_to_256t(p))) {
+    set_launch_error("gemm: out_qk8 needs the bias epilogue of the split 256-tile kernel");
+    return;
+  }
   if (dtype == AACLIP_F16X2) {   // split fp16: the default 256-tile kernel from M = 4096 rows, else the 128-tile kernel
     if (gemm_split_routes_to_256t(p)) {
       launch_gemm256t(dtype, epi, p, s, big_kernel_form(dtype));
       return;
     }
-    if (p.out_qk8) { set_launch_error("gemm: out_qk8 needs the 256-tile kernel"); return; }
     dim3 g(((p.M + 127) / 128) * (p.N / 128));
     if (p.w_exact16) launch16s<3>(epi, p, g, s);
     else launch16s<4>(epi, p, g, s);
@@ -468,29 +457,6 @@ void launch_gemm(int dtype, int epi, const GemmParams& p, hipStream_t s) {
   }
   // variants: 1 the 128-tile kernel; otherwise the 256-tile kernels from M = 4096 rows
   if (g_gemm_variant != 1 && gemm256_applicable(dtype, p) && p.M >= 4096) {
-    // Tail peeling: 256x256 tiles run one per CU in rounds of 256.  When the last round would be
-    // less than 60 % full, the rows of that partial round go to the 128-tile kernel instead (two
-    // workgroups per CU, finer granularity); both kernels produce bit-identical results.
-    const int tiles_n = p.N / 256, tiles_m = (p.M + 255) / 256;
-    const long tiles = (long)tiles_m * tiles_n;
-    const long rem = tiles % 256;
-    if (g_tail_peel && epi != EPI_PATCH && tiles > 256 && rem > 0 && rem < 154) {
-      const int m_full = (int)((tiles - rem) / tiles_n);   // whole M tiles covered by full rounds
-      const long rows_full = (long)m_full * 256;
-      if (rows_full > 0 && rows_full < p.M) {
-        GemmParams a = p, b = p;
-        a.M = (int)rows_full;
-        const size_t es = 2, os = (epi == EPI_BIAS || epi == EPI_BIAS_GELU) ? 2 : 4;
-        b.A = (const char*)p.A + rows_full * p.lda * es;
-        b.out = (char*)p.out + rows_full * p.ldc * os;
-        b.M = p.M - (int)rows_full;
-        launch_gemm256t(dtype, epi, a, s, big_kernel_form(dtype));
-        const int t128 = ((b.M + 127) / 128) * (b.N / 128);
-        if (dtype == AACLIP_F16) launch16<f16>(epi, b, dim3(t128), s);
-        else launch16<bf16>(epi, b, dim3(t128), s);
-        return;
-      }
-    }
     launch_gemm256t(dtype, epi, p, s, big_kernel_form(dtype));
     return;
   }
@@ -500,25 +466,11 @@ void launch_gemm(int dtype, int epi, const GemmParams& p, hipStream_t s) {
     launch16<f16>(epi, p, g, s);
   } else if (dtype == AACLIP_BF16) {
     launch16<bf16>(epi, p, g, s);
+  } else if (tiles < 128) {   // fewer 128-tiles than half the CUs: 64 x 64 tiles (same sums, four times the workgroups)
+    dim3 g64(((p.M + 63) / 64) * (p.N / 64));
+    dispatch_epi(epi, [&](auto e) { hipLaunchKernelGGL((gemm32_kernel<decltype(e)::value, 64>), g64, dim3(256), 0, s, p); });
   } else {
-    if (tiles < 128) {   // fewer 128-tiles than half the CUs: 64 x 64 tiles (same sums, four times the workgroups)
-      dim3 g64(((p.M + 63) / 64) * (p.N / 64));
-      switch (epi) {
-        case EPI_BIAS: hipLaunchKernelGGL((gemm32_kernel<EPI_BIAS, 64>), g64, dim3(256), 0, s, p); break;
-        case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm32_kernel<EPI_BIAS_GELU, 64>), g64, dim3(256), 0, s, p); break;
-        case EPI_BIAS_RESID: hipLaunchKernelGGL((gemm32_kernel<EPI_BIAS_RESID, 64>), g64, dim3(256), 0, s, p); break;
-        case EPI_ACT_F32: hipLaunchKernelGGL((gemm32_kernel<EPI_ACT_F32, 64>), g64, dim3(256), 0, s, p); break;
-        case EPI_PATCH: hipLaunchKernelGGL((gemm32_kernel<EPI_PATCH, 64>), g64, dim3(256), 0, s, p); break;
-      }
-      return;
-    }
-    switch (epi) {
-      case EPI_BIAS: hipLaunchKernelGGL((gemm32_kernel<EPI_BIAS>), g, dim3(256), 0, s, p); break;
-      case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm32_kernel<EPI_BIAS_GELU>), g, dim3(256), 0, s, p); break;
-      case EPI_BIAS_RESID: hipLaunchKernelGGL((gemm32_kernel<EPI_BIAS_RESID>), g, dim3(256), 0, s, p); break;
-      case EPI_ACT_F32: hipLaunchKernelGGL((gemm32_kernel<EPI_ACT_F32>), g, dim3(256), 0, s, p); break;
-      case EPI_PATCH: hipLaunchKernelGGL((gemm32_kernel<EPI_PATCH>), g, dim3(256), 0, s, p); break;
-    }
+    dispatch_epi(epi, [&](auto e) { hipLaunchKernelGGL((gemm32_kernel<decltype(e)::value>), g, dim3(256), 0, s, p); });
   }
 }
 

@@ -296,6 +296,35 @@ AACLIP_DEV void epilogue256t(const GemmParams& p, f32x4 (&acc)[8][4], char* smem
 }
 
 // ---------------------------------------------------------------------------
+// Shared by the three kernels below.  K-loop vocabulary (#undef'd after the last kernel):
+#define WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+#define WAIT_LGKM(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
+#define LGKM0 WAIT_LGKM(0);
+#define BAR __builtin_amdgcn_s_barrier();
+#define PINB __builtin_amdgcn_sched_barrier(0);
+// Split kernels (no register to spare, see srcA): the offset of the odd 16-row tile is recomputed from the even one
+// at every use -- 16 rows further = 8 row pairs = 2048 bytes, and the swizzle's bit 3 flips: (off ^ 128) + 2048.  The
+// xor goes through an opaque asm so that hipcc does not hoist it back into a loop-invariant register.
+#define ODD_OFF(off) ({ int o_; asm volatile("v_xor_b32 %0, 0x80, %1" : "=v"(o_) : "v"(off)); o_ + 2048; })
+// one MFMA of output quadrant (a, b), row tile t, column tile u: an fp16 k-step (MMV: the one-set kernel's plain
+// fragments), or an e4m3 tile -- the two 16-byte fragments of a row are one 32-byte operand (common.h, mma_e4m3); W
+// rows are the MFMA's A side
+#define MMV(a, b, t, u, ks) acc[4 * (a) + (t)][2 * (b) + (u)] = Mma16<T>::mma(fn[u][ks], fm[t][ks], acc[4 * (a) + (t)][2 * (b) + (u)]);
+#define MM(FN, a, b, t, u, ks) acc[4 * (a) + (t)][2 * (b) + (u)] = Mma16<T>::mma(FN[u].get(ks), fm[t].get(ks), acc[4 * (a) + (t)][2 * (b) + (u)]);
+#define MM8(FN, a, b, t, u, KIND) acc[4 * (a) + (t)][2 * (b) + (u)] = mma_e4m3k<(KIND) == 1 ? 1 : 2>(FN[u], fm[t], acc[4 * (a) + (t)][2 * (b) + (u)], SC_PACK);
+// e8m0 scale bytes of the correction tiles (stored operand = value * 2^EXP): T1 act | T1 weight | T2 weight | T2 act
+constexpr int SC_PACK = (127 - SPLIT8_ACT_LO_EXP) | ((127 - SPLIT8_W_HI_EXP) << 8) | ((127 - SPLIT8_W_LO_EXP) << 16) |
+                        ((127 - SPLIT8_ACT_HI_EXP) << 24);
+// LayerNorm folding: this lane's (rstd, -mean*rstd) pairs, requested before the K loop so that they are there at the epilogue
+AACLIP_DEV void prefetch_row_ab(const GemmParams& p, int m_base, int c16, f32x2 (&ab_pre)[8]) {
+#pragma unroll
+  for (int mi = 0; mi < 8; ++mi) {
+    int row = m_base + mi * 16 + c16;
+    row = row < p.M ? row : p.M - 1;
+    ab_pre[mi] = *(const f32x2*)(p.row_ab + 2L * row);
+  }
+}
+
 // Staggered kernel with one N-side fragment set: the form for an odd K-tile count (the two-set kernel below takes K
 // tiles in pairs).  Every phase is split into a LOAD segment (counted DMA wait, LDS fragment reads, the phase's two DMA
 // issues) and a COMPUTE segment (16 MFMAs), each closed by s_barrier, and waves 4-7 run
@@ -374,17 +403,12 @@ __global__ __launch_bounds__(512, 2) void gemm16_256v_kernel(GemmParams p, int P
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(smem + (st) * 65536 + dst), 16, (src) * 2, (kt) * 128, 0, 0);
 #define GA(sub, st, kt) { G1(rsA, srcA[sub][0], dstA[sub][0], st, kt) G1(rsA, srcA[sub][1], dstA[sub][1], st, kt) }
 #define GW(sub, st, kt) { G1(rsW, srcW[sub][0], dstW[sub][0], st, kt) G1(rsW, srcW[sub][1], dstW[sub][1], st, kt) }
-#define WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define LGKM0 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#define BAR __builtin_amdgcn_s_barrier();
-#define PINB __builtin_amdgcn_sched_barrier(0);
 #define LD_M(sb, a)                                                                         \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) _Pragma("unroll") for (int t = 0; t < 4; ++t) \
       fm[t][ks] = *(const vec8*)((sb) + offM[ks][t & 1] + ((a) * 2 + (t >> 1)) * 4096);
 #define LD_N(sb, b)                                                                         \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) _Pragma("unroll") for (int t = 0; t < 2; ++t) \
       fn[t][ks] = *(const vec8*)((sb) + offN[ks][t] + (b) * 4096);
-#define MM(a, b, t, u, ks) acc[4 * (a) + (t)][2 * (b) + (u)] = Mma16<T>::mma(fn[u][ks], fm[t][ks], acc[4 * (a) + (t)][2 * (b) + (u)]);
 // COMPUTE segment: 16 MFMAs in three groups.  (The doubled sched_barriers mark where DMA issues once sat; hipcc
 // allocates registers differently with single ones, so they stay as the kernel was measured.)
 #define QUADV(a, b)                                                          \
@@ -392,13 +416,13 @@ __global__ __launch_bounds__(512, 2) void gemm16_256v_kernel(GemmParams p, int P
     LGKM0                                                                    \
     PINB                                                                     \
     __builtin_amdgcn_s_setprio(1);                                           \
-    MM(a, b, 0, 0, 0) MM(a, b, 0, 1, 0) MM(a, b, 1, 0, 0) MM(a, b, 1, 1, 0)  \
+    MMV(a, b, 0, 0, 0) MMV(a, b, 0, 1, 0) MMV(a, b, 1, 0, 0) MMV(a, b, 1, 1, 0)  \
     PINB PINB                                                                \
-    MM(a, b, 2, 0, 0) MM(a, b, 2, 1, 0) MM(a, b, 3, 0, 0) MM(a, b, 3, 1, 0)  \
-    MM(a, b, 0, 0, 1) MM(a, b, 0, 1, 1)                                      \
+    MMV(a, b, 2, 0, 0) MMV(a, b, 2, 1, 0) MMV(a, b, 3, 0, 0) MMV(a, b, 3, 1, 0)  \
+    MMV(a, b, 0, 0, 1) MMV(a, b, 0, 1, 1)                                      \
     PINB PINB                                                                \
-    MM(a, b, 1, 0, 1) MM(a, b, 1, 1, 1) MM(a, b, 2, 0, 1) MM(a, b, 2, 1, 1)  \
-    MM(a, b, 3, 0, 1) MM(a, b, 3, 1, 1)                                      \
+    MMV(a, b, 1, 0, 1) MMV(a, b, 1, 1, 1) MMV(a, b, 2, 0, 1) MMV(a, b, 2, 1, 1)  \
+    MMV(a, b, 3, 0, 1) MMV(a, b, 3, 1, 1)                                      \
     __builtin_amdgcn_s_setprio(0);                                           \
     PINB                                                                     \
   }
@@ -448,13 +472,8 @@ __global__ __launch_bounds__(512, 2) void gemm16_256v_kernel(GemmParams p, int P
 #undef G1
 #undef GA
 #undef GW
-#undef WAIT_VM
-#undef LGKM0
-#undef BAR
-#undef PINB
 #undef LD_M
 #undef LD_N
-#undef MM
 #undef QUADV
   epilogue256t<T, EPI>(p, acc, smem, tm, tn, wave, lane);
 }
@@ -598,23 +617,11 @@ __global__ __launch_bounds__(512, 2) void gemm16_256x_kernel(GemmParams p, int P
     }
 
   f32x4 acc[8][4];   // zeroed at the head of every tile (below)
-  // LayerNorm folding: this lane's (rstd, -mean*rstd) pairs, requested now so that they are there at the epilogue
   f32x2 ab_pre[8];
   const bool fold_pre = NP == 0 && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) && p.row_ab != nullptr;
-  if (fold_pre) {
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi) {
-      int row = tm * 256 + wr * 128 + mi * 16 + c16;
-      row = row < p.M ? row : p.M - 1;
-      ab_pre[mi] = *(const f32x2*)(p.row_ab + 2L * row);
-    }
-  }
+  if (fold_pre) prefetch_row_ab(p, tm * 256 + wr * 128, c16, ab_pre);
 
   const int nk = vtile_count<NP>(p.K);   // (virtual) K tiles
-  // e8m0 scale bytes of the correction tiles (stored operand = value * 2^EXP): T1 act | T1 weight | T2 weight | T2 act
-  int sc_pack = (127 - SPLIT8_ACT_LO_EXP) | ((127 - SPLIT8_W_HI_EXP) << 8) | ((127 - SPLIT8_W_LO_EXP) << 16) |
-                ((127 - SPLIT8_ACT_HI_EXP) << 24);
-  (void)sc_pack;
 #define DMA(rs, src, dst, st, so) \
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(smem + (st) * 65536 + dst), 16, src, so, 0, 0);
 #define GAx(rs, sub, st, kt) { int kd; const int so = vtile_off<NP>(kt, p.K, kd) + (NP != 0 ? (sub) * subA : 0); \
@@ -623,23 +630,12 @@ __global__ __launch_bounds__(512, 2) void gemm16_256x_kernel(GemmParams p, int P
     DMA(rs, srcW[NP != 0 ? 0 : (sub)][0], dstW[sub][0], st, so) DMA(rs, srcW[NP != 0 ? 0 : (sub)][1], dstW[sub][1], st, so) }
 #define GA(sub, st, kt) GAx(rsA, sub, st, kt)
 #define GW(sub, st, kt) GWx(rsW, sub, st, kt)
-#define WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define LGKM0 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#define BAR __builtin_amdgcn_s_barrier();
-#define PINB __builtin_amdgcn_sched_barrier(0);
-// Split kernels (no register to spare, see srcA): the offset of the odd 16-row tile is recomputed from the even one
-// at every use -- 16 rows further = 8 row pairs = 2048 bytes, and the swizzle's bit 3 flips: (off ^ 128) + 2048.  The
-// xor goes through an opaque asm so that hipcc does not hoist it back into a loop-invariant register.
-#define ODD_OFF(off) ({ int o_; asm volatile("v_xor_b32 %0, 0x80, %1" : "=v"(o_) : "v"(off)); o_ + 2048; })
 #define LD_M(sb, a)                                                                         \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) _Pragma("unroll") for (int t = 0; t < 4; ++t) \
       fm[t].set(ks, *(const vec8*)((sb) + ((NP != 0 && (t & 1)) ? ODD_OFF(offM[ks][0]) : offM[ks][t & 1]) + ((a) * 2 + (t >> 1)) * 4096));
 #define LD_N(FN, sb, b)                                                                     \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) _Pragma("unroll") for (int t = 0; t < 2; ++t) \
       FN[t].set(ks, *(const vec8*)((sb) + ((NP != 0 && t == 1) ? ODD_OFF(offN[ks][0]) : offN[ks][t]) + (b) * 4096));
-#define MM(FN, a, b, t, u, ks) acc[4 * (a) + (t)][2 * (b) + (u)] = Mma16<T>::mma(FN[u].get(ks), fm[t].get(ks), acc[4 * (a) + (t)][2 * (b) + (u)]);
-// e4m3 tile: the two 16-byte fragments of a row are one 32-byte operand (common.h, mma_e4m3); W rows are the MFMA's A side
-#define MM8(FN, a, b, t, u, KIND) acc[4 * (a) + (t)][2 * (b) + (u)] = mma_e4m3k<(KIND) == 1 ? 1 : 2>(FN[u], fm[t], acc[4 * (a) + (t)][2 * (b) + (u)], sc_pack);
 // KIND is a literal (0 fp16 tile, 1 / 2 e4m3 correction tiles): the K loop is unrolled over one period of the tile
 // kinds, so no branch surrounds the MFMAs -- with a run-time branch the accumulators of the two arms meet in phi
 // nodes hipcc does not coalesce (results in fresh registers + 472 v_mov + 200 spilled registers, 4x slower)
@@ -770,15 +766,8 @@ __global__ __launch_bounds__(512, 2) void gemm16_256x_kernel(GemmParams p, int P
 #undef GW
 #undef GAx
 #undef GWx
-#undef WAIT_VM
-#undef LGKM0
-#undef BAR
-#undef PINB
 #undef LD_M
-#undef ODD_OFF
 #undef LD_N
-#undef MM
-#undef MM8
 #undef QUADX
 #undef KTILE
 }
@@ -870,19 +859,9 @@ __global__ __launch_bounds__(256, 2) void gemm16_256h_kernel(GemmParams p, int P
       for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.f;
   f32x2 ab_pre[8];
   const bool fold_pre = NP == 0 && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU) && p.row_ab != nullptr;
-  if (fold_pre) {
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi) {
-      int row = tm * 256 + wr * 128 + mi * 16 + c16;
-      row = row < p.M ? row : p.M - 1;
-      ab_pre[mi] = *(const f32x2*)(p.row_ab + 2L * row);
-    }
-  }
+  if (fold_pre) prefetch_row_ab(p, tm * 256 + wr * 128, c16, ab_pre);
 
   const int nk = vtile_count<NP>(p.K);   // (virtual) K tiles
-  int sc_pack = (127 - SPLIT8_ACT_LO_EXP) | ((127 - SPLIT8_W_HI_EXP) << 8) | ((127 - SPLIT8_W_LO_EXP) << 16) |
-                ((127 - SPLIT8_ACT_HI_EXP) << 24);
-  (void)sc_pack;
 #define DMA(rs, src, dst, so) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(smem + (dst)), 16, src, so, 0, 0);
 // piece j (0..3) of A chunk `sub` of tile kt into stage st: m = {0, 1, 4, 5}[j] + 2 sub; piece j (0..1) of W chunk `sub`: m = 2j + sub
 // (offsets go through plain int locals: a template-dependent expression as a direct argument makes the builtin call
@@ -891,11 +870,6 @@ __global__ __launch_bounds__(256, 2) void gemm16_256h_kernel(GemmParams p, int P
     const int so_ = vtile_off<NP>(kt, p.K, kd) + m_ * rA32; const int ds_ = (st) * 32768 + (wave + 4 * m_) * 1024; DMA(rsA, srcA, ds_, so_) }
 #define PW(sub, j, kt) { int kd; const int m_ = 2 * (j) + (sub); \
     const int so_ = vtile_off<NP>(kt, p.K, kd) + m_ * rW32; const int ds_ = 65536 + (wave + 4 * m_) * 1024; DMA(rsW, srcW, ds_, so_) }
-#define WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define WAIT_LGKM(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
-#define BAR __builtin_amdgcn_s_barrier();
-#define PINB __builtin_amdgcn_sched_barrier(0);
-#define ODD_OFF(off) ({ int o_; asm volatile("v_xor_b32 %0, 0x80, %1" : "=v"(o_) : "v"(off)); o_ + 2048; })
 // row tile t (0..3) of A half a from the A stage at sb; N-side tiles of W half b
 #define LD_M1(sb, a, t)                                                                     \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                           \
@@ -903,8 +877,6 @@ __global__ __launch_bounds__(256, 2) void gemm16_256h_kernel(GemmParams p, int P
 #define LD_N(FN, b)                                                                         \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) _Pragma("unroll") for (int t = 0; t < 2; ++t) \
       FN[t].set(ks, *(const vec8*)(smem + ((NP != 0 && t == 1) ? ODD_OFF(offN[ks][0]) : offN[ks][t]) + (b) * 4096));
-#define MM(FN, a, b, t, u, ks) acc[4 * (a) + (t)][2 * (b) + (u)] = Mma16<T>::mma(FN[u].get(ks), fm[t].get(ks), acc[4 * (a) + (t)][2 * (b) + (u)]);
-#define MM8(FN, a, b, t, u, KIND) acc[4 * (a) + (t)][2 * (b) + (u)] = mma_e4m3k<(KIND) == 1 ? 1 : 2>(FN[u], fm[t], acc[4 * (a) + (t)][2 * (b) + (u)], sc_pack);
 // the MFMAs of row tile t of a quadrant (KIND literal: 0 fp16 tile, 1 / 2 e4m3 correction tiles)
 #define ROWT(FN, a, b, t, KIND)                                                              \
   if ((KIND) != 0) { MM8(FN, a, b, t, 0, KIND) MM8(FN, a, b, t, 1, KIND) }                   \
@@ -1004,52 +976,54 @@ __global__ __launch_bounds__(256, 2) void gemm16_256h_kernel(GemmParams p, int P
 #undef DMA
 #undef PA
 #undef PW
-#undef WAIT_VM
-#undef WAIT_LGKM
-#undef BAR
-#undef PINB
-#undef ODD_OFF
 #undef LD_M1
 #undef LD_N
-#undef MM
-#undef MM8
 #undef ROWT
 #undef KTILE
   epilogue256t<T, EPI, NP != 0, QK8, 2>(p, acc, smem, tm, tn, wave, lane, fold_pre ? ab_pre : nullptr);
 }
+#undef WAIT_VM
+#undef WAIT_LGKM
+#undef LGKM0
+#undef BAR
+#undef PINB
+#undef ODD_OFF
+#undef MMV
+#undef MM
+#undef MM8
 
-// launcher of the half-tile kernel: 8 x PN patches of 256 x 128 tiles per XCD (64 workgroups = the 2 per CU an XCD holds)
-template <typename T, int NP>
-static void launch_h(int epi, const GemmParams& p, hipStream_t s) {
-  const int tiles_n = p.N / 128, tiles_m = (p.M + 255) / 256;
-  int PN = 1;
-  for (int c : {8, 6, 4, 3, 2}) if (tiles_n % c == 0) { PN = c; break; }
-  const int patches_n = tiles_n / PN, PMx = 8;
-  const int pm_x = (tiles_m + PMx - 1) / PMx;
-  const int total_x = patches_n * pm_x;
-  dim3 gx(((total_x + 7) / 8) * 8 * PMx * PN), b(256);
-  const int stg = 1400;   // start offset of the second workgroup of a CU, cycles per K tile
-  switch (epi) {
-    case EPI_BIAS:
-      if constexpr (NP != 0) {
-        if (p.out_qk8) { hipLaunchKernelGGL((gemm16_256h_kernel<T, EPI_BIAS, NP, true>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, stg); break; }
-      }
-      hipLaunchKernelGGL((gemm16_256h_kernel<T, EPI_BIAS, NP>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, stg);
-      break;
-    case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm16_256h_kernel<T, EPI_BIAS_GELU, NP>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, stg); break;
-    case EPI_BIAS_RESID: hipLaunchKernelGGL((gemm16_256h_kernel<T, EPI_BIAS_RESID, NP>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, stg); break;
-    case EPI_ACT_F32: hipLaunchKernelGGL((gemm16_256h_kernel<T, EPI_ACT_F32, NP>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, stg); break;
-    case EPI_PATCH: hipLaunchKernelGGL((gemm16_256h_kernel<T, EPI_PATCH, NP>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, stg); break;
-    default: set_launch_error("gemm: no 256-tile kernel for this epilogue");
-  }
-  if (p.out_qk8 && (epi != EPI_BIAS || NP == 0)) set_launch_error("gemm: out_qk8 goes with the bias epilogue of the split kernels only");
+// XCD patches: PMx x PN tiles of one patch run together on one XCD (32 CUs): 8 x {4, 3, 2, 1} tiles of 256 x 256 (a patch
+// column re-reads the A rows once per XCD, a patch row the W rows: profiles/r04_cfc_patch_shapes.txt), 8 x {8, 6, 4, 3,
+// 2, 1} half tiles of 256 x 128 (64 workgroups = the 2 per CU an XCD holds).  total_x patches, patches_n of them along N;
+// `grid` workgroups cover them with a whole number of patches per XCD.
+struct Grid256 { int PN, PMx, patches_n, total_x, grid; };
+static Grid256 grid256(const GemmParams& p, int tile_n) {
+  const int tiles_n = p.N / tile_n, tiles_m = (p.M + 255) / 256;
+  Grid256 g;
+  g.PMx = 8;
+  g.PN = 1;
+  for (int c : {8, 6, 4, 3, 2}) if (c <= (tile_n == 128 ? 8 : 4) && tiles_n % c == 0) { g.PN = c; break; }
+  g.patches_n = tiles_n / g.PN;
+  g.total_x = g.patches_n * ((tiles_m + g.PMx - 1) / g.PMx);
+  g.grid = ((g.total_x + 7) / 8) * 8 * g.PMx * g.PN;
+  return g;
 }
 
-// XCD patch shape of the 8-wave kernels: PM x PN tiles of one patch run together on one XCD (32 CUs), 8 x {4, 3, 2, 1}
-// (a patch column re-reads the A rows once per XCD, a patch row the W rows: profiles/r04_cfc_patch_shapes.txt)
-static void patch_shape(int tiles_n, int& PMx, int& PN) {
-  PN = (tiles_n % 4 == 0) ? 4 : (tiles_n % 3 == 0) ? 3 : (tiles_n % 2 == 0) ? 2 : 1;
-  PMx = 8;
+// The launchers below rely on launch_gemm for GemmParams::out_qk8: set only with EPI_BIAS on split operands.
+// launcher of the half-tile kernel
+template <typename T, int NP>
+static void launch_h(int epi, const GemmParams& p, hipStream_t s) {
+  const Grid256 g = grid256(p, 128);
+  const int stg = 1400;   // start offset of the second workgroup of a CU, cycles per K tile
+  dispatch_epi(epi, [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    auto run = [&](auto q8) {
+      hipLaunchKernelGGL((gemm16_256h_kernel<T, EPI, NP, decltype(q8)::value>), dim3(g.grid), dim3(256), 0, s, p, g.PN, g.patches_n,
+                         g.total_x, g.PMx, stg);
+    };
+    if constexpr (EPI == EPI_BIAS && NP != 0) dispatch_bool(p.out_qk8 != 0, run);
+    else run(std::false_type{});
+  });
 }
 
 // WALK: one workgroup per CU walks the tiles of the same virtual grid (gemm16_256x_kernel<..., WALK>)
@@ -1067,56 +1041,33 @@ static int walk_grid() {
 // split fp16 (AACLIP_F16X2): the 8-wave kernel on split8 operands, 4 (3: W exact in fp16) virtual tiles per K-tile pair
 template <int NP, bool WALK = false>
 static void launch_split(int epi, const GemmParams& p, hipStream_t s) {
-  const int tiles_n = p.N / 256, tiles_m = (p.M + 255) / 256;
-  int PN, PMx;
-  patch_shape(tiles_n, PMx, PN);
-  const int patches_n = tiles_n / PN;
-  const int pm_x = (tiles_m + PMx - 1) / PMx;
-  const int total_x = patches_n * pm_x;
-  const int vgrid = ((total_x + 7) / 8) * 8 * PMx * PN;
-  dim3 gx(WALK ? (vgrid < walk_grid() ? vgrid : walk_grid()) : vgrid), b(512);
-  switch (epi) {
-    case EPI_BIAS:
-      if (p.out_qk8) hipLaunchKernelGGL((gemm16_256x_kernel<f16, EPI_BIAS, NP, true, WALK>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, vgrid);
-      else hipLaunchKernelGGL((gemm16_256x_kernel<f16, EPI_BIAS, NP, false, WALK>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, vgrid);
-      break;
-    case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm16_256x_kernel<f16, EPI_BIAS_GELU, NP, false, WALK>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, vgrid); break;
-    case EPI_BIAS_RESID: hipLaunchKernelGGL((gemm16_256x_kernel<f16, EPI_BIAS_RESID, NP, false, WALK>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, vgrid); break;
-    case EPI_ACT_F32: hipLaunchKernelGGL((gemm16_256x_kernel<f16, EPI_ACT_F32, NP, false, WALK>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, vgrid); break;
-    case EPI_PATCH: hipLaunchKernelGGL((gemm16_256x_kernel<f16, EPI_PATCH, NP, false, WALK>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, vgrid); break;
-    default: set_launch_error("gemm: no 256-tile kernel for this epilogue");
-  }
-  if (p.out_qk8 && epi != EPI_BIAS) set_launch_error("gemm: out_qk8 goes with the bias epilogue only");
+  const Grid256 g = grid256(p, 256);
+  dim3 gx(WALK ? (g.grid < walk_grid() ? g.grid : walk_grid()) : g.grid);
+  dispatch_epi(epi, [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    auto run = [&](auto q8) {
+      hipLaunchKernelGGL((gemm16_256x_kernel<f16, EPI, NP, decltype(q8)::value, WALK>), gx, dim3(512), 0, s, p, g.PN, g.patches_n,
+                         g.total_x, g.PMx, g.grid);
+    };
+    if constexpr (EPI == EPI_BIAS) dispatch_bool(p.out_qk8 != 0, run);
+    else run(std::false_type{});
+  });
 }
 
 // plain 16-bit operands: the 8-wave kernel with two N-side fragment sets, which takes K tiles in pairs; an odd K-tile
 // count runs the one-set kernel
 template <typename T>
 static void launch_t(int epi, const GemmParams& p, hipStream_t s) {
-  const int tiles_n = p.N / 256, tiles_m = (p.M + 255) / 256;
-  int PN, PMx;
-  patch_shape(tiles_n, PMx, PN);
-  const int patches_n = tiles_n / PN, pm_x = (tiles_m + PMx - 1) / PMx;
-  const int total_x = patches_n * pm_x;
-  dim3 gx(((total_x + 7) / 8) * 8 * PMx * PN), b(512);
+  const Grid256 g = grid256(p, 256);
+  const dim3 gx(g.grid), b(512);
   if (((p.K >> 6) & 1) == 0) {
-    switch (epi) {
-      case EPI_BIAS: hipLaunchKernelGGL((gemm16_256x_kernel<T, EPI_BIAS>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, 0); break;
-      case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm16_256x_kernel<T, EPI_BIAS_GELU>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, 0); break;
-      case EPI_BIAS_RESID: hipLaunchKernelGGL((gemm16_256x_kernel<T, EPI_BIAS_RESID>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, 0); break;
-      case EPI_ACT_F32: hipLaunchKernelGGL((gemm16_256x_kernel<T, EPI_ACT_F32>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, 0); break;
-      case EPI_PATCH: hipLaunchKernelGGL((gemm16_256x_kernel<T, EPI_PATCH>), gx, b, 0, s, p, PN, patches_n, total_x, PMx, 0); break;
-      default: set_launch_error("gemm: no 256-tile kernel for this epilogue");
-    }
-    return;
-  }
-  switch (epi) {
-    case EPI_BIAS: hipLaunchKernelGGL((gemm16_256v_kernel<T, EPI_BIAS>), gx, b, 0, s, p, PN, patches_n, total_x); break;
-    case EPI_BIAS_GELU: hipLaunchKernelGGL((gemm16_256v_kernel<T, EPI_BIAS_GELU>), gx, b, 0, s, p, PN, patches_n, total_x); break;
-    case EPI_BIAS_RESID: hipLaunchKernelGGL((gemm16_256v_kernel<T, EPI_BIAS_RESID>), gx, b, 0, s, p, PN, patches_n, total_x); break;
-    case EPI_ACT_F32: hipLaunchKernelGGL((gemm16_256v_kernel<T, EPI_ACT_F32>), gx, b, 0, s, p, PN, patches_n, total_x); break;
-    case EPI_PATCH: hipLaunchKernelGGL((gemm16_256v_kernel<T, EPI_PATCH>), gx, b, 0, s, p, PN, patches_n, total_x); break;
-    default: set_launch_error("gemm: no 256-tile kernel for this epilogue");
+    dispatch_epi(epi, [&](auto e) {
+      hipLaunchKernelGGL((gemm16_256x_kernel<T, decltype(e)::value>), gx, b, 0, s, p, g.PN, g.patches_n, g.total_x, g.PMx, 0);
+    });
+  } else {
+    dispatch_epi(epi, [&](auto e) {
+      hipLaunchKernelGGL((gemm16_256v_kernel<T, decltype(e)::value>), gx, b, 0, s, p, g.PN, g.patches_n, g.total_x);
+    });
   }
 }
 

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/aaclip.h"
 
 namespace aaclip {
@@ -43,18 +45,33 @@ bool gemm256_applicable(int dtype, const GemmParams& p);
 // 256-tile kernels on 16x16x32 MFMAs (gemm256t.hip), bit-identical to one another: the 8-wave 256 x 256 kernel, the
 // 4-wave 256 x 128 half tile, and the 8-wave kernel walking its tiles (split operands only; plain operands run the
 // 256 x 256 form).  Plain operands with an odd K-tile count run the one-set 8-wave kernel whatever form is asked for.
-// An epilogue without a kernel launches NOTHING and records a launch error (take_launch_error()).
 enum Gemm256Form { GEMM256_TILE, GEMM256_HALF_TILE, GEMM256_WALK };
 void launch_gemm256t(int dtype, int epi, const GemmParams& p, hipStream_t s, Gemm256Form form);
-// Kernel selection for A/B runs: GEMM variants 0 (automatic), 1 (128-tile kernel) and 80 / 81 / 82 (gemm.hip), attention
-// variants 0 and 1 (128-query kernel); both return false for anything else and leave the selection alone.
+// Kernel selection, for the tests that compare the forms with one another: GEMM variants 0 (automatic), 1 (128-tile
+// kernel) and 80 / 81 / 82 (the 256-tile forms, gemm.hip), attention variants 0 and 1 (128-query kernel).  Both return
+// false for anything else and leave the selection alone.
 bool set_gemm_variant(int v);
 bool set_attn_variant(int v);
-void set_tail_peel(int v);
 // Sticky per-thread launch error: set by a launcher that was asked for a kernel it does not have; capi's finish()
 // reports and clears it, so the entry point returns rc < 0 instead of running something else.
 void set_launch_error(const char* msg);
 const char* take_launch_error();
+// Run-time launcher arguments as compile-time constants: f(std::integral_constant<int, EPI_...>{}) / f(std::bool_constant<b>{}).
+// An epilogue nobody knows launches nothing and records a launch error (gemm_check refuses it before any launcher runs).
+template <typename F> void dispatch_epi(int epi, F&& f) {
+  switch (epi) {
+    case EPI_BIAS: f(std::integral_constant<int, EPI_BIAS>{}); break;
+    case EPI_BIAS_GELU: f(std::integral_constant<int, EPI_BIAS_GELU>{}); break;
+    case EPI_BIAS_RESID: f(std::integral_constant<int, EPI_BIAS_RESID>{}); break;
+    case EPI_ACT_F32: f(std::integral_constant<int, EPI_ACT_F32>{}); break;
+    case EPI_PATCH: f(std::integral_constant<int, EPI_PATCH>{}); break;
+    default: set_launch_error("gemm: no kernel for this epilogue");
+  }
+}
+template <typename F> void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
 
 // fused softmax(q k^T) v over packed qkv [B*L, 3*H*64] (q pre-scaled) -> ctx [B*L, H*64]
 // log2q != 0: q is pre-multiplied by log2(e) as well (16-bit kernels only)

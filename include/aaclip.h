@@ -405,7 +405,6 @@ int aaclip_profile_end(float* ms, int* tags, int max_n);
  *             the 8-wave one walking its tiles (split operands; one workgroup per CU) -- bit-identical results; 0
  *             picks the fastest.
  * bits 8..15  attention: 1 = always the 128-query kernel
- * bit 16      peel the partial last round of 256-tile GEMMs to the 128-tile kernel (off by default: -1.6 %)
  * bit 17      turn the LayerNorm folding of aaclip_block(s) off
  * Every selectable kernel computes the same function.  Any other value is rejected (rc < 0) and leaves the selection
  * unchanged. */
