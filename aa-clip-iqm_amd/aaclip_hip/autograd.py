@@ -4,7 +4,8 @@ the adapted text tower (reference model/adapter.py:273-304), whose backward fill
 visual tower up to its tap streams (model/adapter.py:137-170), whose backward fills the layer-adapter gradients, and
 the tap and det heads behind them (:171-184), whose backward fills the seg_proj / det_proj gradients, and the IQM map term of
 the stage-2 loss (reference train.py:173-209: the two-channel half-pixel upsample of sigmoid(cos - cos)), whose backward
-reaches the seg tokens and the two final queries.
+reaches the seg tokens and the two final queries, and the key / value side of the IQM branch (model/adapter.py:205-211
+and the visual cross-attention of model/iqm.py:108-139 over those rows): cross_rows and iqm_visual_rows.
 Forward and backward are HIP kernels; these classes only carry tensors between them.  The saved tensors live in
 ctx.save_for_backward, so they are freed with the graph (after backward(), or when the output is dropped)."""
 from __future__ import annotations
@@ -257,6 +258,97 @@ class TapHead(torch.autograd.Function):
                 d_dw.to(dw.dtype) if need_d and d_dw is not None else None)
 
 
+class CrossRows(torch.autograd.Function):
+    """engine.cross_rows with a backward: qt fp32 [B*R, Dk] x rows x [B*Lk, Dk] (fp32, fp16 or bf16) -> [B*R, Dk], the
+    bits of the inference path.  Saved: qt and x themselves (nothing of size Lk x Dk is added; the backward recomputes
+    the probabilities).  The backward is engine.cross_rows_backward, for the gradients needs_input_grad names only.
+    act ACT_NONE: d x is the gradient with respect to the x given.  act ACT_LEAKY / ACT_RELU (x = that activation's
+    output): the gradient handed back for x is already multiplied by the activation's slope, i.e. it is the gradient of
+    the pre-activation rows -- what iqm_visual_rows(..., pre_activation_grad=True) expects to receive."""
+
+    @staticmethod
+    def forward(ctx, qt, x, B, R, Lk, act):
+        code = {torch.float32: engine.F32, torch.float16: engine.F16, torch.bfloat16: engine.BF16}[x.dtype]
+        qt32 = engine._f32c(qt)
+        xr = x.detach().contiguous()
+        out = engine.cross_rows(qt32, xr, int(B), int(R), int(Lk), code)
+        ctx.dims = (int(B), int(R), int(Lk), code, int(act))
+        ctx.save_for_backward(qt32, xr)
+        return out.view(*qt.shape)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        qt, x = ctx.saved_tensors
+        B, R, Lk, code, act = ctx.dims
+        need_qt, need_x = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_qt or need_x):
+            return None, None, None, None, None, None
+        d_qt, d_x = engine.cross_rows_backward(qt, x.view(B * Lk, -1), d_out.reshape(B * R, -1), B, R, Lk, code, act=act,
+                                               need_qt=need_qt, need_x=need_x)
+        return (d_qt.view_as(d_out) if need_qt else None, d_x.view_as(x).to(x.dtype) if need_x else None,
+                None, None, None, None)
+
+
+class IqmVisualRows(torch.autograd.Function):
+    """The key / value rows of the IQM branch in its projected form, [B, levels * (L - 1), h]: per tap level
+    AdaptedCLIP._iqm_project_level (ln_post, query_adapters[k] with or without the LeakyReLU, CLS row dropped) -- the
+    code and kernels AdaptedCLIP.forward runs, so the rows are its vis_cat bit for bit.
+
+    forward(model, pre_activation_grad, n, *taps [B, L, D], *query_adapters weights).  Saved: the taps (the VisualTaps
+    outputs themselves), the weights and, with the LeakyReLU, the output rows (their sign gives the slope).  The
+    backward runs in fp32 whatever precision the forward ran in: ln_post(tap) again in fp32, the slope of the saved
+    rows (skipped with pre_activation_grad: the incoming gradient is then that of the pre-activation product, as
+    aaclip_cross_rows_backward with act set delivers it), aaclip_gemm_wgrad for d query_adapters[k].weight,
+    aaclip_gemm on the transposed weight and aaclip_layernorm_backward for d tap (ln_post is frozen).  The CLS rows of
+    d tap are exactly zero.  Level slices and the zero CLS row are torch copies."""
+
+    @staticmethod
+    def forward(ctx, model, pre_activation_grad, n, *tw):
+        taps, weights = tw[:n], tw[n:]
+        B, L, D = taps[0].shape
+        icode = engine.plain_code(model._code())
+        h = model.iqm_hidden_size
+        vis_cat = torch.empty(B, n * (L - 1), h, dtype=engine.torch_dtype(icode), device=taps[0].device)
+        for k, tap in enumerate(taps):
+            model._iqm_project_level(tap.detach().reshape(B * L, D), k, vis_cat, B, L, icode)
+        ctx.model, ctx.n, ctx.pre = model, n, bool(pre_activation_grad)
+        ctx.save_for_backward(*taps, *weights, *([vis_cat] if model.relu and not ctx.pre else []))
+        return vis_cat
+
+    @staticmethod
+    def backward(ctx, d_vis):
+        model, n = ctx.model, ctx.n
+        saved = ctx.saved_tensors
+        taps, weights = saved[:n], saved[n:2 * n]
+        B, L, D = taps[0].shape
+        P = L - 1
+        ln_post = model.image_encoder.ln_post
+        grads_t, grads_w = [None] * n, [None] * n
+        d_vis = d_vis.float()
+        if model.relu and not ctx.pre:
+            y = saved[2 * n]
+            d_vis = d_vis * torch.where(y > 0, 1.0, 0.01).to(torch.float32)
+        for k in range(n):
+            need_t, need_w = ctx.needs_input_grad[3 + k], ctx.needs_input_grad[3 + n + k]
+            if not (need_t or need_w):
+                continue
+            w = weights[k]
+            dz = torch.zeros(B, L, w.shape[0], dtype=torch.float32, device=d_vis.device)   # CLS rows stay zero
+            dz[:, 1:, :] = d_vis[:, k * P:(k + 1) * P, :]
+            dz = dz.view(B * L, -1)
+            tap32 = engine._f32c(taps[k]).reshape(B * L, D)
+            if need_w:
+                ln = engine.layernorm(tap32, ln_post.weight, ln_post.bias, out_code=engine.F32)
+                grads_w[k] = engine.gemm_wgrad(dz, ln).to(w.dtype)
+            if need_t:
+                d_ln = torch.empty(B * L, D, dtype=torch.float32, device=d_vis.device)
+                engine.gemm(engine.F32, _lib.EPI_ACT_F32, dz, engine.CACHE.get(w, engine.F32, "transpose"), None, d_ln)
+                d_tap = engine.layernorm_backward(tap32, ln_post.weight, d_ln).view(B, L, D)
+                d_tap[:, 0, :] = 0.0
+                grads_t[k] = d_tap.to(taps[k].dtype)
+        return (None, None, None, *grads_t, *grads_w)
+
+
 def visual_taps(model, image):
     """The tap streams of AdaptedCLIP's visual tower, [B, L, D] each (CLS row included), one per entry of model.levels
     in ascending order, carrying a graph to model.image_adapter["layer_adapters"][i].weight: see VisualTaps.
@@ -269,8 +361,8 @@ def visual_heads(model, image):
     """AdaptedCLIP.forward(image)[:2] with a graph -> (seg_tokens: one [B, L-1, E] tensor of unit rows per tap level,
     det_token [B, E]): visual_taps, then one TapHead per level with the det head on the last one, paired as the forward
     pairs them and bit-identical to it.  The graph reaches image_adapter["layer_adapters"][i].weight, ["seg_proj"][k]
-    and ["det_proj"], whichever of them require grad.  Not built: the IQM branch's backward (the forward's third
-    output); iqm_map_train hands it d_queries."""
+    and ["det_proj"], whichever of them require grad.  Not built: the backward of the IQM branch's 2-row query side
+    (the forward's third output; iqm_map_train hands it d_queries, iqm_visual_rows is its key / value side)."""
     seg_proj = model.image_adapter["seg_proj"]
     det_weight = model.image_adapter["det_proj"].weight
     seg_tokens, det_token = [], None
@@ -300,3 +392,22 @@ def iqm_map_train(seg, queries, img_size):
 
 def seg_loss(preds, mask, terms: int = _lib.SEG_LOSS_ALL):
     return SegLoss.apply(preds, mask, terms)
+
+
+
+def cross_rows(qt, x, B, R, Lk, act=None):
+    """engine.cross_rows with a graph to qt and x: see CrossRows.  act None: the plain gradient."""
+    return CrossRows.apply(qt, x, B, R, Lk, _lib.ACT_NONE if act is None else int(act))
+
+
+def iqm_visual_rows(model, taps, pre_activation_grad=False):
+    """The concatenated key / value rows [B, levels * (L - 1), h] of the IQM branch (the vis_cat of the projected form of
+    AdaptedCLIP.forward, bit for bit) with a graph to every query_adapters[k].weight and to the tap streams
+    taps[k] [B, L, D] (from visual_taps, so the graph reaches layer_adapters): see IqmVisualRows.
+    pre_activation_grad: the gradient that arrives is already that of the pre-activation product (CrossRows with act
+    set, or aaclip_cross_rows_backward with act), so the LeakyReLU slope is not applied again."""
+    taps = list(taps)
+    if len(taps) != len(model.query_adapters):
+        raise ValueError("iqm_visual_rows: one tap stream per query adapter")
+    return IqmVisualRows.apply(model, bool(pre_activation_grad), len(taps), *taps,
+                               *[m.weight for m in model.query_adapters])

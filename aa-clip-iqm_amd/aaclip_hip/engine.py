@@ -916,6 +916,39 @@ def cross_rows(qt: torch.Tensor, x: torch.Tensor, B: int, R: int, Lk: int, x_cod
     return out
 
 
+CROSS_ROWS_BACKWARD_MAX_SLICES = 128   # csrc/kernels.h CRB_MAX_SLICES: key slices per image of aaclip_cross_rows_backward
+
+
+def cross_rows_backward(qt: torch.Tensor, x: torch.Tensor, d_out: torch.Tensor, B: int, R: int, Lk: int, x_code: int,
+                        act: int = _lib.ACT_NONE, need_qt: bool = True, need_x: bool = True,
+                        d_x: Optional[torch.Tensor] = None):
+    """Backward of cross_rows from d_out [B*R, Dk] -> (d qt fp32 [B*R, Dk] or None, d x fp32 [B*Lk, Dk] or None):
+    aaclip_cross_rows_backward.  qt fp32 and x [B*Lk, Dk] (x_code) as the forward read them.  act: the activation whose
+    OUTPUT x is; d x is then the gradient of the pre-activation rows.  d_x given (contiguous fp32 [B*Lk, Dk]): the
+    gradient is ADDED into it (accumulate) and it is returned."""
+    require_gpu(x, "cross_rows_backward")
+    lib = _lib.load()
+    if not (need_qt or need_x):
+        raise ValueError("cross_rows_backward: nothing to compute")
+    Dk = x.shape[-1]
+    if not x.is_contiguous() or x.dtype != _TORCH_DT[x_code] or x.numel() != B * Lk * Dk:
+        raise ValueError("cross_rows_backward: x must be contiguous [B*Lk, Dk] in the dtype x_code names")
+    qt, d_out = _f32c(qt), _f32c(d_out)
+    if qt.numel() != B * R * Dk or d_out.numel() != B * R * Dk:
+        raise ValueError("cross_rows_backward: qt and d_out must be [B*R, Dk]")
+    accumulate = d_x is not None
+    if accumulate and (d_x.dtype != torch.float32 or not d_x.is_contiguous() or d_x.numel() != B * Lk * Dk or not need_x):
+        raise ValueError("cross_rows_backward: d_x must be contiguous fp32 [B*Lk, Dk] (and need_x set)")
+    d_qt = torch.empty(B * R, Dk, dtype=torch.float32, device=x.device) if need_qt else None
+    if need_x and d_x is None:
+        d_x = torch.empty(B * Lk, Dk, dtype=torch.float32, device=x.device)
+    ws = Workspace.get(x.device, lib.aaclip_cross_rows_backward_workspace_bytes(B, R, Lk, Dk))
+    _lib.check(lib.aaclip_cross_rows_backward(x_code, qt.data_ptr(), x.data_ptr(), d_out.data_ptr(), _ptr(d_qt),
+                                              _ptr(d_x) if need_x else None, int(act), int(accumulate), B, R, Lk, Dk,
+                                              ws.data_ptr(), ws.numel(), _stream(x.device)), "cross_rows_backward")
+    return d_qt, (d_x if need_x else None)
+
+
 def cross_rows_levels(qt: torch.Tensor, levels, B: int, R: int, rows_per_image: int, row0: int, Lk: int,
                       Dk: int) -> torch.Tensor:
     """include/aaclip.h aaclip_cross_rows_levels.  qt fp32 [B*R, nseg*Dk]; levels = row buffers, one per segment: fp16 /

@@ -237,6 +237,30 @@ int aaclip_cross_rows(int x_dtype, const float* qt, const void* x, float* out, i
   return finish("cross_rows");
 }
 
+size_t aaclip_cross_rows_backward_workspace_bytes(int B, int R, int Lk, int Dk) {
+  return cross_rows_backward_ws_bytes(B, R, Lk, Dk);
+}
+
+int aaclip_cross_rows_backward(int x_dtype, const float* qt, const void* x, const float* d_out, float* d_qt, float* d_x,
+                               int act, int accumulate, int B, int R, int Lk, int Dk, void* ws, size_t ws_bytes,
+                               void* stream) {
+  REQUIRE(plain_dtype_ok(x_dtype), "cross_rows_backward: bad dtype (fp32, fp16 or bf16)");
+  REQUIRE(qt && x && d_out && ws, "cross_rows_backward: null pointer");
+  REQUIRE(d_qt || d_x, "cross_rows_backward: nothing to compute (d_qt and d_x are both NULL)");
+  REQUIRE(act >= AACLIP_ACT_NONE && act <= AACLIP_ACT_RELU, "cross_rows_backward: bad activation");
+  REQUIRE(B > 0 && R > 0 && Lk > 0 && Dk > 0, "cross_rows_backward: empty problem");
+  REQUIRE(B <= 65535, "cross_rows_backward: grid limit (B <= 65535)");
+  if (const char* m = cross_rows_check(R, Lk, Dk)) {
+    char buf[256];
+    snprintf(buf, sizeof(buf), "cross_rows_backward: %s", m);
+    return fail(-1, buf);
+  }
+  REQUIRE_ALIGNED16("cross_rows_backward", qt, x, d_out, d_qt, d_x, ws);
+  REQUIRE(ws_bytes >= cross_rows_backward_ws_bytes(B, R, Lk, Dk), "cross_rows_backward: workspace too small");
+  launch_cross_rows_backward(x_dtype, qt, x, d_out, d_qt, d_x, act, accumulate, B, R, Lk, Dk, ws, (hipStream_t)stream);
+  return finish("cross_rows_backward");
+}
+
 size_t aaclip_cross_rows_levels_workspace_bytes(int B, int nseg, int Lk, int Dk) {
   if (B < 1 || nseg < 1 || Lk < 1 || Dk < 1) return 0;
   return cross_rows_levels_ws_bytes(B, nseg, Lk, Dk);

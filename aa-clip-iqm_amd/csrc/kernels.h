@@ -178,6 +178,13 @@ void launch_iqm_map_train(const float* seg, const float* q, float* grid, float* 
 void launch_iqm_map_train_bwd(const float* seg, const float* q, const float* grid, const float* d_preds, float* d_seg,
                               float* d_q, int B, int g, int E, int S, void* ws, hipStream_t s);
 
+// ---- iqm_backward.hip : backward of aaclip_cross_rows (d_qt [B, R, Dk] and d_x [B, Lk, Dk]; either may be null)
+constexpr int CRB_MAX_SLICES = 128;   // key slices per image: slices x B workgroups, slices x R x Dk partial sums of d_qt
+int cross_rows_backward_slices(int Lk);
+size_t cross_rows_backward_ws_bytes(int B, int R, int Lk, int Dk);
+void launch_cross_rows_backward(int x_dtype, const float* qt, const void* x, const float* dout, float* d_qt, float* d_x,
+                                int act, int accumulate, int B, int R, int Lk, int Dk, void* ws, hipStream_t s);
+
 // ---- text_backward.hip : backward of the adapted text tower (fp32, fixed-order reductions)
 constexpr int ATTN_BWD_MAX_L = 128;
 constexpr int WGRAD_MAX_CHUNKS = 16;

@@ -7,8 +7,8 @@ Of stage 2 (the image adapters) the loss is here: `stage2_text_loss`, the forwar
 which adds the IQM map terms (aaclip_hip.autograd.iqm_map_train) for given final queries, with their gradient to the seg
 tokens and to those queries.
 
-Not here: the training-time datasets, main(), the IQM branch's own backward (from the queries'
-gradient to the branch's parameters and the tap streams) and train_image_adapter.  `train_text_adapter` is fed by any
+Not here: the training-time datasets, main(), the backward of the IQM branch's 2-row query
+side (the key / value side is built: aaclip_hip.autograd.cross_rows and iqm_visual_rows) and train_image_adapter.  `train_text_adapter` is fed by any
 iterable of {"image", "mask", "class_name"} batches.
 """
 from __future__ import annotations
@@ -126,7 +126,8 @@ def stage2_loss(adapted_model, image, mask, label, anchors, img_size, iqm_querie
     train yet.
     A query width other than the seg tokens' raises ValueError: the reference draws a fresh random nn.Linear at every
     step there (train.py:175-179), which cannot be reproduced.
-    Not built: the IQM branch's own backward and train_image_adapter."""
+    Not built: the backward of the IQM branch's 2-row query side (from these queries' gradient to the effective queries
+    of autograd.cross_rows; the key / value side behind them is autograd.iqm_visual_rows) and train_image_adapter."""
     E = adapted_model.image_adapter["seg_proj"][0].weight.shape[0]
     if iqm_queries.dim() != 3 or iqm_queries.shape[1] != 2 or iqm_queries.shape[-1] != E:
         raise ValueError(f"stage2_loss: iqm_queries must be [B, 2, {E}] (the seg tokens' width), got "

@@ -353,7 +353,11 @@ int aaclip_row_head_backward(const float* x, const int32_t* tokens, const float*
  * D, E supported row widths (256, 512, 768, 1024), L > 1, B*L < 2^29, act one of AACLIP_ACT_*.
  * ws_bytes >= aaclip_tap_head_backward_workspace_bytes(B, L, D, E): 0 for an empty problem, monotonic in each
  * argument.  Errors carry the "tap_head_backward:" prefix.
- * Not built: the backward of the IQM branch (aaclip_tap_head_keep_rows' rows feed it) -- see DESIGN.md section 7. */
+ * The IQM branch's backward: built is its key / value side, from the gradient of the cross-attention's weighted row sums
+ * to query_adapters and the tap streams (aaclip_cross_rows_backward below plus aaclip_gemm_wgrad, aaclip_gemm and
+ * aaclip_layernorm_backward; aaclip_hip/autograd.py iqm_visual_rows).  Not built: the backward of the 2-row query side
+ * (the IQM layers' own Linears and LayerNorms, class_query_mlp, the feature projections, the text cross-attention)
+ * and a training route for the folded 16-bit aaclip_cross_rows_levels form -- see DESIGN.md section 7. */
 size_t aaclip_tap_head_backward_workspace_bytes(int B, int L, int D, int E);
 int aaclip_tap_head_backward(const float* x, const float* ln_post_w, const float* ln_post_b, const float* proj_w,
                              const float* proj_wt, int act, const float* d_seg, const float* det_w, const float* det_wt,
@@ -440,6 +444,27 @@ int aaclip_adapter_mix(float* x, const float* a, long rows, int D, float weight,
 size_t aaclip_cross_rows_workspace_bytes(int B, int R, int Lk, int Dk);
 int aaclip_cross_rows(int x_dtype, const float* qt, const void* x, float* out, int B, int R, int Lk, int Dk, void* ws,
                       size_t ws_bytes, void* stream);
+/* Backward of aaclip_cross_rows from d_out [B, R, Dk]: with p_rj the forward's probabilities (recomputed: nothing of
+ * size Lk x Dk is kept from the forward or placed in the workspace), g_rj = d_out[b, r] . x[b, j] and
+ * delta_r = sum_j p_rj g_rj,
+ *   ds_rj = p_rj (g_rj - delta_r),  d_qt[b, r] = sum_j ds_rj x[b, j],  d_x[b, j] = sum_r (p_rj d_out[b, r] + ds_rj qt[b, r]).
+ * qt, d_out, d_qt [B, R, Dk] and d_x [B, Lk, Dk] are fp32 whatever x_dtype (fp32, fp16, bf16) is; d_qt or d_x may be
+ * NULL, not both.  accumulate != 0: d_x += the gradient (both IQM layers, and the key and the value role inside a
+ * layer, read the same rows: their gradients are summed in place); 0: d_x is overwritten.  d_qt is always overwritten.
+ * act (AACLIP_ACT_*): the contribution to d_x is multiplied by the activation's derivative taken from the sign of the
+ * row's own value -- x is then the activation's OUTPUT, both activations keep the sign, slope 1 for x > 0 and 0.01
+ * (LEAKY) / 0 (RELU) for x <= 0, the kink convention stated at aaclip_adapter_mix_backward -- so that d_x is the
+ * gradient of the pre-activation product without a pass of its own over the rows.
+ * R, Lk, Dk as aaclip_cross_rows (R 4, 8, 12 or 16; Dk 256, 512, 768 or 1024; Lk >= 1), B <= 65535.  Every pointer and
+ * the workspace 16-byte aligned.  ws_bytes >= aaclip_cross_rows_backward_workspace_bytes(B, R, Lk, Dk) = scores and
+ * d_out products [B, Lk, 32], row statistics and per-slice partial sums of d_qt (at most 128 slices per image); 0 for
+ * an empty problem, monotonic in each argument.  No atomics, every sum in a fixed order: two calls on the same inputs
+ * give the same bits, and each element of d_x is written by one thread.  All checks precede the first launch; errors
+ * carry the "cross_rows_backward:" prefix. */
+size_t aaclip_cross_rows_backward_workspace_bytes(int B, int R, int Lk, int Dk);
+int aaclip_cross_rows_backward(int x_dtype, const float* qt, const void* x, const float* d_out, float* d_qt, float* d_x,
+                               int act, int accumulate, int B, int R, int Lk, int Dk, void* ws, size_t ws_bytes,
+                               void* stream);
 /* The same over up to 4 SEGMENTS of 16-bit rows that share one softmax, on the matrix cores: segment s has its own row
  * buffer x[s] (image b's keys are rows b * rows_per_image + row0 + j, j < Lk, of ldx elements each, the first Dk of
  * which are read) and its own effective queries: qt, out [B, R, nseg, Dk] fp32,
