@@ -17,6 +17,7 @@ ABI_VERSION = 9   # include/aaclip.h AACLIP_ABI_VERSION this binding was written
 F32, F16, BF16, F16X2 = 0, 1, 2, 3   # F16X2: split fp16 (hi + lo pairs), include/aaclip.h
 EXACT16_QKV, EXACT16_OUT, EXACT16_FC, EXACT16_PROJ, EXACT16_ADAPTER = 1, 2, 4, 8, 16
 ACT_NONE, ACT_LEAKY, ACT_RELU = 0, 1, 2
+ACT_GELU = 3   # aaclip_act_backward only
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_ACT_F32 = 0, 1, 2, 3
 SEG_LOSS_FOCAL, SEG_LOSS_DICE0, SEG_LOSS_DICE1, SEG_LOSS_ALL = 1, 2, 4, 7
 
@@ -96,6 +97,14 @@ SIGNATURES = {
     "aaclip_residual_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _f, _vp]),
     "aaclip_combine3": (_i, [_vp, _vp, _vp, _f, _f, _f, _vp, _l, _vp]),
     "aaclip_linear_smallk": (_i, [_i, _vp, _vp, _vp, _vp, _l, _i, _i, _vp]),
+    "aaclip_small_attention_backward": (_i, [_vp] * 7 + [_i] * 5 + [_f, _vp]),
+    "aaclip_layernorm_param_grad_workspace_bytes": (_sz, [_l, _i]),
+    "aaclip_layernorm_param_grad": (_i, [_vp, _vp, _vp, _vp, _l, _i, _f, _vp, _sz, _vp]),
+    "aaclip_bias_grad_workspace_bytes": (_sz, [_l, _i]),
+    "aaclip_bias_grad": (_i, [_vp, _l, _vp, _l, _i, _vp, _sz, _vp]),
+    "aaclip_act_backward": (_i, [_i, _vp, _vp, _vp, _l, _vp]),
+    "aaclip_linear_smallk_backward_workspace_bytes": (_sz, [_l, _i, _i]),
+    "aaclip_linear_smallk_backward": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _vp, _sz, _vp]),
     "aaclip_drop_cls_rows": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "aaclip_iqm_map": (_i, [C.POINTER(_vp), _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _sz, _vp]),
     "aaclip_set_gemm_variant": (_i, [_i]),

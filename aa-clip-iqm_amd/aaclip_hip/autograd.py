@@ -5,7 +5,9 @@ visual tower up to its tap streams (model/adapter.py:137-170), whose backward fi
 the tap and det heads behind them (:171-184), whose backward fills the seg_proj / det_proj gradients, and the IQM map term of
 the stage-2 loss (reference train.py:173-209: the two-channel half-pixel upsample of sigmoid(cos - cos)), whose backward
 reaches the seg tokens and the two final queries, and the key / value side of the IQM branch (model/adapter.py:205-211
-and the visual cross-attention of model/iqm.py:108-139 over those rows): cross_rows and iqm_visual_rows.
+and the visual cross-attention of model/iqm.py:108-139 over those rows): cross_rows and iqm_visual_rows, and the branch's
+2-row query side (model/adapter.py:186-269, model/iqm.py:572-673) from the final queries back to every parameter it
+reads, to those rows and to the CLS row of the last tap: IqmQueries / iqm_queries, visual_outputs.
 Forward and backward are HIP kernels; these classes only carry tensors between them.  The saved tensors live in
 ctx.save_for_backward, so they are freed with the graph (after backward(), or when the output is dropped)."""
 from __future__ import annotations
@@ -349,6 +351,294 @@ class IqmVisualRows(torch.autograd.Function):
         return (None, None, None, *grads_t, *grads_w)
 
 
+IQM_TRAIN_WIDTHS = (256, 512, 768, 1024)          # row widths of aaclip_cross_rows / aaclip_cross_rows_backward
+_ATTENTIONS = ("attention", "crossattention", "text_crossattention")
+
+
+def _iqm_param_names(model):
+    """The parameters the query side of the IQM branch reads, by their state_dict names, in the order IqmQueries takes
+    them (IQMLayer.intermediate / .output, visual_weight and text_weight are not read and are not here)."""
+    names = [f"class_query_mlp.{i}.{p}" for i in (0, 2) for p in ("weight", "bias")] + ["pos_embedding"]
+    names += ["iqm.layernorm.weight", "iqm.layernorm.bias"]
+    for l in range(len(model.iqm.encoder.layer)):
+        pre = f"iqm.encoder.layer.{l}."
+        for att in _ATTENTIONS:
+            for m in ("attention.query", "attention.key", "attention.value", "output.dense", "output.LayerNorm"):
+                names += [f"{pre}{att}.{m}.weight", f"{pre}{att}.{m}.bias"]
+        for m in ("intermediate_query.dense", "output_query.dense", "output_query.LayerNorm"):
+            names += [f"{pre}{m}.weight", f"{pre}{m}.bias"]
+    for m in ("visual_feature_proj", "text_feature_proj", "iqm_layer_norm"):
+        names += [m + ".weight", m + ".bias"]
+    return names
+
+
+def _iqm_train_check(model):
+    """The configurations IqmQueries covers: the last tap is the tower's final stream, and both cross-attentions take
+    the aaclip_cross_rows form of IQM._attend."""
+    n_blocks = len(model.image_encoder.transformer.resblocks)
+    if not model.levels or max(model.levels) != n_blocks:
+        raise NotImplementedError("iqm_queries: model.levels must end at the tower's last block (the CLS row of the final "
+                                  "stream is read from the last tap)")
+    R = 2 * model.iqm.num_attention_heads
+    widths = (model.iqm_hidden_size, model.text_feature_proj.weight.shape[0])
+    if R % 4 or R > 16 or any(w not in IQM_TRAIN_WIDTHS for w in widths):
+        raise NotImplementedError("iqm_queries: training covers queries x heads in {4, 8, 12, 16} and row widths "
+                                  "256 / 512 / 768 / 1024 (the aaclip_cross_rows form of the cross-attentions)")
+
+
+def _dx(d_y, weight):
+    """d_y [M, out] . W [out, in] -> [M, in] fp32: the input gradient of x W^T"""
+    out = torch.empty(d_y.shape[0], weight.shape[1], dtype=torch.float32, device=d_y.device)
+    return engine.gemm(engine.F32, _lib.EPI_ACT_F32, d_y, engine.CACHE.get(weight, engine.F32, "transpose"), None, out)
+
+
+def _dx_t(d_y, weight):
+    """d_y [M, in] . W^T -> [M, out] fp32: the input gradient of x W (a product that ran on the transposed weight)"""
+    out = torch.empty(d_y.shape[0], weight.shape[0], dtype=torch.float32, device=d_y.device)
+    return engine.gemm(engine.F32, _lib.EPI_ACT_F32, d_y, engine.CACHE.get(weight, engine.F32), None, out)
+
+
+def _wgrad(dz, u):
+    """aaclip_gemm_wgrad over column blocks of at most 1024 output features of dz"""
+    O = dz.shape[1]
+    if O <= 1024:
+        return engine.gemm_wgrad(dz, u)
+    return torch.cat([engine.gemm_wgrad(dz[:, o:o + 1024], u) for o in range(0, O, 1024)], dim=0)
+
+
+def _sum(a, b, c=None):
+    return engine.combine3(a, b, c, 1.0, 1.0, 1.0)
+
+
+class IqmQueries(torch.autograd.Function):
+    """The query side of the IQM branch in its projected form (AdaptedCLIP._iqm_branch, IQM.forward / _attend) with a
+    backward: forward(model, rows, tap, anchors, *parameters named by _iqm_param_names) -> final queries [B, 2, h].
+    rows [B, Lk, h] are autograd.iqm_visual_rows(model, taps, pre_activation_grad=model.relu), tap [B, L, D] the last tap
+    stream (its CLS row feeds class_query_mlp), anchors [B, 768, 2] constants.  The calls are those of the model in its
+    order, so wherever AdaptedCLIP.forward takes the projected form the queries are its bits.
+    Saved: the fp32 intermediates of every step ([2B, h], [2B H, .], the [2B, 2048] pre-GELU rows from one extra
+    EPI_ACT_F32 product), the text rows and the rows tensor itself -- nothing else of size Lk x h.
+    The backward runs in fp32 whatever precision the forward ran in (16-bit casts count as the identity) and walks the
+    forward in reverse on aaclip_gemm (transposed cached weights), aaclip_gemm_wgrad, aaclip_layernorm_backward,
+    aaclip_cross_rows_backward (accumulating over roles and layers; its act applies the LeakyReLU slope of the rows) and
+    the entries of csrc/iqm_query_backward.hip.  key.bias of both cross-attentions is softmax-invariant: exact zeros."""
+
+    @staticmethod
+    def forward(ctx, model, rows, tap, anchors, *params):
+        from ._lib import ACT_RELU, EPI_ACT_F32, EPI_BIAS, EPI_BIAS_GELU
+        code = engine.plain_code(model._code())
+        dt = engine.torch_dtype(code)
+        iqm, h, H = model.iqm, model.iqm_hidden_size, model.iqm.num_attention_heads
+        B, L, _ = tap.shape
+        dev = tap.device
+        te = anchors.detach().to(dev)
+        if te.dim() != 3 or te.shape[0] != B or te.shape[-1] != 2:
+            raise NotImplementedError("iqm_queries: text_embeddings must be [B, 768, 2]")
+        nq, R, eps = 2, 2 * H, iqm.eps
+        scale = 1.0 / (h // H) ** 0.5
+        S = {}
+
+        def f32(n, d):
+            return torch.empty(n, d, dtype=torch.float32, device=dev)
+
+        def lin(x, m, act=0):
+            out = f32(x.shape[0], m.weight.shape[0])
+            return engine.gemm(code, EPI_ACT_F32, x, engine.CACHE.get(m.weight, code), engine._f32c(m.bias), out, act=act)
+
+        def tail(att, ctxv, hin, key):
+            dense = lin(ctxv.to(dt), att.output.dense)
+            S[key + "ctx"], S[key + "dense"] = ctxv, dense
+            return engine.residual_layernorm(dense, hin, att.output.LayerNorm, eps)
+
+        def self_att(att, hin, key):
+            hq = hin.to(dt)
+            q = lin(hq, att.attention.query)
+            k = torch.empty(hq.shape[0], h, dtype=dt, device=dev)
+            v = torch.empty_like(k)
+            engine.gemm(code, EPI_BIAS, hq, engine.CACHE.get(att.attention.key.weight, code),
+                        engine._f32c(att.attention.key.bias), k)
+            engine.gemm(code, EPI_BIAS, hq, engine.CACHE.get(att.attention.value.weight, code),
+                        engine._f32c(att.attention.value.bias), v)
+            S[key + "q"], S[key + "k"], S[key + "v"] = q, k.float(), v.float()
+            return tail(att, engine.small_attention(q, k, v, B, nq, nq, H, code), hin, key)
+
+        def cross_att(att, hin, enc, Lk, proj, key):
+            q = lin(hin.to(dt), att.attention.query)
+            qm = engine.head_expand(q, H, scale, code)
+            kin = att.attention.key.weight.shape[1]
+            qt = engine.gemm(code, EPI_ACT_F32, qm, engine.CACHE.get(att.attention.key.weight, code, "transpose"), None,
+                             f32(B * R, kin))
+            S[key + "qm"], S[key + "qt"] = qm.float(), qt
+            if proj is not None:
+                qx = engine.gemm(code, EPI_ACT_F32, qt.to(dt), engine.CACHE.get(proj.weight, code, "transpose"), None,
+                                 f32(B * R, proj.weight.shape[1]))
+                xbar = engine.cross_rows(qx, enc, B, R, Lk, code)
+                ebar = lin(xbar.to(dt), proj)
+                S[key + "qx"], S[key + "xbar"] = qx, xbar
+            elif enc.dtype in (torch.float16, torch.bfloat16) and enc.shape[-1] in (768, 1024):
+                ebar = engine.cross_rows_levels(qt, [enc], B, R, Lk, 0, Lk, enc.shape[-1])
+            else:
+                ebar = engine.cross_rows(qt, enc, B, R, Lk, code)
+            S[key + "ebar"] = ebar
+            full = lin(ebar.to(dt), att.attention.value)
+            return tail(att, engine.head_diag(full, H), hin, key)
+
+        cls = tap.detach().reshape(B, L, -1)[:, 0, :].to(dt).contiguous()
+        m0, m2 = model.class_query_mlp[0], model.class_query_mlp[2]
+        t1 = lin(cls, m0, act=ACT_RELU)
+        cq = lin(t1.to(dt), m2)
+        pos = engine._f32c(model.pos_embedding)[:, :2, :].expand(B, 2, h).contiguous()
+        query = engine.combine3(cq.unsqueeze(1).expand(B, 2, h).contiguous(), pos, None, 1.0, 1.0, 0.0)
+        tp, vp = model.text_feature_proj, model.visual_feature_proj
+        txt = engine.linear_smallk(te, tp.weight, tp.bias, code)
+        Lt, Lv = te.shape[1], rows.shape[1]
+        vis = rows.detach().to(dt).reshape(-1, rows.shape[-1]).contiguous()
+        S["cls"], S["t1"], S["query"], S["te"], S["txt"], S["vis"] = cls.float(), t1, query, engine._f32c(te), txt, vis
+        hcur = engine.residual_layernorm(query.reshape(B * nq, h), None, iqm.layernorm, eps)
+        for l, layer in enumerate(iqm.encoder.layer):
+            key = f"{l}."
+            S[key + "h"] = hcur
+            a = self_att(layer.attention, hcur, key + "a.")
+            c = cross_att(layer.crossattention, a, vis, Lv, vp, key + "c.")
+            t = cross_att(layer.text_crossattention, c, txt, Lt, None, key + "t.")
+            mix = engine.combine3(a, c, t, 0.4, 0.3, 0.3)
+            mi, mo = layer.intermediate_query.dense, layer.output_query.dense
+            inter = torch.empty(B * nq, mi.weight.shape[0], dtype=dt, device=dev)
+            engine.gemm(code, EPI_BIAS_GELU, mix.to(dt), engine.CACHE.get(mi.weight, code), engine._f32c(mi.bias), inter)
+            z = lin(mix.to(dt), mi)                                  # the pre-GELU rows, for the backward only
+            dense = lin(inter, mo)
+            S[key + "a"], S[key + "c"], S[key + "mix"], S[key + "z"] = a, c, mix, z
+            S[key + "inter"], S[key + "dense"] = inter.float(), dense
+            hcur = engine.residual_layernorm(dense, mix, layer.output_query.LayerNorm, eps)
+        S["last"] = hcur
+        out = engine.residual_layernorm(hcur, None, model.iqm_layer_norm, model.iqm_layer_norm.eps)
+        ctx.model, ctx.keys, ctx.dims = model, list(S), (B, L, Lv, Lt, code)
+        ctx.names = _iqm_param_names(model)
+        ctx.save_for_backward(*S.values())
+        return out.view(B, 2, h)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        from ._lib import ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_RELU
+        model, names = ctx.model, ctx.names
+        B, L, Lv, Lt, code = ctx.dims
+        S = dict(zip(ctx.keys, ctx.saved_tensors))
+        iqm, h, H = model.iqm, model.iqm_hidden_size, model.iqm.num_attention_heads
+        nq, R, eps = 2, 2 * H, iqm.eps
+        scale = 1.0 / (h // H) ** 0.5
+        wanted = {n for i, n in enumerate(names) if ctx.needs_input_grad[4 + i]}
+        need_rows, need_tap = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        need_txt = bool({"text_feature_proj.weight", "text_feature_proj.bias"} & wanted)
+        G = {}
+        buf = {"rows": None, "txt": None}
+
+        def linear_params(name, dz, u):
+            if name + ".weight" in wanted:
+                G[name + ".weight"] = _wgrad(dz, u)
+            if name + ".bias" in wanted:
+                G[name + ".bias"] = engine.bias_grad(dz)
+
+        def ln_bwd(name, ln, x, d_y, e):
+            if name + ".weight" in wanted or name + ".bias" in wanted:
+                G[name + ".weight"], G[name + ".bias"] = engine.layernorm_param_grad(x, d_y, e)
+            return engine.layernorm_backward(x, ln.weight, d_y, eps=e)
+
+        def tail_bwd(name, att, key, hin, d_y):
+            """-> (d of the residual input, d ctx)"""
+            s = engine.combine3(S[key + "dense"], hin, None, 1.0, 1.0, 0.0)
+            d_s = ln_bwd(name + "output.LayerNorm", att.output.LayerNorm, s, d_y, eps)
+            linear_params(name + "output.dense", d_s, S[key + "ctx"])
+            return d_s, _dx(d_s, att.output.dense.weight)
+
+        def self_bwd(name, att, key, hin, d_y):
+            d_h, d_ctx = tail_bwd(name, att, key, hin, d_y)
+            d_q, d_k, d_v = engine.small_attention_backward(S[key + "q"], S[key + "k"], S[key + "v"], d_ctx, B, nq, nq, H)
+            for m, dz in (("query", d_q), ("key", d_k), ("value", d_v)):
+                linear_params(f"{name}attention.{m}", dz, hin)
+            d_h = _sum(d_h, _dx(d_q, att.attention.query.weight), _dx(d_k, att.attention.key.weight))
+            return _sum(d_h, _dx(d_v, att.attention.value.weight))
+
+        def cross_bwd(name, att, key, hin, proj, d_y):
+            d_h, d_ctx = tail_bwd(name, att, key, hin, d_y)
+            d_full = engine.head_expand(d_ctx, H, 1.0, engine.F32)             # the gradient of head_diag
+            linear_params(name + "attention.value", d_full, S[key + "ebar"])
+            d_ebar = _dx(d_full, att.attention.value.weight)
+            qt = S[key + "qt"]
+            if proj is not None:
+                pname = "visual_feature_proj"
+                if pname + ".weight" in wanted:                                # ebar = xbar P^T + b_p
+                    G.setdefault(pname + ".weight", []).append(_wgrad(d_ebar, S[key + "xbar"]))
+                if pname + ".bias" in wanted:
+                    G.setdefault(pname + ".bias", []).append(engine.bias_grad(d_ebar))
+                d_xbar = _dx(d_ebar, proj.weight)
+                act = ACT_LEAKY if model.relu else ACT_NONE
+                d_qx, buf["rows"] = engine.cross_rows_backward(S[key + "qx"], S["vis"], d_xbar, B, R, Lv, code, act=act,
+                                                               need_x=need_rows, d_x=buf["rows"])
+                if pname + ".weight" in wanted:                                # qx = qt P
+                    G[pname + ".weight"].append(_wgrad(qt, d_qx))
+                d_qt = _dx_t(d_qx, proj.weight)
+            else:
+                d_qt, buf["txt"] = engine.cross_rows_backward(qt, S["txt"], d_ebar, B, R, Lt, code, need_x=need_txt,
+                                                              d_x=buf["txt"])
+            kname = name + "attention.key"
+            if kname + ".weight" in wanted:                                    # qt = qm W_k
+                G[kname + ".weight"] = _wgrad(S[key + "qm"], d_qt)
+            if kname + ".bias" in wanted:                                      # softmax-invariant
+                G[kname + ".bias"] = torch.zeros_like(att.attention.key.bias, dtype=torch.float32)
+            d_qm = _dx_t(d_qt, att.attention.key.weight)
+            d_q = engine.combine3(engine.head_diag(d_qm, H), None, None, scale, 0.0, 0.0)   # the gradient of head_expand
+            linear_params(name + "attention.query", d_q, hin)
+            return _sum(d_h, _dx(d_q, att.attention.query.weight))
+
+        d = engine._f32c(d_out).reshape(B * nq, h)
+        d = ln_bwd("iqm_layer_norm", model.iqm_layer_norm, S["last"], d, model.iqm_layer_norm.eps)
+        vp = model.visual_feature_proj
+        for l in range(len(iqm.encoder.layer) - 1, -1, -1):
+            layer, key, name = iqm.encoder.layer[l], f"{l}.", f"iqm.encoder.layer.{l}."
+            mix, a, c, hin = S[key + "mix"], S[key + "a"], S[key + "c"], S[key + "h"]
+            s = engine.combine3(S[key + "dense"], mix, None, 1.0, 1.0, 0.0)
+            d_s = ln_bwd(name + "output_query.LayerNorm", layer.output_query.LayerNorm, s, d, eps)
+            linear_params(name + "output_query.dense", d_s, S[key + "inter"])
+            d_z = engine.act_backward(ACT_GELU, S[key + "z"], _dx(d_s, layer.output_query.dense.weight), in_place=True)
+            linear_params(name + "intermediate_query.dense", d_z, mix)
+            d_mix = _sum(d_s, _dx(d_z, layer.intermediate_query.dense.weight))
+            d_c = cross_bwd(name + "text_crossattention.", layer.text_crossattention, key + "t.", c, None,
+                            engine.combine3(d_mix, None, None, 0.3, 0.0, 0.0))
+            d_a = cross_bwd(name + "crossattention.", layer.crossattention, key + "c.", a, vp,
+                            engine.combine3(d_mix, d_c, None, 0.3, 1.0, 0.0))
+            d = self_bwd(name + "attention.", layer.attention, key + "a.", hin,
+                         engine.combine3(d_mix, d_a, None, 0.4, 1.0, 0.0))
+        d_query = ln_bwd("iqm.layernorm", iqm.layernorm, S["query"].reshape(B * nq, h), d, eps)
+        if "pos_embedding" in wanted:
+            g = torch.zeros_like(model.pos_embedding, dtype=torch.float32)
+            g[:, :2, :] = engine.bias_grad(d_query.view(B, 2 * h)).view(1, 2, h)
+            G["pos_embedding"] = g
+        dq3 = d_query.view(B, 2, h)
+        d_cq = _sum(dq3[:, 0, :].contiguous(), dq3[:, 1, :].contiguous())
+        m0, m2 = model.class_query_mlp[0], model.class_query_mlp[2]
+        linear_params("class_query_mlp.2", d_cq, S["t1"])
+        d_z1 = engine.act_backward(ACT_RELU, S["t1"], _dx(d_cq, m2.weight), in_place=True)
+        linear_params("class_query_mlp.0", d_z1, S["cls"])
+        d_tap = None
+        if need_tap:
+            d_tap = torch.zeros(B, L, m0.weight.shape[1], dtype=torch.float32, device=d.device)
+            d_tap[:, 0, :] = _dx(d_z1, m0.weight)
+        if need_txt:
+            d_w, d_b = engine.linear_smallk_backward(S["te"], buf["txt"])
+            G["text_feature_proj.weight"], G["text_feature_proj.bias"] = d_w, d_b
+        for n in ("visual_feature_proj.weight", "visual_feature_proj.bias"):   # fixed order: layer by layer, last first
+            parts = G.get(n)
+            if parts:
+                total = parts[0]
+                for p in parts[1:]:
+                    total = _sum(total, p)
+                G[n] = total
+        params = dict(model.named_parameters())
+        grads = [G[n].view_as(params[n]).to(params[n].dtype) if n in wanted else None for n in names]
+        d_rows = buf["rows"].view(B, Lv, -1) if need_rows else None
+        return (None, d_rows, d_tap, None, *grads)
+
+
 def visual_taps(model, image):
     """The tap streams of AdaptedCLIP's visual tower, [B, L, D] each (CLS row included), one per entry of model.levels
     in ascending order, carrying a graph to model.image_adapter["layer_adapters"][i].weight: see VisualTaps.
@@ -357,22 +647,45 @@ def visual_taps(model, image):
     return list(VisualTaps.apply(model, image, *[m.weight for m in model.image_adapter["layer_adapters"]]))
 
 
-def visual_heads(model, image):
+def visual_heads(model, image, taps=None):
     """AdaptedCLIP.forward(image)[:2] with a graph -> (seg_tokens: one [B, L-1, E] tensor of unit rows per tap level,
     det_token [B, E]): visual_taps, then one TapHead per level with the det head on the last one, paired as the forward
     pairs them and bit-identical to it.  The graph reaches image_adapter["layer_adapters"][i].weight, ["seg_proj"][k]
-    and ["det_proj"], whichever of them require grad.  Not built: the backward of the IQM branch's 2-row query side
-    (the forward's third output; iqm_map_train hands it d_queries, iqm_visual_rows is its key / value side)."""
+    and ["det_proj"], whichever of them require grad.  taps: the streams of a visual_taps(model, image) call the caller
+    has already made (visual_outputs shares them with the IQM branch); None computes them here."""
     seg_proj = model.image_adapter["seg_proj"]
     det_weight = model.image_adapter["det_proj"].weight
     seg_tokens, det_token = [], None
-    for k, tap in enumerate(visual_taps(model, image)):
+    for k, tap in enumerate(visual_taps(model, image) if taps is None else taps):
         if k == len(model.levels) - 1:
             seg, det_token = TapHead.apply(model, tap, seg_proj[k].weight, det_weight)
         else:
             seg = TapHead.apply(model, tap, seg_proj[k].weight, None)
         seg_tokens.append(seg)
     return seg_tokens, det_token
+
+
+def iqm_queries(model, taps, anchors):
+    """The IQM branch's final queries [B, 2, h] = AdaptedCLIP.forward(image, anchors)[2].last_hidden_state, with a graph
+    to every parameter the branch reads (model.iqm, class_query_mlp, visual_feature_proj, text_feature_proj,
+    iqm_layer_norm, pos_embedding[:, :2]), to query_adapters and, through the taps [B, L, D] (from visual_taps), to
+    layer_adapters: iqm_visual_rows for the key / value rows, IqmQueries for the 2-row query side.  The anchors
+    [B, 768, 2] take no gradient.  NotImplementedError (before any launch): model.levels does not end at the tower's
+    last block, or a configuration outside the aaclip_cross_rows form (see _iqm_train_check)."""
+    _iqm_train_check(model)
+    taps = list(taps)
+    rows = iqm_visual_rows(model, taps, pre_activation_grad=model.relu)
+    params = dict(model.named_parameters())
+    return IqmQueries.apply(model, rows, taps[-1], anchors, *[params[n] for n in _iqm_param_names(model)])
+
+
+def visual_outputs(model, image, anchors):
+    """AdaptedCLIP.forward(image, text_embeddings=anchors) with a graph -> (seg_tokens, det_token, queries [B, 2, h])
+    from ONE visual_taps call: visual_heads and iqm_queries on the same tap streams."""
+    _iqm_train_check(model)
+    taps = visual_taps(model, image)
+    seg_tokens, det_token = visual_heads(model, image, taps=taps)
+    return seg_tokens, det_token, iqm_queries(model, taps, anchors)
 
 
 def encode_text(model, tokens):

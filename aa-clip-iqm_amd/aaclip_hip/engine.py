@@ -1023,6 +1023,97 @@ def linear_smallk(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# backward building blocks of the IQM branch's query side (include/aaclip.h, csrc/iqm_query_backward.hip): fp32
+SMALL_ATTENTION_BACKWARD_MAX_KEYS = 256   # csrc/kernels.h SAB_MAXK
+
+
+def small_attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, d_out: torch.Tensor, B: int, nq: int,
+                             Lk: int, heads: int, need_q: bool = True, need_k: bool = True, need_v: bool = True):
+    """Backward of small_attention for fp32 k / v -> (d q [B*nq, D], d k [B*Lk, D], d v [B*Lk, D]), None where not
+    needed: aaclip_small_attention_backward."""
+    require_gpu(q, "small_attention_backward")
+    if not (need_q or need_k or need_v):
+        raise ValueError("small_attention_backward: nothing to compute")
+    q, k, v, d_out = _f32c(q), _f32c(k), _f32c(v), _f32c(d_out)
+    D = q.shape[-1]
+    hd = D // heads
+    d_q = torch.empty_like(q) if need_q else None
+    d_k = torch.empty_like(k) if need_k else None
+    d_v = torch.empty_like(v) if need_v else None
+    _lib.check(_lib.load().aaclip_small_attention_backward(q.data_ptr(), k.data_ptr(), v.data_ptr(), d_out.data_ptr(),
+                                                           _ptr(d_q), _ptr(d_k), _ptr(d_v), B, nq, Lk, heads, hd,
+                                                           1.0 / (hd ** 0.5), _stream(q.device)),
+               "small_attention_backward")
+    return d_q, d_k, d_v
+
+
+def layernorm_param_grad(x: torch.Tensor, d_y: torch.Tensor, eps: float):
+    """(d weight [D], d bias [D]) of y = LayerNorm(x) over fp32 rows [rows, D]: aaclip_layernorm_param_grad."""
+    require_gpu(x, "layernorm_param_grad")
+    lib = _lib.load()
+    x, d_y = _f32c(x), _f32c(d_y)
+    D = x.shape[-1]
+    rows = x.numel() // D
+    d_w = torch.empty(D, dtype=torch.float32, device=x.device)
+    d_b = torch.empty_like(d_w)
+    ws = Workspace.get(x.device, lib.aaclip_layernorm_param_grad_workspace_bytes(rows, D))
+    _lib.check(lib.aaclip_layernorm_param_grad(x.data_ptr(), d_y.data_ptr(), d_w.data_ptr(), d_b.data_ptr(), rows, D,
+                                               float(eps), ws.data_ptr(), ws.numel(), _stream(x.device)),
+               "layernorm_param_grad")
+    return d_w, d_b
+
+
+def bias_grad(dz: torch.Tensor, N: Optional[int] = None) -> torch.Tensor:
+    """db[n] = sum_r dz[r, n] over the first N columns (default: all) of contiguous fp32 dz [rows, ldz]."""
+    require_gpu(dz, "bias_grad")
+    lib = _lib.load()
+    dz = _f32c(dz)
+    rows, ldz = dz.shape
+    N = ldz if N is None else int(N)
+    db = torch.empty(N, dtype=torch.float32, device=dz.device)
+    ws = Workspace.get(dz.device, lib.aaclip_bias_grad_workspace_bytes(rows, N))
+    _lib.check(lib.aaclip_bias_grad(dz.data_ptr(), ldz, db.data_ptr(), rows, N, ws.data_ptr(), ws.numel(),
+                                    _stream(dz.device)), "bias_grad")
+    return db
+
+
+def act_backward(act: int, zy: torch.Tensor, d_y: torch.Tensor, in_place: bool = False) -> torch.Tensor:
+    """d z = d y * act': ACT_GELU from the pre-activation zy, ACT_RELU from the activation's output zy.
+    in_place: d z overwrites d_y (contiguous fp32)."""
+    require_gpu(zy, "act_backward")
+    zy = _f32c(zy)
+    if in_place:
+        if d_y.dtype != torch.float32 or not d_y.is_contiguous():
+            raise ValueError("act_backward: in_place needs a contiguous fp32 d_y")
+    else:
+        d_y = _f32c(d_y)
+    if d_y.numel() != zy.numel():
+        raise ValueError("act_backward: zy and d_y must have the same number of elements")
+    d_z = d_y if in_place else torch.empty_like(d_y)
+    _lib.check(_lib.load().aaclip_act_backward(int(act), zy.data_ptr(), d_y.data_ptr(), d_z.data_ptr(), zy.numel(),
+                                               _stream(zy.device)), "act_backward")
+    return d_z
+
+
+def linear_smallk_backward(x: torch.Tensor, d_y: torch.Tensor):
+    """(d weight [N, K], d bias [N]) of y = x W^T + b for in_features K <= 4; x [..., K], d_y [R, N] fp32."""
+    require_gpu(d_y, "linear_smallk_backward")
+    lib = _lib.load()
+    x, d_y = _f32c(x), _f32c(d_y)
+    K = x.shape[-1]
+    R, N = d_y.shape
+    if x.numel() != R * K:
+        raise ValueError("linear_smallk_backward: x must hold one row of K values per row of d_y")
+    d_w = torch.empty(N, K, dtype=torch.float32, device=d_y.device)
+    d_b = torch.empty(N, dtype=torch.float32, device=d_y.device)
+    ws = Workspace.get(d_y.device, lib.aaclip_linear_smallk_backward_workspace_bytes(R, N, K))
+    _lib.check(lib.aaclip_linear_smallk_backward(x.data_ptr(), d_y.data_ptr(), d_w.data_ptr(), d_b.data_ptr(), R, N, K,
+                                                 ws.data_ptr(), ws.numel(), _stream(d_y.device)),
+               "linear_smallk_backward")
+    return d_w, d_b
+
+
 def drop_cls_rows(src: torch.Tensor, dst: torch.Tensor, B: int, L: int, row_off: int, code: int) -> None:
     """src [B*L, E] -> rows 1.. of every image into dst [B, rows_per_image, E] at row_off."""
     E = src.shape[-1]

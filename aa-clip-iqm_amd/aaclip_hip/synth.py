@@ -252,7 +252,9 @@ def synth_iqm_state_dict(cfg: ClipCfg, levels: int = 4, relu: bool = False, hidd
         p = f"iqm.encoder.layer.{l}."
         for att in ("attention", "crossattention", "text_crossattention"):
             for m in ("query", "key", "value"):
-                lin(p + att + ".attention." + m, hidden, hidden)
+                # the text cross-attention reads text_feature_proj's 768-wide rows whatever the branch's own width is
+                in_f = 768 if att == "text_crossattention" and m != "query" else hidden
+                lin(p + att + ".attention." + m, hidden, in_f)
             lin(p + att + ".output.dense", hidden, hidden)
             ln(p + att + ".output.LayerNorm", hidden)
         for suffix in ("", "_query"):

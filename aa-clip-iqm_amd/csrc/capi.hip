@@ -319,6 +319,74 @@ int aaclip_linear_smallk(int out_dtype, const float* x, const float* W, const fl
   return finish("linear_smallk");
 }
 
+// ---- iqm_query_backward.hip
+int aaclip_small_attention_backward(const float* q, const float* k, const float* v, const float* d_out, float* d_q,
+                                    float* d_k, float* d_v, int B, int nq, int Lk, int H, int hd, float scale,
+                                    void* stream) {
+  REQUIRE(q && k && v && d_out, "small_attention_backward: null pointer");
+  REQUIRE(d_q || d_k || d_v, "small_attention_backward: nothing to compute (d_q, d_k and d_v are all NULL)");
+  REQUIRE(B > 0 && nq > 0 && Lk > 0 && H > 0 && hd > 0, "small_attention_backward: empty problem");
+  REQUIRE(B <= 65535 && H <= 65535, "small_attention_backward: grid limit (B, H <= 65535)");
+  REQUIRE(nq <= 4, "small_attention_backward: 1..4 queries per image");
+  REQUIRE(Lk <= SAB_MAXK, "small_attention_backward: 1..256 keys");
+  REQUIRE(hd % 4 == 0 && hd <= 128, "small_attention_backward: head size must be a multiple of 4, <= 128");
+  REQUIRE_ALIGNED16("small_attention_backward", q, k, v, d_out, d_q, d_k, d_v);
+  launch_small_attention_backward(q, k, v, d_out, d_q, d_k, d_v, B, nq, Lk, H, hd, scale, (hipStream_t)stream);
+  return finish("small_attention_backward");
+}
+
+size_t aaclip_layernorm_param_grad_workspace_bytes(long rows, int D) { return layernorm_param_grad_ws_bytes(rows, D); }
+
+int aaclip_layernorm_param_grad(const float* x, const float* d_y, float* d_w, float* d_b, long rows, int D, float eps,
+                                void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(x && d_y && ws, "layernorm_param_grad: null pointer");
+  REQUIRE(d_w || d_b, "layernorm_param_grad: nothing to compute (d_w and d_b are both NULL)");
+  REQUIRE(rows > 0 && D > 0, "layernorm_param_grad: empty problem");
+  REQUIRE(D % 64 == 0 && D <= 4096, "layernorm_param_grad: D must be a multiple of 64, <= 4096");
+  REQUIRE(rows < (1L << 31), "layernorm_param_grad: too many rows");
+  REQUIRE_ALIGNED16("layernorm_param_grad", x, d_y, d_w, d_b, ws);
+  REQUIRE(ws_bytes >= layernorm_param_grad_ws_bytes(rows, D), "layernorm_param_grad: workspace too small");
+  launch_layernorm_param_grad(x, d_y, d_w, d_b, rows, D, eps, ws, (hipStream_t)stream);
+  return finish("layernorm_param_grad");
+}
+
+size_t aaclip_bias_grad_workspace_bytes(long rows, int N) { return bias_grad_ws_bytes(rows, N); }
+
+int aaclip_bias_grad(const float* dz, long ldz, float* db, long rows, int N, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(dz && db && ws, "bias_grad: null pointer");
+  REQUIRE(rows > 0 && N > 0, "bias_grad: empty problem");
+  REQUIRE(ldz >= N, "bias_grad: ldz must be at least N");
+  REQUIRE_ALIGNED16("bias_grad", dz, db, ws);
+  REQUIRE(ws_bytes >= bias_grad_ws_bytes(rows, N), "bias_grad: workspace too small");
+  launch_bias_grad(dz, ldz, db, rows, N, ws, (hipStream_t)stream);
+  return finish("bias_grad");
+}
+
+int aaclip_act_backward(int act, const float* zy, const float* d_y, float* d_z, long n, void* stream) {
+  REQUIRE(act == AACLIP_ACT_GELU || act == AACLIP_ACT_RELU, "act_backward: bad activation (GELU or RELU)");
+  REQUIRE(zy && d_y && d_z, "act_backward: null pointer");
+  REQUIRE(n > 0, "act_backward: empty problem");
+  REQUIRE_ALIGNED16("act_backward", zy, d_y, d_z);
+  launch_iqm_act_backward(act, zy, d_y, d_z, n, (hipStream_t)stream);
+  return finish("act_backward");
+}
+
+size_t aaclip_linear_smallk_backward_workspace_bytes(long R, int N, int K) {
+  return linear_smallk_backward_ws_bytes(R, N, K);
+}
+
+int aaclip_linear_smallk_backward(const float* x, const float* d_y, float* d_w, float* d_b, long R, int N, int K, void* ws,
+                                  size_t ws_bytes, void* stream) {
+  REQUIRE(x && d_y && ws, "linear_smallk_backward: null pointer");
+  REQUIRE(d_w || d_b, "linear_smallk_backward: nothing to compute (d_w and d_b are both NULL)");
+  REQUIRE(R > 0 && N > 0 && K > 0, "linear_smallk_backward: empty problem");
+  REQUIRE(K <= 4, "linear_smallk_backward: in_features must be 1..4");
+  REQUIRE_ALIGNED16("linear_smallk_backward", x, d_y, d_w, d_b, ws);
+  REQUIRE(ws_bytes >= linear_smallk_backward_ws_bytes(R, N, K), "linear_smallk_backward: workspace too small");
+  launch_linear_smallk_backward(x, d_y, d_w, d_b, R, N, K, ws, (hipStream_t)stream);
+  return finish("linear_smallk_backward");
+}
+
 int aaclip_drop_cls_rows(int dtype, const void* src, void* dst, int B, int L, int E, int rows_per_image, int row_off,
                          void* stream) {
   REQUIRE(plain_dtype_ok(dtype), "drop_cls_rows: bad dtype (fp32, fp16 or bf16)");

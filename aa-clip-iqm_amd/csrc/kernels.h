@@ -185,6 +185,24 @@ size_t cross_rows_backward_ws_bytes(int B, int R, int Lk, int Dk);
 void launch_cross_rows_backward(int x_dtype, const float* qt, const void* x, const float* dout, float* d_qt, float* d_x,
                                 int act, int accumulate, int B, int R, int Lk, int Dk, void* ws, hipStream_t s);
 
+// ---- iqm_query_backward.hip : backward building blocks of the IQM branch's 2-row query side (fp32, fixed-order sums)
+constexpr int SAB_MAXK = 256;          // keys of small_attention_backward: one per thread
+constexpr int IQB_CHUNK_ROWS = 32;     // rows of a chunk of the column sums, up to IQB_MAX_CHUNKS chunks (then longer ones)
+constexpr int IQB_MAX_CHUNKS = 64;
+int iqb_chunks(long rows);
+void launch_small_attention_backward(const float* q, const float* k, const float* v, const float* dout, float* d_q,
+                                     float* d_k, float* d_v, int B, int nq, int Lk, int H, int hd, float scale,
+                                     hipStream_t s);
+size_t layernorm_param_grad_ws_bytes(long rows, int D);
+void launch_layernorm_param_grad(const float* x, const float* dy, float* d_w, float* d_b, long rows, int D, float eps,
+                                 void* ws, hipStream_t s);
+size_t bias_grad_ws_bytes(long rows, int N);
+void launch_bias_grad(const float* dz, long ldz, float* db, long rows, int N, void* ws, hipStream_t s);
+void launch_iqm_act_backward(int act, const float* zy, const float* dy, float* dz, long n, hipStream_t s);
+size_t linear_smallk_backward_ws_bytes(long R, int N, int K);
+void launch_linear_smallk_backward(const float* x, const float* dy, float* d_w, float* d_b, long R, int N, int K, void* ws,
+                                   hipStream_t s);
+
 // ---- text_backward.hip : backward of the adapted text tower (fp32, fixed-order reductions)
 constexpr int ATTN_BWD_MAX_L = 128;
 constexpr int WGRAD_MAX_CHUNKS = 16;

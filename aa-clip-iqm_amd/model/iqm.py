@@ -13,7 +13,7 @@ cannot be reproduced or checkpointed:
   * `visual_feature_proj` / `text_feature_proj` are created by the reference INSIDE forward with fresh random weights
     (adapter.py:213-218, 241-243) and never saved; here they are ordinary parameters (Linear(hidden, hidden) and
     Linear(2, 768): 2 because the anchors arrive as [B, 768, 2]) that are initialised once and saved with the rest;
-  * dropout is the identity (eval); there is no training path.
+  * dropout is the identity: the training path (aaclip_hip.autograd.iqm_queries) runs this eval forward with a graph.
 The modules below are parameter containers: every product runs on the library's MFMA GEMM, the rest on the small
 kernels of csrc/iqm.hip (aaclip_small_attention, aaclip_residual_layernorm, ...).
 """

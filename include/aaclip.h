@@ -58,7 +58,8 @@ extern "C" {
 #define AACLIP_ABI_VERSION 9   /* 9: attention and block backward for rows of any length (the *_long entry points) */
 
 enum { AACLIP_F32 = 0, AACLIP_F16 = 1, AACLIP_BF16 = 2, AACLIP_F16X2 = 3 };
-enum { AACLIP_ACT_NONE = 0, AACLIP_ACT_LEAKY = 1, AACLIP_ACT_RELU = 2 };
+enum { AACLIP_ACT_NONE = 0, AACLIP_ACT_LEAKY = 1, AACLIP_ACT_RELU = 2,
+       AACLIP_ACT_GELU = 3 /* aaclip_act_backward only */ };
 /* generic GEMM epilogues (aaclip_gemm) */
 enum { AACLIP_EPI_BIAS = 0, AACLIP_EPI_BIAS_GELU = 1, AACLIP_EPI_BIAS_RESID = 2, AACLIP_EPI_ACT_F32 = 3 };
 
@@ -500,6 +501,41 @@ int aaclip_combine3(const float* a, const float* b, const float* c, float wa, fl
  * out_dtype. */
 int aaclip_linear_smallk(int out_dtype, const float* x, const float* W, const float* bias, void* y, long R, int N, int K,
                          void* stream);
+/* ---- Backward building blocks of the IQM branch's 2-row query side (class_query_mlp, IQM.layernorm, the self-attention,
+ * the query-side products of the cross-attentions, the feed-forward and iqm_layer_norm): what aaclip_gemm (fp32, on the
+ * transposed weight), aaclip_gemm_wgrad, aaclip_layernorm_backward and aaclip_cross_rows_backward do not cover.  The
+ * gradient of aaclip_head_expand is aaclip_head_diag times the scale and the other way round, that of aaclip_combine3 is
+ * aaclip_combine3.  fp32 only; no atomics, every sum in a fixed order: two calls on the same inputs give the same bits.
+ * Every pointer (and workspace) 16-byte aligned; all checks precede the first launch; each entry's errors carry its own
+ * name as prefix.  Every *_workspace_bytes is 0 for an empty problem and monotonic in each argument. */
+
+/* Backward of aaclip_small_attention for fp32 k and v.  q, d_out, d_q [B, nq, H*hd]; k, v, d_k, d_v [B*Lk, H*hd].  With
+ * p_a = softmax_j(scale q_a . k_j) recomputed, g_aj = d_out_a . v_j, ds_aj = p_aj (g_aj - sum_j p_aj g_aj):
+ *   d_v_j = sum_a p_aj d_out_a,  d_k_j = scale sum_a ds_aj q_a,  d_q_a = scale sum_j ds_aj k_j.
+ * d_q, d_k, d_v may each be NULL, not all three.  nq <= 4, hd a multiple of 4 and <= 128 (the forward's limits), Lk in
+ * 1..256, B and H <= 65535.  One workgroup per (head, image); each element of d_k and d_v is written by one thread. */
+int aaclip_small_attention_backward(const float* q, const float* k, const float* v, const float* d_out, float* d_q,
+                                    float* d_k, float* d_v, int B, int nq, int Lk, int H, int hd, float scale,
+                                    void* stream);
+/* d_w[c] = sum_r d_y[r, c] xhat[r, c], d_b[c] = sum_r d_y[r, c], xhat = (x - mean) * rstd of row r under eps: the affine
+ * parameters of y = LayerNorm(x).  For LayerNorm(a + b) pass x = a + b (aaclip_combine3); the input gradient is
+ * aaclip_layernorm_backward.  x, d_y [rows, D]; rows >= 1; D a multiple of 64, <= 4096; d_w or d_b may be NULL, not both. */
+size_t aaclip_layernorm_param_grad_workspace_bytes(long rows, int D);
+int aaclip_layernorm_param_grad(const float* x, const float* d_y, float* d_w, float* d_b, long rows, int D, float eps,
+                                void* ws, size_t ws_bytes, void* stream);
+/* db[n] = sum_r dz[r, n] for dz [rows, ldz >= N] (only the first N columns of a row are read). */
+size_t aaclip_bias_grad_workspace_bytes(long rows, int N);
+int aaclip_bias_grad(const float* dz, long ldz, float* db, long rows, int N, void* ws, size_t ws_bytes, void* stream);
+/* d_z = d_y * act'.  AACLIP_ACT_GELU (erf form): zy is the PRE-ACTIVATION z, act' = Phi(z) + z phi(z).
+ * AACLIP_ACT_RELU: zy is the activation's OUTPUT, act' = 1 for zy > 0 and 0 otherwise (the kink convention stated at
+ * aaclip_adapter_mix_backward).  n elements; d_z may alias d_y. */
+int aaclip_act_backward(int act, const float* zy, const float* d_y, float* d_z, long n, void* stream);
+/* Backward of aaclip_linear_smallk for its parameters: dW[n, k] = sum_r d_y[r, n] x[r, k], db[n] = sum_r d_y[r, n];
+ * x fp32 [R, K], d_y fp32 [R, N], K in 1..4; d_w or d_b may be NULL, not both.  The rows are cut into chunks whose
+ * partial sums are added in chunk order.  No d_x: the anchors are constants in stage 2. */
+size_t aaclip_linear_smallk_backward_workspace_bytes(long R, int N, int K);
+int aaclip_linear_smallk_backward(const float* x, const float* d_y, float* d_w, float* d_b, long R, int N, int K, void* ws,
+                                  size_t ws_bytes, void* stream);
 /* Rows 1..L-1 of every image of src [B, L, E] (dtype) -> rows row_off.. of every image of dst [B, rows_per_image, E]:
  * the torch.cat over dim 1 of the projected tap levels without their CLS row (model/adapter.py:171,206-211). */
 int aaclip_drop_cls_rows(int dtype, const void* src, void* dst, int B, int L, int E, int rows_per_image, int row_off,
