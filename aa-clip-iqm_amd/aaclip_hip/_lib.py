@@ -79,6 +79,11 @@ SIGNATURES = {
     "aaclip_resample_ksize": (_i, [_i, _i]),
     "aaclip_resample_table": (_i, [_i, _i, _vp, _vp]),
     "aaclip_preprocess": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aaclip_color_jitter_workspace_bytes": (_sz, [_i, _i, _i]),
+    "aaclip_color_jitter": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "aaclip_nearest_table": (_i, [_i, _i, _vp]),
+    "aaclip_mask_preprocess": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "aaclip_augment_geometric": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aaclip_row_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp] + [_i] * 6 + [_vp, _sz, _vp]),
     "aaclip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _l, _i, _f, _vp]),
     "aaclip_gemm": (_i, [_i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _f, _vp]),

@@ -872,6 +872,110 @@ def preprocess(src_u8: torch.Tensor, img_size: int, mean=CLIP_MEAN, std=CLIP_STD
 
 
 # ------------------------------------------------------------------------------------------------
+# train-time input work (reference dataset/__init__.py:37-102): every random number is an argument
+def _param(t: torch.Tensor, dtype: torch.dtype, shape: tuple, dev: torch.device, what: str) -> torch.Tensor:
+    """A per-frame parameter array as the kernels read it: `dtype`, contiguous, on `dev` (host tensors are uploaded)"""
+    t = torch.as_tensor(t)
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{what} must have shape {shape}, got {tuple(t.shape)}")
+    return t.to(device=dev, dtype=dtype).contiguous()
+
+
+def color_jitter(src_u8: torch.Tensor, factors: torch.Tensor, apply: torch.Tensor,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [B,H,W,3] on the GPU -> uint8 [B,H,W,3]: Pillow's ImageEnhance Brightness, Contrast, Color in that order.
+    factors fp32 [B,3]; apply int32 [B], bit 0 / 1 / 2 selects the brightness / contrast / saturation step.
+    out: None (a new tensor) or a contiguous tensor of src's shape; `out=src_u8` works in place."""
+    require_gpu(src_u8, "color_jitter")
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[-1] != 3:
+        raise ValueError("color_jitter expects uint8 [B, H, W, 3]")
+    if out is None:
+        src_u8 = src_u8.contiguous()
+        out = torch.empty_like(src_u8)
+    elif (not src_u8.is_contiguous() or not out.is_contiguous() or out.dtype != torch.uint8
+          or out.shape != src_u8.shape or out.device != src_u8.device):
+        raise ValueError("color_jitter: with out given, src and out must be contiguous uint8 tensors of one shape and device")
+    B, H, W, _ = src_u8.shape
+    dev = src_u8.device
+    factors = _param(factors, torch.float32, (B, 3), dev, "color_jitter: factors")
+    apply = _param(apply, torch.int32, (B,), dev, "color_jitter: apply")
+    lib = _lib.load()
+    ws = Workspace.get(dev, lib.aaclip_color_jitter_workspace_bytes(B, H, W))
+    _lib.check(lib.aaclip_color_jitter(src_u8.data_ptr(), out.data_ptr(), B, H, W, factors.data_ptr(), apply.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), _stream(dev)), "color_jitter")
+    return out
+
+
+def nearest_table(in_size: int, out_size: int) -> torch.Tensor:
+    """Host table of Pillow's NEAREST resize of one axis: int32 [out], the source index of every output index."""
+    idx = torch.empty(out_size, dtype=torch.int32)
+    _lib.check(_lib.load().aaclip_nearest_table(int(in_size), int(out_size), idx.data_ptr()), "nearest_table")
+    return idx
+
+
+_NEAREST_TABLES: Dict[tuple, tuple] = {}
+
+
+def mask_preprocess(mask_u8: torch.Tensor, img_size: int, normal: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [B,Hm,Wm] on the GPU -> fp32 [B,1,S,S] of 0 / 1: Resize((S,S), NEAREST), ToTensor, != 0.
+    normal [B] (any integer / bool dtype) or None: a set entry gives an all-zero mask, its source is not read."""
+    require_gpu(mask_u8, "mask_preprocess")
+    if mask_u8.dtype != torch.uint8 or mask_u8.dim() != 3:
+        raise ValueError("mask_preprocess expects uint8 [B, H, W]")
+    mask_u8 = mask_u8.contiguous()
+    B, Hm, Wm = mask_u8.shape
+    dev = mask_u8.device
+    key = (dev, Hm, Wm, img_size)
+    tabs = _NEAREST_TABLES.get(key)
+    if tabs is None:
+        tabs = (nearest_table(Wm, img_size).to(dev), nearest_table(Hm, img_size).to(dev))
+        _NEAREST_TABLES[key] = tabs
+    if normal is not None:
+        normal = _param(normal, torch.int32, (B,), dev, "mask_preprocess: normal")
+    out = torch.empty(B, 1, img_size, img_size, device=dev, dtype=torch.float32)
+    _lib.check(_lib.load().aaclip_mask_preprocess(mask_u8.data_ptr(), B, Hm, Wm, img_size, tabs[0].data_ptr(),
+                                                  tabs[1].data_ptr(), _ptr(normal), out.data_ptr(), _stream(dev)),
+               "mask_preprocess")
+    return out
+
+
+def augment_geometric(image: torch.Tensor, mask: torch.Tensor, angle_deg: torch.Tensor, shift: torch.Tensor,
+                      flags: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """image fp32 [B,3,S,S], mask fp32 [B,1,S,S] on the GPU -> (image, mask) after, per frame, rotation by angle_deg
+    (flags bit 0), shift by shift[b] = (tx, ty) (bit 1), horizontal flip (bit 2), vertical flip (bit 3), in that order:
+    nearest sampling, zero fill.  angle_deg fp32 [B], shift int32 [B,2], flags int32 [B]."""
+    require_gpu(image, "augment_geometric")
+    require_gpu(mask, "augment_geometric")
+    if (image.dtype != torch.float32 or image.dim() != 4 or image.shape[1] != 3 or image.shape[2] != image.shape[3]
+            or mask.dtype != torch.float32 or tuple(mask.shape) != (image.shape[0], 1) + tuple(image.shape[2:])):
+        raise ValueError("augment_geometric expects fp32 image [B, 3, S, S] and fp32 mask [B, 1, S, S]")
+    image, mask = image.contiguous(), mask.contiguous()
+    B, _, S, _ = image.shape
+    dev = image.device
+    angle_deg = _param(angle_deg, torch.float32, (B,), dev, "augment_geometric: angle_deg")
+    shift = _param(shift, torch.int32, (B, 2), dev, "augment_geometric: shift")
+    flags = _param(flags, torch.int32, (B,), dev, "augment_geometric: flags")
+    image_out, mask_out = torch.empty_like(image), torch.empty_like(mask)
+    _lib.check(_lib.load().aaclip_augment_geometric(image.data_ptr(), mask.data_ptr(), B, S, angle_deg.data_ptr(),
+                                                    shift.data_ptr(), flags.data_ptr(), image_out.data_ptr(),
+                                                    mask_out.data_ptr(), _stream(dev)), "augment_geometric")
+    return image_out, mask_out
+
+
+def train_preprocess(frames_u8: torch.Tensor, masks_u8: torch.Tensor, normal: torch.Tensor, params: dict,
+                     img_size: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The reference's train-time transform of one group of equally sized frames (dataset/__init__.py:37-102) for GIVEN
+    random numbers: colour jitter -> BICUBIC resize, ToTensor, Normalize (preprocess, unchanged) on the frames, NEAREST
+    resize and != 0 on the masks, then rotation / shift / flips of both together.
+    frames_u8 uint8 [B,H,W,3], masks_u8 uint8 [B,Hm,Wm], normal [B] (set: the frame has no mask), all on the GPU;
+    params: the dict of dataset.draw_augment_params -> (image fp32 [B,3,S,S], mask fp32 [B,1,S,S])."""
+    frames = color_jitter(frames_u8, params["color_factors"], params["color_apply"])
+    image = preprocess(frames, img_size)
+    mask = mask_preprocess(masks_u8, img_size, normal)
+    return augment_geometric(image, mask, params["angle"], params["shift"], params["flags"])
+
+
+# ------------------------------------------------------------------------------------------------
 # IQM side branch (reference model/iqm.py, model/adapter.py:186-269, test_last.py:102-147): thin wrappers of the C ABI
 def gemm(code: int, epi: int, a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor,
          act: int = 0) -> torch.Tensor:

@@ -1170,6 +1170,64 @@ int aaclip_preprocess(const uint8_t* src, int B, int Hs, int Ws, int S, const in
   return finish("preprocess");
 }
 
+// ---- train-time input work (augment.hip)
+static inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+
+size_t aaclip_color_jitter_workspace_bytes(int B, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0) return 0;
+  return up256((size_t)B * color_jitter_sum_blocks((long)H * W) * 8 + (size_t)B * 4);
+}
+
+int aaclip_color_jitter(const uint8_t* src, uint8_t* dst, int B, int H, int W, const float* factors,
+                        const int32_t* apply, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(src && dst && factors && apply && ws, "color_jitter: null pointer");
+  REQUIRE(B > 0 && B <= 65535 && H >= 1 && W >= 1 && H <= (1 << 16) && W <= (1 << 16), "color_jitter: bad frame shape");
+  const size_t bytes = (size_t)B * H * W * 3;
+  REQUIRE(bytes <= ((size_t)1 << 36), "color_jitter: more than 64 GiB of frames in one call");
+  REQUIRE(src == dst || !ranges_overlap(src, bytes, dst, bytes),
+          "color_jitter: dst must be src itself (in place) or not overlap it");
+  REQUIRE(((uintptr_t)ws & 7) == 0, "color_jitter: workspace must be 8-byte aligned");
+  REQUIRE(ws_bytes >= aaclip_color_jitter_workspace_bytes(B, H, W), "color_jitter: workspace too small");
+  launch_color_jitter(src, dst, B, H, W, factors, apply, ws, (hipStream_t)stream);
+  return finish("color_jitter");
+}
+
+int aaclip_nearest_table(int in_size, int out_size, int32_t* idx) {
+  REQUIRE(idx, "nearest_table: null pointer");
+  REQUIRE(in_size >= 1 && out_size >= 1 && in_size <= (1 << 16) && out_size <= (1 << 16),
+          "nearest_table: sizes must be 1..65536");
+  nearest_table(in_size, out_size, idx);
+  return 0;
+}
+
+int aaclip_mask_preprocess(const uint8_t* src, int B, int Hm, int Wm, int S, const int32_t* xmap, const int32_t* ymap,
+                           const int32_t* normal, float* out, void* stream) {
+  REQUIRE(src && xmap && ymap && out, "mask_preprocess: null pointer");
+  REQUIRE(B > 0 && B <= 65535 && Hm >= 1 && Wm >= 1 && Hm <= (1 << 16) && Wm <= (1 << 16),
+          "mask_preprocess: bad source shape");
+  REQUIRE(S >= 1 && S <= 4096, "mask_preprocess: output size must be 1..4096");
+  launch_mask_preprocess(src, B, Hm, Wm, S, xmap, ymap, normal, out, (hipStream_t)stream);
+  return finish("mask_preprocess");
+}
+
+int aaclip_augment_geometric(const float* image, const float* mask, int B, int S, const float* angle_deg,
+                             const int32_t* shift, const int32_t* flags, float* image_out, float* mask_out,
+                             void* stream) {
+  REQUIRE(image && mask && angle_deg && shift && flags && image_out && mask_out, "augment_geometric: null pointer");
+  REQUIRE(B > 0 && B <= 65535, "augment_geometric: batch must be 1..65535");
+  REQUIRE(S >= 1 && S <= 4096, "augment_geometric: size must be 1..4096");
+  const size_t plane = (size_t)S * S * 4, ni = (size_t)B * 3 * plane, nm = (size_t)B * plane;
+  REQUIRE(!ranges_overlap(image_out, ni, image, ni) && !ranges_overlap(image_out, ni, mask, nm) &&
+              !ranges_overlap(mask_out, nm, image, ni) && !ranges_overlap(mask_out, nm, mask, nm) &&
+              !ranges_overlap(image_out, ni, mask_out, nm),
+          "augment_geometric: the outputs must not overlap the inputs or each other (every pixel is a gather)");
+  launch_augment_geometric(image, mask, B, S, angle_deg, shift, flags, image_out, mask_out, (hipStream_t)stream);
+  return finish("augment_geometric");
+}
+
 int aaclip_text_embed(const int32_t* tokens, const float* table, const float* pos, float* x, int n, int T, int D,
                       int vocab, void* stream) {
   REQUIRE(tokens && table && pos && x, "text_embed: null pointer");

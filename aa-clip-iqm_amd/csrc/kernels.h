@@ -243,4 +243,16 @@ void launch_preprocess(const uint8_t* src, int B, int Hs, int Ws, int S, const i
                        const int32_t* vb, const int32_t* vk, int ky, int TY, int lds_rows, int pitch, const float* lut,
                        float* out, hipStream_t s);
 
+// ---- augment.hip : train-time colour jitter (Pillow-exact), mask resize, rotation / shift / flips in one gather
+int color_jitter_sum_blocks(long pixels);   // workgroups per frame of the luma sum = 64-bit partials per frame
+// ws: [B * color_jitter_sum_blocks(H * W)] 64-bit partial sums, then [B] int32 means
+void launch_color_jitter(const uint8_t* src, uint8_t* dst, int B, int H, int W, const float* factors,
+                         const int32_t* apply, void* ws, hipStream_t s);
+void nearest_table(int in_size, int out_size, int32_t* idx);   // host buffer
+void launch_mask_preprocess(const uint8_t* src, int B, int Hm, int Wm, int S, const int32_t* xmap, const int32_t* ymap,
+                            const int32_t* normal, float* out, hipStream_t s);
+void launch_augment_geometric(const float* image, const float* mask, int B, int S, const float* angle_deg,
+                              const int32_t* shift, const int32_t* flags, float* image_out, float* mask_out,
+                              hipStream_t s);
+
 }  // namespace aaclip

@@ -10,10 +10,19 @@ Stage 2 (reference train.py:117-237) fits the image adapters and the IQM branch:
 (aaclip_hip.autograd.visual_outputs: tap streams, tap / det heads and the IQM branch's final queries, each with its HIP
 backward), and `train_image_adapter` is the reference's epoch loop around it.
 
-Not here: the training-time datasets and main().
+`main` is the reference's entry point (train.py:240-436) around the two loops: the same arguments and defaults, model
+construction, optimisers, scheduler, resume rules and DataLoaders; `run(args)` is everything after the parser, so that
+a caller can hand in its own model factory.  The train-time datasets are dataset.get_train_datasets; with
+`--device_augment` their per-sample input work (colour jitter, resize, normalise, mask resize, rotation / shift /
+flips) runs as HIP kernels on raw uint8 frames (aaclip_hip.engine.train_preprocess) instead of in the workers.
+
+    python train.py --dataset MVTec --training_mode full_shot --iqm_hidden_size 768 --save_path ckpt/run [--device_augment]
+
+(stage2_loss needs the IQM queries as wide as the seg tokens, 768 for ViT-L-14-336: see its docstring.)
 """
 from __future__ import annotations
 
+import argparse
 import logging
 import os
 
@@ -22,6 +31,7 @@ from torch import nn
 
 import forward_utils as FU
 from aaclip_hip import autograd
+from model.clip import create_model
 
 CHECKPOINT_NAME = "text_adapter.pth"
 # reference train.py:131-132,156,163: the weight of the text-anchor maps against the IQM maps, and the two halvings
@@ -192,3 +202,164 @@ def train_image_adapter(model: nn.Module, text_embeddings, train_loader, optimiz
         torch.save(state, os.path.join(save_path, IMAGE_CHECKPOINT_NAME))
         torch.save(state, os.path.join(save_path, f"image_adapter_{epoch + 1}.pth"))
     return model
+
+
+# ------------------------------------------------------------------------------------------------ entry point
+NUM_WORKERS = 4                                  # reference train.py:380
+HOST_THREADS = 4                                 # reference train.py:27-34
+
+
+# name -> (default, help): the reference's command line (train.py:241-284); types follow the defaults
+ARGUMENTS = {
+    "model_name": ("ViT-L-14-336", "model config under model/model_configs"),
+    "img_size": (518, "side of the square input image"),
+    "surgery_until_layer": (20, "stage 1: V-V attention from this visual block on"),
+    "dataset": ("VisA", "training dataset, a key of dataset.constants.DATA_PATH"),
+    "shot": (32, "samples per class of the few-shot metadata file"),
+    "text_batch_size": (16, "stage 1 batch"),
+    "image_batch_size": (2, "stage 2 batch"),
+    "text_epoch": (5, "stage 1 epochs"),
+    "image_epoch": (20, "stage 2 epochs"),
+    "text_lr": (0.00001, "stage 1 learning rate"),
+    "image_lr": (0.0005, "stage 2 learning rate (the IQM group runs at a tenth)"),
+    "seed": (111, None),
+    "save_path": ("ckpt/baseline", "checkpoints and train.log; an existing directory is resumed"),
+    "text_norm_weight": (0.1, "weight of the anchor-overlap term of stage 1"),
+    "text_adapt_weight": (0.1, None),
+    "image_adapt_weight": (0.1, None),
+    "text_adapt_until": (3, "text blocks with an adapter"),
+    "image_adapt_until": (6, "visual blocks with an adapter"),
+    "iqm_hidden_size": (512, "width of the IQM branch; stage2_loss needs the seg tokens' width"),
+    "iqm_num_layers": (2, None),
+    "iqm_num_heads": (8, None),
+    "iqm_weight": (0.4, "accepted like the reference does, which never reads it (IQM_WEIGHT is fixed)"),
+}
+
+
+def build_parser() -> argparse.ArgumentParser:
+    """The reference's arguments and defaults plus --device_augment."""
+    parser = argparse.ArgumentParser(description="Training")
+    for name, (default, text) in ARGUMENTS.items():
+        parser.add_argument("--" + name, type=type(default), default=default, help=text)
+    parser.add_argument("--relu", action="store_true", help="ReLU instead of LeakyReLU behind the projections")
+    parser.add_argument("--training_mode", type=str, default="few_shot", choices=["few_shot", "full_shot"])
+    parser.add_argument("--criterion", type=str, default=["dice_loss", "focal_loss"], nargs="+",
+                        help="accepted like the reference does, which never reads it")
+    parser.add_argument("--device_augment", action="store_true",
+                        help="colour jitter, resize, normalise and the geometric augmentation on the GPU")
+    return parser
+
+
+def _loader(dataset, batch_size, device, device_augment):
+    from torch.utils.data import DataLoader
+
+    import dataset as D
+    kwargs = {"num_workers": NUM_WORKERS, "pin_memory": True} if device.type == "cuda" else {}
+    if not device_augment:
+        return DataLoader(dataset, batch_size=batch_size, shuffle=True, **kwargs)
+    return D.DeviceAugmentLoader(DataLoader(dataset, batch_size=batch_size, shuffle=True, collate_fn=D.collate_raw,
+                                            **kwargs), device)
+
+
+def run(args, model_factory=create_model, levels=(6, 12, 18, 24)):
+    """Everything of the reference's main() after the parser (train.py:287-436).  model_factory: called twice with
+    create_model's keywords (model_name, img_size, device, pretrained="openai", require_pretrained=True) -> a CLIP;
+    levels: the tap levels, which the reference hard-codes.  Returns the trained model."""
+    import dataset as D
+    from model.adapter import AdaptedCLIP
+    from utils import setup_seed
+
+    setup_seed(args.seed)
+    os.makedirs(args.save_path, exist_ok=True)
+    logger = logging.getLogger(__name__)
+    logging.basicConfig(filename=os.path.join(args.save_path, "train.log"), encoding="utf-8", level=logging.INFO)
+    logger.info("args: %s", vars(args))
+    use_cuda = torch.cuda.is_available()
+    device = torch.device("cuda:0" if use_cuda else "cpu")
+    levels = list(levels)
+    # the frozen image side of stage 1: CLIP after "surgery"
+    clip_surgery = model_factory(model_name=args.model_name, img_size=args.img_size, device=device, pretrained="openai",
+                                 require_pretrained=True)
+    clip_surgery.eval()
+    clip_surgery.visual.DAPM_replace(DPAM_layer=args.surgery_until_layer)
+    clip_model = model_factory(model_name=args.model_name, img_size=args.img_size, device=device, pretrained="openai",
+                               require_pretrained=True)
+    clip_model.eval()
+    model = AdaptedCLIP(clip_model=clip_model, text_adapt_weight=args.text_adapt_weight,
+                        image_adapt_weight=args.image_adapt_weight, text_adapt_until=args.text_adapt_until,
+                        image_adapt_until=args.image_adapt_until, levels=levels, relu=args.relu,
+                        iqm_hidden_size=args.iqm_hidden_size, iqm_num_layers=args.iqm_num_layers,
+                        iqm_num_heads=args.iqm_num_heads).to(device)
+    model.eval()
+    # only what an optimizer below steps asks for a gradient
+    image_params = list(model.image_adapter.parameters())
+    iqm_params = (list(model.iqm.parameters()) + list(model.class_query_mlp.parameters())
+                  + list(model.query_adapters.parameters()))
+    for p in list(model.parameters()) + list(clip_surgery.parameters()):
+        p.requires_grad_(False)
+    for p in list(model.text_adapter.parameters()) + image_params + iqm_params:
+        p.requires_grad_(True)
+    text_optimizer = torch.optim.Adam(model.text_adapter.parameters(), lr=args.text_lr, betas=(0.5, 0.999))
+    image_optimizer = torch.optim.AdamW([{"params": image_params, "lr": args.image_lr, "weight_decay": 1e-4},
+                                         {"params": iqm_params, "lr": args.image_lr * 0.1, "weight_decay": 1e-3}],
+                                        betas=(0.9, 0.999))
+    image_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(image_optimizer, T_max=args.image_epoch, eta_min=1e-6)
+    # resume (train.py:356-375)
+    text_start_epoch = 0
+    text_file = os.path.join(args.save_path, CHECKPOINT_NAME)
+    if os.path.exists(text_file):
+        checkpoint = torch.load(text_file, map_location=device)
+        model.text_adapter.load_state_dict(checkpoint["text_adapter"])
+        text_optimizer.load_state_dict(checkpoint["text_optimizer"])
+        text_start_epoch = checkpoint["epoch"]
+        adapt_text = not (text_start_epoch == (args.text_epoch - 1))
+    else:
+        adapt_text = args.text_epoch != 0
+    image_start_epoch = 0
+    image_file = os.path.join(args.save_path, IMAGE_CHECKPOINT_NAME)
+    if os.path.exists(image_file):
+        checkpoint = torch.load(image_file, map_location=device)
+        image_start_epoch = checkpoint["epoch"]
+        model.image_adapter.load_state_dict(checkpoint["image_adapter"])
+        image_optimizer.load_state_dict(checkpoint["image_optimizer"])
+        if "iqm_branch" in checkpoint:           # the reference never saves the branch it trains
+            load_iqm_branch_state(model, checkpoint["iqm_branch"])
+    # datasets
+    if args.training_mode == "full_shot":
+        args.shot = -1
+    logger.info("loading dataset ...")
+    text_dataset, image_dataset = D.get_train_datasets(args.dataset, args.img_size, args.training_mode, args.shot, logger,
+                                                       device_augment=args.device_augment)
+    text_dataloader = _loader(text_dataset, args.text_batch_size, device, args.device_augment)
+    logger.info("loading image adaptation dataset ...")
+    image_dataloader = _loader(image_dataset, args.image_batch_size, device, args.device_augment)
+    # training
+    if adapt_text:
+        model = train_text_adapter(adapted_model=model, clip_surgery=clip_surgery, text_norm_weight=args.text_norm_weight,
+                                   train_loader=text_dataloader, optimizer=text_optimizer, device=device,
+                                   start_epoch=text_start_epoch, dataset_name=args.dataset, save_path=args.save_path,
+                                   text_epoch=args.text_epoch, img_size=args.img_size, logger=logger, levels=levels)
+    del text_dataloader, text_dataset, clip_surgery, text_optimizer
+    if use_cuda:
+        torch.cuda.empty_cache()
+    with torch.no_grad():
+        text_embeddings = FU.get_adapted_text_embedding(clip_model if args.text_epoch == 0 else model, args.dataset,
+                                                        device)
+    return train_image_adapter(model=model, text_embeddings=text_embeddings, image_epoch=args.image_epoch,
+                               train_loader=image_dataloader, optimizer=image_optimizer, scheduler=image_scheduler,
+                               device=device, start_epoch=image_start_epoch, save_path=args.save_path,
+                               img_size=args.img_size, logger=logger)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    for name in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS", "VECLIB_MAXIMUM_THREADS",
+                 "NUMEXPR_NUM_THREADS"):
+        os.environ[name] = str(HOST_THREADS)
+    torch.set_num_threads(HOST_THREADS)
+    os.environ["TOKENIZERS_PARALLELISM"] = "false"
+    return run(args)
+
+
+if __name__ == "__main__":
+    main()

@@ -380,6 +380,38 @@ int aaclip_resample_table(int in_size, int out_size, int32_t* bounds, int32_t* c
 int aaclip_preprocess(const uint8_t* src, int B, int Hs, int Ws, int S, const int32_t* hbounds, const int32_t* hcoefs,
                       const int32_t* vbounds, const int32_t* vcoefs, const float* lut, float* out, void* stream);
 
+/* Train-time input work on raw frames (reference dataset/__init__.py:37-102).  The reference draws its random numbers
+ * inside DataLoader workers; here every drawn number is an argument, so a call is a pure function of its inputs and two
+ * calls give the same bits.  All checks run before the first launch.  Errors carry the entry point's name as prefix.
+ *   aaclip_color_jitter: src / dst uint8 [B,H,W,3] (device; dst == src is allowed, a partial overlap is not).  Per
+ *   frame b: factors[3b .. 3b+2] = brightness, contrast, saturation factor (fp32, device), apply[b] bit 0 / 1 / 2 =
+ *   run that step (int32, device); a clear bit skips the step.  Each step is Pillow's ImageEnhance: blend(degenerate,
+ *   image, factor) = fp32 d + f * (s - d), clipped to [0, 255], truncated; degenerate = 0 (brightness), the constant
+ *   int(mean(L) + 0.5) of the frame after its brightness step (contrast), the pixel's own L (saturation);
+ *   L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16.  The mean is an exact integer sum.  ws 8-byte aligned,
+ *   ws_bytes >= aaclip_color_jitter_workspace_bytes(B, H, W) (0 for an empty problem).
+ *   aaclip_nearest_table is a HOST function: idx[out_size] = source index of every output index under Pillow's NEAREST
+ *   resize of one axis (identity for equal sizes); the caller uploads it.
+ *   aaclip_mask_preprocess: src uint8 [B,Hm,Wm] (device) -> out fp32 [B,1,S,S], 1 where the NEAREST-resized mask is
+ *   non-zero: Resize((S,S), NEAREST) -> ToTensor -> (!= 0).  xmap [S] / ymap [S]: aaclip_nearest_table(Wm / Hm, S) on
+ *   the device (entries are clamped into the source).  normal int32 [B] (device) or NULL: a non-zero entry writes
+ *   zeros for that frame without reading its source.
+ *   aaclip_augment_geometric: image fp32 [B,3,S,S], mask fp32 [B,1,S,S] -> image_out, mask_out of the same shapes, none
+ *   overlapping another.  Per frame (device arrays): angle_deg fp32 [B], shift int32 [B,2] = (tx, ty), flags int32 [B]:
+ *   bit 0 rotate by angle_deg (counter-clockwise, about the centre), bit 1 shift by (tx, ty), bit 2 horizontal flip,
+ *   bit 3 vertical flip -- applied in that order, nearest sampling, zero fill, as torchvision's RandomRotation /
+ *   RandomAffine / RandomHorizontalFlip / RandomVerticalFlip do on a tensor.  One gather per output pixel composes the
+ *   four; the rotation's source coordinate is evaluated in fp64. */
+size_t aaclip_color_jitter_workspace_bytes(int B, int H, int W);
+int aaclip_color_jitter(const uint8_t* src, uint8_t* dst, int B, int H, int W, const float* factors,
+                        const int32_t* apply, void* ws, size_t ws_bytes, void* stream);
+int aaclip_nearest_table(int in_size, int out_size, int32_t* idx);
+int aaclip_mask_preprocess(const uint8_t* src, int B, int Hm, int Wm, int S, const int32_t* xmap, const int32_t* ymap,
+                           const int32_t* normal, float* out, void* stream);
+int aaclip_augment_geometric(const float* image, const float* mask, int B, int S, const float* angle_deg,
+                             const int32_t* shift, const int32_t* flags, float* image_out, float* mask_out,
+                             void* stream);
+
 /* Text embedding: x[i*T+t] = token_embedding[tokens[i,t]] + positional_embedding[t].
  * Replaces reference model/adapter.py:277-281 (model/model.py:192-194).  Token ids outside [0, vocab) are CLAMPED
  * to 0 / vocab - 1 (the reference's nn.Embedding raises instead); D a multiple of 4. */
