@@ -7,7 +7,8 @@ the stage-2 loss (reference train.py:173-209: the two-channel half-pixel upsampl
 reaches the seg tokens and the two final queries, and the key / value side of the IQM branch (model/adapter.py:205-211
 and the visual cross-attention of model/iqm.py:108-139 over those rows): cross_rows and iqm_visual_rows, and the branch's
 2-row query side (model/adapter.py:186-269, model/iqm.py:572-673) from the final queries back to every parameter it
-reads, to those rows and to the CLS row of the last tap: IqmQueries / iqm_queries, visual_outputs.
+reads, to those rows and to the CLS row of the last tap: IqmQueries / iqm_queries, visual_outputs.  That side has no
+forward of its own here: IqmQueries runs the model's (AdaptedCLIP._iqm_branch) with a record of the intermediates.
 Forward and backward are HIP kernels; these classes only carry tensors between them.  The saved tensors live in
 ctx.save_for_backward, so they are freed with the graph (after backward(), or when the output is dropped)."""
 from __future__ import annotations
@@ -351,7 +352,6 @@ class IqmVisualRows(torch.autograd.Function):
         return (None, None, None, *grads_t, *grads_w)
 
 
-IQM_TRAIN_WIDTHS = (256, 512, 768, 1024)          # row widths of aaclip_cross_rows / aaclip_cross_rows_backward
 _ATTENTIONS = ("attention", "crossattention", "text_crossattention")
 
 
@@ -379,9 +379,8 @@ def _iqm_train_check(model):
     if not model.levels or max(model.levels) != n_blocks:
         raise NotImplementedError("iqm_queries: model.levels must end at the tower's last block (the CLS row of the final "
                                   "stream is read from the last tap)")
-    R = 2 * model.iqm.num_attention_heads
     widths = (model.iqm_hidden_size, model.text_feature_proj.weight.shape[0])
-    if R % 4 or R > 16 or any(w not in IQM_TRAIN_WIDTHS for w in widths):
+    if not all(model.iqm.cross_rows_form(2, w) for w in widths):
         raise NotImplementedError("iqm_queries: training covers queries x heads in {4, 8, 12, 16} and row widths "
                                   "256 / 512 / 768 / 1024 (the aaclip_cross_rows form of the cross-attentions)")
 
@@ -411,13 +410,14 @@ def _sum(a, b, c=None):
 
 
 class IqmQueries(torch.autograd.Function):
-    """The query side of the IQM branch in its projected form (AdaptedCLIP._iqm_branch, IQM.forward / _attend) with a
-    backward: forward(model, rows, tap, anchors, *parameters named by _iqm_param_names) -> final queries [B, 2, h].
+    """The query side of the IQM branch in its projected form with a backward:
+    forward(model, rows, tap, anchors, *parameters named by _iqm_param_names) -> final queries [B, 2, h].
     rows [B, Lk, h] are autograd.iqm_visual_rows(model, taps, pre_activation_grad=model.relu), tap [B, L, D] the last tap
-    stream (its CLS row feeds class_query_mlp), anchors [B, 768, 2] constants.  The calls are those of the model in its
-    order, so wherever AdaptedCLIP.forward takes the projected form the queries are its bits.
-    Saved: the fp32 intermediates of every step ([2B, h], [2B H, .], the [2B, 2048] pre-GELU rows from one extra
-    EPI_ACT_F32 product), the text rows and the rows tensor itself -- nothing else of size Lk x h.
+    stream (its CLS row feeds class_query_mlp), anchors [B, 768, 2] constants.  The forward IS the model's:
+    AdaptedCLIP._iqm_branch(..., levels=None, record=S), the code AdaptedCLIP.forward runs, so wherever that takes the
+    projected form the queries are its bits.  Saved: the record S and nothing else -- IQM.forward (model/iqm.py) lists
+    its keys: the fp32 intermediates of every step ([2B, h], [2B H, .], the [2B, 2048] pre-GELU rows from one extra
+    EPI_ACT_F32 product), the text rows and the rows tensor itself, nothing else of size Lk x h.
     The backward runs in fp32 whatever precision the forward ran in (16-bit casts count as the identity) and walks the
     forward in reverse on aaclip_gemm (transposed cached weights), aaclip_gemm_wgrad, aaclip_layernorm_backward,
     aaclip_cross_rows_backward (accumulating over roles and layers; its act applies the LeakyReLU slope of the rows) and
@@ -425,97 +425,16 @@ class IqmQueries(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, rows, tap, anchors, *params):
-        from ._lib import ACT_RELU, EPI_ACT_F32, EPI_BIAS, EPI_BIAS_GELU
         code = engine.plain_code(model._code())
-        dt = engine.torch_dtype(code)
-        iqm, h, H = model.iqm, model.iqm_hidden_size, model.iqm.num_attention_heads
         B, L, _ = tap.shape
-        dev = tap.device
-        te = anchors.detach().to(dev)
-        if te.dim() != 3 or te.shape[0] != B or te.shape[-1] != 2:
+        if anchors.dim() != 3 or anchors.shape[0] != B or anchors.shape[-1] != 2:
             raise NotImplementedError("iqm_queries: text_embeddings must be [B, 768, 2]")
-        nq, R, eps = 2, 2 * H, iqm.eps
-        scale = 1.0 / (h // H) ** 0.5
         S = {}
-
-        def f32(n, d):
-            return torch.empty(n, d, dtype=torch.float32, device=dev)
-
-        def lin(x, m, act=0):
-            out = f32(x.shape[0], m.weight.shape[0])
-            return engine.gemm(code, EPI_ACT_F32, x, engine.CACHE.get(m.weight, code), engine._f32c(m.bias), out, act=act)
-
-        def tail(att, ctxv, hin, key):
-            dense = lin(ctxv.to(dt), att.output.dense)
-            S[key + "ctx"], S[key + "dense"] = ctxv, dense
-            return engine.residual_layernorm(dense, hin, att.output.LayerNorm, eps)
-
-        def self_att(att, hin, key):
-            hq = hin.to(dt)
-            q = lin(hq, att.attention.query)
-            k = torch.empty(hq.shape[0], h, dtype=dt, device=dev)
-            v = torch.empty_like(k)
-            engine.gemm(code, EPI_BIAS, hq, engine.CACHE.get(att.attention.key.weight, code),
-                        engine._f32c(att.attention.key.bias), k)
-            engine.gemm(code, EPI_BIAS, hq, engine.CACHE.get(att.attention.value.weight, code),
-                        engine._f32c(att.attention.value.bias), v)
-            S[key + "q"], S[key + "k"], S[key + "v"] = q, k.float(), v.float()
-            return tail(att, engine.small_attention(q, k, v, B, nq, nq, H, code), hin, key)
-
-        def cross_att(att, hin, enc, Lk, proj, key):
-            q = lin(hin.to(dt), att.attention.query)
-            qm = engine.head_expand(q, H, scale, code)
-            kin = att.attention.key.weight.shape[1]
-            qt = engine.gemm(code, EPI_ACT_F32, qm, engine.CACHE.get(att.attention.key.weight, code, "transpose"), None,
-                             f32(B * R, kin))
-            S[key + "qm"], S[key + "qt"] = qm.float(), qt
-            if proj is not None:
-                qx = engine.gemm(code, EPI_ACT_F32, qt.to(dt), engine.CACHE.get(proj.weight, code, "transpose"), None,
-                                 f32(B * R, proj.weight.shape[1]))
-                xbar = engine.cross_rows(qx, enc, B, R, Lk, code)
-                ebar = lin(xbar.to(dt), proj)
-                S[key + "qx"], S[key + "xbar"] = qx, xbar
-            elif enc.dtype in (torch.float16, torch.bfloat16) and enc.shape[-1] in (768, 1024):
-                ebar = engine.cross_rows_levels(qt, [enc], B, R, Lk, 0, Lk, enc.shape[-1])
-            else:
-                ebar = engine.cross_rows(qt, enc, B, R, Lk, code)
-            S[key + "ebar"] = ebar
-            full = lin(ebar.to(dt), att.attention.value)
-            return tail(att, engine.head_diag(full, H), hin, key)
-
-        cls = tap.detach().reshape(B, L, -1)[:, 0, :].to(dt).contiguous()
-        m0, m2 = model.class_query_mlp[0], model.class_query_mlp[2]
-        t1 = lin(cls, m0, act=ACT_RELU)
-        cq = lin(t1.to(dt), m2)
-        pos = engine._f32c(model.pos_embedding)[:, :2, :].expand(B, 2, h).contiguous()
-        query = engine.combine3(cq.unsqueeze(1).expand(B, 2, h).contiguous(), pos, None, 1.0, 1.0, 0.0)
-        tp, vp = model.text_feature_proj, model.visual_feature_proj
-        txt = engine.linear_smallk(te, tp.weight, tp.bias, code)
-        Lt, Lv = te.shape[1], rows.shape[1]
-        vis = rows.detach().to(dt).reshape(-1, rows.shape[-1]).contiguous()
-        S["cls"], S["t1"], S["query"], S["te"], S["txt"], S["vis"] = cls.float(), t1, query, engine._f32c(te), txt, vis
-        hcur = engine.residual_layernorm(query.reshape(B * nq, h), None, iqm.layernorm, eps)
-        for l, layer in enumerate(iqm.encoder.layer):
-            key = f"{l}."
-            S[key + "h"] = hcur
-            a = self_att(layer.attention, hcur, key + "a.")
-            c = cross_att(layer.crossattention, a, vis, Lv, vp, key + "c.")
-            t = cross_att(layer.text_crossattention, c, txt, Lt, None, key + "t.")
-            mix = engine.combine3(a, c, t, 0.4, 0.3, 0.3)
-            mi, mo = layer.intermediate_query.dense, layer.output_query.dense
-            inter = torch.empty(B * nq, mi.weight.shape[0], dtype=dt, device=dev)
-            engine.gemm(code, EPI_BIAS_GELU, mix.to(dt), engine.CACHE.get(mi.weight, code), engine._f32c(mi.bias), inter)
-            z = lin(mix.to(dt), mi)                                  # the pre-GELU rows, for the backward only
-            dense = lin(inter, mo)
-            S[key + "a"], S[key + "c"], S[key + "mix"], S[key + "z"] = a, c, mix, z
-            S[key + "inter"], S[key + "dense"] = inter.float(), dense
-            hcur = engine.residual_layernorm(dense, mix, layer.output_query.LayerNorm, eps)
-        S["last"] = hcur
-        out = engine.residual_layernorm(hcur, None, model.iqm_layer_norm, model.iqm_layer_norm.eps)
-        ctx.model, ctx.keys, ctx.dims = model, list(S), (B, L, Lv, Lt, code)
+        out = model._iqm_branch(tap.detach(), rows.detach(), anchors.detach(), B, L, code, levels=None, record=S)
+        ctx.model, ctx.keys, ctx.dims = model, list(S), (B, L, rows.shape[1], anchors.shape[1], code)
         ctx.names = _iqm_param_names(model)
         ctx.save_for_backward(*S.values())
-        return out.view(B, 2, h)
+        return out.last_hidden_state
 
     @staticmethod
     def backward(ctx, d_out):

@@ -21,7 +21,7 @@ from aaclip_hip import autograd, engine
 from aaclip_hip._lib import ACT_LEAKY, ACT_RELU, EPI_ACT_F32, EPI_BIAS
 
 from .adapter_modules import SimpleAdapter, SimpleProj
-from .iqm import IQM, IQMOutput, sinusoidal_positions
+from .iqm import IQM, IQMOutput, linear_f32, sinusoidal_positions
 from .transformer import set_precision
 
 
@@ -173,25 +173,25 @@ class AdaptedCLIP(nn.Module):
             engine.gemm(code, EPI_BIAS, ln, w, zb, tmp)
         engine.drop_cls_rows(tmp, vis_cat, B, L, k * (L - 1), code)
 
-    # -- reference model/adapter.py:186-269
-    def _iqm_branch(self, xs, vis_cat, text_embeddings, B, L, code, levels=None):
+    # -- reference model/adapter.py:186-269.  record: see IQM.forward (a dict collects what the backward needs; the training
+    #    path, autograd.IqmQueries, calls this with one and levels=None)
+    def _iqm_branch(self, xs, vis_cat, text_embeddings, B, L, code, levels=None, record=None):
         dt = engine.torch_dtype(code)
         h = self.iqm_hidden_size
-        dev = xs.device
-        te = text_embeddings.to(dev)
+        te = text_embeddings.to(xs.device)
         if te.dim() != 3 or te.shape[0] != B or te.shape[-1] != 2:
             raise NotImplementedError(
                 "the IQM branch is built for text_embeddings of shape [B, 768, 2] (what test_last.py:84 and train.py "
                 "pass): the reference would re-create text_feature_proj with another in_features for any other form")
         # 1. queries: class_query_mlp(CLS row) for both, plus the first two sinusoidal positions (:191-203)
-        cls = xs.view(B, L, -1)[:, 0, :].to(dt).contiguous()
+        cls = xs.reshape(B, L, -1)[:, 0, :].to(dt).contiguous()
         m0, m2 = self.class_query_mlp[0], self.class_query_mlp[2]
-        t1 = torch.empty(B, h, dtype=torch.float32, device=dev)
-        engine.gemm(code, EPI_ACT_F32, cls, engine.CACHE.get(m0.weight, code), engine._f32c(m0.bias), t1, act=ACT_RELU)
-        cq = torch.empty(B, h, dtype=torch.float32, device=dev)
-        engine.gemm(code, EPI_ACT_F32, t1.to(dt), engine.CACHE.get(m2.weight, code), engine._f32c(m2.bias), cq)
+        t1 = linear_f32(code, cls, m0.weight, m0.bias, act=ACT_RELU)
+        cq = linear_f32(code, t1.to(dt), m2.weight, m2.bias)
         pos = engine._f32c(self.pos_embedding)[:, :2, :].expand(B, 2, h).contiguous()
         query = engine.combine3(cq.unsqueeze(1).expand(B, 2, h).contiguous(), pos, None, 1.0, 1.0, 0.0)
+        if record is not None:
+            record.update(cls=cls.float(), t1=t1, query=query, te=engine._f32c(te))
         # 2. patch rows of all levels -> query space (:210-221): visual_feature_proj is NOT applied to the 5476 rows per
         #    image; it is folded into the two cross-attentions that read them (IQM._attend, enc_proj)
         vp = self.visual_feature_proj
@@ -200,7 +200,7 @@ class AdaptedCLIP(nn.Module):
         txt = engine.linear_smallk(te, tp.weight, tp.bias, code)
         out = self.iqm(query_embeds=query, query_length=2, encoder_hidden_states=vis_cat,
                        text_encoder_hidden_states=txt.view(B, te.shape[1], tp.weight.shape[0]), code=code,
-                       encoder_proj=(vp.weight, vp.bias), encoder_levels=levels)
+                       encoder_proj=(vp.weight, vp.bias), encoder_levels=levels, record=record)
         hfin = engine.residual_layernorm(out.last_hidden_state.reshape(B * 2, h), None, self.iqm_layer_norm,
                                          self.iqm_layer_norm.eps)                             # :265-266
         return IQMOutput(hfin.view(B, 2, h), pooler_output=out.last_hidden_state.reshape(B, 2, h)[:, 0, :])

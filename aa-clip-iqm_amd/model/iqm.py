@@ -13,7 +13,9 @@ cannot be reproduced or checkpointed:
   * `visual_feature_proj` / `text_feature_proj` are created by the reference INSIDE forward with fresh random weights
     (adapter.py:213-218, 241-243) and never saved; here they are ordinary parameters (Linear(hidden, hidden) and
     Linear(2, 768): 2 because the anchors arrive as [B, 768, 2]) that are initialised once and saved with the rest;
-  * dropout is the identity: the training path (aaclip_hip.autograd.iqm_queries) runs this eval forward with a graph.
+  * dropout is the identity.
+There is ONE forward: the training path (aaclip_hip.autograd.iqm_queries) runs this same code with a `record` dict that
+collects what its backward needs (IQM.forward lists the keys), so inference and training cannot drift apart.
 The modules below are parameter containers: every product runs on the library's MFMA GEMM, the rest on the small
 kernels of csrc/iqm.hip (aaclip_small_attention, aaclip_residual_layernorm, ...).
 """
@@ -27,6 +29,15 @@ from torch import nn
 
 from aaclip_hip import engine
 from aaclip_hip._lib import EPI_ACT_F32, EPI_BIAS, EPI_BIAS_GELU
+
+
+def linear_f32(code: int, x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = 0,
+               transpose: bool = False) -> torch.Tensor:
+    """fp32 output of a Linear on the GEMM: act(x W^T + bias) for x [M, in] in the compute dtype and the Linear's own
+    weight [out, in] (prepared once, engine.CACHE); transpose: x [M, out] -> x W, the product on the transposed weight."""
+    w = engine.CACHE.get(weight, code, "transpose") if transpose else engine.CACHE.get(weight, code)
+    out = torch.empty(x.shape[0], w.shape[0], dtype=torch.float32, device=x.device)
+    return engine.gemm(code, EPI_ACT_F32, x, w, None if bias is None else engine._f32c(bias), out, act=act)
 
 
 class IQMOutput:
@@ -102,76 +113,80 @@ class IQM(nn.Module):
         self.encoder = _Encoder(num_hidden_layers, hidden_size, encoder_hidden_size, text_encoder_hidden_size,
                                 intermediate_size, layer_norm_eps)
 
+    def cross_rows_form(self, nq: int, width: int) -> bool:
+        """Whether a cross-attention of nq queries per image over rows `width` wide takes the aaclip_cross_rows form of
+        _attend: queries x heads in {4, 8, 12, 16} and a row width of that kernel (and of aaclip_cross_rows_backward,
+        so these are also the configurations the training path covers)."""
+        R = nq * self.num_attention_heads
+        return R % 4 == 0 and R <= 16 and width in (256, 512, 768, 1024)
+
+    def _tail(self, att: _Attention, h: torch.Tensor, code: int, ebar=None, ctx=None, record=None, key: str = ""):
+        """The end of one IQM_Attention: ctx [B*nq, D] as it is, or the value product of the probability-weighted rows
+        ebar [B*nq*H, Dk] and its head-diagonal blocks; then output.dense and LayerNorm(. + h)."""
+        dt = engine.torch_dtype(code)
+        if ctx is None:
+            ctx = engine.head_diag(linear_f32(code, ebar.to(dt), att.attention.value.weight, att.attention.value.bias),
+                                   self.num_attention_heads)
+        dense = linear_f32(code, ctx.to(dt), att.output.dense.weight, att.output.dense.bias)
+        if record is not None:
+            record[key + "ctx"], record[key + "dense"] = ctx, dense
+            if ebar is not None:
+                record[key + "ebar"] = ebar
+        return engine.residual_layernorm(dense, h, att.output.LayerNorm, self.eps)
+
     # ---- one IQM_Attention: q from h [B*nq, D] (fp32), k/v = Linear(enc) where enc is [B*Lk, Dk] in the compute dtype
     def _attend(self, att: _Attention, h: torch.Tensor, enc: Optional[torch.Tensor], B: int, nq: int, Lk: int,
-                code: int, enc_proj=None, enc_levels=None) -> torch.Tensor:
+                code: int, enc_proj=None, enc_levels=None, record=None, key: str = "") -> torch.Tensor:
+        """record (see forward) takes this attention's entries under the prefix `key`."""
         dt = engine.torch_dtype(code)
-        D = self.hidden_size
+        D, H = self.hidden_size, self.num_attention_heads
+        rows_form = enc_levels is None and enc is not None and self.cross_rows_form(nq, enc.shape[-1])
+        if record is not None and not rows_form and (enc is not None or enc_levels is not None):
+            raise NotImplementedError("IQM: a record covers the self-attention and the aaclip_cross_rows form of the "
+                                      "cross-attentions (queries x heads in {4, 8, 12, 16}, row widths 256 / 512 / 768 / "
+                                      "1024), not the folded levels and not the small_attention path")
         hq = h.to(dt)                                      # [B*nq, D]: 2 rows per image
-        q = torch.empty(B * nq, D, dtype=torch.float32, device=h.device)
-        engine.gemm(code, EPI_ACT_F32, hq, engine.CACHE.get(att.attention.query.weight, code),
-                    engine._f32c(att.attention.query.bias), q)
-        H = self.num_attention_heads
+        q = linear_f32(code, hq, att.attention.query.weight, att.attention.query.bias)
+        if enc_levels is not None or rows_form:
+            qm = engine.head_expand(q, H, 1.0 / math.sqrt(D // H), code)                         # [B*nq*H, D]
+            qt = linear_f32(code, qm, att.attention.key.weight, transpose=True)                  # [B*nq*H, Dk]
+            if record is not None:
+                record[key + "qm"], record[key + "qt"] = qm.float(), qt
         if enc_levels is not None:
             # the rows are level s's LayerNorm'ed tap rows t, enc = P (W_qa[s] t) + b_p (query_adapters, torch.cat,
             # visual_feature_proj: reference model/adapter.py:205-221), every step linear: all of it moves to the query
             # side and behind the weighted sums (include/aaclip.h, aaclip_cross_rows_levels) -- no per-row product at all
             lv = enc_levels
             pw, pb = enc_proj
-            qm = engine.head_expand(q, H, 1.0 / math.sqrt(D // H), code)                         # [B*nq*H, D]
-            kin = att.attention.key.weight.shape[1]
-            qt = torch.empty(B * nq * H, kin, dtype=torch.float32, device=h.device)
-            engine.gemm(code, EPI_ACT_F32, qm, engine.CACHE.get(att.attention.key.weight, code, "transpose"), None, qt)
-            qx = torch.empty(B * nq * H, pw.shape[1], dtype=torch.float32, device=h.device)
-            engine.gemm(code, EPI_ACT_F32, qt.to(dt), engine.CACHE.get(pw, code, "transpose"), None, qx)
+            qx = linear_f32(code, qt.to(dt), pw, transpose=True)
             nseg, Dk = len(lv["rows"]), lv["width"]
             u = torch.empty(B * nq * H, nseg * Dk, dtype=torch.float32, device=h.device)
             engine.gemm(code, EPI_ACT_F32, qx.to(dt), lv["w_in"], None, u)        # u[., s] = W_qa[s]^T qx
             tbar = engine.cross_rows_levels(u, lv["rows"], B, nq * H, lv["rows_per_image"], lv["row0"], lv["keys"], Dk)
             xbar = torch.empty(B * nq * H, pw.shape[1], dtype=torch.float32, device=h.device)
             engine.gemm(code, EPI_ACT_F32, tbar.to(dt), lv["w_out"], None, xbar)  # sum_s W_qa[s] tbar[., s]
-            ebar = torch.empty(B * nq * H, kin, dtype=torch.float32, device=h.device)
-            engine.gemm(code, EPI_ACT_F32, xbar.to(dt), engine.CACHE.get(pw, code), engine._f32c(pb), ebar)
-            full = torch.empty(B * nq * H, D, dtype=torch.float32, device=h.device)
-            engine.gemm(code, EPI_ACT_F32, ebar.to(dt), engine.CACHE.get(att.attention.value.weight, code),
-                        engine._f32c(att.attention.value.bias), full)
-            ctx = engine.head_diag(full, H)
-            dense = torch.empty(B * nq, D, dtype=torch.float32, device=h.device)
-            engine.gemm(code, EPI_ACT_F32, ctx.to(dt), engine.CACHE.get(att.output.dense.weight, code),
-                        engine._f32c(att.output.dense.bias), dense)
-            return engine.residual_layernorm(dense, h, att.output.LayerNorm, self.eps)
-        if enc is not None and (nq * H) % 4 == 0 and nq * H <= 16 and enc.shape[-1] in (256, 512, 768, 1024):
+            return self._tail(att, h, code, ebar=linear_f32(code, xbar.to(dt), pw, pb))
+        if rows_form:
             # cross-attention over MANY rows for a handful of queries: W_k moves to the query side and W_v behind the
             # probability-weighted sum of the raw rows (include/aaclip.h, aaclip_cross_rows): the reference's key /
             # value projections of all Lk rows (2 x Lk x Dk x D MACs per image, reference model/iqm.py:116-121) become
             # two [nq*H, .] products.  b_k only shifts every score of a row by the same amount: softmax-invariant.
-            qm = engine.head_expand(q, H, 1.0 / math.sqrt(D // H), code)                         # [B*nq*H, D]
-            kin = att.attention.key.weight.shape[1]
-            qt = torch.empty(B * nq * H, kin, dtype=torch.float32, device=h.device)
-            engine.gemm(code, EPI_ACT_F32, qm, engine.CACHE.get(att.attention.key.weight, code, "transpose"), None, qt)
             if enc_proj is not None:
                 # the rows are enc = P x + b_p of raw rows x (AdaptedCLIP.visual_feature_proj on the concatenated levels,
                 # reference model/adapter.py:213-221): the same algebra once more -- (P^T qt) . x_j + const on the way
                 # in, P (sum_j p_j x_j) + b_p on the way out -- and the [B*Lk, .] projection is never computed
                 pw, pb = enc_proj
-                qx = torch.empty(B * nq * H, pw.shape[1], dtype=torch.float32, device=h.device)
-                engine.gemm(code, EPI_ACT_F32, qt.to(dt), engine.CACHE.get(pw, code, "transpose"), None, qx)
+                qx = linear_f32(code, qt.to(dt), pw, transpose=True)
                 xbar = engine.cross_rows(qx, enc, B, nq * H, Lk, code)
-                ebar = torch.empty(B * nq * H, kin, dtype=torch.float32, device=h.device)
-                engine.gemm(code, EPI_ACT_F32, xbar.to(dt), engine.CACHE.get(pw, code), engine._f32c(pb), ebar)
+                ebar = linear_f32(code, xbar.to(dt), pw, pb)
+                if record is not None:
+                    record[key + "qx"], record[key + "xbar"] = qx, xbar
             elif enc.dtype in (torch.float16, torch.bfloat16) and enc.shape[-1] in (768, 1024):
                 # 16-bit rows: the matrix-core kernel, one segment (the anchor tokens of the text cross-attention)
                 ebar = engine.cross_rows_levels(qt, [enc], B, nq * H, Lk, 0, Lk, enc.shape[-1])
             else:
                 ebar = engine.cross_rows(qt, enc, B, nq * H, Lk, code)                           # [B*nq*H, Dk] fp32
-            full = torch.empty(B * nq * H, D, dtype=torch.float32, device=h.device)
-            engine.gemm(code, EPI_ACT_F32, ebar.to(dt), engine.CACHE.get(att.attention.value.weight, code),
-                        engine._f32c(att.attention.value.bias), full)
-            ctx = engine.head_diag(full, H)
-            dense = torch.empty(B * nq, D, dtype=torch.float32, device=h.device)
-            engine.gemm(code, EPI_ACT_F32, ctx.to(dt), engine.CACHE.get(att.output.dense.weight, code),
-                        engine._f32c(att.output.dense.bias), dense)
-            return engine.residual_layernorm(dense, h, att.output.LayerNorm, self.eps)
+            return self._tail(att, h, code, ebar=ebar, record=record, key=key)
         src = hq if enc is None else enc
         k = torch.empty(src.shape[0], D, dtype=dt, device=h.device)      # compute dtype (fp32 on the fp32 path)
         v = torch.empty_like(k)
@@ -179,22 +194,39 @@ class IQM(nn.Module):
                     engine._f32c(att.attention.key.bias), k)
         engine.gemm(code, EPI_BIAS, src, engine.CACHE.get(att.attention.value.weight, code),
                     engine._f32c(att.attention.value.bias), v)
-        ctx = engine.small_attention(q, k, v, B, nq, Lk, self.num_attention_heads, code)
-        dense = torch.empty(B * nq, D, dtype=torch.float32, device=h.device)
-        engine.gemm(code, EPI_ACT_F32, ctx.to(dt), engine.CACHE.get(att.output.dense.weight, code),
-                    engine._f32c(att.output.dense.bias), dense)
-        return engine.residual_layernorm(dense, h, att.output.LayerNorm, self.eps)
+        if record is not None:
+            record[key + "q"], record[key + "k"], record[key + "v"] = q, k.float(), v.float()
+        return self._tail(att, h, code, ctx=engine.small_attention(q, k, v, B, nq, Lk, H, code), record=record, key=key)
 
     def forward(self, query_embeds: torch.Tensor, query_length: Optional[int] = None,
                 encoder_hidden_states: Optional[torch.Tensor] = None,
                 text_encoder_hidden_states: Optional[torch.Tensor] = None, code: Optional[int] = None,
-                encoder_proj=None, encoder_levels=None, **_unused):
+                encoder_proj=None, encoder_levels=None, record: Optional[dict] = None, **_unused):
         """query_embeds fp32 [B, nq, D]; encoder_hidden_states [B, Lv, D] and text_encoder_hidden_states [B, Lt, D] in
         the compute dtype (or fp32) -> IQMOutput.  reference model/iqm.py:572-673 with all masks zero.
         encoder_proj = (weight, bias): encoder_hidden_states are the rows BEFORE that Linear; it is folded into the
         cross-attention (see _attend) instead of being applied to every row.
         encoder_levels (instead of encoder_hidden_states; AdaptedCLIP._iqm_levels builds it): the LayerNorm'ed rows of
-        the tap levels themselves plus the concatenated query_adapters weights -- the level projections fold too."""
+        the tap levels themselves plus the concatenated query_adapters weights -- the level projections fold too.
+
+        record: None keeps nothing alive.  A dict receives what a backward of this forward needs (the training path,
+        aaclip_hip.autograd.IqmQueries, saves its values), and the forward is the same launches plus, per layer, the one
+        EPI_ACT_F32 product of the pre-GELU rows.  Every entry is fp32 (16-bit results are stored as fp32 copies)
+        except `vis` and `txt`.  The keys, with l the layer index:
+          vis, txt               the key / value rows [B*Lv, D] and [B*Lt, Dt] as the cross-attentions read them
+          last                   the encoder output [B*nq, D]
+          {l}.h  .a  .c  .mix    the layer's input, the outputs of the self- and the visual cross-attention, the fusion
+          {l}.z  .inter  .dense  the feed-forward: pre-GELU rows, GELU output, output_query.dense
+          {l}.a. {l}.c. {l}.t.   prefixes of the self-, the visual cross- and the text cross-attention:
+            ctx, dense           all three: the attention output [B*nq, D] and output.dense of it
+            q, k, v              the self-attention's projections
+            qm, qt, ebar         both cross-attentions: the head-expanded queries, those times W_k, the weighted rows
+            qx, xbar             the visual one: qt times encoder_proj's weight, the weighted raw rows
+        AdaptedCLIP._iqm_branch adds cls, t1, query and te (the CLS rows, class_query_mlp's hidden rows, query_embeds,
+        the anchors).  Only the self-attention and the aaclip_cross_rows form have a backward: with a record,
+        encoder_levels or a cross-attention outside cross_rows_form raises NotImplementedError."""
+        if record is not None and encoder_levels is not None:
+            raise NotImplementedError("IQM: no record (no backward) for the folded form, encoder_levels")
         engine.require_gpu(query_embeds, "IQM")
         if code is None:
             code = engine.dtype_code(getattr(self, "precision", "fp32"))
@@ -214,20 +246,29 @@ class IQM(nn.Module):
             Lv = encoder_hidden_states.shape[1]
         txt = text_encoder_hidden_states.to(dt).reshape(-1, text_encoder_hidden_states.shape[-1]).contiguous()
         Lt = text_encoder_hidden_states.shape[1]
+        rec = record is not None
+        if rec:
+            record["vis"], record["txt"] = vis, txt
         h = engine.residual_layernorm(engine._f32c(query_embeds).reshape(B * nq, D), None, self.layernorm, self.eps)
-        for layer in self.encoder.layer:
-            a = self._attend(layer.attention, h, None, B, nq, nq, code)
+        for l, layer in enumerate(self.encoder.layer):
+            a = self._attend(layer.attention, h, None, B, nq, nq, code, record=record, key=f"{l}.a.")
             c = self._attend(layer.crossattention, a, vis, B, nq, Lv, code, enc_proj=encoder_proj,
-                             enc_levels=encoder_levels)
-            t = self._attend(layer.text_crossattention, c, txt, B, nq, Lt, code)
+                             enc_levels=encoder_levels, record=record, key=f"{l}.c.")
+            t = self._attend(layer.text_crossattention, c, txt, B, nq, Lt, code, record=record, key=f"{l}.t.")
             mix = engine.combine3(a, c, t, 0.4, 0.3, 0.3)                                            # iqm.py:311-315
-            inter = torch.empty(B * nq, layer.intermediate_query.dense.weight.shape[0], dtype=dt, device=h.device)
-            engine.gemm(code, EPI_BIAS_GELU, mix.to(dt), engine.CACHE.get(layer.intermediate_query.dense.weight, code),
-                        engine._f32c(layer.intermediate_query.dense.bias), inter)
-            dense = torch.empty(B * nq, D, dtype=torch.float32, device=h.device)
-            engine.gemm(code, EPI_ACT_F32, inter, engine.CACHE.get(layer.output_query.dense.weight, code),
-                        engine._f32c(layer.output_query.dense.bias), dense)
+            mi, mo = layer.intermediate_query.dense, layer.output_query.dense
+            mx = mix.to(dt)
+            inter = torch.empty(B * nq, mi.weight.shape[0], dtype=dt, device=h.device)
+            engine.gemm(code, EPI_BIAS_GELU, mx, engine.CACHE.get(mi.weight, code), engine._f32c(mi.bias), inter)
+            if rec:
+                z = linear_f32(code, mx, mi.weight, mi.bias)             # the pre-GELU rows, for the backward only
+            dense = linear_f32(code, inter, mo.weight, mo.bias)
+            if rec:
+                record.update({f"{l}.h": h, f"{l}.a": a, f"{l}.c": c, f"{l}.mix": mix, f"{l}.z": z,
+                               f"{l}.inter": inter.float(), f"{l}.dense": dense})
             h = engine.residual_layernorm(dense, mix, layer.output_query.LayerNorm, self.eps)
+        if rec:
+            record["last"] = h
         return IQMOutput(h.view(B, nq, D))
 
 

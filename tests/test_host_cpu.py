@@ -9,6 +9,7 @@ import re
 import pytest
 import torch
 
+import engine_standins as SI
 from aaclip_hip import _lib, engine, synth
 from conftest import GOLDEN, REPO
 
@@ -496,67 +497,8 @@ def test_iqm_cross_attention_foldings_agree_on_cpu(monkeypatch):
     from model.iqm import IQM
     F32 = _lib.F32
 
-    def fake_gemm(code, epi, a, w, bias, out, act=0):
-        y = a.double() @ w.double().t()
-        if bias is not None:
-            y = y + bias.double()
-        if epi == _lib.EPI_BIAS_GELU:
-            y = 0.5 * y * (1 + torch.erf(y / math.sqrt(2)))
-        out.copy_(y.to(out.dtype))
-        return out
-
-    class FakeCache:
-        def get(self, w, code, kind=None):
-            w = w.detach().float()
-            return w.t().contiguous() if kind == "transpose" else w
-
-    def fake_head_expand(q, H, scale, code):
-        rows, D = q.shape
-        hd = D // H
-        out = torch.zeros(rows, H, D)
-        for h in range(H):
-            out[:, h, h * hd:(h + 1) * hd] = q[:, h * hd:(h + 1) * hd] * scale
-        return out.view(rows * H, D)
-
-    def fake_head_diag(full, H):
-        rows, D = full.shape[0] // H, full.shape[1]
-        hd = D // H
-        f = full.view(rows, H, D)
-        return torch.cat([f[:, h, h * hd:(h + 1) * hd] for h in range(H)], 1).contiguous()
-
-    def fake_cross_rows(qt, x, B, R, Lk, code):
-        Dk = x.shape[-1]
-        p = torch.softmax(qt.double().view(B, R, Dk) @ x.double().view(B, Lk, Dk).transpose(1, 2), -1)
-        return (p @ x.double().view(B, Lk, Dk)).float().view(B * R, Dk)
-
-    def fake_cross_rows_levels(qt, levels, B, R, rpi, row0, Lk, Dk):
-        n = len(levels)
-        q = qt.double().view(B, R, n, Dk)
-        keys = [x.double().view(B, rpi, -1)[:, row0:row0 + Lk, :Dk] for x in levels]
-        p = torch.softmax(torch.cat([torch.einsum("brd,bjd->brj", q[:, :, s], keys[s]) for s in range(n)], -1), -1)
-        out = torch.stack([torch.einsum("brj,bjd->brd", p[:, :, s * Lk:(s + 1) * Lk], keys[s]) for s in range(n)], 2)
-        return out.float().reshape(B * R, n * Dk)
-
-    def fake_small_attention(q, k, v, B, nq, Lk, H, code):
-        D = q.shape[-1]
-        hd = D // H
-        qh = q.double().view(B, nq, H, hd).transpose(1, 2)
-        kh = k.double().view(B, Lk, H, hd).transpose(1, 2)
-        vh = v.double().view(B, Lk, H, hd).transpose(1, 2)
-        return (torch.softmax(qh @ kh.transpose(-1, -2) / math.sqrt(hd), -1) @ vh).transpose(1, 2).reshape(B * nq, D).float()
-
-    def fake_res_ln(a, b, ln, eps):
-        x = a if b is None else a + b
-        return torch.nn.functional.layer_norm(x, (x.shape[-1],), ln.weight, ln.bias, eps)
-
-    monkeypatch.setattr(engine, "gemm", fake_gemm)
-    monkeypatch.setattr(engine, "CACHE", FakeCache())
-    monkeypatch.setattr(engine, "head_expand", fake_head_expand)
-    monkeypatch.setattr(engine, "head_diag", fake_head_diag)
-    monkeypatch.setattr(engine, "cross_rows", fake_cross_rows)
-    monkeypatch.setattr(engine, "cross_rows_levels", fake_cross_rows_levels)
-    monkeypatch.setattr(engine, "small_attention", fake_small_attention)
-    monkeypatch.setattr(engine, "residual_layernorm", fake_res_ln)
+    fake_small_attention, fake_res_ln = SI.small_attention, SI.residual_layernorm
+    SI.install(monkeypatch)
 
     torch.manual_seed(3)
     B, nq, H, hid, Dtap, L, nlev = 2, 2, 4, 256, 48, 9, 3          # 8 effective queries, 3 levels of 8 patch rows

@@ -1,6 +1,7 @@
 """CPU side of the IQM query-side backward: the new symbols and their signatures, the Python surface, the workspace
 sizes, every device-free argument error of every new entry, the conditioning of the cases (fp32 CPU autograd against
-fp64), stage2_loss with given queries, and train_image_adapter's call order and checkpoint with a stub model and loss."""
+fp64), stage2_loss with given queries, train_image_adapter's call order and checkpoint with a stub model and loss, and
+the one forward of the query side with and without a record (outputs, keys and the calls per engine function)."""
 import ctypes as C
 import inspect
 import logging
@@ -329,3 +330,146 @@ def test_train_image_adapter_call_order_and_checkpoint(tmp_path, monkeypatch):
     train.load_iqm_branch_state(fresh, last["iqm_branch"])
     assert torch.equal(fresh.iqm.weight, model.iqm.weight)
     assert "iqm_branch" in train.train_image_adapter.__doc__
+
+
+# ---------------------------------------------------------------------------------------------- one forward, with a record
+# Calls per engine function at the parent commit (060b204), counted with the stand-ins of engine_standins.py on the
+# inputs of iqm_inputs() / branch_stub() below, its model/iqm.py, model/adapter.py and aaclip_hip/autograd.py run from a
+# scratch copy of `git show`: IQM.forward; IqmQueries.forward (driven with a stub ctx and the stub model); and the calls
+# AdaptedCLIP._iqm_branch makes outside IQM.forward (its total minus IQM.forward's on the same tensors).
+# Per layer: 16 gemm at inference (self-attention 4, visual cross-attention 6, text cross-attention 4, feed-forward 2) and
+# a 17th with a record, the pre-GELU rows; the text rows are fp32 here, so both cross-attentions are on cross_rows.
+PARENT_IQM_FORWARD = {"gemm": 32, "head_expand": 4, "head_diag": 4, "cross_rows": 4, "small_attention": 2,
+                      "residual_layernorm": 9, "combine3": 2}
+PARENT_IQM_QUERIES_FORWARD = {"gemm": 36, "head_expand": 4, "head_diag": 4, "cross_rows": 4, "small_attention": 2,
+                              "residual_layernorm": 10, "combine3": 3, "linear_smallk": 1}
+PARENT_BRANCH_OUTSIDE_IQM = {"gemm": 2, "residual_layernorm": 1, "combine3": 1, "linear_smallk": 1}
+IQM_LAYERS, IQM_HID, IQM_HEADS, IQM_B, IQM_LV, IQM_LT = 2, 256, 4, 2, 24, 11
+
+
+def build_iqm(seed=5, text_width=IQM_HID):
+    from model.iqm import IQM
+    torch.manual_seed(seed)
+    iqm = IQM(hidden_size=IQM_HID, num_hidden_layers=IQM_LAYERS, num_attention_heads=IQM_HEADS,
+              encoder_hidden_size=IQM_HID, text_encoder_hidden_size=text_width, intermediate_size=64)
+    with torch.no_grad():
+        for p in iqm.parameters():
+            p.normal_(0, 0.1 if p.dim() > 1 else 0.3)
+        for m in iqm.modules():
+            if isinstance(m, torch.nn.LayerNorm):
+                m.weight.add_(1.0)
+    return iqm
+
+
+def iqm_inputs():
+    """IQM.forward's arguments: queries [2, 2, 256], visual rows [2, 24, 256] with an encoder_proj, text rows
+    [2, 11, 256], fp32"""
+    g = torch.Generator().manual_seed(6)
+    r = lambda *s: torch.randn(*s, generator=g)
+    return dict(query_embeds=r(IQM_B, 2, IQM_HID), query_length=2, encoder_hidden_states=r(IQM_B, IQM_LV, IQM_HID),
+                text_encoder_hidden_states=r(IQM_B, IQM_LT, IQM_HID) * 0.7, code=_lib.F32,
+                encoder_proj=(r(IQM_HID, IQM_HID) * 0.1, r(IQM_HID) * 0.2))
+
+
+def record_keys(layers, branch):
+    """The key set IQM.forward documents (branch: with the four AdaptedCLIP._iqm_branch adds)"""
+    keys = {"vis", "txt", "last"} | ({"cls", "t1", "query", "te"} if branch else set())
+    for l in range(layers):
+        keys |= {f"{l}.{k}" for k in ("h", "a", "c", "mix", "z", "inter", "dense")}
+        keys |= {f"{l}.a.{k}" for k in ("ctx", "dense", "q", "k", "v")}
+        keys |= {f"{l}.c.{k}" for k in ("ctx", "dense", "qm", "qt", "ebar", "qx", "xbar")}
+        keys |= {f"{l}.t.{k}" for k in ("ctx", "dense", "qm", "qt", "ebar")}
+    return keys
+
+
+def branch_stub():
+    """The least of an AdaptedCLIP that its _iqm_branch and IqmQueries.forward read, and their inputs (rows, tap, anchors)"""
+    from model.adapter import AdaptedCLIP
+
+    class Stub(torch.nn.Module):
+        _iqm_branch = AdaptedCLIP._iqm_branch
+
+        def __init__(self):
+            super().__init__()
+            self.iqm, self.iqm_hidden_size, self.relu = build_iqm(), IQM_HID, False
+            self.class_query_mlp = torch.nn.Sequential(torch.nn.Linear(32, IQM_HID), torch.nn.ReLU(),
+                                                       torch.nn.Linear(IQM_HID, IQM_HID))
+            self.visual_feature_proj = torch.nn.Linear(IQM_HID, IQM_HID)
+            self.text_feature_proj = torch.nn.Linear(2, IQM_HID)
+            self.pos_embedding = torch.nn.Parameter(torch.randn(1, 8, IQM_HID) * 0.1)
+            self.iqm_layer_norm = torch.nn.LayerNorm(IQM_HID)
+
+        def _code(self):
+            return _lib.F32
+
+    g = torch.Generator().manual_seed(8)
+    return (Stub(), torch.randn(IQM_B, IQM_LV, IQM_HID, generator=g), torch.randn(IQM_B, 5, 32, generator=g),
+            torch.randn(IQM_B, IQM_LT, 2, generator=g))
+
+
+class StubCtx:
+    def save_for_backward(self, *tensors):
+        self.saved = tensors
+
+
+def test_iqm_forward_with_and_without_a_record(monkeypatch):
+    """One IQM.forward serves inference and training: a record changes neither the output nor the launches (but for the
+    one product of the pre-GELU rows per layer), holds exactly the documented keys, and nothing is launched before the
+    cases without a backward are refused."""
+    import engine_standins as SI
+    iqm, kw = build_iqm(), iqm_inputs()
+    plain, rec, S = {}, {}, {}
+    with torch.no_grad():
+        SI.install(monkeypatch, plain)
+        want = iqm(**kw).last_hidden_state
+        SI.install(monkeypatch, rec)
+        got = iqm(**kw, record=S).last_hidden_state
+    assert plain.pop("require_gpu") == 1 and rec.pop("require_gpu") == 1
+    assert torch.equal(got, want) and float(want.abs().max()) > 0.5
+    assert set(S) == record_keys(IQM_LAYERS, branch=False)
+    for k, t in S.items():
+        assert t.dtype == (engine.torch_dtype(kw["code"]) if k in ("vis", "txt") else torch.float32), k
+    assert S["0.c.qm"].shape == (IQM_B * 2 * IQM_HEADS, IQM_HID) and S["1.z"].shape == (IQM_B * 2, 64)
+    assert plain == PARENT_IQM_FORWARD
+    want_rec = {k: v - PARENT_BRANCH_OUTSIDE_IQM.get(k, 0) for k, v in PARENT_IQM_QUERIES_FORWARD.items()}
+    assert rec == {k: v for k, v in want_rec.items() if v}
+    assert {k: rec[k] - plain[k] for k in rec} == dict.fromkeys(rec, 0) | {"gemm": IQM_LAYERS}
+    # the cases the backward does not cover: refused before anything runs
+    none = {}
+    SI.install(monkeypatch, none)
+    lv = {"rows": [torch.zeros(IQM_B * 5, 32)], "rows_per_image": 5, "row0": 1, "keys": 4, "width": 32,
+          "w_in": torch.zeros(32, IQM_HID), "w_out": torch.zeros(IQM_HID, 32)}
+    with pytest.raises(NotImplementedError):
+        iqm(**{**kw, "encoder_hidden_states": None}, encoder_levels=lv, record={})
+    assert none == {}
+    narrow = dict(kw, text_encoder_hidden_states=torch.zeros(IQM_B, IQM_LT, 64))     # no aaclip_cross_rows width
+    iq2 = build_iqm(text_width=64)
+    with torch.no_grad():
+        assert iq2(**narrow).last_hidden_state.shape == (IQM_B, 2, IQM_HID)          # inference: the small_attention path
+        assert none.get("small_attention", 0) > IQM_LAYERS
+        with pytest.raises(NotImplementedError):
+            iq2(**narrow, record={})
+
+
+def test_iqm_queries_forward_is_the_models_branch(monkeypatch):
+    """IqmQueries.forward is a caller of AdaptedCLIP._iqm_branch: the queries of the model's own call, the whole record
+    saved, and the launches IqmQueries.forward made when it carried its own copy of the branch."""
+    import engine_standins as SI
+    model, rows, tap, anchors = branch_stub()
+    counts, ctx = {}, StubCtx()
+    with torch.no_grad():
+        SI.install(monkeypatch)
+        want = model._iqm_branch(tap, rows, anchors, IQM_B, tap.shape[1], _lib.F32).last_hidden_state
+        SI.install(monkeypatch, counts)
+        got = autograd.IqmQueries.forward(ctx, model, rows, tap, anchors)
+    assert torch.equal(got, want) and got.shape == (IQM_B, 2, IQM_HID)
+    assert set(ctx.keys) == record_keys(IQM_LAYERS, branch=True) and len(ctx.saved) == len(ctx.keys)
+    assert ctx.dims == (IQM_B, tap.shape[1], IQM_LV, IQM_LT, _lib.F32)
+    S = dict(zip(ctx.keys, ctx.saved))
+    assert all(t.dtype == torch.float32 for t in S.values())
+    assert S["vis"].data_ptr() == rows.data_ptr() and torch.equal(S["te"], anchors)
+    assert torch.equal(S["cls"], tap[:, 0, :]) and bool((S["t1"] >= 0).all()) and bool((S["t1"] == 0).any())
+    counts.pop("require_gpu")
+    assert counts == PARENT_IQM_QUERIES_FORWARD
+    with pytest.raises(NotImplementedError, match="text_embeddings"):
+        autograd.IqmQueries.forward(StubCtx(), model, rows, tap, anchors[:, :, :1])
