@@ -72,6 +72,12 @@ SIGNATURES = {
     "aaclip_block_backward_long_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "aaclip_block_backward_long": (_i, [_vp, C.POINTER(BlockWeights), C.POINTER(BlockWeights), _f] + [_i] * 6
                                    + [_vp, _vp, _vp, _vp, _sz, _vp]),
+    "aaclip_split3_rows": (_i, [_vp, _vp, _l, _i, _vp]),
+    "aaclip_attention_backward_long_bf16x3_workspace_bytes": (_sz, [_i, _i, _i]),
+    "aaclip_attention_backward_long_bf16x3": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "aaclip_block_backward_long_bf16x3_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "aaclip_block_backward_long_bf16x3": (_i, [_vp] + [C.POINTER(BlockWeights)] * 3 + [_f] + [_i] * 6
+                                          + [_vp, _vp, _vp, _vp, _sz, _vp]),
     "aaclip_row_head_backward": (_i, [_vp] * 6 + [_i, _vp, _vp, _vp] + [_i] * 5 + [_vp, _sz, _vp]),
     "aaclip_tap_head_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "aaclip_tap_head_backward": (_i, [_vp] * 5 + [_i] + [_vp] * 7 + [_i] * 4 + [_vp, _sz, _vp]),

@@ -15,7 +15,42 @@ from __future__ import annotations
 
 import torch
 
+import contextlib
+import os
+
 from . import _lib, engine
+
+# Arithmetic of the visual blocks' backward (VisualTaps): "fp32" (default, the exact-fp32 MFMA) or "bf16x3" (the
+# three-term bf16 entries, include/aaclip.h "bf16x3").  The environment variable AACLIP_BACKWARD sets the initial value,
+# in the manner of AACLIP_COMPUTE.  Forward outputs and losses do not depend on it; the text tower, the heads, the IQM
+# branch and every row of at most 128 tokens keep their fp32 kernels whatever it says.
+def backward_precision_from_env(environ=os.environ) -> str:
+    """AACLIP_BACKWARD: unset or empty = fp32; an unknown value raises ValueError"""
+    return engine.backward_precision_name(environ.get("AACLIP_BACKWARD") or "fp32")
+
+
+_backward_precision = backward_precision_from_env()
+
+
+def backward_precision() -> str:
+    return _backward_precision
+
+
+def set_backward_precision(mode) -> None:
+    global _backward_precision
+    _backward_precision = engine.backward_precision_name(mode)
+
+
+@contextlib.contextmanager
+def use_backward_precision(mode):
+    """with use_backward_precision("bf16x3"): the graphs BUILT inside (VisualTaps.forward records the mode) run their
+    visual-block backward in that arithmetic; the previous mode is restored on exit."""
+    before = backward_precision()
+    set_backward_precision(mode)
+    try:
+        yield
+    finally:
+        set_backward_precision(before)
 
 
 class SimilarityMapTrain(torch.autograd.Function):
@@ -165,8 +200,8 @@ class VisualTaps(torch.autograd.Function):
     that leaves the stream after every block in its own buffer -- the kernels of the no-grad path, so the taps are
     bit-identical to what AdaptedCLIP.forward feeds its heads.  Saved (ctx.save_for_backward: freed with the graph):
     the inputs of the blocks the backward revisits, i.e. the patch-embed output and the per-block streams from the
-    first trainable adapter's block on, and nothing else.  The backward runs in fp32 whatever precision the forward
-    ran in: from the last tapped level down it adds d_tap into the running stream gradient at every tapped level and
+    first trainable adapter's block on, and nothing else.  The backward runs in fp32 (or, when
+    backward_precision() said so at forward time, in bf16x3) whatever precision the forward ran in: from the last tapped level down it adds d_tap into the running stream gradient at every tapped level and
     calls engine.block_backward(in_place=True), which recomputes the block from its input; it stops at the first block
     whose adapter requires grad (the patch embedding is frozen).  Blocks above the last tapped level are never run.
     When no layer adapter requires grad nothing is saved."""
@@ -191,6 +226,8 @@ class VisualTaps(torch.autograd.Function):
         need = [i for i in range(min(until, len(blocks))) if ctx.needs_input_grad[2 + i]]
         ctx.first = need[0] if need else None
         ctx.model, ctx.B, ctx.L, ctx.levels = model, B, L, levels
+        # rows of at most 128 tokens keep the stage-1 kernels whatever is selected
+        ctx.precision = backward_precision() if L > engine.ATTN_BWD_SHORT_MAX_L else "fp32"
         if ctx.first is not None:
             ins = [x0] + outs[:-1]          # ins[i]: the input of block i
             ctx.save_for_backward(*ins[ctx.first:], *weights)
@@ -219,7 +256,7 @@ class VisualTaps(torch.autograd.Function):
             aw = weights[i] if i < until else None
             _, d_aw = engine.block_backward(ins[i - ctx.first], blocks[i], B, L, v.transformer.heads, d_x, causal=False,
                                             adapter_weight=aw, mix=model.i_w, need_input_grad=i > ctx.first,
-                                            in_place=True)
+                                            in_place=True, precision=ctx.precision)
             if aw is not None and ctx.needs_input_grad[2 + i]:
                 grads[i] = d_aw.to(aw.dtype)
         return (None, None, *grads)

@@ -105,6 +105,40 @@ def join_split8(t: torch.Tensor, C: int) -> torch.Tensor:
     return hi + lo
 
 
+BACKWARD_PRECISIONS = ("fp32", "bf16x3")   # arithmetic of the visual blocks' backward (autograd.backward_precision)
+
+
+def backward_precision_name(precision) -> str:
+    name = str(precision).lower()
+    if name not in BACKWARD_PRECISIONS:
+        raise ValueError(f"unknown backward precision {precision!r}; use fp32 or bf16x3")
+    return name
+
+
+def split3_weight(w: torch.Tensor, q_rows: int = 0) -> torch.Tensor:
+    """[N, K] -> the stacked bf16 weight [N, 3K] = [Wh | Wh | Wl] of the bf16x3 backward (include/aaclip.h): Wh =
+    bf16(w), Wl = bf16(w - Wh).  Against split3 rows [Ah | Al | Ah] a plain bf16 product over 3K sums Ah.Wh + Al.Wh +
+    Ah.Wl.  q_rows: that many leading rows are multiplied by 1/8 first (the q scale, a power of two: exact).  Pure
+    torch, on w's device; load-time work (WeightCache)."""
+    v = w.detach().float()
+    if q_rows:
+        v = v.clone()
+        v[:q_rows] *= 0.125
+    hi = v.to(torch.bfloat16)
+    lo = (v - hi.float()).to(torch.bfloat16)
+    return torch.cat([hi, hi, lo], dim=1).contiguous()
+
+
+def split3_rows(x: torch.Tensor) -> torch.Tensor:
+    """fp32 [rows, K] -> split3 rows, bf16 [rows, 3K] = [hi | lo | hi] (aaclip_split3_rows); K a multiple of 64."""
+    require_gpu(x, "split3_rows")
+    x = _f32c(x)
+    rows, K = x.shape
+    out = torch.empty(rows, 3 * K, dtype=torch.bfloat16, device=x.device)
+    _lib.check(_lib.load().aaclip_split3_rows(x.data_ptr(), out.data_ptr(), rows, K, _stream(x.device)), "split3_rows")
+    return out
+
+
 def _stream(dev: torch.device) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
@@ -160,7 +194,10 @@ class WeightCache:
         self._c: Dict[Tuple[int, int, str], tuple] = {}
 
     def get(self, p: torch.Tensor, code: int, kind: str = "plain") -> torch.Tensor:
-        """kind: 'plain' | 'transpose' | 'conv'.  Code F16X2: split8 weight rows as uint8 [out, 4*in]; with a '+exact'
+        """kind: 'plain' | 'transpose' | 'conv', or one of the bf16x3 backward's (code BF16: 'split3' the stacked weight
+        of split3_weight, 'split3_t' the same of the transpose, 'split3_q' the stacked in_proj weight with its q rows
+        times 1/8; code F32: 'scale_q' the in_proj bias with its q entries times 1/8).
+        Code F16X2: split8 weight rows as uint8 [out, 4*in]; with a '+exact'
         suffix the 3-plane form [out, 3*in] when every value is exact in fp16 and in_features is a multiple of 256
         (the kernels then skip the weight-lo correction tile) -- tell them apart by the shape."""
         key = (id(p), code, kind)
@@ -170,6 +207,14 @@ class WeightCache:
         src = p.detach()
         allow_exact = kind.endswith("+exact")
         kind = kind.split("+")[0]
+        if kind in ("split3", "split3_t", "split3_q"):
+            out = split3_weight(src.t() if kind == "split3_t" else src,
+                                q_rows=src.shape[0] // 3 if kind == "split3_q" else 0)
+            return self._put(key, p, out)
+        if kind == "scale_q":
+            out = src.float().clone()
+            out[: out.shape[0] // 3] *= 0.125
+            return self._put(key, p, out)
         if kind == "transpose":          # [in, out] parameter used as x @ P  ->  [out, in]
             src = src.t()
         elif kind == "conv":             # conv1.weight [D,3,ps,ps] -> [D, Kpad]
@@ -186,6 +231,9 @@ class WeightCache:
             out = split_rows(src32, weight=True, exact=exact)
         else:
             out = src.to(_TORCH_DT[code]).contiguous()
+        return self._put(key, p, out)
+
+    def _put(self, key, p: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         cache = self._c
 
         def _drop(_ref, key=key):
@@ -673,13 +721,21 @@ def _long_rows(L: int, long_rows: Optional[bool]) -> bool:
 
 
 def attention_backward(qkv: torch.Tensor, d_ctx: torch.Tensor, B: int, L: int, heads: int, causal: bool,
-                       dq_scale: float = 1.0, long_rows: Optional[bool] = None) -> torch.Tensor:
+                       dq_scale: float = 1.0, long_rows: Optional[bool] = None, precision: str = "fp32") -> torch.Tensor:
     """packed fp32 q|k|v rows [B*L, 3*H*64] (q pre-scaled) + d ctx [B*L, H*64] -> d qkv: aaclip_attention_backward for
-    L <= 128, aaclip_attention_backward_long above (long_rows: see _long_rows)."""
+    L <= 128, aaclip_attention_backward_long above (long_rows: see _long_rows).  precision "bf16x3": the tiled
+    three-term bf16 entry (aaclip_attention_backward_long_bf16x3) at any L."""
+    precision = backward_precision_name(precision)
     require_gpu(qkv, "attention_backward")
     qkv, d_ctx = _f32c(qkv), _f32c(d_ctx)
     out = torch.empty_like(qkv)
     lib = _lib.load()
+    if precision == "bf16x3":
+        ws = Workspace.get(qkv.device, lib.aaclip_attention_backward_long_bf16x3_workspace_bytes(int(B), int(L), int(heads)))
+        _lib.check(lib.aaclip_attention_backward_long_bf16x3(qkv.data_ptr(), d_ctx.data_ptr(), out.data_ptr(), B, L, heads,
+                                                             int(causal), float(dq_scale), ws.data_ptr(), ws.numel(),
+                                                             _stream(qkv.device)), "attention_backward_long_bf16x3")
+        return out
     if _long_rows(L, long_rows):
         ws = Workspace.get(qkv.device, lib.aaclip_attention_backward_long_workspace_bytes(int(B), int(L), int(heads)))
         _lib.check(lib.aaclip_attention_backward_long(qkv.data_ptr(), d_ctx.data_ptr(), out.data_ptr(), B, L, heads,
@@ -731,12 +787,39 @@ def pack_block_transposed(block, adapter_weight: Optional[torch.Tensor]) -> Tupl
     return w, refs
 
 
+def pack_block_split3(block) -> Tuple[BlockWeights, list]:
+    """The `w3` argument of aaclip_block_backward_long_bf16x3: the stacked bf16 weights [N, 3K], in_proj (weight and
+    fp32 bias) with its q rows times 1/8."""
+    refs: list = []
+    w = BlockWeights()
+    w.qkv_w = _keep(refs, CACHE.get(block.attn.in_proj_weight, BF16, "split3_q"))
+    w.qkv_b = _keep(refs, CACHE.get(block.attn.in_proj_bias, F32, "scale_q"))
+    w.out_w = _keep(refs, CACHE.get(block.attn.out_proj.weight, BF16, "split3"))
+    w.fc_w = _keep(refs, CACHE.get(block.mlp.c_fc.weight, BF16, "split3"))
+    w.proj_w = _keep(refs, CACHE.get(block.mlp.c_proj.weight, BF16, "split3"))
+    return w, refs
+
+
+def pack_block_split3_transposed(block, adapter_weight: Optional[torch.Tensor]) -> Tuple[BlockWeights, list]:
+    """The `wt3` argument: the stacked bf16 transposes [in, 3 * out]; the adapter's transpose stays fp32."""
+    refs: list = []
+    w = BlockWeights()
+    w.qkv_w = _keep(refs, CACHE.get(block.attn.in_proj_weight, BF16, "split3_t"))
+    w.out_w = _keep(refs, CACHE.get(block.attn.out_proj.weight, BF16, "split3_t"))
+    w.fc_w = _keep(refs, CACHE.get(block.mlp.c_fc.weight, BF16, "split3_t"))
+    w.proj_w = _keep(refs, CACHE.get(block.mlp.c_proj.weight, BF16, "split3_t"))
+    if adapter_weight is not None:
+        w.adapter_w = _keep(refs, CACHE.get(adapter_weight, F32, "transpose"))
+    return w, refs
+
+
 def block_backward(x_in: torch.Tensor, block, B: int, L: int, heads: int, d_out: torch.Tensor, causal: bool = False,
                    adapter_weight: Optional[torch.Tensor] = None, mix: float = 0.0, need_input_grad: bool = True,
-                   in_place: bool = False, long_rows: Optional[bool] = None):
+                   in_place: bool = False, long_rows: Optional[bool] = None, precision: str = "fp32"):
     """Backward of one block from its input x_in [B*L, D] -> (d x_in or None, d adapter weight [D, D] or None):
     aaclip_block_backward for L <= 128, aaclip_block_backward_long above (long_rows: see _long_rows).
-    in_place: d x_in overwrites d_out."""
+    in_place: d x_in overwrites d_out.  precision "bf16x3": aaclip_block_backward_long_bf16x3 at any L."""
+    precision = backward_precision_name(precision)
     require_gpu(x_in, "block_backward")
     lib = _lib.load()
     if x_in.dtype != torch.float32 or not x_in.is_contiguous() or d_out.dtype != torch.float32 or not d_out.is_contiguous():
@@ -744,9 +827,20 @@ def block_backward(x_in: torch.Tensor, block, B: int, L: int, heads: int, d_out:
     D = x_in.shape[1]
     F = block.mlp.c_fc.weight.shape[0]
     w, refs = pack_block(block, F32, adapter_weight)
-    wt, refs_t = pack_block_transposed(block, adapter_weight) if need_input_grad else (BlockWeights(), [])
+    wt, refs_t = (pack_block_transposed(block, adapter_weight) if need_input_grad and precision == "fp32"
+                  else (BlockWeights(), []))
     d_in = (d_out if in_place else torch.empty_like(d_out)) if need_input_grad else None
     d_aw = torch.empty(D, D, dtype=torch.float32, device=x_in.device) if adapter_weight is not None else None
+    if precision == "bf16x3":
+        w3, refs3 = pack_block_split3(block)
+        wt3, refs_t = pack_block_split3_transposed(block, adapter_weight) if need_input_grad else (BlockWeights(), [])
+        ws = Workspace.get(x_in.device, lib.aaclip_block_backward_long_bf16x3_workspace_bytes(int(B), int(L), int(D), int(F)))
+        _lib.check(lib.aaclip_block_backward_long_bf16x3(
+            x_in.data_ptr(), C.byref(w), C.byref(w3), C.byref(wt3), float(mix), B, L, D, heads, F,
+            ATTN_CAUSAL if causal else ATTN_FULL, d_out.data_ptr(), _ptr(d_in), _ptr(d_aw), ws.data_ptr(), ws.numel(),
+            _stream(x_in.device)), "block_backward_bf16x3")
+        del refs, refs3, refs_t
+        return d_in, d_aw
     if _long_rows(L, long_rows):
         ws = Workspace.get(x_in.device, lib.aaclip_block_backward_long_workspace_bytes(int(B), int(L), int(D), int(F)))
         entry = lib.aaclip_block_backward_long

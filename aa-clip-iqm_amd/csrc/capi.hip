@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "bf16x3.h"
 #include "kernels.h"
 
 using namespace aaclip;
@@ -1023,6 +1024,136 @@ int aaclip_block_backward_long(const float* x_in, const aaclip_block_weights* w,
                                float* d_in, float* d_adapter_w, void* ws, size_t ws_bytes, void* stream) {
   return block_backward_body(true, x_in, w, wt, mix, B, L, D, H, F, attn_mode, d_out, d_in, d_adapter_w, ws, ws_bytes,
                              stream);
+}
+
+// ---- The three-term bf16 backward of the visual blocks (bf16x3.h; include/aaclip.h, "bf16x3")
+
+int aaclip_split3_rows(const float* src, void* dst, long rows, int K, void* stream) {
+  REQUIRE(src && dst, "split3_rows: null pointer");
+  REQUIRE(rows > 0 && K > 0 && K % 64 == 0, "split3_rows: rows must be positive and K a positive multiple of 64");
+  REQUIRE(rows < (1L << 40) / K, "split3_rows: problem too large");
+  REQUIRE_ALIGNED16("split3_rows", src, dst);
+  launch_split3_rows(src, dst, rows, K, (hipStream_t)stream);
+  return finish("split3_rows");
+}
+
+size_t aaclip_attention_backward_long_bf16x3_workspace_bytes(int B, int L, int H) {
+  return attention_backward_long_bf16x3_ws_bytes(B, L, H);
+}
+
+int aaclip_attention_backward_long_bf16x3(const float* qkv, const float* d_ctx, float* d_qkv, int B, int L, int H,
+                                          int causal, float dq_scale, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(qkv && d_ctx && d_qkv && ws, "attention_backward_long_bf16x3: null pointer");
+  if (const char* m = attention_backward_long_check(B, L, H)) return fail(-1, m);
+  REQUIRE_ALIGNED16("attention_backward_long_bf16x3", qkv, d_ctx, d_qkv, ws);
+  REQUIRE(ws_bytes >= attention_backward_long_bf16x3_ws_bytes(B, L, H),
+          "attention_backward_long_bf16x3: workspace too small");
+  launch_attention_backward_long_bf16x3(qkv, d_ctx, d_qkv, B, L, H, causal != 0, dq_scale, ws, (hipStream_t)stream);
+  return finish("attention_backward_long_bf16x3");
+}
+
+// one buffer for every split3 A operand of the block: each is read by the product right behind the pass that writes it
+static size_t bf16x3_rows_bytes(long rows, int D, int F) {
+  return up256((size_t)rows * 3 * (size_t)(F > 3 * D ? F : 3 * D) * 2);
+}
+
+size_t aaclip_block_backward_long_bf16x3_workspace_bytes(int B, int L, int D, int F) {
+  if (B <= 0 || L <= 0 || D <= 0 || F < 0) return 0;
+  const long rows = (long)B * L;
+  return tb_layout(rows, D, F).total + bf16x3_rows_bytes(rows, D, F) +
+         attention_backward_long_bf16x3_ws_bytes(B, L, (D + 63) / 64);
+}
+
+// block_backward_body(long_rows) step for step; the eight products of the block proper are bf16 GEMMs over K' = 3K on
+// split3 rows against the stacked weights, the attention backward is the bf16x3 one.  The recomputed forward attention,
+// the adapter's three products and every row op are the fp32 kernels of block_backward_body.
+int aaclip_block_backward_long_bf16x3(const float* x_in, const aaclip_block_weights* w, const aaclip_block_weights* w3,
+                                      const aaclip_block_weights* wt3, float mix, int B, int L, int D, int H, int F,
+                                      int attn_mode, const float* d_out, float* d_in, float* d_adapter_w, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  REQUIRE(x_in && w && w3 && wt3 && d_out && ws, "block_backward_bf16x3: null pointer");
+  REQUIRE(w->struct_bytes == sizeof(aaclip_block_weights) && w3->struct_bytes == sizeof(aaclip_block_weights) &&
+              wt3->struct_bytes == sizeof(aaclip_block_weights),
+          "block_backward_bf16x3: aaclip_block_weights.struct_bytes does not match this library");
+  REQUIRE(attn_mode == AACLIP_ATTN_FULL || attn_mode == AACLIP_ATTN_CAUSAL,
+          "block_backward_bf16x3: attn_mode must be AACLIP_ATTN_FULL or AACLIP_ATTN_CAUSAL");
+  REQUIRE(B > 0 && L > 0, "block_backward_bf16x3: empty batch");
+  REQUIRE(D == 64 * H, "block_backward_bf16x3: D must equal 64*H (head dim 64)");
+  REQUIRE_ROW_WIDTH(D);
+  REQUIRE(F > 0 && F % 128 == 0, "block_backward_bf16x3: F must be a multiple of 128");
+  if (const char* m = attention_backward_long_check(B, L, H)) return fail(-1, m);
+  const long rows = (long)B * L;
+  REQUIRE(rows < (1L << 31) / 4, "block_backward_bf16x3: too many rows");
+  REQUIRE(w->ln1_w && w->ln1_b && w->out_b && w->ln2_w && w->ln2_b && w->fc_b && w->proj_b,
+          "block_backward_bf16x3: null weight pointer");
+  REQUIRE(w3->qkv_w && w3->qkv_b && w3->out_w && w3->fc_w && w3->proj_w,
+          "block_backward_bf16x3: null stacked weight pointer");
+  const bool adapter = w->adapter_w != nullptr;
+  REQUIRE(adapter || d_in, "block_backward_bf16x3: nothing to compute (no adapter and d_in is NULL)");
+  REQUIRE(!adapter || d_adapter_w, "block_backward_bf16x3: d_adapter_w is required for a block with an adapter");
+  REQUIRE(!d_in || (wt3->qkv_w && wt3->out_w && wt3->fc_w && wt3->proj_w && (!adapter || wt3->adapter_w)),
+          "block_backward_bf16x3: null transposed weight pointer");
+  const TbLayout l = tb_layout(rows, D, F);
+  const size_t a3_bytes = bf16x3_rows_bytes(rows, D, F);
+  REQUIRE(ws_bytes >= l.total + a3_bytes + attention_backward_long_bf16x3_ws_bytes(B, L, H),
+          "block_backward_bf16x3: workspace too small");
+  REQUIRE_ALIGNED16("block_backward_bf16x3", x_in, d_out, d_in, d_adapter_w, ws, w->ln1_w, w->ln2_w, w->adapter_w,
+                    w3->qkv_w, w3->out_w, w3->fc_w, w3->proj_w, wt3->qkv_w, wt3->out_w, wt3->fc_w, wt3->proj_w,
+                    wt3->adapter_w);
+  hipStream_t s = (hipStream_t)stream;
+  char* base = (char*)ws;
+  float *h = (float*)(base + l.h), *qkv = (float*)(base + l.qkv), *ctx = (float*)(base + l.ctx);
+  float *x1 = (float*)(base + l.x1), *f = (float*)(base + l.f), *g = (float*)(base + l.g), *x2 = (float*)(base + l.x2);
+  float *z = (float*)(base + l.z), *dx = (float*)(base + l.dx), *dqkv = (float*)(base + l.dqkv);
+  float* tmp = (float*)(base + l.tmp);
+  void* a3 = base + l.total;
+  void* attn_ws = base + l.total + a3_bytes;
+  const int M = (int)rows;
+  const int causal = attn_mode == AACLIP_ATTN_CAUSAL;
+  // out[M, N] (fp32) = A[M, K] . W[N, K]^T (+ bias) in three terms: a3 holds A's split3 rows, W3 is [N, 3K] bf16
+  auto product = [&](const void* W3, const float* bias, float* out, int N, int K, const float* resid) {
+    GemmParams p = gemm_params(a3, 3L * K, W3, bias, out, N, M, N, 3 * K);
+    p.resid = resid;
+    launch_gemm(AACLIP_BF16, resid ? EPI_BIAS_RESID : EPI_ACT_F32, p, s);
+  };
+  // ---- the block's internals again from its input; qkv comes out with q scaled: w3->qkv_w and w3->qkv_b carry 1/8
+  launch_layernorm(AACLIP_F32, x_in, w->ln1_w, w->ln1_b, h, rows, D, 1e-5f, s);
+  launch_split3_rows(h, a3, rows, D, s);
+  product(w3->qkv_w, (const float*)w3->qkv_b, qkv, 3 * D, D, nullptr);
+  launch_attention(AACLIP_F32, qkv, ctx, B, L, H, causal, 0, s);
+  launch_split3_rows(ctx, a3, rows, D, s);
+  product(w3->out_w, (const float*)w->out_b, x1, D, D, x_in);
+  launch_layernorm(AACLIP_F32, x1, w->ln2_w, w->ln2_b, h, rows, D, 1e-5f, s);
+  launch_split3_rows(h, a3, rows, D, s);
+  product(w3->fc_w, (const float*)w->fc_b, f, F, D, nullptr);
+  const float* dy = d_out;   // gradient of the stream after the MLP half
+  if (adapter) {
+    launch_gelu_forward_split3(f, a3, rows, F, s);
+    product(w3->proj_w, (const float*)w->proj_b, x2, D, F, x1);
+    GemmParams p = gemm_params(x2, D, w->adapter_w, nullptr, z, D, M, D, D);
+    launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+    launch_adapter_mix_backward(x2, z, d_out, z, dx, rows, D, mix, s);   // z <- dz, dx <- the direct d x2
+    launch_wgrad(z, D, x2, D, d_adapter_w, rows, D, D, base + l.wg, s);
+    if (!d_in) return finish("block_backward_bf16x3");
+    p = gemm_params(z, D, wt3->adapter_w, nullptr, tmp, D, M, D, D);
+    launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+    launch_add_rows(dx, tmp, dx, rows * D, s);
+    dy = dx;
+  }
+  // ---- x2 = x1 + c_proj(gelu(f)),  f = c_fc(ln_2 x1)
+  launch_split3_rows(dy, a3, rows, D, s);
+  product(wt3->proj_w, nullptr, g, F, D, nullptr);
+  launch_gelu_backward_split3(f, g, a3, rows, F, s);
+  product(wt3->fc_w, nullptr, tmp, D, F, nullptr);
+  launch_layernorm_backward(x1, w->ln2_w, tmp, dy, dx, nullptr, rows, D, 1e-5f, s);   // dx <- d x1
+  // ---- x1 = x_in + out_proj(attention(qkv)),  qkv = in_proj(ln_1 x_in), q scaled
+  launch_split3_rows(dx, a3, rows, D, s);
+  product(wt3->out_w, nullptr, tmp, D, D, nullptr);
+  launch_attention_backward_long_bf16x3(qkv, tmp, dqkv, B, L, H, causal, 0.125f, attn_ws, s);
+  launch_split3_rows(dqkv, a3, rows, 3 * D, s);
+  product(wt3->qkv_w, nullptr, tmp, D, 3 * D, nullptr);
+  launch_layernorm_backward(x_in, w->ln1_w, tmp, dx, d_in, nullptr, rows, D, 1e-5f, s);
+  return finish("block_backward_bf16x3");
 }
 
 int aaclip_row_head_backward(const float* x, const int32_t* tokens, const float* ln_w, const float* ln_b,

@@ -19,6 +19,15 @@ flips) runs as HIP kernels on raw uint8 frames (aaclip_hip.engine.train_preproce
     python train.py --dataset MVTec --training_mode full_shot --iqm_hidden_size 768 --save_path ckpt/run [--device_augment]
 
 (stage2_loss needs the IQM queries as wide as the seg tokens, 768 for ViT-L-14-336: see its docstring.)
+
+The backward of the visual blocks is fp32 by default.  The environment variable AACLIP_BACKWARD selects its arithmetic
+without a command-line argument (the parser stays the reference's):
+
+    AACLIP_BACKWARD=bf16x3 python train.py --dataset MVTec --training_mode full_shot --iqm_hidden_size 768 --save_path ckpt/run
+
+runs those blocks' products and attention backward as three-term bf16 sums on the bf16 MFMA
+(aaclip_hip.autograd.backward_precision, include/aaclip.h "bf16x3"); forward outputs and loss values are the same bits
+in both modes, the text tower and everything outside the visual blocks stay fp32.
 """
 from __future__ import annotations
 

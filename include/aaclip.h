@@ -328,6 +328,49 @@ int aaclip_block_backward_long(const float* x_in, const aaclip_block_weights* w,
                                float mix, int B, int L, int D, int H, int F, int attn_mode, const float* d_out,
                                float* d_in, float* d_adapter_w, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- bf16x3: a second, opt-in arithmetic for the backward of the visual blocks.  A value v is carried as
+ * hi = bf16(v), lo = bf16(v - hi) (round to nearest even; bf16 has fp32's exponent, so there is no scale anywhere) and a
+ * product is summed as Ah.Bh + Al.Bh + Ah.Bl in fp32 accumulators on the bf16 MFMA: about 16 significant bits per
+ * operand over fp32's whole range, at 3/16 of the matrix-pipe time of the exact-fp32 MFMA.  The fp32 entry points above
+ * are unchanged and stay the default; nothing selects these by itself.
+ *
+ * aaclip_split3_rows: fp32 src [rows, K] -> bf16 dst [rows, 3K] = [hi | lo | hi] per row, the A operand of
+ * aaclip_gemm(AACLIP_BF16) over K' = 3K against a stacked weight [N, 3K] = [Wh | Wh | Wl]: one plain bf16 product
+ * then accumulates exactly the three terms.  K a multiple of 64, pointers 16-byte aligned. */
+int aaclip_split3_rows(const float* src, void* dst, long rows, int K, void* stream);
+
+/* aaclip_attention_backward_long in this arithmetic: the same arguments, layouts (fp32 in, fp32 out), masks, dq_scale
+ * and refusals; the same three passes (statistics, dk | dv, dq) behind a pre-pass that writes the hi and lo planes of q,
+ * k, v and d_ctx into the workspace.  The row statistics, the exponent and ds = p (dp - delta) are fp32; p and ds are
+ * split in registers.  No atomics, nothing of size L x L in memory, every output element summed by one wave in a fixed
+ * order: repeated calls give the same bits.  The workspace holds the statistics and the planes
+ * (1024 bytes per image, head and row). */
+size_t aaclip_attention_backward_long_bf16x3_workspace_bytes(int B, int L, int H);
+int aaclip_attention_backward_long_bf16x3(const float* qkv, const float* d_ctx, float* d_qkv, int B, int L, int H,
+                                          int causal, float dq_scale, void* ws, size_t ws_bytes, void* stream);
+
+/* aaclip_block_backward_long in this arithmetic: the same recomputation from x_in in the same order.  The eight
+ * products of the block proper (in_proj, out_proj, c_fc, c_proj and their four input-gradient products) run as bf16
+ * products over 3K on split3 rows, the attention backward is the entry above; the recomputed forward attention, the
+ * adapter's three products and every row op are the fp32 kernels of aaclip_block_backward_long.  Which field is read
+ * from which struct, and as what:
+ *   w    fp32: ln1_w, ln1_b, out_b, ln2_w, ln2_b, fc_b, proj_b, adapter_w [D, D] (NULL = no adapter).  Its qkv_w, qkv_b,
+ *        out_w, fc_w and proj_w are not read.
+ *   w3   bf16 stacked weights [N, 3K] = [Wh | Wh | Wl]: qkv_w [3D, 3D] with its first D rows (q) times 1/8, out_w
+ *        [D, 3D], fc_w [F, 3D], proj_w [D, 3F]; fp32: qkv_b [3D] with its first D entries times 1/8 (the q scale is a
+ *        power of two, so this is exact and qkv comes out pre-scaled without a column scale in the epilogue).  Nothing
+ *        else is read.
+ *   wt3  bf16 stacked TRANSPOSED weights (unscaled): qkv_w [D, 9D], out_w [D, 3D], fc_w [D, 3F], proj_w [F, 3D]; fp32:
+ *        adapter_w [D, D], the transposed adapter weight.  Not read when d_in is NULL.
+ * d_out, d_in (may alias d_out, may be NULL), d_adapter_w and mix as in aaclip_block_backward.  Rejected before a launch:
+ * null pointers, D != 64*H, a bad attn_mode, F not a multiple of 128, a row width the row kernels do not take, misaligned
+ * pointers and ws_bytes < aaclip_block_backward_long_bf16x3_workspace_bytes(B, L, D, F). */
+size_t aaclip_block_backward_long_bf16x3_workspace_bytes(int B, int L, int D, int F);
+int aaclip_block_backward_long_bf16x3(const float* x_in, const aaclip_block_weights* w, const aaclip_block_weights* w3,
+                                      const aaclip_block_weights* wt3, float mix, int B, int L, int D, int H, int F,
+                                      int attn_mode, const float* d_out, float* d_in, float* d_adapter_w, void* ws,
+                                      size_t ws_bytes, void* stream);
+
 /* Backward of aaclip_row_head(AACLIP_F32): x, tokens, ln_w, ln_b, act, mode as there; proj_w [E, D] and its transpose
  * proj_wt [D, E] in fp32 (proj_wt may be NULL when d_x is); d_out [n, E].  d_proj_w (out) [E, D], overwritten.  d_x
  * (out, may be NULL) [n*T, D]: zero except the n picked rows, which receive the LayerNorm input gradient -- a scatter of
