@@ -103,6 +103,8 @@ SIGNATURES = {
     "aaclip_cross_rows_backward": (_i, [_i] + [_vp] * 5 + [_i] * 6 + [_vp, _sz, _vp]),
     "aaclip_cross_rows_levels_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "aaclip_cross_rows_levels": (_i, [_i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _l, _vp, _sz, _vp]),
+    "aaclip_cross_rows_levels_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "aaclip_cross_rows_levels_backward": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 7 + [_l, _vp, _sz, _vp]),
     "aaclip_head_expand": (_i, [_i, _vp, _vp, _l, _i, _i, _f, _vp]),
     "aaclip_head_diag": (_i, [_vp, _vp, _l, _i, _i, _vp]),
     "aaclip_residual_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _f, _vp]),

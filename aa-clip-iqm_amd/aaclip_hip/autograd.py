@@ -9,6 +9,8 @@ and the visual cross-attention of model/iqm.py:108-139 over those rows): cross_r
 2-row query side (model/adapter.py:186-269, model/iqm.py:572-673) from the final queries back to every parameter it
 reads, to those rows and to the CLS row of the last tap: IqmQueries / iqm_queries, visual_outputs.  That side has no
 forward of its own here: IqmQueries runs the model's (AdaptedCLIP._iqm_branch) with a record of the intermediates.
+iqm_train_form() "folded" selects IqmQueriesFolded instead: the same branch in the folded 16-bit form of inference
+(aaclip_cross_rows_levels on the LayerNorm'ed tap rows), with aaclip_cross_rows_levels_backward behind it.
 Forward and backward are HIP kernels; these classes only carry tensors between them.  The saved tensors live in
 ctx.save_for_backward, so they are freed with the graph (after backward(), or when the output is dropped)."""
 from __future__ import annotations
@@ -51,6 +53,49 @@ def use_backward_precision(mode):
         yield
     finally:
         set_backward_precision(before)
+
+
+# The form the IQM branch TRAINS in (iqm_queries, visual_outputs): "projected" (default: the projected key / value rows
+# of IqmVisualRows + IqmQueries, whatever form inference takes) or "folded" (IqmQueriesFolded: the folded 16-bit form
+# AdaptedCLIP.forward runs at the project's defaults, so that what is trained is what is served).  The environment
+# variable AACLIP_IQM_TRAIN_FORM sets the initial value.
+IQM_TRAIN_FORMS = ("projected", "folded")
+
+
+def iqm_train_form_name(form) -> str:
+    name = str(form).strip().lower()
+    if name not in IQM_TRAIN_FORMS:
+        raise ValueError(f"unknown IQM train form {form!r}: one of {IQM_TRAIN_FORMS}")
+    return name
+
+
+def iqm_train_form_from_env(environ=os.environ) -> str:
+    """AACLIP_IQM_TRAIN_FORM: unset or empty = projected; an unknown value raises ValueError"""
+    return iqm_train_form_name(environ.get("AACLIP_IQM_TRAIN_FORM") or "projected")
+
+
+_iqm_train_form = iqm_train_form_from_env()
+
+
+def iqm_train_form() -> str:
+    return _iqm_train_form
+
+
+def set_iqm_train_form(form) -> None:
+    global _iqm_train_form
+    _iqm_train_form = iqm_train_form_name(form)
+
+
+@contextlib.contextmanager
+def use_iqm_train_form(form):
+    """with use_iqm_train_form("folded"): the graphs BUILT inside train the IQM branch in that form; the previous form
+    is restored on exit."""
+    before = iqm_train_form()
+    set_iqm_train_form(form)
+    try:
+        yield
+    finally:
+        set_iqm_train_form(before)
 
 
 class SimilarityMapTrain(torch.autograd.Function):
@@ -268,34 +313,41 @@ class TapHead(torch.autograd.Function):
 
     forward(model, tap [B, L, D], seg_proj weight, det_proj weight or None) -> seg [B, L-1, E], or (seg, det [B, E])
     with a det weight: exactly engine.tap_head at the model's precision, so the outputs do not depend on whether
-    gradients are on.  Saved: the tap (the VisualTaps output itself, no copy) and the weights.  The backward is
+    gradients are on.  A fifth argument keep_rows = True appends ln_post(tap) in the tower's 16-bit layout
+    (engine.tap_head(keep_rows=True): what the folded IQM branch reads), marked non-differentiable.  Saved: the tap (the VisualTaps output itself, no copy) and the weights.  The backward is
     engine.tap_head_backward, fp32 whatever precision the forward ran in, recomputing the head from the tap; an output
     the loss does not read contributes nothing (its part is skipped), and a tap without a graph skips the
     input-gradient products."""
 
     @staticmethod
-    def forward(ctx, model, tap, proj_weight, det_weight):
+    def forward(ctx, model, tap, proj_weight, det_weight, keep_rows=False):
         B, L, D = tap.shape
-        seg, det = engine.tap_head(tap.reshape(B * L, D), model.image_encoder.ln_post, proj_weight, model.relu, B, L,
-                                   model._code(), det_weight=det_weight)
-        ctx.model = model
+        res = engine.tap_head(tap.reshape(B * L, D), model.image_encoder.ln_post, proj_weight, model.relu, B, L,
+                              model._code(), det_weight=det_weight, keep_rows=bool(keep_rows))
+        ctx.model, ctx.has_det = model, det_weight is not None
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(tap, proj_weight, det_weight)
-        return seg if det is None else (seg, det)
+        outs = (res[0],) + ((res[1],) if ctx.has_det else ())
+        if keep_rows:                 # ln_post(tap) as the head wrote it: a constant for its readers, no gradient
+            ctx.mark_non_differentiable(res[2])
+            outs += (res[2],)
+        return outs[0] if len(outs) == 1 else outs
 
     @staticmethod
-    def backward(ctx, d_seg, d_det=None):
+    def backward(ctx, d_seg, *more):
+        d_det = more[0] if ctx.has_det and more else None
         tap, pw, dw = ctx.saved_tensors
-        _, need_x, need_p, need_d = ctx.needs_input_grad
+        _, need_x, need_p, need_d = ctx.needs_input_grad[:4]
+        flag = (None,) * (len(ctx.needs_input_grad) - 4)          # keep_rows, when it was passed
         if (d_seg is None and d_det is None) or not (need_x or need_p or need_d):
-            return None, None, None, None
+            return (None, None, None, None) + flag
         model = ctx.model
         d_x, d_pw, d_dw = engine.tap_head_backward(
             tap, model.image_encoder.ln_post, pw, _lib.ACT_LEAKY if model.relu else _lib.ACT_NONE, d_seg,
             det_weight=dw if d_det is not None else None, d_det=d_det, need_input_grad=need_x)
         return (None, d_x.view_as(tap).to(tap.dtype) if need_x else None,
                 d_pw.to(pw.dtype) if need_p and d_pw is not None else None,
-                d_dw.to(dw.dtype) if need_d and d_dw is not None else None)
+                d_dw.to(dw.dtype) if need_d and d_dw is not None else None) + flag
 
 
 class CrossRows(torch.autograd.Function):
@@ -411,7 +463,12 @@ def _iqm_param_names(model):
 
 def _iqm_train_check(model):
     """The configurations IqmQueries covers: the last tap is the tower's final stream, and both cross-attentions take
-    the aaclip_cross_rows form of IQM._attend."""
+    the aaclip_cross_rows form of IQM._attend.  With iqm_train_form() "folded" (IqmQueriesFolded) the model's forward
+    must fold as well (AdaptedCLIP.iqm_folds_levels); the text cross-attention keeps its aaclip_cross_rows form."""
+    if iqm_train_form() == "folded" and not model.iqm_folds_levels():
+        raise NotImplementedError("iqm_queries: the IQM train form is \"folded\", but this model's forward does not fold "
+                                  "(AdaptedCLIP.iqm_folds_levels: a 16-bit tower 768 or 1024 wide, no LeakyReLU in "
+                                  "query_adapters, at most 4 tap levels, at most 8 heads)")
     n_blocks = len(model.image_encoder.transformer.resblocks)
     if not model.levels or max(model.levels) != n_blocks:
         raise NotImplementedError("iqm_queries: model.levels must end at the tower's last block (the CLS row of the final "
@@ -446,6 +503,126 @@ def _sum(a, b, c=None):
     return engine.combine3(a, b, c, 1.0, 1.0, 1.0)
 
 
+def _iqm_query_walk(model, names, S, B, Lt, code, wanted, d_out, rows_step):
+    """The backward walk of the IQM branch's 2-row query side, shared by the projected and the folded form: from d_out
+    [B, 2, h] in reverse through AdaptedCLIP._iqm_branch / IQM.forward on the record S, for the parameters `wanted` (a
+    set of the names in `names`).  rows_step(key, d_xbar) -> d_qx is the one step that differs: the visual
+    cross-attention's weighted rows, from the gradient of xbar (the input of visual_feature_proj on the way out) to the
+    gradient of qx (qt times visual_feature_proj's weight on the way in); it keeps the key / value side's gradients to
+    itself.  -> (G: name -> fp32 gradient, d_cls [B, D]: the gradient of the CLS rows of the last tap)."""
+    from ._lib import ACT_GELU, ACT_RELU
+    iqm, h, H = model.iqm, model.iqm_hidden_size, model.iqm.num_attention_heads
+    nq, R, eps = 2, 2 * H, iqm.eps
+    scale = 1.0 / (h // H) ** 0.5
+    need_txt = bool({"text_feature_proj.weight", "text_feature_proj.bias"} & wanted)
+    G = {}
+    buf = {"txt": None}
+
+    def linear_params(name, dz, u):
+        if name + ".weight" in wanted:
+            G[name + ".weight"] = _wgrad(dz, u)
+        if name + ".bias" in wanted:
+            G[name + ".bias"] = engine.bias_grad(dz)
+
+    def ln_bwd(name, ln, x, d_y, e):
+        if name + ".weight" in wanted or name + ".bias" in wanted:
+            G[name + ".weight"], G[name + ".bias"] = engine.layernorm_param_grad(x, d_y, e)
+        return engine.layernorm_backward(x, ln.weight, d_y, eps=e)
+
+    def tail_bwd(name, att, key, hin, d_y):
+        """-> (d of the residual input, d ctx)"""
+        s = engine.combine3(S[key + "dense"], hin, None, 1.0, 1.0, 0.0)
+        d_s = ln_bwd(name + "output.LayerNorm", att.output.LayerNorm, s, d_y, eps)
+        linear_params(name + "output.dense", d_s, S[key + "ctx"])
+        return d_s, _dx(d_s, att.output.dense.weight)
+
+    def self_bwd(name, att, key, hin, d_y):
+        d_h, d_ctx = tail_bwd(name, att, key, hin, d_y)
+        d_q, d_k, d_v = engine.small_attention_backward(S[key + "q"], S[key + "k"], S[key + "v"], d_ctx, B, nq, nq, H)
+        for m, dz in (("query", d_q), ("key", d_k), ("value", d_v)):
+            linear_params(f"{name}attention.{m}", dz, hin)
+        d_h = _sum(d_h, _dx(d_q, att.attention.query.weight), _dx(d_k, att.attention.key.weight))
+        return _sum(d_h, _dx(d_v, att.attention.value.weight))
+
+    def cross_bwd(name, att, key, hin, proj, d_y):
+        d_h, d_ctx = tail_bwd(name, att, key, hin, d_y)
+        d_full = engine.head_expand(d_ctx, H, 1.0, engine.F32)             # the gradient of head_diag
+        linear_params(name + "attention.value", d_full, S[key + "ebar"])
+        d_ebar = _dx(d_full, att.attention.value.weight)
+        qt = S[key + "qt"]
+        if proj is not None:
+            pname = "visual_feature_proj"
+            if pname + ".weight" in wanted:                                # ebar = xbar P^T + b_p
+                G.setdefault(pname + ".weight", []).append(_wgrad(d_ebar, S[key + "xbar"]))
+            if pname + ".bias" in wanted:
+                G.setdefault(pname + ".bias", []).append(engine.bias_grad(d_ebar))
+            d_qx = rows_step(key, _dx(d_ebar, proj.weight))
+            if pname + ".weight" in wanted:                                # qx = qt P
+                G[pname + ".weight"].append(_wgrad(qt, d_qx))
+            d_qt = _dx_t(d_qx, proj.weight)
+        else:
+            d_qt, buf["txt"] = engine.cross_rows_backward(qt, S["txt"], d_ebar, B, R, Lt, code, need_x=need_txt,
+                                                          d_x=buf["txt"])
+        kname = name + "attention.key"
+        if kname + ".weight" in wanted:                                    # qt = qm W_k
+            G[kname + ".weight"] = _wgrad(S[key + "qm"], d_qt)
+        if kname + ".bias" in wanted:                                      # softmax-invariant
+            G[kname + ".bias"] = torch.zeros_like(att.attention.key.bias, dtype=torch.float32)
+        d_qm = _dx_t(d_qt, att.attention.key.weight)
+        d_q = engine.combine3(engine.head_diag(d_qm, H), None, None, scale, 0.0, 0.0)   # the gradient of head_expand
+        linear_params(name + "attention.query", d_q, hin)
+        return _sum(d_h, _dx(d_q, att.attention.query.weight))
+
+    d = engine._f32c(d_out).reshape(B * nq, h)
+    d = ln_bwd("iqm_layer_norm", model.iqm_layer_norm, S["last"], d, model.iqm_layer_norm.eps)
+    vp = model.visual_feature_proj
+    for l in range(len(iqm.encoder.layer) - 1, -1, -1):
+        layer, key, name = iqm.encoder.layer[l], f"{l}.", f"iqm.encoder.layer.{l}."
+        mix, a, c, hin = S[key + "mix"], S[key + "a"], S[key + "c"], S[key + "h"]
+        s = engine.combine3(S[key + "dense"], mix, None, 1.0, 1.0, 0.0)
+        d_s = ln_bwd(name + "output_query.LayerNorm", layer.output_query.LayerNorm, s, d, eps)
+        linear_params(name + "output_query.dense", d_s, S[key + "inter"])
+        d_z = engine.act_backward(ACT_GELU, S[key + "z"], _dx(d_s, layer.output_query.dense.weight), in_place=True)
+        linear_params(name + "intermediate_query.dense", d_z, mix)
+        d_mix = _sum(d_s, _dx(d_z, layer.intermediate_query.dense.weight))
+        d_c = cross_bwd(name + "text_crossattention.", layer.text_crossattention, key + "t.", c, None,
+                        engine.combine3(d_mix, None, None, 0.3, 0.0, 0.0))
+        d_a = cross_bwd(name + "crossattention.", layer.crossattention, key + "c.", a, vp,
+                        engine.combine3(d_mix, d_c, None, 0.3, 1.0, 0.0))
+        d = self_bwd(name + "attention.", layer.attention, key + "a.", hin,
+                     engine.combine3(d_mix, d_a, None, 0.4, 1.0, 0.0))
+    d_query = ln_bwd("iqm.layernorm", iqm.layernorm, S["query"].reshape(B * nq, h), d, eps)
+    if "pos_embedding" in wanted:
+        g = torch.zeros_like(model.pos_embedding, dtype=torch.float32)
+        g[:, :2, :] = engine.bias_grad(d_query.view(B, 2 * h)).view(1, 2, h)
+        G["pos_embedding"] = g
+    dq3 = d_query.view(B, 2, h)
+    d_cq = _sum(dq3[:, 0, :].contiguous(), dq3[:, 1, :].contiguous())
+    m0, m2 = model.class_query_mlp[0], model.class_query_mlp[2]
+    linear_params("class_query_mlp.2", d_cq, S["t1"])
+    d_z1 = engine.act_backward(ACT_RELU, S["t1"], _dx(d_cq, m2.weight), in_place=True)
+    linear_params("class_query_mlp.0", d_z1, S["cls"])
+    if need_txt:
+        d_w, d_b = engine.linear_smallk_backward(S["te"], buf["txt"])
+        G["text_feature_proj.weight"], G["text_feature_proj.bias"] = d_w, d_b
+    for n in ("visual_feature_proj.weight", "visual_feature_proj.bias"):   # fixed order: layer by layer, last first
+        if G.get(n):
+            G[n] = _sum_in_order(G[n])
+    return G, (lambda: _dx(d_z1, m0.weight))
+
+
+def _sum_in_order(parts):
+    total = parts[0]
+    for p in parts[1:]:
+        total = _sum(total, p)
+    return total
+
+
+def _param_grads(model, names, wanted, G):
+    params = dict(model.named_parameters())
+    return [G[n].view_as(params[n]).to(params[n].dtype) if n in wanted else None for n in names]
+
+
 class IqmQueries(torch.autograd.Function):
     """The query side of the IQM branch in its projected form with a backward:
     forward(model, rows, tap, anchors, *parameters named by _iqm_param_names) -> final queries [B, 2, h].
@@ -475,124 +652,111 @@ class IqmQueries(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_out):
-        from ._lib import ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_RELU
+        from ._lib import ACT_LEAKY, ACT_NONE
         model, names = ctx.model, ctx.names
         B, L, Lv, Lt, code = ctx.dims
         S = dict(zip(ctx.keys, ctx.saved_tensors))
-        iqm, h, H = model.iqm, model.iqm_hidden_size, model.iqm.num_attention_heads
-        nq, R, eps = 2, 2 * H, iqm.eps
-        scale = 1.0 / (h // H) ** 0.5
+        R = 2 * model.iqm.num_attention_heads
         wanted = {n for i, n in enumerate(names) if ctx.needs_input_grad[4 + i]}
         need_rows, need_tap = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        need_txt = bool({"text_feature_proj.weight", "text_feature_proj.bias"} & wanted)
-        G = {}
-        buf = {"rows": None, "txt": None}
+        act = ACT_LEAKY if model.relu else ACT_NONE
+        buf = {"rows": None}
 
-        def linear_params(name, dz, u):
-            if name + ".weight" in wanted:
-                G[name + ".weight"] = _wgrad(dz, u)
-            if name + ".bias" in wanted:
-                G[name + ".bias"] = engine.bias_grad(dz)
+        def rows_step(key, d_xbar):
+            d_qx, buf["rows"] = engine.cross_rows_backward(S[key + "qx"], S["vis"], d_xbar, B, R, Lv, code, act=act,
+                                                           need_x=need_rows, d_x=buf["rows"])
+            return d_qx
 
-        def ln_bwd(name, ln, x, d_y, e):
-            if name + ".weight" in wanted or name + ".bias" in wanted:
-                G[name + ".weight"], G[name + ".bias"] = engine.layernorm_param_grad(x, d_y, e)
-            return engine.layernorm_backward(x, ln.weight, d_y, eps=e)
-
-        def tail_bwd(name, att, key, hin, d_y):
-            """-> (d of the residual input, d ctx)"""
-            s = engine.combine3(S[key + "dense"], hin, None, 1.0, 1.0, 0.0)
-            d_s = ln_bwd(name + "output.LayerNorm", att.output.LayerNorm, s, d_y, eps)
-            linear_params(name + "output.dense", d_s, S[key + "ctx"])
-            return d_s, _dx(d_s, att.output.dense.weight)
-
-        def self_bwd(name, att, key, hin, d_y):
-            d_h, d_ctx = tail_bwd(name, att, key, hin, d_y)
-            d_q, d_k, d_v = engine.small_attention_backward(S[key + "q"], S[key + "k"], S[key + "v"], d_ctx, B, nq, nq, H)
-            for m, dz in (("query", d_q), ("key", d_k), ("value", d_v)):
-                linear_params(f"{name}attention.{m}", dz, hin)
-            d_h = _sum(d_h, _dx(d_q, att.attention.query.weight), _dx(d_k, att.attention.key.weight))
-            return _sum(d_h, _dx(d_v, att.attention.value.weight))
-
-        def cross_bwd(name, att, key, hin, proj, d_y):
-            d_h, d_ctx = tail_bwd(name, att, key, hin, d_y)
-            d_full = engine.head_expand(d_ctx, H, 1.0, engine.F32)             # the gradient of head_diag
-            linear_params(name + "attention.value", d_full, S[key + "ebar"])
-            d_ebar = _dx(d_full, att.attention.value.weight)
-            qt = S[key + "qt"]
-            if proj is not None:
-                pname = "visual_feature_proj"
-                if pname + ".weight" in wanted:                                # ebar = xbar P^T + b_p
-                    G.setdefault(pname + ".weight", []).append(_wgrad(d_ebar, S[key + "xbar"]))
-                if pname + ".bias" in wanted:
-                    G.setdefault(pname + ".bias", []).append(engine.bias_grad(d_ebar))
-                d_xbar = _dx(d_ebar, proj.weight)
-                act = ACT_LEAKY if model.relu else ACT_NONE
-                d_qx, buf["rows"] = engine.cross_rows_backward(S[key + "qx"], S["vis"], d_xbar, B, R, Lv, code, act=act,
-                                                               need_x=need_rows, d_x=buf["rows"])
-                if pname + ".weight" in wanted:                                # qx = qt P
-                    G[pname + ".weight"].append(_wgrad(qt, d_qx))
-                d_qt = _dx_t(d_qx, proj.weight)
-            else:
-                d_qt, buf["txt"] = engine.cross_rows_backward(qt, S["txt"], d_ebar, B, R, Lt, code, need_x=need_txt,
-                                                              d_x=buf["txt"])
-            kname = name + "attention.key"
-            if kname + ".weight" in wanted:                                    # qt = qm W_k
-                G[kname + ".weight"] = _wgrad(S[key + "qm"], d_qt)
-            if kname + ".bias" in wanted:                                      # softmax-invariant
-                G[kname + ".bias"] = torch.zeros_like(att.attention.key.bias, dtype=torch.float32)
-            d_qm = _dx_t(d_qt, att.attention.key.weight)
-            d_q = engine.combine3(engine.head_diag(d_qm, H), None, None, scale, 0.0, 0.0)   # the gradient of head_expand
-            linear_params(name + "attention.query", d_q, hin)
-            return _sum(d_h, _dx(d_q, att.attention.query.weight))
-
-        d = engine._f32c(d_out).reshape(B * nq, h)
-        d = ln_bwd("iqm_layer_norm", model.iqm_layer_norm, S["last"], d, model.iqm_layer_norm.eps)
-        vp = model.visual_feature_proj
-        for l in range(len(iqm.encoder.layer) - 1, -1, -1):
-            layer, key, name = iqm.encoder.layer[l], f"{l}.", f"iqm.encoder.layer.{l}."
-            mix, a, c, hin = S[key + "mix"], S[key + "a"], S[key + "c"], S[key + "h"]
-            s = engine.combine3(S[key + "dense"], mix, None, 1.0, 1.0, 0.0)
-            d_s = ln_bwd(name + "output_query.LayerNorm", layer.output_query.LayerNorm, s, d, eps)
-            linear_params(name + "output_query.dense", d_s, S[key + "inter"])
-            d_z = engine.act_backward(ACT_GELU, S[key + "z"], _dx(d_s, layer.output_query.dense.weight), in_place=True)
-            linear_params(name + "intermediate_query.dense", d_z, mix)
-            d_mix = _sum(d_s, _dx(d_z, layer.intermediate_query.dense.weight))
-            d_c = cross_bwd(name + "text_crossattention.", layer.text_crossattention, key + "t.", c, None,
-                            engine.combine3(d_mix, None, None, 0.3, 0.0, 0.0))
-            d_a = cross_bwd(name + "crossattention.", layer.crossattention, key + "c.", a, vp,
-                            engine.combine3(d_mix, d_c, None, 0.3, 1.0, 0.0))
-            d = self_bwd(name + "attention.", layer.attention, key + "a.", hin,
-                         engine.combine3(d_mix, d_a, None, 0.4, 1.0, 0.0))
-        d_query = ln_bwd("iqm.layernorm", iqm.layernorm, S["query"].reshape(B * nq, h), d, eps)
-        if "pos_embedding" in wanted:
-            g = torch.zeros_like(model.pos_embedding, dtype=torch.float32)
-            g[:, :2, :] = engine.bias_grad(d_query.view(B, 2 * h)).view(1, 2, h)
-            G["pos_embedding"] = g
-        dq3 = d_query.view(B, 2, h)
-        d_cq = _sum(dq3[:, 0, :].contiguous(), dq3[:, 1, :].contiguous())
-        m0, m2 = model.class_query_mlp[0], model.class_query_mlp[2]
-        linear_params("class_query_mlp.2", d_cq, S["t1"])
-        d_z1 = engine.act_backward(ACT_RELU, S["t1"], _dx(d_cq, m2.weight), in_place=True)
-        linear_params("class_query_mlp.0", d_z1, S["cls"])
+        G, d_cls = _iqm_query_walk(model, names, S, B, Lt, code, wanted, d_out, rows_step)
         d_tap = None
         if need_tap:
-            d_tap = torch.zeros(B, L, m0.weight.shape[1], dtype=torch.float32, device=d.device)
-            d_tap[:, 0, :] = _dx(d_z1, m0.weight)
-        if need_txt:
-            d_w, d_b = engine.linear_smallk_backward(S["te"], buf["txt"])
-            G["text_feature_proj.weight"], G["text_feature_proj.bias"] = d_w, d_b
-        for n in ("visual_feature_proj.weight", "visual_feature_proj.bias"):   # fixed order: layer by layer, last first
-            parts = G.get(n)
-            if parts:
-                total = parts[0]
-                for p in parts[1:]:
-                    total = _sum(total, p)
-                G[n] = total
-        params = dict(model.named_parameters())
-        grads = [G[n].view_as(params[n]).to(params[n].dtype) if n in wanted else None for n in names]
+            d_tap = torch.zeros(B, L, model.class_query_mlp[0].weight.shape[1], dtype=torch.float32, device=d_out.device)
+            d_tap[:, 0, :] = d_cls()
         d_rows = buf["rows"].view(B, Lv, -1) if need_rows else None
-        return (None, d_rows, d_tap, None, *grads)
+        return (None, d_rows, d_tap, None, *_param_grads(model, names, wanted, G))
+
+
+class IqmQueriesFolded(torch.autograd.Function):
+    """The IQM branch in the folded 16-bit form AdaptedCLIP.forward runs at the project's defaults, with a backward:
+    forward(model, n, anchors, *taps, *rows, *query_adapters weights, *parameters named by _iqm_param_names) -> final
+    queries [B, 2, h].  taps: the n tap streams [B, L, D] (visual_taps); rows: ln_post of them in the tower's 16-bit
+    layout, the very buffers engine.tap_head(keep_rows=True) wrote (constants here: their gradient is returned for the
+    taps).  The forward IS the model's: AdaptedCLIP._iqm_levels and _iqm_branch(..., levels, record=S), so the queries
+    are AdaptedCLIP.forward's bits.  Saved: the record (IQM.forward lists its keys: 2-row and [2 B H, .] intermediates),
+    the taps, the rows and the weights -- nothing of size Lk x D is added to what the heads keep anyway.
+    The backward runs in fp32 on the 16-bit row values as they are (other 16-bit casts count as the identity): the
+    query-side walk of IqmQueries with the visual cross-attention's step replaced by
+        d_xbar -> d tbar = d_xbar W_out,  d W_qa[s] += d_xbar^T tbar[., s]        (xbar = sum_s tbar[., s] W_qa[s]^T)
+        aaclip_cross_rows_levels_backward -> d_u and, accumulated over the layers, d ln rows per level
+        d W_qa[s] += qx^T d_u[., s],  d_qx = sum_s d_u[., s] W_qa[s]^T           (u[., s] = qx W_qa[s])
+    and d tap[k] = aaclip_layernorm_backward of ln_post on the d ln rows (CLS rows exactly zero; the last tap's CLS rows
+    then take class_query_mlp's share).  Sums over layers and roles run in a fixed order: last layer first, and within a
+    layer the way out (xbar) before the way in (u)."""
+
+    @staticmethod
+    def forward(ctx, model, n, anchors, *tensors):
+        taps, rows, qa = tensors[:n], tensors[n:2 * n], tensors[2 * n:3 * n]
+        code = engine.plain_code(model._code())
+        B, L, _ = taps[0].shape
+        if anchors.dim() != 3 or anchors.shape[0] != B or anchors.shape[-1] != 2:
+            raise NotImplementedError("iqm_queries: text_embeddings must be [B, 768, 2]")
+        levels = model._iqm_levels([r.detach() for r in rows], L, code)
+        S = {}
+        out = model._iqm_branch(taps[-1].detach(), None, anchors.detach(), B, L, code, levels=levels, record=S)
+        S.pop("vis")                                     # the levels dict: its row buffers are saved below
+        ctx.model, ctx.n, ctx.keys, ctx.dims = model, n, list(S), (B, L, anchors.shape[1], code)
+        ctx.names = _iqm_param_names(model)
+        ctx.save_for_backward(*S.values(), *taps, *rows, *qa)
+        return out.last_hidden_state
+
+    @staticmethod
+    def backward(ctx, d_out):
+        model, names, n = ctx.model, ctx.names, ctx.n
+        B, L, Lt, code = ctx.dims
+        saved = ctx.saved_tensors
+        nk = len(ctx.keys)
+        S = dict(zip(ctx.keys, saved[:nk]))
+        taps, rows, qa = saved[nk:nk + n], saved[nk + n:nk + 2 * n], saved[nk + 2 * n:nk + 3 * n]
+        R = 2 * model.iqm.num_attention_heads
+        D, h = qa[0].shape[1], qa[0].shape[0]
+        need_taps = [ctx.needs_input_grad[3 + k] for k in range(n)]
+        need_qa = [ctx.needs_input_grad[3 + 2 * n + k] for k in range(n)]
+        wanted = {nm for i, nm in enumerate(names) if ctx.needs_input_grad[3 + 3 * n + i]}
+        w_in = torch.cat([w.detach().float().t() for w in qa], 0).contiguous()           # [n*D, h]
+        w_out = torch.cat([w.detach().float() for w in qa], 1).contiguous()              # [h, n*D]
+        d_ln = None                                                                      # per level [B*L, D]
+        parts = [[] for _ in range(n)]
+
+        def rows_step(key, d_xbar):
+            nonlocal d_ln
+            M = d_xbar.shape[0]
+            tbar, qx = S[key + "tbar"], S[key + "qx"]
+            for k in range(n):
+                if need_qa[k]:
+                    parts[k].append(_wgrad(d_xbar, tbar[:, k * D:(k + 1) * D]))
+            d_tbar = torch.empty(M, n * D, dtype=torch.float32, device=d_xbar.device)
+            engine.gemm(engine.F32, _lib.EPI_ACT_F32, d_xbar, w_in, None, d_tbar)
+            d_u, d_ln = engine.cross_rows_levels_backward(S[key + "u"], list(rows), d_tbar, B, R, L, 1, L - 1, D,
+                                                          need_x=any(need_taps), d_x=d_ln)
+            for k in range(n):
+                if need_qa[k]:
+                    parts[k].append(_wgrad(qx, d_u[:, k * D:(k + 1) * D]))
+            d_qx = torch.empty(M, h, dtype=torch.float32, device=d_xbar.device)
+            return engine.gemm(engine.F32, _lib.EPI_ACT_F32, d_u, w_out, None, d_qx)
+
+        G, d_cls = _iqm_query_walk(model, names, S, B, Lt, code, wanted, d_out, rows_step)
+        ln_post = model.image_encoder.ln_post
+        d_taps = [None] * n
+        for k in range(n):
+            if need_taps[k]:
+                tap32 = engine._f32c(taps[k]).reshape(B * L, D)
+                d_tap = engine.layernorm_backward(tap32, ln_post.weight, d_ln[k]).view(B, L, D)
+                d_tap[:, 0, :] = 0.0
+                if k == n - 1:
+                    d_tap[:, 0, :] = d_cls()
+                d_taps[k] = d_tap.to(taps[k].dtype)
+        d_qa = [_sum_in_order(parts[k]).to(qa[k].dtype) if need_qa[k] else None for k in range(n)]
+        return (None, None, None, *d_taps, *([None] * n), *d_qa, *_param_grads(model, names, wanted, G))
 
 
 def visual_taps(model, image):
@@ -603,43 +767,64 @@ def visual_taps(model, image):
     return list(VisualTaps.apply(model, image, *[m.weight for m in model.image_adapter["layer_adapters"]]))
 
 
-def visual_heads(model, image, taps=None):
+def visual_heads(model, image, taps=None, keep_rows=False):
     """AdaptedCLIP.forward(image)[:2] with a graph -> (seg_tokens: one [B, L-1, E] tensor of unit rows per tap level,
     det_token [B, E]): visual_taps, then one TapHead per level with the det head on the last one, paired as the forward
     pairs them and bit-identical to it.  The graph reaches image_adapter["layer_adapters"][i].weight, ["seg_proj"][k]
     and ["det_proj"], whichever of them require grad.  taps: the streams of a visual_taps(model, image) call the caller
-    has already made (visual_outputs shares them with the IQM branch); None computes them here."""
+    has already made (visual_outputs shares them with the IQM branch); None computes them here.
+    keep_rows: -> (seg_tokens, det_token, rows) with rows[k] = ln_post(tap k) as the head wrote it in the tower's 16-bit
+    layout (engine.tap_head(keep_rows=True)): what the folded IQM branch reads, without a second pass over the taps."""
     seg_proj = model.image_adapter["seg_proj"]
     det_weight = model.image_adapter["det_proj"].weight
-    seg_tokens, det_token = [], None
+    seg_tokens, det_token, rows = [], None, []
     for k, tap in enumerate(visual_taps(model, image) if taps is None else taps):
-        if k == len(model.levels) - 1:
-            seg, det_token = TapHead.apply(model, tap, seg_proj[k].weight, det_weight)
-        else:
-            seg = TapHead.apply(model, tap, seg_proj[k].weight, None)
-        seg_tokens.append(seg)
-    return seg_tokens, det_token
+        last = k == len(model.levels) - 1
+        res = TapHead.apply(model, tap, seg_proj[k].weight, det_weight if last else None, *([True] if keep_rows else []))
+        res = res if isinstance(res, tuple) else (res,)
+        seg_tokens.append(res[0])
+        if last:
+            det_token = res[1]
+        if keep_rows:
+            rows.append(res[-1])
+    return (seg_tokens, det_token, rows) if keep_rows else (seg_tokens, det_token)
 
 
-def iqm_queries(model, taps, anchors):
+def iqm_queries(model, taps, anchors, rows=None):
     """The IQM branch's final queries [B, 2, h] = AdaptedCLIP.forward(image, anchors)[2].last_hidden_state, with a graph
     to every parameter the branch reads (model.iqm, class_query_mlp, visual_feature_proj, text_feature_proj,
     iqm_layer_norm, pos_embedding[:, :2]), to query_adapters and, through the taps [B, L, D] (from visual_taps), to
     layer_adapters: iqm_visual_rows for the key / value rows, IqmQueries for the 2-row query side.  The anchors
     [B, 768, 2] take no gradient.  NotImplementedError (before any launch): model.levels does not end at the tower's
-    last block, or a configuration outside the aaclip_cross_rows form (see _iqm_train_check)."""
+    last block, or a configuration outside the aaclip_cross_rows form (see _iqm_train_check).
+    With iqm_train_form() "folded" the branch runs and trains in the folded 16-bit form of AdaptedCLIP.forward
+    (IqmQueriesFolded) -- same destinations, same bits as inference; NotImplementedError before any launch when the
+    model's forward does not fold.  rows (folded form only): ln_post of the taps as visual_heads(keep_rows=True)
+    returned them; None runs engine.tap_head(keep_rows=True) on the taps here."""
     _iqm_train_check(model)
     taps = list(taps)
-    rows = iqm_visual_rows(model, taps, pre_activation_grad=model.relu)
     params = dict(model.named_parameters())
+    if iqm_train_form() == "folded":
+        if rows is None:
+            B, L, D = taps[0].shape
+            rows = [engine.tap_head(t.detach().reshape(B * L, D), model.image_encoder.ln_post, sp.weight, model.relu, B,
+                                    L, model._code(), keep_rows=True)[2]
+                    for t, sp in zip(taps, model.image_adapter["seg_proj"])]
+        return IqmQueriesFolded.apply(model, len(taps), anchors, *taps, *rows, *[m.weight for m in model.query_adapters],
+                                      *[params[n] for n in _iqm_param_names(model)])
+    rows = iqm_visual_rows(model, taps, pre_activation_grad=model.relu)
     return IqmQueries.apply(model, rows, taps[-1], anchors, *[params[n] for n in _iqm_param_names(model)])
 
 
 def visual_outputs(model, image, anchors):
     """AdaptedCLIP.forward(image, text_embeddings=anchors) with a graph -> (seg_tokens, det_token, queries [B, 2, h])
-    from ONE visual_taps call: visual_heads and iqm_queries on the same tap streams."""
+    from ONE visual_taps call: visual_heads and iqm_queries on the same tap streams.  In the folded train form the
+    branch reads the LayerNorm'ed rows the heads wrote: neither the tower nor the heads run twice."""
     _iqm_train_check(model)
     taps = visual_taps(model, image)
+    if iqm_train_form() == "folded":
+        seg_tokens, det_token, rows = visual_heads(model, image, taps=taps, keep_rows=True)
+        return seg_tokens, det_token, iqm_queries(model, taps, anchors, rows=rows)
     seg_tokens, det_token = visual_heads(model, image, taps=taps)
     return seg_tokens, det_token, iqm_queries(model, taps, anchors)
 

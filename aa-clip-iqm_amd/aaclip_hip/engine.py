@@ -1154,14 +1154,9 @@ def cross_rows_levels(qt: torch.Tensor, levels, B: int, R: int, rows_per_image: 
     require_gpu(qt, "cross_rows_levels")
     lib = _lib.load()
     nseg = len(levels)
-    x0 = levels[0]
-    if x0.dtype == torch.uint8:
-        xc, ldx = _lib.F16, x0.shape[1] // 2
-    else:
-        xc, ldx = {torch.float16: F16, torch.bfloat16: BF16}[x0.dtype], x0.shape[1]
-    for x in levels:
-        if x.dtype != x0.dtype or x.shape != x0.shape or not x.is_contiguous() or x.device != qt.device:
-            raise ValueError("cross_rows_levels: the level buffers must agree in dtype, shape and device")
+    xc, ldx = _level_rows(levels, "cross_rows_levels")
+    if levels[0].device != qt.device:
+        raise ValueError("cross_rows_levels: the level buffers must agree in dtype, shape and device")
     if qt.shape != (B * R, nseg * Dk) or qt.dtype != torch.float32 or not qt.is_contiguous():
         raise ValueError("cross_rows_levels: qt must be contiguous fp32 [B*R, nseg*Dk]")
     ptrs = (C.c_void_p * nseg)(*[x.data_ptr() for x in levels])
@@ -1170,6 +1165,59 @@ def cross_rows_levels(qt: torch.Tensor, levels, B: int, R: int, rows_per_image: 
     _lib.check(lib.aaclip_cross_rows_levels(xc, qt.data_ptr(), ptrs, nseg, out.data_ptr(), B, R, rows_per_image, row0, Lk,
                                             Dk, ldx, ws.data_ptr(), ws.numel(), _stream(qt.device)), "cross_rows_levels")
     return out
+
+
+def _level_rows(levels, what: str):
+    """-> (x dtype code, row stride in elements) of the level buffers of cross_rows_levels: fp16 / bf16 rows, or uint8
+    split8 rows whose fp16 halves are read"""
+    x0 = levels[0]
+    if x0.dtype == torch.uint8:
+        xc, ldx = _lib.F16, x0.shape[1] // 2
+    elif x0.dtype in (torch.float16, torch.bfloat16):
+        xc, ldx = {torch.float16: F16, torch.bfloat16: BF16}[x0.dtype], x0.shape[1]
+    else:
+        raise ValueError(f"{what}: the level buffers must be fp16, bf16 or uint8 split8 rows")
+    for x in levels:
+        if x.dtype != x0.dtype or x.shape != x0.shape or not x.is_contiguous() or x.device != x0.device:
+            raise ValueError(f"{what}: the level buffers must agree in dtype, shape and device")
+    return xc, ldx
+
+
+def cross_rows_levels_backward(qt: torch.Tensor, levels, d_out: torch.Tensor, B: int, R: int, rows_per_image: int,
+                               row0: int, Lk: int, Dk: int, need_qt: bool = True, need_x: bool = True, d_x=None,
+                               overwrite: bool = False):
+    """Backward of cross_rows_levels from d_out [B*R, nseg*Dk] -> (d qt fp32 [B*R, nseg*Dk] or None, d x: a list of fp32
+    [B*rows_per_image, Dk] per level or None): aaclip_cross_rows_levels_backward.  qt and levels as the forward took
+    them.  d_x given (a list of contiguous fp32 [B*rows_per_image, Dk]): the gradient is ADDED into its key rows
+    (accumulate; with overwrite it replaces them) and the list is returned; its other rows are left as they are.
+    Buffers made here are zero outside the key rows."""
+    require_gpu(qt, "cross_rows_levels_backward")
+    lib = _lib.load()
+    if not (need_qt or need_x):
+        raise ValueError("cross_rows_levels_backward: nothing to compute")
+    nseg = len(levels)
+    xc, ldx = _level_rows(levels, "cross_rows_levels_backward")
+    rows = levels[0].shape[0]
+    qt, d_out = _f32c(qt), _f32c(d_out)
+    if qt.numel() != B * R * nseg * Dk or d_out.numel() != qt.numel() or rows != B * rows_per_image:
+        raise ValueError("cross_rows_levels_backward: qt and d_out must be [B*R, nseg*Dk], the levels [B*rows_per_image, .]")
+    accumulate = d_x is not None and not overwrite
+    if d_x is not None and (not need_x or len(d_x) != nseg or any(
+            g.dtype != torch.float32 or not g.is_contiguous() or g.shape != (rows, Dk) or g.device != qt.device
+            for g in d_x)):
+        raise ValueError("cross_rows_levels_backward: d_x must be one contiguous fp32 [B*rows_per_image, Dk] per level "
+                         "(and need_x set)")
+    d_qt = torch.empty(B * R, nseg * Dk, dtype=torch.float32, device=qt.device) if need_qt else None
+    if need_x and d_x is None:
+        d_x = [torch.zeros(rows, Dk, dtype=torch.float32, device=qt.device) for _ in range(nseg)]
+    xp = (C.c_void_p * nseg)(*[x.data_ptr() for x in levels])
+    gp = (C.c_void_p * nseg)(*[g.data_ptr() for g in d_x]) if need_x else None
+    ws = Workspace.get(qt.device, lib.aaclip_cross_rows_levels_backward_workspace_bytes(B, R, nseg, Lk, Dk))
+    _lib.check(lib.aaclip_cross_rows_levels_backward(xc, qt.data_ptr(), xp, nseg, d_out.data_ptr(), _ptr(d_qt), gp,
+                                                     int(accumulate), B, R, rows_per_image, row0, Lk, Dk, ldx,
+                                                     ws.data_ptr(), ws.numel(), _stream(qt.device)),
+               "cross_rows_levels_backward")
+    return d_qt, (list(d_x) if need_x else None)
 
 
 def head_expand(q: torch.Tensor, heads: int, scale: float, code: int) -> torch.Tensor:

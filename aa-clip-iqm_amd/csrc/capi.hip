@@ -282,6 +282,31 @@ int aaclip_cross_rows_levels(int x_dtype, const float* qt, const void* const* x,
   return finish("cross_rows_levels");
 }
 
+size_t aaclip_cross_rows_levels_backward_workspace_bytes(int B, int R, int nseg, int Lk, int Dk) {
+  return cross_rows_levels_backward_ws_bytes(B, R, nseg, Lk, Dk);
+}
+
+int aaclip_cross_rows_levels_backward(int x_dtype, const float* qt, const void* const* x, int nseg, const float* d_out,
+                                      float* d_qt, float* const* d_x, int accumulate, int B, int R, int rows_per_image,
+                                      int row0, int Lk, int Dk, long ldx, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(qt && x && d_out && ws, "cross_rows_levels_backward: null pointer");
+  REQUIRE(d_qt || d_x, "cross_rows_levels_backward: nothing to compute (d_qt and d_x are both NULL)");
+  REQUIRE(B > 0 && B <= 65535, "cross_rows_levels_backward: bad batch (1 <= B <= 65535)");
+  if (const char* m = cross_rows_levels_backward_check(x_dtype, R, nseg, Lk, Dk, ldx)) return fail(-1, m);
+  REQUIRE(row0 >= 0 && rows_per_image >= row0 + Lk,
+          "cross_rows_levels_backward: the keys [row0, row0 + Lk) must lie inside an image's rows");
+  REQUIRE((long)rows_per_image * ldx * 2 < (1L << 31), "cross_rows_levels_backward: an image's rows must span < 2 GiB");
+  REQUIRE_ALIGNED16("cross_rows_levels_backward", qt, d_out, d_qt, ws);
+  for (int i = 0; i < nseg; ++i) {
+    REQUIRE(x[i] && ((uintptr_t)x[i] & 15) == 0, "cross_rows_levels_backward: segment pointers must be non-NULL and 16-byte aligned");
+    if (d_x) REQUIRE(d_x[i] && ((uintptr_t)d_x[i] & 15) == 0, "cross_rows_levels_backward: d_x pointers must be non-NULL and 16-byte aligned");
+  }
+  REQUIRE(ws_bytes >= cross_rows_levels_backward_ws_bytes(B, R, nseg, Lk, Dk), "cross_rows_levels_backward: workspace too small");
+  launch_cross_rows_levels_backward(x_dtype, qt, x, nseg, d_out, d_qt, d_x, accumulate, B, R, rows_per_image, row0, Lk, Dk,
+                                    ldx, ws, (hipStream_t)stream);
+  return finish("cross_rows_levels_backward");
+}
+
 int aaclip_head_expand(int dtype, const float* q, void* qm, long rows, int H, int D, float scale, void* stream) {
   REQUIRE(plain_dtype_ok(dtype), "head_expand: bad dtype (fp32, fp16 or bf16)");
   REQUIRE(q && qm && rows > 0 && H > 0 && D > 0 && D % H == 0, "head_expand: bad arguments");

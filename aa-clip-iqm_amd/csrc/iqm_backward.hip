@@ -11,7 +11,8 @@
 //   crb_scores_kernel   SG[b, j, 0:16] = s_.j and SG[b, j, 16:32] = g_.j as ONE [32 keys x Dk] . [Dk x 32] product per
 //                       tile ([qt ; d_out] padded to 16 + 16 columns); each wave sums its quarter of Dk, the four
 //                       quarters are added in wave order through LDS.
-//   crb_stats_kernel    per (b, r): m = max_j s, 1 / sum_j e^(s - m) and delta_r = sum_j p_rj g_rj, read from SG.  One
+//   crb_stats_kernel    (crb_common.h) per (b, r): m = max_j s, 1 / sum_j e^(s - m) and delta_r = sum_j p_rj g_rj,
+//                       read from SG.  One
 //                       workgroup per row reduces over all keys with a fixed tree, so there are no per-slice (m, l)
 //                       partials to merge: SG is Lk x 32 floats per image and stays in L2.  delta comes from the very
 //                       p g products it is subtracted from, not from a forward output.
@@ -22,36 +23,10 @@
 //   crb_combine_kernel  d_qt = the slices' partials added in slice order.
 // No atomics; every output element is written by one thread and summed in a fixed order: two calls give the same bits.
 #include "common.h"
+#include "crb_common.h"
 #include "kernels.h"
 
 namespace aaclip {
-
-namespace {
-
-constexpr float CRB_LOG2E = 1.4426950408889634f;
-
-AACLIP_DEV int crb_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
-AACLIP_DEV float crb_p(float s, float m, float linv) { return __builtin_amdgcn_exp2f((s - m) * CRB_LOG2E) * linv; }
-
-template <typename T> AACLIP_DEV float crb_ld1(const T* p) { return (float)*p; }
-template <typename T> AACLIP_DEV f32x4 crb_ld4(const T* p) {
-  typedef T t4 __attribute__((ext_vector_type(4)));
-  const t4 v = *(const t4*)p;
-  return (f32x4){(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-}
-
-AACLIP_DEV float crb_block_sum(float v, float* red, int tid) {   // fixed tree over the 256 threads
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-}  // namespace
 
 // grid (slices, B).  Column c of the right-hand side: qt row c for c < 16, d_out row c - 16 otherwise (zero past R).
 // The k index of MFMA step 4 c + e in half h is column d0 + 8 c + 4 h + e of the rows: both halves load 16 bytes.
@@ -102,37 +77,6 @@ __global__ __launch_bounds__(256) void crb_scores_kernel(const float* __restrict
       if (key < j1) sg[((long)b * Lk + key) * 32 + (ln & 31)] = v;
     }
     __syncthreads();
-  }
-}
-
-// grid (R, B): stats[(b * 16 + r) * 4 ..] = {max_j s, 1 / sum_j e^(s - max), delta}
-__global__ __launch_bounds__(256) void crb_stats_kernel(const float* __restrict__ sg, float* __restrict__ stats, int Lk) {
-  __shared__ float red[256];
-  const int tid = threadIdx.x;
-  const int q = blockIdx.x, b = blockIdx.y;
-  const float* base = sg + (long)b * Lk * 32 + q;
-  float m = -INFINITY;
-  for (int j = tid; j < Lk; j += 256) m = fmaxf(m, base[(long)j * 32]);
-  __syncthreads();
-  red[tid] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]);
-    __syncthreads();
-  }
-  m = red[0];
-  float l = 0.f;
-  for (int j = tid; j < Lk; j += 256) l += crb_p(base[(long)j * 32], m, 1.0f);
-  l = crb_block_sum(l, red, tid);
-  const float linv = 1.0f / l;
-  float d = 0.f;
-  for (int j = tid; j < Lk; j += 256) d = fmaf(crb_p(base[(long)j * 32], m, linv), base[(long)j * 32 + 16], d);
-  d = crb_block_sum(d, red, tid);
-  if (tid == 0) {
-    float* o = stats + ((long)b * 16 + q) * 4;
-    o[0] = m;
-    o[1] = linv;
-    o[2] = d;
   }
 }
 
@@ -260,7 +204,6 @@ __global__ __launch_bounds__(256) void crb_combine_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int crb_per(int Lk) { return 64 * ((Lk + 64 * CRB_MAX_SLICES - 1) / (64 * CRB_MAX_SLICES)); }
 int cross_rows_backward_slices(int Lk) {
   const int per = crb_per(Lk);
   return (Lk + per - 1) / per;

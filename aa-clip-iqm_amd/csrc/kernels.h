@@ -185,6 +185,14 @@ size_t cross_rows_backward_ws_bytes(int B, int R, int Lk, int Dk);
 void launch_cross_rows_backward(int x_dtype, const float* qt, const void* x, const float* dout, float* d_qt, float* d_x,
                                 int act, int accumulate, int B, int R, int Lk, int Dk, void* ws, hipStream_t s);
 
+// ---- iqm_levels_backward.hip : backward of aaclip_cross_rows_levels (qt, d_out, d_qt [B, R, nseg, Dk]; d_x[s] fp32
+// [B * rows_per_image, Dk]; d_qt or the whole d_x array may be null); a segment's keys are sliced as above
+const char* cross_rows_levels_backward_check(int x_dtype, int R, int nseg, int Lk, int Dk, long ldx);
+size_t cross_rows_levels_backward_ws_bytes(int B, int R, int nseg, int Lk, int Dk);
+void launch_cross_rows_levels_backward(int x_dtype, const float* qt, const void* const* x, int nseg, const float* dout,
+                                       float* d_qt, float* const* d_x, int accumulate, int B, int R, int rows_per_image,
+                                       int row0, int Lk, int Dk, long ldx, void* ws, hipStream_t s);
+
 // ---- iqm_query_backward.hip : backward building blocks of the IQM branch's 2-row query side (fp32, fixed-order sums)
 constexpr int SAB_MAXK = 256;          // keys of small_attention_backward: one per thread
 constexpr int IQB_CHUNK_ROWS = 32;     // rows of a chunk of the column sums, up to IQB_MAX_CHUNKS chunks (then longer ones)

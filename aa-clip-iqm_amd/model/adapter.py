@@ -77,6 +77,20 @@ class AdaptedCLIP(nn.Module):
     def _code(self) -> int:
         return engine.dtype_code(getattr(self.clipmodel, "precision", "fp32"))
 
+    def iqm_folds_levels(self, code=None, width=None) -> bool:
+        """Whether the IQM branch runs its visual cross-attention in the folded form -- the one rule AdaptedCLIP.forward
+        and the training path (aaclip_hip.autograd, iqm_train_form "folded") both ask.  16-bit towers without the
+        LeakyReLU in query_adapters: every step from the LayerNorm'ed tap rows to the keys and values of the IQM
+        cross-attention is linear, so the branch reads those rows as they are (_iqm_levels); otherwise the levels are
+        projected and concatenated like the reference does (_iqm_project_level).  aaclip_cross_rows_levels takes at most
+        4 segments: more tap levels keep the projected form.  code / width: the compute dtype code and the tower width
+        (defaults: the model's own)."""
+        code = self._code() if code is None else code
+        width = self.image_encoder.embed_dim if width is None else width
+        return (not self.relu and code in (engine.F16, engine.BF16, engine.F16X2)
+                and 2 * self.iqm.num_attention_heads <= 16 and width in (768, 1024)
+                and len(self.levels) <= engine.CROSS_ROWS_MAX_SEGMENTS)
+
     # -- reference model/adapter.py:125-135
     def forward_original(self, x, modality="visual"):
         if modality != "visual":
@@ -104,13 +118,7 @@ class AdaptedCLIP(nn.Module):
         icode = engine.plain_code(code)
         dt = engine.torch_dtype(icode)
         P = L - 1
-        # 16-bit towers without the LeakyReLU in query_adapters: every step from the LayerNorm'ed tap rows to the keys and
-        # values of the IQM cross-attention is linear, so the branch reads those rows as they are (_iqm_levels); otherwise
-        # the levels are projected and concatenated like the reference does (_iqm_project_level)
-        # (aaclip_cross_rows_levels takes at most 4 segments: more tap levels keep the projected form)
-        fold_levels = (iqm_on and not self.relu and code in (engine.F16, engine.BF16, engine.F16X2)
-                       and 2 * self.iqm.num_attention_heads <= 16 and xs.shape[-1] in (768, 1024)
-                       and n_levels <= engine.CROSS_ROWS_MAX_SEGMENTS)
+        fold_levels = iqm_on and self.iqm_folds_levels(code, xs.shape[-1])
         ln_rows = []
         vis_cat = (torch.empty(B, n_levels * P, self.iqm_hidden_size, dtype=dt, device=xs.device)
                    if iqm_on and not fold_levels else None)
@@ -174,7 +182,7 @@ class AdaptedCLIP(nn.Module):
         engine.drop_cls_rows(tmp, vis_cat, B, L, k * (L - 1), code)
 
     # -- reference model/adapter.py:186-269.  record: see IQM.forward (a dict collects what the backward needs; the training
-    #    path, autograd.IqmQueries, calls this with one and levels=None)
+    #    path calls this with one: autograd.IqmQueries with levels=None, autograd.IqmQueriesFolded with the levels)
     def _iqm_branch(self, xs, vis_cat, text_embeddings, B, L, code, levels=None, record=None):
         dt = engine.torch_dtype(code)
         h = self.iqm_hidden_size

@@ -15,7 +15,8 @@ cannot be reproduced or checkpointed:
     Linear(2, 768): 2 because the anchors arrive as [B, 768, 2]) that are initialised once and saved with the rest;
   * dropout is the identity.
 There is ONE forward: the training path (aaclip_hip.autograd.iqm_queries) runs this same code with a `record` dict that
-collects what its backward needs (IQM.forward lists the keys), so inference and training cannot drift apart.
+collects what its backward needs (IQM.forward lists the keys), so inference and training cannot drift apart -- in the
+projected form and in the folded 16-bit form of the visual cross-attention alike.
 The modules below are parameter containers: every product runs on the library's MFMA GEMM, the rest on the small
 kernels of csrc/iqm.hip (aaclip_small_attention, aaclip_residual_layernorm, ...).
 """
@@ -120,6 +121,12 @@ class IQM(nn.Module):
         R = nq * self.num_attention_heads
         return R % 4 == 0 and R <= 16 and width in (256, 512, 768, 1024)
 
+    def levels_form_has_backward(self, nq: int, levels: dict) -> bool:
+        """Whether a record of the folded form (encoder_levels) has a backward: the domain of
+        aaclip_cross_rows_levels_backward -- queries x heads in {4, 8, 12, 16}, rows 768 or 1024 wide, 1..4 levels."""
+        R = nq * self.num_attention_heads
+        return R % 4 == 0 and R <= 16 and levels["width"] in (768, 1024) and 1 <= len(levels["rows"]) <= 4
+
     def _tail(self, att: _Attention, h: torch.Tensor, code: int, ebar=None, ctx=None, record=None, key: str = ""):
         """The end of one IQM_Attention: ctx [B*nq, D] as it is, or the value product of the probability-weighted rows
         ebar [B*nq*H, Dk] and its head-diagonal blocks; then output.dense and LayerNorm(. + h)."""
@@ -141,10 +148,10 @@ class IQM(nn.Module):
         dt = engine.torch_dtype(code)
         D, H = self.hidden_size, self.num_attention_heads
         rows_form = enc_levels is None and enc is not None and self.cross_rows_form(nq, enc.shape[-1])
-        if record is not None and not rows_form and (enc is not None or enc_levels is not None):
-            raise NotImplementedError("IQM: a record covers the self-attention and the aaclip_cross_rows form of the "
-                                      "cross-attentions (queries x heads in {4, 8, 12, 16}, row widths 256 / 512 / 768 / "
-                                      "1024), not the folded levels and not the small_attention path")
+        if record is not None and not rows_form and enc is not None:
+            raise NotImplementedError("IQM: a record covers the self-attention, the folded levels and the aaclip_cross_rows "
+                                      "form of the cross-attentions (queries x heads in {4, 8, 12, 16}, row widths 256 / "
+                                      "512 / 768 / 1024), not the small_attention path")
         hq = h.to(dt)                                      # [B*nq, D]: 2 rows per image
         q = linear_f32(code, hq, att.attention.query.weight, att.attention.query.bias)
         if enc_levels is not None or rows_form:
@@ -165,7 +172,9 @@ class IQM(nn.Module):
             tbar = engine.cross_rows_levels(u, lv["rows"], B, nq * H, lv["rows_per_image"], lv["row0"], lv["keys"], Dk)
             xbar = torch.empty(B * nq * H, pw.shape[1], dtype=torch.float32, device=h.device)
             engine.gemm(code, EPI_ACT_F32, tbar.to(dt), lv["w_out"], None, xbar)  # sum_s W_qa[s] tbar[., s]
-            return self._tail(att, h, code, ebar=linear_f32(code, xbar.to(dt), pw, pb))
+            if record is not None:
+                record.update({key + "qx": qx, key + "u": u, key + "tbar": tbar, key + "xbar": xbar})
+            return self._tail(att, h, code, ebar=linear_f32(code, xbar.to(dt), pw, pb), record=record, key=key)
         if rows_form:
             # cross-attention over MANY rows for a handful of queries: W_k moves to the query side and W_v behind the
             # probability-weighted sum of the raw rows (include/aaclip.h, aaclip_cross_rows): the reference's key /
@@ -213,7 +222,8 @@ class IQM(nn.Module):
         aaclip_hip.autograd.IqmQueries, saves its values), and the forward is the same launches plus, per layer, the one
         EPI_ACT_F32 product of the pre-GELU rows.  Every entry is fp32 (16-bit results are stored as fp32 copies)
         except `vis` and `txt`.  The keys, with l the layer index:
-          vis, txt               the key / value rows [B*Lv, D] and [B*Lt, Dt] as the cross-attentions read them
+          vis, txt               the key / value rows [B*Lv, D] and [B*Lt, Dt] as the cross-attentions read them; with
+                                 encoder_levels, vis is that dict itself (its row buffers are what the kernel read)
           last                   the encoder output [B*nq, D]
           {l}.h  .a  .c  .mix    the layer's input, the outputs of the self- and the visual cross-attention, the fusion
           {l}.z  .inter  .dense  the feed-forward: pre-GELU rows, GELU output, output_query.dense
@@ -222,11 +232,17 @@ class IQM(nn.Module):
             q, k, v              the self-attention's projections
             qm, qt, ebar         both cross-attentions: the head-expanded queries, those times W_k, the weighted rows
             qx, xbar             the visual one: qt times encoder_proj's weight, the weighted raw rows
+            u, tbar              the visual one with encoder_levels: qx times the query_adapters weights [B*nq*H,
+                                 levels*Dk] and the weighted tap rows per level (xbar is then their sum through w_out)
         AdaptedCLIP._iqm_branch adds cls, t1, query and te (the CLS rows, class_query_mlp's hidden rows, query_embeds,
-        the anchors).  Only the self-attention and the aaclip_cross_rows form have a backward: with a record,
-        encoder_levels or a cross-attention outside cross_rows_form raises NotImplementedError."""
-        if record is not None and encoder_levels is not None:
-            raise NotImplementedError("IQM: no record (no backward) for the folded form, encoder_levels")
+        the anchors).  The self-attention, the aaclip_cross_rows form and the folded levels inside the domain of
+        aaclip_cross_rows_levels_backward have a backward: with a record, anything else raises NotImplementedError
+        before a launch."""
+        if (record is not None and encoder_levels is not None
+                and not self.levels_form_has_backward(query_embeds.shape[1], encoder_levels)):
+            raise NotImplementedError("IQM: no record (no backward) for these folded levels: "
+                                      "aaclip_cross_rows_levels_backward covers queries x heads in {4, 8, 12, 16} over "
+                                      "1..4 levels of rows 768 or 1024 wide")
         engine.require_gpu(query_embeds, "IQM")
         if code is None:
             code = engine.dtype_code(getattr(self, "precision", "fp32"))
@@ -248,7 +264,7 @@ class IQM(nn.Module):
         Lt = text_encoder_hidden_states.shape[1]
         rec = record is not None
         if rec:
-            record["vis"], record["txt"] = vis, txt
+            record["vis"], record["txt"] = (encoder_levels if encoder_levels is not None else vis), txt
         h = engine.residual_layernorm(engine._f32c(query_embeds).reshape(B * nq, D), None, self.layernorm, self.eps)
         for l, layer in enumerate(self.encoder.layer):
             a = self._attend(layer.attention, h, None, B, nq, nq, code, record=record, key=f"{l}.a.")

@@ -28,6 +28,17 @@ without a command-line argument (the parser stays the reference's):
 runs those blocks' products and attention backward as three-term bf16 sums on the bf16 MFMA
 (aaclip_hip.autograd.backward_precision, include/aaclip.h "bf16x3"); forward outputs and loss values are the same bits
 in both modes, the text tower and everything outside the visual blocks stay fp32.
+
+The IQM branch trains in its projected form by default: query_adapters applied to every patch row of every tap level,
+whatever form inference takes.  At the defaults (a 16-bit tower, no --relu) inference runs the branch's visual
+cross-attention in the folded 16-bit form instead, on the LayerNorm'ed tap rows themselves, and
+
+    AACLIP_IQM_TRAIN_FORM=folded python train.py --dataset MVTec --training_mode full_shot --iqm_hidden_size 768 --save_path ckpt/run
+
+trains that very forward (aaclip_hip.autograd.iqm_train_form, IqmQueriesFolded; include/aaclip.h
+aaclip_cross_rows_levels_backward): the queries the loss sees are the bits test_last.py evaluates.  It raises
+NotImplementedError before any launch on a model whose forward does not fold (fp32, --relu, a tower neither 768 nor
+1024 wide).
 """
 from __future__ import annotations
 

@@ -397,11 +397,12 @@ int aaclip_row_head_backward(const float* x, const int32_t* tokens, const float*
  * D, E supported row widths (256, 512, 768, 1024), L > 1, B*L < 2^29, act one of AACLIP_ACT_*.
  * ws_bytes >= aaclip_tap_head_backward_workspace_bytes(B, L, D, E): 0 for an empty problem, monotonic in each
  * argument.  Errors carry the "tap_head_backward:" prefix.
- * The IQM branch's backward: built is its key / value side, from the gradient of the cross-attention's weighted row sums
- * to query_adapters and the tap streams (aaclip_cross_rows_backward below plus aaclip_gemm_wgrad, aaclip_gemm and
- * aaclip_layernorm_backward; aaclip_hip/autograd.py iqm_visual_rows).  Not built: the backward of the 2-row query side
- * (the IQM layers' own Linears and LayerNorms, class_query_mlp, the feature projections, the text cross-attention)
- * and a training route for the folded 16-bit aaclip_cross_rows_levels form -- see DESIGN.md section 7. */
+ * The IQM branch's backward: its key / value side in the projected form, from the gradient of the cross-attention's
+ * weighted row sums to query_adapters and the tap streams (aaclip_cross_rows_backward below plus aaclip_gemm_wgrad,
+ * aaclip_gemm and aaclip_layernorm_backward; aaclip_hip/autograd.py iqm_visual_rows), the 2-row query side (the entries
+ * under "Backward building blocks of the IQM branch's query side"), and the folded 16-bit aaclip_cross_rows_levels form
+ * that inference runs at the defaults (aaclip_cross_rows_levels_backward; aaclip_hip/autograd.py IqmQueriesFolded,
+ * selected by AACLIP_IQM_TRAIN_FORM=folded) -- see DESIGN.md section 10. */
 size_t aaclip_tap_head_backward_workspace_bytes(int B, int L, int D, int E);
 int aaclip_tap_head_backward(const float* x, const float* ln_post_w, const float* ln_post_b, const float* proj_w,
                              const float* proj_wt, int act, const float* d_seg, const float* det_w, const float* det_wt,
@@ -556,6 +557,28 @@ size_t aaclip_cross_rows_levels_workspace_bytes(int B, int nseg, int Lk, int Dk)
 int aaclip_cross_rows_levels(int x_dtype, const float* qt, const void* const* x, int nseg, float* out, int B, int R,
                              int rows_per_image, int row0, int Lk, int Dk, long ldx, void* ws, size_t ws_bytes,
                              void* stream);
+/* Backward of aaclip_cross_rows_levels from d_out [B, R, nseg, Dk]: with p the forward's one softmax over all (s, j)
+ * (recomputed: nothing of size Lk x Dk is kept from the forward or placed in the workspace),
+ * g_(r,s,j) = d_out[b, r, s] . x[s][b, j] and delta_r = sum_(s,j) p g,
+ *   ds = p (g - delta_r),  d_qt[b, r, s] = sum_j ds_(r,s,j) x[s][b, j],
+ *   d_x[s][b, j] = sum_r (p_(r,s,j) d_out[b, r, s] + ds_(r,s,j) qt[b, r, s]).
+ * fp32 arithmetic on the 16-bit row values as they are.  qt, d_out, d_qt fp32 [B, R, nseg, Dk]; x as the forward takes
+ * it; d_x[s] fp32 [B * rows_per_image, Dk] (dense rows of Dk floats), addressed by the same row index
+ * b * rows_per_image + row0 + j as x[s]: rows outside the key range (the CLS row) are never written.  d_qt may be NULL,
+ * or d_x (the whole array) may be NULL, not both.  accumulate != 0: d_x[s] += the gradient (the two IQM layers read
+ * the same rows); 0: the key rows of d_x[s] are overwritten.  d_qt is always overwritten.
+ * x_dtype AACLIP_F16 or AACLIP_BF16; R 4, 8, 12 or 16; nseg 1..4; Dk 768 or 1024; Lk >= 1; ldx >= Dk and a multiple of 8
+ * (2 Dk for the fp16 halves of split8 rows); rows_per_image >= row0 + Lk, row0 >= 0, an image's rows of x[s] span less
+ * than 2 GiB (as for the forward); B <= 65535; every pointer and the
+ * workspace 16-byte aligned.  ws_bytes >= aaclip_cross_rows_levels_backward_workspace_bytes(B, R, nseg, Lk, Dk) =
+ * scores and d_out products [B, nseg, Lk, 32], row statistics and per-slice partial sums of d_qt (at most 128 slices
+ * per segment); 0 for an empty problem, monotonic in each argument.  No atomics, every sum in a fixed order: two calls
+ * on the same inputs give the same bits, and each element of d_x is written by one thread.  All checks precede the
+ * first launch; errors carry the "cross_rows_levels_backward:" prefix. */
+size_t aaclip_cross_rows_levels_backward_workspace_bytes(int B, int R, int nseg, int Lk, int Dk);
+int aaclip_cross_rows_levels_backward(int x_dtype, const float* qt, const void* const* x, int nseg, const float* d_out,
+                                      float* d_qt, float* const* d_x, int accumulate, int B, int R, int rows_per_image,
+                                      int row0, int Lk, int Dk, long ldx, void* ws, size_t ws_bytes, void* stream);
 int aaclip_head_expand(int dtype, const float* q, void* qm, long rows, int H, int D, float scale, void* stream);
 int aaclip_head_diag(const float* full, float* ctx, long rows, int H, int D, void* stream);
 /* softmax(q k^T * scale) v per (image, head) for nq <= 4 queries over Lk <= 8192 keys: the core of
