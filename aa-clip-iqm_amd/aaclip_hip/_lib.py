@@ -90,6 +90,14 @@ SIGNATURES = {
     "aaclip_nearest_table": (_i, [_i, _i, _vp]),
     "aaclip_mask_preprocess": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "aaclip_augment_geometric": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aaclip_metrics_range_workspace_bytes": (_sz, [_l, _l]),
+    "aaclip_metrics_range": (_i, [_vp, _vp, _l, _l, _vp, _vp, _vp, _sz, _vp]),
+    "aaclip_metrics_normalise": (_i, [_vp, _vp, _l, _vp, _vp]),
+    "aaclip_metrics_sort_workspace_bytes": (_sz, [_l]),
+    "aaclip_metrics_sort_group_items": (_l, []),
+    "aaclip_metrics_sort": (_i, [_vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aaclip_metrics_curve_workspace_bytes": (_sz, [_l]),
+    "aaclip_metrics_curve": (_i, [_vp, _vp, _l, _i, _vp, _vp, _sz, _vp]),
     "aaclip_row_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp] + [_i] * 6 + [_vp, _sz, _vp]),
     "aaclip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _l, _i, _f, _vp]),
     "aaclip_gemm": (_i, [_i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _f, _vp]),

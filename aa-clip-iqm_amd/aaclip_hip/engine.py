@@ -13,6 +13,7 @@ the compute dtype and cached per parameter version.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import weakref
@@ -1067,6 +1068,152 @@ def train_preprocess(frames_u8: torch.Tensor, masks_u8: torch.Tensor, normal: to
     image = preprocess(frames, img_size)
     mask = mask_preprocess(masks_u8, img_size, normal)
     return augment_geometric(image, mask, params["angle"], params["shift"], params["flags"])
+
+
+# ------------------------------------------------------------------------------------------------
+# exact AUROC / AP of one class on the device (csrc/metrics.hip; forward_utils.metrics_eval_device)
+METRICS_MAX_N = 2 ** 31 - 1
+CURVE_RECORD_WORDS = 6          # int64 words: num, P, N, groups, ap (fp64 bits), scores outside [0, 1] of a packed sort
+CurveMetrics = collections.namedtuple("CurveMetrics", "auroc ap P N image_max num groups")
+
+
+def _metrics_inputs(scores: torch.Tensor, labels: Optional[torch.Tensor], what: str):
+    require_gpu(scores, what)
+    if labels is not None:
+        require_gpu(labels, what)
+    if scores.dtype != torch.float32 or (labels is not None and labels.dtype != torch.uint8):
+        raise ValueError(f"{what} expects fp32 scores and uint8 labels")
+    scores = scores.contiguous().view(-1)
+    if labels is not None:
+        labels = labels.contiguous().view(-1)
+        if labels.numel() != scores.numel() or labels.device != scores.device:
+            raise ValueError(f"{what}: scores and labels must have one size and device")
+    if not 2 <= scores.numel() <= METRICS_MAX_N:
+        raise ValueError(f"{what}: 2 .. 2^31 - 1 scores, got {scores.numel()}")
+    return scores, labels
+
+
+def metrics_range(scores: torch.Tensor, labels: Optional[torch.Tensor] = None, per_image: int = 0):
+    """-> (record, image_max): the device record of aaclip_metrics_range (int64 [3]: min | max as two fp32, non-finite
+    count, positive count; metrics_range_host reads it) and the fp32 maximum of every `per_image` scores (None for 0)."""
+    scores, labels = _metrics_inputs(scores, labels, "metrics_range")
+    n, dev = scores.numel(), scores.device
+    if per_image < 0 or (per_image and n % per_image):
+        raise ValueError(f"metrics_range: {n} scores are no multiple of per_image = {per_image}")
+    lib = _lib.load()
+    record = torch.empty(3, dtype=torch.int64, device=dev)
+    image_max = torch.empty(n // per_image, dtype=torch.float32, device=dev) if per_image else None
+    ws = Workspace.get(dev, lib.aaclip_metrics_range_workspace_bytes(n, per_image))
+    _lib.check(lib.aaclip_metrics_range(scores.data_ptr(), _ptr(labels), n, per_image, _ptr(image_max), record.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _stream(dev)), "metrics_range")
+    return record, image_max
+
+
+def metrics_range_host(record: torch.Tensor) -> dict:
+    """The range record on the host (one synchronising copy of 24 bytes)."""
+    r = record.cpu()
+    mn, mx = r[:1].view(torch.float32).tolist()
+    return {"min": mn, "max": mx, "nonfinite": int(r[1]), "positives": int(r[2])}
+
+
+def metrics_normalise(scores: torch.Tensor, record: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(x - min) / (max - min) in fp32 with numpy's bits when the record's max != 1, else x; decided on the device."""
+    require_gpu(scores, "metrics_normalise")
+    if scores.dtype != torch.float32 or record.dtype != torch.int64 or record.numel() != 3 or not record.is_cuda:
+        raise ValueError("metrics_normalise expects fp32 scores and the record of metrics_range")
+    scores = scores.contiguous()
+    if out is None:
+        out = torch.empty_like(scores)
+    elif out.dtype != torch.float32 or out.shape != scores.shape or not out.is_contiguous() or out.device != scores.device:
+        raise ValueError("metrics_normalise: out must be a contiguous fp32 tensor of scores' shape and device")
+    _lib.check(_lib.load().aaclip_metrics_normalise(scores.data_ptr(), out.data_ptr(), scores.numel(), record.data_ptr(),
+                                                    _stream(scores.device)), "metrics_normalise")
+    return out
+
+
+def metrics_sort(scores: torch.Tensor, labels: torch.Tensor, packed: bool, out_of_range: Optional[torch.Tensor] = None):
+    """-> (keys, labels_sorted, out_of_range): the ascending keys of aaclip_metrics_sort as int32 [n] (read them as
+    uint32), the labels in their order (None when packed: bit 0 of the key) and the device count (int64 [1]) of
+    scores outside [0, 1] that a packed sort met."""
+    scores, labels = _metrics_inputs(scores, labels, "metrics_sort")
+    if labels is None:
+        raise ValueError("metrics_sort needs labels")
+    n, dev = scores.numel(), scores.device
+    lib = _lib.load()
+    keys = torch.empty(n, dtype=torch.int32, device=dev)
+    labels_sorted = None if packed else torch.empty(n, dtype=torch.uint8, device=dev)
+    if out_of_range is None:
+        out_of_range = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = Workspace.get(dev, lib.aaclip_metrics_sort_workspace_bytes(n))
+    _lib.check(lib.aaclip_metrics_sort(scores.data_ptr(), labels.data_ptr(), n, int(bool(packed)), keys.data_ptr(),
+                                       _ptr(labels_sorted), out_of_range.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _stream(dev)), "metrics_sort")
+    return keys, labels_sorted, out_of_range
+
+
+def metrics_curve(keys: torch.Tensor, labels_sorted: Optional[torch.Tensor], packed: bool,
+                  record: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sorted keys -> the device record (int64 [CURVE_RECORD_WORDS]; words 0..4 are written: num, P, N, groups, ap bits)."""
+    require_gpu(keys, "metrics_curve")
+    if keys.dtype != torch.int32 or keys.dim() != 1 or not keys.is_contiguous() or not 2 <= keys.numel() <= METRICS_MAX_N:
+        raise ValueError("metrics_curve expects the int32 [n] keys of metrics_sort")
+    if not packed and (labels_sorted is None or labels_sorted.dtype != torch.uint8 or labels_sorted.numel() != keys.numel()
+                       or not labels_sorted.is_contiguous() or labels_sorted.device != keys.device):
+        raise ValueError("metrics_curve: keys without a packed label need the uint8 [n] labels of metrics_sort")
+    n, dev = keys.numel(), keys.device
+    if record is None:
+        record = torch.zeros(CURVE_RECORD_WORDS, dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    ws = Workspace.get(dev, lib.aaclip_metrics_curve_workspace_bytes(n))
+    _lib.check(lib.aaclip_metrics_curve(keys.data_ptr(), None if packed else labels_sorted.data_ptr(), n,
+                                        int(bool(packed)), record.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+               "metrics_curve")
+    return record
+
+
+def curve_metrics(scores: torch.Tensor, labels: torch.Tensor, per_image: int = 0,
+                  record: Optional[torch.Tensor] = None, normalise: bool = True) -> CurveMetrics:
+    """sklearn's roc_auc_score and average_precision_score of the min-max normalised scores (reference
+    forward_utils.py:246-253,288-296), exactly, on the device: scores fp32, labels uint8 (0 / non-zero), any shape of one
+    size.  -> CurveMetrics(auroc, ap, P, N, image_max, num, groups): auroc = num / (2 P N) with the integer numerator
+    num, ap the fp64 sum over the `groups` distinct scores, image_max the fp32 device tensor of the NORMALISED maximum
+    of every `per_image` scores (None for per_image = 0).
+    Raises ValueError before anything is sorted when a score is not finite, when max == min (the reference divides by
+    zero there) or when the labels hold one class only (sklearn raises).  record: an int64 [CURVE_RECORD_WORDS] device
+    tensor to receive the device record (it is not written when the call raises).
+    normalise=False takes the scores as they are (metrics_eval's image scores are normalised before they are combined
+    with the map maxima, not after); equal scores are then one tie group, not an error."""
+    scores, labels = _metrics_inputs(scores, labels, "curve_metrics")
+    if labels is None:
+        raise ValueError("curve_metrics needs labels")
+    if record is not None and (record.dtype != torch.int64 or record.numel() != CURVE_RECORD_WORDS or not record.is_cuda
+                               or not record.is_contiguous()):
+        raise ValueError(f"curve_metrics: record must be a contiguous int64 [{CURVE_RECORD_WORDS}] device tensor")
+    n = scores.numel()
+    rng, image_max = metrics_range(scores, labels, per_image)
+    r = metrics_range_host(rng)
+    if r["nonfinite"]:
+        raise ValueError(f"curve_metrics: {r['nonfinite']} of {n} scores are not finite")
+    if normalise and r["max"] == r["min"]:
+        raise ValueError("curve_metrics: all scores are equal (max == min): the min-max normalisation divides by zero")
+    if r["positives"] == 0 or r["positives"] == n:
+        raise ValueError("curve_metrics: only one class present in the labels; AUROC and AP are not defined")
+    norm = metrics_normalise(scores, rng) if normalise else scores
+    if normalise and image_max is not None:
+        metrics_normalise(image_max, rng, out=image_max)
+    # the label rides in the key where every sorted score lies in [0, 1]: normalised, or passed through inside it
+    packed = (normalise and r["max"] != 1.0) or (r["min"] >= 0.0 and r["max"] <= 1.0)
+    if record is None:
+        record = torch.zeros(CURVE_RECORD_WORDS, dtype=torch.int64, device=scores.device)
+    keys, labels_sorted, _ = metrics_sort(norm, labels, packed, out_of_range=record[CURVE_RECORD_WORDS - 1:])
+    del norm
+    metrics_curve(keys, labels_sorted, packed, record)
+    h = record.cpu()
+    num, P, N, groups, _, outside = (int(v) for v in h)
+    if outside:
+        raise RuntimeError(f"curve_metrics: {outside} normalised scores fell outside [0, 1]")
+    assert P == r["positives"] and P + N == n, (P, N, r, n)
+    return CurveMetrics(num / (2 * P * N), float(h[4:5].view(torch.float64)), P, N, image_max, num, groups)
 
 
 # ------------------------------------------------------------------------------------------------

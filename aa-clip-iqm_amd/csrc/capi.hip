@@ -1384,6 +1384,94 @@ int aaclip_augment_geometric(const float* image, const float* mask, int B, int S
   return finish("augment_geometric");
 }
 
+// ---- exact AUROC / AP (metrics.hip)
+static inline bool metrics_n_ok(long n) { return n >= 2 && n <= 2147483647L; }
+
+size_t aaclip_metrics_range_workspace_bytes(long n, long per_image) {
+  if (!metrics_n_ok(n) || per_image < 0 || (per_image > 0 && n % per_image != 0)) return 0;
+  return up256(metrics_range_ws_bytes(n, per_image));
+}
+
+int aaclip_metrics_range(const float* scores, const uint8_t* labels, long n, long per_image, float* image_max,
+                         void* record, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(scores && record && ws, "metrics_range: null pointer");
+  REQUIRE(metrics_n_ok(n), "metrics_range: n must be 2 .. 2^31 - 1");
+  REQUIRE(per_image >= 0 && (per_image == 0 || n % per_image == 0), "metrics_range: n must be a multiple of per_image");
+  REQUIRE(!image_max || per_image > 0, "metrics_range: image maxima need per_image > 0");
+  REQUIRE((((uintptr_t)scores | (uintptr_t)image_max) & 3) == 0 && (((uintptr_t)record | (uintptr_t)ws) & 7) == 0,
+          "metrics_range: scores / image_max must be 4-byte, record / workspace 8-byte aligned");
+  const size_t range_need = aaclip_metrics_range_workspace_bytes(n, per_image);
+  REQUIRE(!ranges_overlap(ws, range_need, scores, (size_t)n * 4) && !ranges_overlap(ws, range_need, record, 24) &&
+              !ranges_overlap(record, 24, scores, (size_t)n * 4) && !(labels && ranges_overlap(ws, range_need, labels, (size_t)n)) &&
+              !(image_max && (ranges_overlap(ws, range_need, image_max, (size_t)(n / per_image) * 4) ||
+                              ranges_overlap(image_max, (size_t)(n / per_image) * 4, scores, (size_t)n * 4) ||
+                              ranges_overlap(image_max, (size_t)(n / per_image) * 4, record, 24))),
+          "metrics_range: scores, labels, outputs and workspace must not overlap one another");
+  REQUIRE(ws_bytes >= range_need, "metrics_range: workspace too small");
+  launch_metrics_range(scores, labels, n, per_image, image_max, record, ws, (hipStream_t)stream);
+  return finish("metrics_range");
+}
+
+int aaclip_metrics_normalise(const float* scores, float* out, long n, const void* range_record, void* stream) {
+  REQUIRE(scores && out && range_record, "metrics_normalise: null pointer");
+  REQUIRE(n >= 1 && n <= 2147483647L, "metrics_normalise: n must be 1 .. 2^31 - 1");
+  REQUIRE((((uintptr_t)scores | (uintptr_t)out) & 3) == 0 && ((uintptr_t)range_record & 7) == 0,
+          "metrics_normalise: scores / out must be 4-byte, the record 8-byte aligned");
+  REQUIRE(scores == out || !ranges_overlap(scores, (size_t)n * 4, out, (size_t)n * 4),
+          "metrics_normalise: out must be scores itself (in place) or not overlap it");
+  launch_metrics_normalise(scores, out, n, range_record, (hipStream_t)stream);
+  return finish("metrics_normalise");
+}
+
+size_t aaclip_metrics_sort_workspace_bytes(long n) { return metrics_n_ok(n) ? up256(metrics_sort_ws_bytes(n)) : 0; }
+long aaclip_metrics_sort_group_items(void) { return metrics_sort_group_items(); }
+
+int aaclip_metrics_sort(const float* scores, const uint8_t* labels, long n, int packed, uint32_t* keys,
+                        uint8_t* labels_sorted, unsigned long long* out_of_range, void* ws, size_t ws_bytes,
+                        void* stream) {
+  REQUIRE(scores && labels && keys && out_of_range && ws, "metrics_sort: null pointer");
+  REQUIRE(packed == 0 || packed == 1, "metrics_sort: packed must be 0 or 1");
+  REQUIRE(packed || labels_sorted, "metrics_sort: labels_sorted is required when the label is not packed into the key");
+  REQUIRE(metrics_n_ok(n), "metrics_sort: n must be 2 .. 2^31 - 1");
+  REQUIRE((((uintptr_t)scores | (uintptr_t)keys) & 3) == 0 && (((uintptr_t)out_of_range | (uintptr_t)ws) & 7) == 0,
+          "metrics_sort: scores / keys must be 4-byte, out_of_range / workspace 8-byte aligned");
+  REQUIRE(!ranges_overlap(keys, (size_t)n * 4, scores, (size_t)n * 4) &&
+              !(labels_sorted && ranges_overlap(labels_sorted, (size_t)n, labels, (size_t)n)),
+          "metrics_sort: the outputs must not overlap the inputs");
+  const size_t sort_need = aaclip_metrics_sort_workspace_bytes(n);   // the workspace holds the other half of the ping-pong
+  REQUIRE(!ranges_overlap(ws, sort_need, scores, (size_t)n * 4) && !ranges_overlap(ws, sort_need, labels, (size_t)n) &&
+              !ranges_overlap(ws, sort_need, keys, (size_t)n * 4) && !ranges_overlap(ws, sort_need, out_of_range, 8) &&
+              !(labels_sorted && ranges_overlap(ws, sort_need, labels_sorted, (size_t)n)) &&
+              !ranges_overlap(out_of_range, 8, keys, (size_t)n * 4) &&
+              !(labels_sorted && (ranges_overlap(out_of_range, 8, labels_sorted, (size_t)n) ||
+                                  ranges_overlap(keys, (size_t)n * 4, labels_sorted, (size_t)n))),
+          "metrics_sort: inputs, outputs and workspace must not overlap one another");
+  REQUIRE(ws_bytes >= sort_need, "metrics_sort: workspace too small");
+  launch_metrics_sort(scores, labels, n, packed, keys, labels_sorted, out_of_range, ws, (hipStream_t)stream);
+  return finish("metrics_sort");
+}
+
+size_t aaclip_metrics_curve_workspace_bytes(long n) { return metrics_n_ok(n) ? up256(metrics_curve_ws_bytes(n)) : 0; }
+
+int aaclip_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
+                         size_t ws_bytes, void* stream) {
+  REQUIRE(keys && record && ws, "metrics_curve: null pointer");
+  REQUIRE(packed == 0 || packed == 1, "metrics_curve: packed must be 0 or 1");
+  REQUIRE(packed || labels_sorted, "metrics_curve: labels_sorted is required when the label is not packed into the key");
+  REQUIRE(metrics_n_ok(n), "metrics_curve: n must be 2 .. 2^31 - 1");
+  REQUIRE(((uintptr_t)keys & 3) == 0 && (((uintptr_t)record | (uintptr_t)ws) & 7) == 0,
+          "metrics_curve: keys must be 4-byte, record / workspace 8-byte aligned");
+  const size_t curve_need = aaclip_metrics_curve_workspace_bytes(n);
+  REQUIRE(!ranges_overlap(ws, curve_need, keys, (size_t)n * 4) && !ranges_overlap(ws, curve_need, record, 40) &&
+              !ranges_overlap(record, 40, keys, (size_t)n * 4) &&
+              !(labels_sorted && (ranges_overlap(ws, curve_need, labels_sorted, (size_t)n) ||
+                                  ranges_overlap(record, 40, labels_sorted, (size_t)n))),
+          "metrics_curve: keys, labels, record and workspace must not overlap one another");
+  REQUIRE(ws_bytes >= curve_need, "metrics_curve: workspace too small");
+  launch_metrics_curve(keys, labels_sorted, n, packed, record, ws, (hipStream_t)stream);
+  return finish("metrics_curve");
+}
+
 int aaclip_text_embed(const int32_t* tokens, const float* table, const float* pos, float* x, int n, int T, int D,
                       int vocab, void* stream) {
   REQUIRE(tokens && table && pos && x, "text_embed: null pointer");

@@ -263,4 +263,18 @@ void launch_augment_geometric(const float* image, const float* mask, int B, int 
                               const int32_t* shift, const int32_t* flags, float* image_out, float* mask_out,
                               hipStream_t s);
 
+// ---- metrics.hip : exact AUROC / AP of one class: range, normalise, ordered keys, stable radix sort, curve sums
+long metrics_range_partials(long n, long per_image);   // workgroups of the first range stage (per_image 0: one segment)
+size_t metrics_range_ws_bytes(long n, long per_image);
+void launch_metrics_range(const float* scores, const uint8_t* labels, long n, long per_image, float* image_max,
+                          void* record, void* ws, hipStream_t s);
+void launch_metrics_normalise(const float* in, float* out, long n, const void* record, hipStream_t s);
+long metrics_sort_group_items();                       // keys one workgroup of the sort takes
+size_t metrics_sort_ws_bytes(long n);
+void launch_metrics_sort(const float* scores, const uint8_t* labels, long n, int packed, uint32_t* keys,
+                         uint8_t* labels_sorted, unsigned long long* out_of_range, void* ws, hipStream_t s);
+size_t metrics_curve_ws_bytes(long n);
+void launch_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
+                          hipStream_t s);
+
 }  // namespace aaclip

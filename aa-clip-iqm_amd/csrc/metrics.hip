@@ -1,0 +1,533 @@
+// Exact AUROC / average precision of one class on the device (forward_utils.metrics_eval_device), five steps:
+//   range      min / max / non-finite count / positive count of the scores, and the maximum of every image
+//   normalise  (x - min) / (max - min) in fp32 where max != 1, the bits numpy gives (reference forward_utils.py:246-253)
+//   keys       an order-preserving uint32 image of every score; the 0 / 1 label in bit 0 where the scores lie in [0, 1]
+//   sort       stable LSD radix sort, four passes of 8-bit digits
+//   curve      tie groups of the sorted keys -> integer AUROC numerator and the fp64 AP sum
+// The numbers are sklearn's roc_auc_score / average_precision_score: the same tie groups and the same definitions.
+// No floating-point atomics; every floating-point sum runs in an order fixed by n alone, so two calls give the same bits.
+#include "common.h"
+#include "kernels.h"
+#include <math.h>
+
+namespace aaclip {
+
+static constexpr int MT = 256;   // threads of every workgroup in this file (4 waves)
+typedef unsigned long long u64;
+static inline size_t up256_bytes(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// ---------------------------------------------------------------------------------------------------- range
+// A SEGMENT is one image (per_image elements), or the whole array when per_image is 0.  Stage 1: blocks_per_segment
+// workgroups per segment, each a strided share; stage 2: one workgroup folds the partials in index order.
+static constexpr int RANGE_ITEMS = 4096;        // elements of a segment per workgroup before another one is added
+static constexpr int RANGE_MAX_BLOCKS = 1024;   // workgroups per segment at the most
+
+struct RangePartial {
+  float mn, mx;
+  u64 bad, pos;
+};
+struct RangeRecord {   // include/aaclip.h aaclip_metrics_range_record
+  float mn, mx;
+  u64 bad, pos;
+};
+
+long metrics_range_blocks(long seg_len) {
+  const long b = (seg_len + RANGE_ITEMS - 1) / RANGE_ITEMS;
+  return b < 1 ? 1 : (b < RANGE_MAX_BLOCKS ? b : RANGE_MAX_BLOCKS);
+}
+long metrics_range_partials(long n, long per_image) {
+  const long seg_len = per_image > 0 ? per_image : n;
+  return (n / seg_len) * metrics_range_blocks(seg_len);
+}
+size_t metrics_range_ws_bytes(long n, long per_image) {
+  return (size_t)metrics_range_partials(n, per_image) * sizeof(RangePartial);
+}
+
+__global__ __launch_bounds__(MT) void metrics_range_partial_kernel(const float* __restrict__ scores,
+                                                                   const uint8_t* __restrict__ labels, long seg_len,
+                                                                   int blocks, RangePartial* __restrict__ partial) {
+  __shared__ float s_mn[MT], s_mx[MT];
+  __shared__ u64 s_bad[MT], s_pos[MT];
+  const long seg = blockIdx.x / blocks;
+  const int blk = blockIdx.x % blocks;
+  const long base = seg * seg_len;
+  float mn = INFINITY, mx = -INFINITY;
+  u64 bad = 0, pos = 0;
+  for (long i = (long)blk * MT + threadIdx.x; i < seg_len; i += (long)blocks * MT) {
+    const float x = scores[base + i];
+    if (isfinite(x)) {
+      mn = fminf(mn, x);
+      mx = fmaxf(mx, x);
+    } else {
+      ++bad;
+    }
+    if (labels) pos += labels[base + i] != 0;
+  }
+  const int t = threadIdx.x;
+  s_mn[t] = mn, s_mx[t] = mx, s_bad[t] = bad, s_pos[t] = pos;
+  __syncthreads();
+  for (int o = MT / 2; o > 0; o >>= 1) {
+    if (t < o) {
+      s_mn[t] = fminf(s_mn[t], s_mn[t + o]);
+      s_mx[t] = fmaxf(s_mx[t], s_mx[t + o]);
+      s_bad[t] += s_bad[t + o];
+      s_pos[t] += s_pos[t + o];
+    }
+    __syncthreads();
+  }
+  if (t == 0) partial[blockIdx.x] = RangePartial{s_mn[0], s_mx[0], s_bad[0], s_pos[0]};
+}
+
+// one workgroup: the record over all partials, then the maximum of every segment
+__global__ __launch_bounds__(MT) void metrics_range_fold_kernel(const RangePartial* __restrict__ partial, long segs,
+                                                                int blocks, RangeRecord* __restrict__ rec,
+                                                                float* __restrict__ image_max) {
+  __shared__ float s_mn[MT], s_mx[MT];
+  __shared__ u64 s_bad[MT], s_pos[MT];
+  const int t = threadIdx.x;
+  const long total = segs * blocks;
+  float mn = INFINITY, mx = -INFINITY;
+  u64 bad = 0, pos = 0;
+  for (long i = t; i < total; i += MT) {
+    const RangePartial p = partial[i];
+    mn = fminf(mn, p.mn);
+    mx = fmaxf(mx, p.mx);
+    bad += p.bad;
+    pos += p.pos;
+  }
+  s_mn[t] = mn, s_mx[t] = mx, s_bad[t] = bad, s_pos[t] = pos;
+  __syncthreads();
+  for (int o = MT / 2; o > 0; o >>= 1) {
+    if (t < o) {
+      s_mn[t] = fminf(s_mn[t], s_mn[t + o]);
+      s_mx[t] = fmaxf(s_mx[t], s_mx[t + o]);
+      s_bad[t] += s_bad[t + o];
+      s_pos[t] += s_pos[t + o];
+    }
+    __syncthreads();
+  }
+  if (t == 0) *rec = RangeRecord{s_mn[0], s_mx[0], s_bad[0], s_pos[0]};
+  if (image_max)
+    for (long s = t; s < segs; s += MT) {
+      float m = -INFINITY;
+      for (int b = 0; b < blocks; ++b) m = fmaxf(m, partial[s * blocks + b].mx);
+      image_max[s] = m;
+    }
+}
+
+void launch_metrics_range(const float* scores, const uint8_t* labels, long n, long per_image, float* image_max,
+                          void* record, void* ws, hipStream_t s) {
+  const long seg_len = per_image > 0 ? per_image : n;
+  const long segs = n / seg_len;
+  const int blocks = (int)metrics_range_blocks(seg_len);
+  RangePartial* partial = (RangePartial*)ws;
+  hipLaunchKernelGGL(metrics_range_partial_kernel, dim3((unsigned)(segs * blocks)), dim3(MT), 0, s, scores, labels,
+                     seg_len, blocks, partial);
+  hipLaunchKernelGGL(metrics_range_fold_kernel, dim3(1), dim3(MT), 0, s, partial, segs, blocks, (RangeRecord*)record,
+                     image_max);
+}
+
+// ------------------------------------------------------------------------------------------------ normalise
+// numpy's float32 (x - min) / (max - min): an IEEE subtraction and a correctly rounded division (the file is built
+// with -ffp-contract=off).  The decision is the reference's `if preds.max() != 1`, read from the device record.
+__global__ __launch_bounds__(MT) void metrics_normalise_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                               long n, const RangeRecord* __restrict__ rec) {
+  const long i = (long)blockIdx.x * MT + threadIdx.x;
+  if (i >= n) return;
+  const float mn = rec->mn, mx = rec->mx;
+  const float x = in[i];
+  out[i] = mx != 1.0f ? __fdiv_rn(x - mn, mx - mn) : x;
+}
+
+void launch_metrics_normalise(const float* in, float* out, long n, const void* record, hipStream_t s) {
+  hipLaunchKernelGGL(metrics_normalise_kernel, dim3((unsigned)((n + MT - 1) / MT)), dim3(MT), 0, s, in, out, n,
+                     (const RangeRecord*)record);
+}
+
+// ----------------------------------------------------------------------------------------------------- keys
+// -0.0 becomes +0.0 first, so that equal floats share one key.  packed: the scores lie in [0, 1], their bit pattern is
+// at most 0x3F800000 < 2^30 and already ordered: key = bits << 1 | label.  A score outside [0, 1] is counted in
+// *out_of_range (an integer atomic; the caller refuses the result).  Otherwise the key is the usual ordered image of
+// all 32 bits (sign flipped for positive floats, every bit for negative ones) and the label travels beside it.
+__global__ __launch_bounds__(MT) void metrics_keys_kernel(const float* __restrict__ scores,
+                                                          const uint8_t* __restrict__ labels, long n, int packed,
+                                                          uint32_t* __restrict__ keys, u64* __restrict__ out_of_range) {
+  const long i = (long)blockIdx.x * MT + threadIdx.x;
+  if (i >= n) return;
+  uint32_t b = __float_as_uint(scores[i]);
+  if (b == 0x80000000u) b = 0;
+  if (packed) {
+    if (b > 0x3F800000u) {
+      atomicAdd(out_of_range, 1ull);
+      b = 0x3F800000u;
+    }
+    keys[i] = (b << 1) | (labels[i] != 0 ? 1u : 0u);
+  } else {
+    keys[i] = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+  }
+}
+
+// ----------------------------------------------------------------------------------------------------- sort
+// The unit of the sort is a CHUNK: 2048 consecutive keys, walked by one wave in 32 rounds of 64.  A workgroup is four
+// waves = four chunks; every chunk has its own row of the digit table [chunks][256].  Per pass:
+//   histogram   digit counts of every chunk (integer LDS atomics)                             -> table
+//   scan        table <- exclusive prefix in (digit, chunk) order = the first output index of every (chunk, digit):
+//               column sums of row segments, one workgroup over the segment sums and the 256 digit totals, apply
+//   scatter     a wave walks its chunk in index order; in a round, the lanes that hold the same digit find each other
+//               with eight ballots, rank themselves by lane number, and the lowest of them advances the chunk's
+//               counter of that digit: equal digits keep their input order, which makes the sort stable
+static constexpr int SORT_ROUNDS = 32;
+static constexpr int SORT_CHUNK = 64 * SORT_ROUNDS;
+static constexpr int SORT_WAVES = MT / 64;
+static constexpr int SCAN_SEGMENTS = 256;   // row segments of the table scan at the most
+
+long metrics_sort_chunks(long n) { return (n + SORT_CHUNK - 1) / SORT_CHUNK; }
+long metrics_sort_group_items() { return (long)SORT_CHUNK * SORT_WAVES; }
+
+__global__ __launch_bounds__(MT) void sort_hist_kernel(const uint32_t* __restrict__ keys, long n, int shift,
+                                                       uint32_t* __restrict__ table, long chunks) {
+  __shared__ uint32_t cnt[SORT_WAVES][256];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) cnt[w][lane + 64 * k] = 0;
+  __syncthreads();
+  const long chunk = (long)blockIdx.x * SORT_WAVES + w;
+  const long base = chunk * SORT_CHUNK;
+  if (chunk < chunks) {
+#pragma unroll 4
+    for (int r = 0; r < SORT_ROUNDS; ++r) {
+      const long i = base + r * 64 + lane;
+      if (i < n) atomicAdd(&cnt[w][(keys[i] >> shift) & 255u], 1u);
+    }
+  }
+  __syncthreads();
+  if (chunk < chunks) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) table[chunk * 256 + lane + 64 * k] = cnt[w][lane + 64 * k];
+  }
+}
+
+// grid = segments; thread d: seg_sum[s][d] = sum of column d over the segment's rows
+__global__ __launch_bounds__(MT) void sort_scan_sum_kernel(const uint32_t* __restrict__ table, long chunks, long seg_len,
+                                                           uint32_t* __restrict__ seg_sum) {
+  const long r0 = (long)blockIdx.x * seg_len, r1 = r0 + seg_len < chunks ? r0 + seg_len : chunks;
+  uint32_t acc = 0;
+  for (long r = r0; r < r1; ++r) acc += table[r * 256 + threadIdx.x];
+  seg_sum[(long)blockIdx.x * 256 + threadIdx.x] = acc;
+}
+
+// one workgroup; thread d: seg_sum[.][d] <- (keys with a smaller digit) + (keys of digit d in earlier segments)
+__global__ __launch_bounds__(MT) void sort_scan_base_kernel(uint32_t* __restrict__ seg_sum, int segments) {
+  __shared__ uint32_t base[256];
+  const int d = threadIdx.x;
+  uint32_t total = 0;
+  for (int s = 0; s < segments; ++s) total += seg_sum[s * 256 + d];
+  base[d] = total;
+  __syncthreads();
+  if (d == 0) {
+    uint32_t run = 0;
+    for (int j = 0; j < 256; ++j) {
+      const uint32_t c = base[j];
+      base[j] = run;
+      run += c;
+    }
+  }
+  __syncthreads();
+  uint32_t run = base[d];
+  for (int s = 0; s < segments; ++s) {
+    const uint32_t c = seg_sum[s * 256 + d];
+    seg_sum[s * 256 + d] = run;
+    run += c;
+  }
+}
+
+// grid = segments; thread d walks its column over the segment's rows: count -> first output index
+__global__ __launch_bounds__(MT) void sort_scan_apply_kernel(uint32_t* __restrict__ table, long chunks, long seg_len,
+                                                             const uint32_t* __restrict__ seg_sum) {
+  const long r0 = (long)blockIdx.x * seg_len, r1 = r0 + seg_len < chunks ? r0 + seg_len : chunks;
+  uint32_t run = seg_sum[(long)blockIdx.x * 256 + threadIdx.x];
+  for (long r = r0; r < r1; ++r) {
+    const uint32_t c = table[r * 256 + threadIdx.x];
+    table[r * 256 + threadIdx.x] = run;
+    run += c;
+  }
+}
+
+__global__ __launch_bounds__(MT) void sort_scatter_kernel(const uint32_t* __restrict__ keys_in,
+                                                          uint32_t* __restrict__ keys_out,
+                                                          const uint8_t* __restrict__ lab_in,
+                                                          uint8_t* __restrict__ lab_out, long n, int shift,
+                                                          const uint32_t* __restrict__ table, long chunks) {
+  __shared__ uint32_t first[SORT_WAVES][256];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long chunk = (long)blockIdx.x * SORT_WAVES + w;
+  if (chunk < chunks) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) first[w][lane + 64 * k] = table[chunk * 256 + lane + 64 * k];
+  }
+  __syncthreads();
+  if (chunk >= chunks) return;
+  // from here on a wave only touches its own row of `first`: the lanes of a wave run in lockstep, the accesses are
+  // volatile and separated by wave barriers, so a round reads the counters the round before it left
+  volatile uint32_t* mine = first[w];
+  const u64 below = (1ull << lane) - 1;
+  const long base = chunk * SORT_CHUNK;
+  for (int r = 0; r < SORT_ROUNDS; ++r) {
+    if (base + r * 64 >= n) break;   // the same for every lane
+    const long i = base + r * 64 + lane;
+    const bool valid = i < n;
+    const uint32_t key = valid ? keys_in[i] : 0u;
+    const uint32_t d = (key >> shift) & 255u;
+    u64 same = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const bool bit = (d >> b) & 1u;
+      const u64 vote = __ballot(bit);
+      same &= bit ? vote : ~vote;
+    }
+    const uint32_t rank = (uint32_t)__popcll(same & below);
+    const uint32_t start = mine[d];
+    __builtin_amdgcn_wave_barrier();
+    if (valid && rank == 0) mine[d] = start + (uint32_t)__popcll(same);
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t pos = start + rank;
+    if (valid && (long)pos < n) {   // pos < n holds whenever the table is the scan of this input's histogram
+      keys_out[pos] = key;
+      if (lab_in) lab_out[pos] = lab_in[i];
+    }
+  }
+}
+
+size_t metrics_sort_ws_bytes(long n) {
+  const long chunks = metrics_sort_chunks(n);
+  return up256_bytes((size_t)n * 4) + up256_bytes((size_t)n) + (size_t)chunks * 1024 + (size_t)SCAN_SEGMENTS * 1024;
+}
+
+// ws: [keys B: n uint32] [labels B: n bytes] [table: chunks x 256 uint32] [segment sums: 256 x 256 uint32]
+// The keys start in `keys` and are back there after the fourth pass; so are the labels in `labels_sorted`.
+void launch_metrics_sort(const float* scores, const uint8_t* labels, long n, int packed, uint32_t* keys,
+                         uint8_t* labels_sorted, unsigned long long* out_of_range, void* ws, hipStream_t s) {
+  const long chunks = metrics_sort_chunks(n);
+  char* p = (char*)ws;
+  uint32_t* keys_b = (uint32_t*)p;
+  p += up256_bytes((size_t)n * 4);
+  uint8_t* lab_b = (uint8_t*)p;
+  p += up256_bytes((size_t)n);
+  uint32_t* table = (uint32_t*)p;
+  p += (size_t)chunks * 1024;
+  uint32_t* seg_sum = (uint32_t*)p;
+  const long seg_len = (chunks + SCAN_SEGMENTS - 1) / SCAN_SEGMENTS;
+  const int segments = (int)((chunks + seg_len - 1) / seg_len);
+  const unsigned groups = (unsigned)((chunks + SORT_WAVES - 1) / SORT_WAVES);
+  (void)hipMemsetAsync(out_of_range, 0, sizeof(u64), s);
+  hipLaunchKernelGGL(metrics_keys_kernel, dim3((unsigned)((n + MT - 1) / MT)), dim3(MT), 0, s, scores, labels, n, packed,
+                     keys, out_of_range);
+  for (int pass = 0; pass < 4; ++pass) {
+    const uint32_t* src = pass & 1 ? keys_b : keys;
+    uint32_t* dst = pass & 1 ? keys : keys_b;
+    const uint8_t* lsrc = packed ? nullptr : (pass == 0 ? labels : (pass & 1 ? lab_b : labels_sorted));
+    uint8_t* ldst = packed ? nullptr : (pass & 1 ? labels_sorted : lab_b);
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(groups), dim3(MT), 0, s, src, n, 8 * pass, table, chunks);
+    hipLaunchKernelGGL(sort_scan_sum_kernel, dim3(segments), dim3(MT), 0, s, table, chunks, seg_len, seg_sum);
+    hipLaunchKernelGGL(sort_scan_base_kernel, dim3(1), dim3(MT), 0, s, seg_sum, segments);
+    hipLaunchKernelGGL(sort_scan_apply_kernel, dim3(segments), dim3(MT), 0, s, table, chunks, seg_len, seg_sum);
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3(groups), dim3(MT), 0, s, src, dst, lsrc, ldst, n, 8 * pass, table,
+                       chunks);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- curve
+// Over the ascending keys, element i STARTS a tie group when i == 0 or its score differs from that of i - 1; read from
+// the top (descending thresholds, as sklearn walks them) that element is the last of its group.  One prefix sum of
+// 64-bit words (start << 32 | label) gives, at every start i, the number of groups before it and E = the positives
+// before it; both are below 2^31, so the halves never meet.  Three levels: sums of tiles of 4096, one workgroup over
+// the tile sums, then the tiles again, which write the compact list marks[g] = i << 32 | E.
+// Group g = [i, i2) with i2 the next start (n after the last one), E2 likewise (P after the last one):
+//   tp = P - E, fp = (n - i) - tp at its mark; tp0 = P - E2, fp0 = (n - i2) - tp0 at the mark before it (0, 0 for the
+//   top group).  num += (fp - fp0)(tp + tp0) in uint64 (at most n^2 / 2 < 2^61);
+//   AP += ((tp - tp0) / P) (tp / (tp + fp)) in fp64.
+static constexpr int CURVE_ITEMS = 16;
+static constexpr int CURVE_TILE = MT * CURVE_ITEMS;
+static constexpr int CURVE_MAX_BLOCKS = 1024;   // workgroups of the group sums = partials the last kernel folds
+
+struct CurveRecord {   // include/aaclip.h aaclip_metrics_curve_record (its sixth word is written by the sort)
+  u64 num, P, N, groups;
+  double ap;
+};
+
+long metrics_curve_tiles(long n) { return (n + CURVE_TILE - 1) / CURVE_TILE; }
+long metrics_curve_blocks(long n) {
+  const long b = (n + MT - 1) / MT;
+  return b < CURVE_MAX_BLOCKS ? b : CURVE_MAX_BLOCKS;
+}
+
+AACLIP_DEV u64 curve_word(const uint32_t* __restrict__ keys, const uint8_t* __restrict__ lab, long i, int packed) {
+  const uint32_t k = keys[i];
+  const uint32_t score = packed ? k >> 1 : k;
+  const u64 label = packed ? (k & 1u) : (lab[i] != 0 ? 1u : 0u);
+  bool start = i == 0;
+  if (!start) {
+    const uint32_t kp = keys[i - 1];
+    start = (packed ? kp >> 1 : kp) != score;
+  }
+  return ((u64)start << 32) | label;
+}
+
+AACLIP_DEV u64 curve_thread_sum(const uint32_t* __restrict__ keys, const uint8_t* __restrict__ lab, long n, int packed,
+                                long first) {
+  u64 acc = 0;
+#pragma unroll 4
+  for (int j = 0; j < CURVE_ITEMS; ++j)
+    if (first + j < n) acc += curve_word(keys, lab, first + j, packed);
+  return acc;
+}
+
+__global__ __launch_bounds__(MT) void curve_tile_sum_kernel(const uint32_t* __restrict__ keys,
+                                                            const uint8_t* __restrict__ lab, long n, int packed,
+                                                            u64* __restrict__ tile_sum) {
+  __shared__ u64 red[MT];
+  const int t = threadIdx.x;
+  red[t] = curve_thread_sum(keys, lab, n, packed, (long)blockIdx.x * CURVE_TILE + (long)t * CURVE_ITEMS);
+  __syncthreads();
+  for (int o = MT / 2; o > 0; o >>= 1) {
+    if (t < o) red[t] += red[t + o];
+    __syncthreads();
+  }
+  if (t == 0) tile_sum[blockIdx.x] = red[0];
+}
+
+// exclusive prefix of `mine` over the workgroup's threads, in thread order (integers: any order gives the same sum)
+AACLIP_DEV u64 block_exclusive_scan(u64 mine, u64* lds) {
+  const int t = threadIdx.x;
+  lds[t] = mine;
+  __syncthreads();
+  for (int o = 1; o < MT; o <<= 1) {
+    const u64 add = t >= o ? lds[t - o] : 0;
+    __syncthreads();
+    lds[t] += add;
+    __syncthreads();
+  }
+  return lds[t] - mine;
+}
+
+// one workgroup: tile_sum <- its exclusive prefix, *total <- the sum of all (groups << 32 | positives)
+__global__ __launch_bounds__(MT) void curve_tile_scan_kernel(u64* __restrict__ tile_sum, long tiles,
+                                                             u64* __restrict__ total) {
+  __shared__ u64 lds[MT];
+  const int t = threadIdx.x;
+  const long per = (tiles + MT - 1) / MT;
+  const long j0 = t * per < tiles ? t * per : tiles, j1 = j0 + per < tiles ? j0 + per : tiles;
+  u64 acc = 0;
+  for (long j = j0; j < j1; ++j) acc += tile_sum[j];
+  u64 run = block_exclusive_scan(acc, lds);
+  if (t == MT - 1) *total = run + acc;
+  for (long j = j0; j < j1; ++j) {
+    const u64 c = tile_sum[j];
+    tile_sum[j] = run;
+    run += c;
+  }
+}
+
+__global__ __launch_bounds__(MT) void curve_mark_kernel(const uint32_t* __restrict__ keys,
+                                                        const uint8_t* __restrict__ lab, long n, int packed,
+                                                        const u64* __restrict__ tile_prefix, u64* __restrict__ marks) {
+  __shared__ u64 lds[MT];
+  const long first = (long)blockIdx.x * CURVE_TILE + (long)threadIdx.x * CURVE_ITEMS;
+  const u64 mine = curve_thread_sum(keys, lab, n, packed, first);
+  u64 run = tile_prefix[blockIdx.x] + block_exclusive_scan(mine, lds);
+#pragma unroll 4
+  for (int j = 0; j < CURVE_ITEMS; ++j) {
+    const long i = first + j;
+    if (i >= n) break;
+    const u64 word = curve_word(keys, lab, i, packed);
+    const u64 g = run >> 32;
+    if ((word >> 32) && g < (u64)n) marks[g] = ((u64)i << 32) | (run & 0xFFFFFFFFull);   // g < groups <= n
+    run += word;
+  }
+}
+
+// Workgroup b sums a contiguous share of the groups, counted from the top; a thread takes every 256th of them, the
+// threads are folded by a tree: the order depends on n and the number of groups alone.
+__global__ __launch_bounds__(MT) void curve_group_kernel(const u64* __restrict__ marks, const u64* __restrict__ total,
+                                                         long n, u64* __restrict__ part_num,
+                                                         double* __restrict__ part_ap) {
+  __shared__ u64 s_num[MT];
+  __shared__ double s_ap[MT];
+  const int t = threadIdx.x;
+  const u64 tot = *total;
+  const long G = (long)(tot >> 32), P = (long)(tot & 0xFFFFFFFFull);
+  const long per = (G + gridDim.x - 1) / gridDim.x;
+  const long k0 = (long)blockIdx.x * per, k1 = k0 + per < G ? k0 + per : G;
+  u64 num = 0;
+  double ap = 0.0;
+  for (long k = k0 + t; k < k1; k += MT) {
+    const long g = G - 1 - k;
+    const u64 a = marks[g];
+    const long i = (long)(a >> 32), E = (long)(a & 0xFFFFFFFFull);
+    long i2 = n, E2 = P;
+    if (g + 1 < G) {
+      const u64 b = marks[g + 1];
+      i2 = (long)(b >> 32), E2 = (long)(b & 0xFFFFFFFFull);
+    }
+    const long tp = P - E, fp = (n - i) - tp, tp0 = P - E2, fp0 = (n - i2) - tp0;
+    num += (u64)(fp - fp0) * (u64)(tp + tp0);
+    ap += ((double)(tp - tp0) / (double)P) * ((double)tp / (double)(tp + fp));
+  }
+  s_num[t] = num, s_ap[t] = ap;
+  __syncthreads();
+  for (int o = MT / 2; o > 0; o >>= 1) {
+    if (t < o) {
+      s_num[t] += s_num[t + o];
+      s_ap[t] += s_ap[t + o];
+    }
+    __syncthreads();
+  }
+  if (t == 0) part_num[blockIdx.x] = s_num[0], part_ap[blockIdx.x] = s_ap[0];
+}
+
+// the partials in index order, by one thread
+__global__ void curve_final_kernel(const u64* __restrict__ part_num, const double* __restrict__ part_ap, int parts,
+                                   const u64* __restrict__ total, long n, CurveRecord* __restrict__ rec) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  u64 num = 0;
+  double ap = 0.0;
+  for (int j = 0; j < parts; ++j) {
+    num += part_num[j];
+    ap += part_ap[j];
+  }
+  const u64 tot = *total;
+  const u64 P = tot & 0xFFFFFFFFull;
+  rec->num = num, rec->P = P, rec->N = (u64)n - P, rec->groups = tot >> 32, rec->ap = ap;
+}
+
+size_t metrics_curve_ws_bytes(long n) {
+  return up256_bytes((size_t)metrics_curve_tiles(n) * 8) + 256 + up256_bytes((size_t)n * 8) +
+         2 * up256_bytes((size_t)metrics_curve_blocks(n) * 8);
+}
+
+// ws: [tile sums: tiles x 8] [total: 8] [marks: n x 8] [partial numerators] [partial AP sums]
+void launch_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
+                          hipStream_t s) {
+  const long tiles = metrics_curve_tiles(n);
+  const int parts = (int)metrics_curve_blocks(n);
+  char* p = (char*)ws;
+  u64* tile_sum = (u64*)p;
+  p += up256_bytes((size_t)tiles * 8);
+  u64* total = (u64*)p;
+  p += 256;
+  u64* marks = (u64*)p;
+  p += up256_bytes((size_t)n * 8);
+  u64* part_num = (u64*)p;
+  p += up256_bytes((size_t)parts * 8);
+  double* part_ap = (double*)p;
+  hipLaunchKernelGGL(curve_tile_sum_kernel, dim3((unsigned)tiles), dim3(MT), 0, s, keys, labels_sorted, n, packed,
+                     tile_sum);
+  hipLaunchKernelGGL(curve_tile_scan_kernel, dim3(1), dim3(MT), 0, s, tile_sum, tiles, total);
+  hipLaunchKernelGGL(curve_mark_kernel, dim3((unsigned)tiles), dim3(MT), 0, s, keys, labels_sorted, n, packed, tile_sum,
+                     marks);
+  hipLaunchKernelGGL(curve_group_kernel, dim3(parts), dim3(MT), 0, s, marks, total, n, part_num, part_ap);
+  hipLaunchKernelGGL(curve_final_kernel, dim3(1), dim3(64), 0, s, part_num, part_ap, parts, total, n,
+                     (CurveRecord*)record);
+}
+
+}  // namespace aaclip

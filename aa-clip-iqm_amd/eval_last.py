@@ -1,0 +1,230 @@
+"""The evaluation harness of test_last.py with the metrics on the GPU and with the IQM branch this project's own
+training saves.  test_last.py itself stays the reference-shaped script with the host metrics; this module adds, with
+the same names and arguments:
+
+  get_predictions(..., on_device=False)   True: masks (uint8 0 / 1), maps and image scores stay tensors on the device,
+                                          no per-batch copy to the host
+  evaluate(..., device_metrics=False)     True: one class's tensors live on the GPU at a time and
+                                          forward_utils.metrics_eval_device computes the row there (a radix sort and
+                                          exact curve sums: the numbers sklearn gives), instead of copying every batch
+                                          to the host for sklearn; the rows are the very rows of test_last.evaluate
+  load_adapters(model, save_path, logger) as test_last.load_adapters, and -- unless a separate iqm_branch.pth exists,
+                                          which keeps precedence -- the IQM branch from the "iqm_branch" entry that
+                                          train.train_image_adapter writes into image_adapter_<epoch>.pth; test_last.py
+                                          evaluates the branch with its seeded initialisation after training
+  main(argv)                              the arguments and steps of test_last.main plus --device_metrics
+
+python eval_last.py --save_path ... [--device_metrics] [every argument of test_last.py]
+"""
+from __future__ import annotations
+
+import argparse
+import logging
+import os
+from glob import glob
+from typing import Dict, List
+
+import numpy as np
+import torch
+
+import test_last as TL
+from aaclip_hip import engine
+from aaclip_hip.shard import gather_predictions, shard_range
+from dataset import DOMAINS
+from forward_utils import calculate_anomaly_map, image_score, metrics_eval_device
+
+
+def get_predictions(model, class_text_embeddings: torch.Tensor, test_loader, device, img_size: int,
+                    dataset: str = "MVTec", use_iqm: bool = True, on_device: bool = False):
+    """test_last.get_predictions; on_device: masks [N,1,S,S] uint8, preds [N,S,S] and preds_image [N] fp32 are device
+    tensors (labels [N] and the file names stay on the host)."""
+    if not on_device:
+        return TL.get_predictions(model, class_text_embeddings, test_loader, device, img_size, dataset, use_iqm)
+    masks, labels, preds, preds_image, file_names = [], [], [], [], []
+    domain = DOMAINS[dataset]
+    for input_data in test_loader:
+        image = input_data["image"].to(device, non_blocking=True)
+        assert len(set(input_data["class_name"])) == 1, "mixed class not supported"
+        masks.append((input_data["mask"].to(device, non_blocking=True) != 0).to(torch.uint8))
+        labels.append(np.asarray(torch.as_tensor(input_data["label"]).cpu().numpy()))
+        file_names.extend(input_data["file_name"])
+        if image.dtype == torch.uint8:                       # raw HWC frames: resize + normalise on the GPU
+            image = engine.preprocess(image, img_size)
+        epoch_text_feature = class_text_embeddings.unsqueeze(0).repeat(image.size(0), 1, 1) if use_iqm else None
+        patch_features, det_feature, iqm_outputs = model(image, text_embeddings=epoch_text_feature)
+        preds_image.append(image_score(det_feature, class_text_embeddings).float())
+        final_map = calculate_anomaly_map(patch_features, class_text_embeddings, img_size, domain=domain)
+        if iqm_outputs is not None:
+            final_map = engine.iqm_map(patch_features, iqm_outputs.last_hidden_state, img_size, base=final_map,
+                                       w_base=TL.TEXT_WEIGHT, w_iqm=TL.IQM_WEIGHT)
+        preds.append(final_map)
+    return (torch.cat(masks, dim=0), np.concatenate(labels, axis=0), torch.cat(preds, dim=0),
+            torch.cat(preds_image, dim=0), file_names)
+
+
+def evaluate(model, image_datasets: Dict[str, torch.utils.data.Dataset], text_embeddings: Dict[str, torch.Tensor],
+             device, img_size: int, dataset: str, batch_size: int = 32, loader_kwargs=None, logger=None,
+             use_iqm: bool = True, device_metrics: bool = False) -> List[dict]:
+    """test_last.evaluate; device_metrics: the class's masks, maps and image scores stay on the GPU, the row comes from
+    metrics_eval_device, and the tensors are released before the next class.  Under torch.distributed the shards are
+    gathered as host arrays exactly as in test_last.evaluate (so the gloo rehearsal path keeps working) and the
+    gathered arrays of a class are uploaded once."""
+    if not device_metrics:
+        return TL.evaluate(model, image_datasets, text_embeddings, device, img_size, dataset, batch_size=batch_size,
+                           loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm)
+    import torch.distributed as dist
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    rank = dist.get_rank() if world > 1 else 0
+    rows = []
+    for class_name, image_dataset in image_datasets.items():
+        total = len(image_dataset)
+        if world > 1:
+            b, e = shard_range(total, rank, world)
+            image_dataset = torch.utils.data.Subset(image_dataset, list(range(b, e)))
+        if len(image_dataset) > 0:
+            loader = torch.utils.data.DataLoader(image_dataset, batch_size=batch_size, shuffle=False, **(loader_kwargs or {}))
+            with torch.no_grad():
+                masks, labels, preds, preds_image, _ = get_predictions(
+                    model=model, class_text_embeddings=text_embeddings[class_name], test_loader=loader, device=device,
+                    img_size=img_size, dataset=dataset, use_iqm=use_iqm, on_device=world == 1)
+        else:   # more ranks than images of this class
+            masks = np.zeros((0, 1, img_size, img_size), np.float32)
+            labels, preds_image = np.zeros((0,), np.int64), np.zeros((0,), np.float32)
+            preds = np.zeros((0, img_size, img_size), np.float32)
+        if world > 1:
+            gdev = device if dist.get_backend() == "nccl" else None
+            masks, labels, preds, preds_image = gather_predictions(
+                ((masks != 0).astype(np.uint8), labels.astype(np.int64), preds.astype(np.float32),
+                 preds_image.astype(np.float32)), total, device=gdev)
+            masks = torch.from_numpy(np.ascontiguousarray(masks)).to(device)
+            preds = torch.from_numpy(np.ascontiguousarray(preds)).to(device)
+        rows.append(metrics_eval_device(masks, labels, preds, preds_image, class_name, domain=DOMAINS[dataset]))
+        del masks, preds, preds_image          # released before the next class is evaluated
+        if logger:
+            logger.info("%s", rows[-1])
+    avg = {c: float(np.mean([r[c] for r in rows])) for c in TL.NUMERIC_COLS}
+    avg["class name"] = "Average"
+    rows.append(avg)
+    return rows
+
+
+def load_adapters(model, save_path: str, logger=None) -> bool:
+    """As test_last.load_adapters (reference test_last.py:230-251: optional text adapter, newest image adapter by epoch
+    number), then the IQM branch, which the reference never saves: a separate iqm_branch.pth (flat AdaptedCLIP
+    state_dict keys) if present, else the "iqm_branch" entry of that newest image_adapter_<epoch>.pth, {module name:
+    state_dict} as train.train_image_adapter writes it (train.iqm_branch_state), else the seeded initialisation.
+    Logs which source was used."""
+    text_file = glob(os.path.join(save_path, "text_adapter.pth"))
+    adapt_text = len(text_file) > 0
+    if adapt_text:
+        ckpt = torch.load(text_file[0], map_location="cpu", weights_only=True)
+        model.text_adapter.load_state_dict(ckpt["text_adapter"])
+    files = glob(os.path.join(save_path, "image_adapter_*.pth"))
+    assert len(files) > 0, "image adapter checkpoint not found"
+    files = sorted(files, key=lambda x: int(x.split("_")[-1].split(".")[0]))
+    ckpt = torch.load(files[-1], map_location="cpu", weights_only=True)
+    model.image_adapter.load_state_dict(ckpt["image_adapter"])
+    if logger:
+        logger.info("load model from epoch %s", ckpt.get("epoch"))
+    iqm_file = os.path.join(save_path, "iqm_branch.pth")
+    if os.path.exists(iqm_file):
+        sd = torch.load(iqm_file, map_location="cpu", weights_only=True)
+        missing, unexpected = model.load_state_dict(sd.get("iqm_branch", sd), strict=False)
+        assert not unexpected, unexpected
+        source = iqm_file
+    elif "iqm_branch" in ckpt:
+        import train
+        train.load_iqm_branch_state(model, ckpt["iqm_branch"])
+        source = f'the "iqm_branch" entry of {files[-1]}'
+    else:
+        source = None
+    if logger:
+        if source:
+            logger.info("IQM branch weights loaded from %s", source)
+        else:
+            logger.info("no IQM branch weights in %s: the branch keeps its seeded initialisation", save_path)
+    return adapt_text
+
+
+def build_parser() -> argparse.ArgumentParser:
+    """test_last.py's arguments with its defaults (see the notes on the IQM flags there), plus --device_metrics"""
+    parser = argparse.ArgumentParser(description="AA-CLIP evaluation on MI355X, metrics on the host or on the GPU")
+    parser.add_argument("--model_name", type=str, default="ViT-L-14-336")
+    parser.add_argument("--img_size", type=int, default=518)
+    parser.add_argument("--relu", action="store_true")
+    parser.add_argument("--dataset", type=str, default="MVTec")
+    parser.add_argument("--shot", type=int, default=4)
+    parser.add_argument("--batch_size", type=int, default=32)
+    parser.add_argument("--image_batch_size", type=int, default=32)
+    parser.add_argument("--seed", type=int, default=111)
+    parser.add_argument("--save_path", type=str, default="ckpt/baseline")
+    parser.add_argument("--text_adapt_weight", type=float, default=0.1)
+    parser.add_argument("--image_adapt_weight", type=float, default=0.1)
+    parser.add_argument("--text_adapt_until", type=int, default=3)
+    parser.add_argument("--image_adapt_until", type=int, default=6)
+    parser.add_argument("--iqm_hidden_size", type=int, default=768)
+    parser.add_argument("--iqm_num_layers", type=int, default=2)
+    parser.add_argument("--iqm_num_heads", type=int, default=8)
+    parser.add_argument("--iqm_weight", type=float, default=0.7)
+    parser.add_argument("--precision", type=str, default="fp16x2", help="fp16x2 (default), fp32, fp16 or bf16")
+    parser.add_argument("--device_preprocess", action="store_true", help="resize + normalise on the GPU")
+    parser.add_argument("--device_metrics", action="store_true",
+                        help="pixel / image AUROC and AP on the GPU (exact: the numbers of the host path) instead of sklearn")
+    parser.add_argument("--iqm", choices=["on", "off"], default="on",
+                        help="on: maps = 0.6 text + 0.4 IQM like the reference; off: text-only branch")
+    return parser
+
+
+def main(argv=None):
+    """The steps of test_last.main with this module's load_adapters and evaluate."""
+    from dataset import get_dataset
+    from forward_utils import get_adapted_text_embedding
+    from model.adapter import AdaptedCLIP
+    from model.clip import create_model
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.iqm_hidden_size != 768:
+        parser.error("--iqm_hidden_size must be 768 (the visual features' width; see test_last.py)")
+    TL.setup_seed(args.seed)
+    os.makedirs(args.save_path, exist_ok=True)
+    logger = logging.getLogger(__name__)
+    logging.basicConfig(filename=os.path.join(args.save_path, "test.log"), encoding="utf-8", level=logging.INFO)
+    logger.info("args: %s", vars(args))
+    if not torch.cuda.is_available():
+        raise RuntimeError("the AA-CLIP HIP path needs an MI355X; there is no CPU fallback")
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
+    device = torch.device("cuda", local)
+    torch.cuda.set_device(device)
+    if world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group(os.environ.get("AACLIP_BENCH_BACKEND", "nccl"))
+    clip_model = create_model(model_name=args.model_name, img_size=args.img_size, device=device, pretrained="openai",
+                              require_pretrained=True, precision=args.precision)
+    clip_model.eval()
+    model = AdaptedCLIP(clip_model=clip_model, text_adapt_weight=args.text_adapt_weight,
+                        image_adapt_weight=args.image_adapt_weight, text_adapt_until=args.text_adapt_until,
+                        image_adapt_until=args.image_adapt_until, relu=args.relu,
+                        iqm_hidden_size=args.iqm_hidden_size, iqm_num_layers=args.iqm_num_layers,
+                        iqm_num_heads=args.iqm_num_heads).to(device)
+    model.eval()
+    adapt_text = load_adapters(model, args.save_path, logger)
+    image_datasets = get_dataset(args.dataset, args.img_size, None, args.shot, "test", logger=logger,
+                                 device_preprocess=args.device_preprocess)
+    with torch.no_grad():
+        text_embeddings = get_adapted_text_embedding(model if adapt_text else clip_model, args.dataset, device)
+    rows = evaluate(model, image_datasets, text_embeddings, device, args.img_size, args.dataset,
+                    batch_size=args.image_batch_size, loader_kwargs={"num_workers": 4, "pin_memory": True},
+                    logger=logger, use_iqm=args.iqm == "on", device_metrics=args.device_metrics)
+    table = TL.format_table(rows)
+    logger.info("final results:\n%s", table)
+    if int(os.environ.get("RANK", "0")) == 0:
+        print(table)
+    if world > 1:
+        torch.distributed.destroy_process_group()
+    return rows
+
+
+if __name__ == "__main__":
+    main()

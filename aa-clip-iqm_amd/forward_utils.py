@@ -171,6 +171,43 @@ def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names
             "image AUC": round(image_auc, 4) * 100, "image AP": round(image_ap, 4) * 100}
 
 
+def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, class_names, domain):
+    """metrics_eval with the sort and the curve sums on the GPU (csrc/metrics.hip through engine.curve_metrics): the same
+    arguments, shape handling, domain rule, `image_label.max() != image_label.min()` rule, result dict and rounding, and
+    the same numbers -- sklearn's tie groups and definitions, an integer AUROC numerator, an fp64 AP sum.
+    pixel_preds (fp32) and pixel_label (uint8 0 / 1, or anything whose non-zero entries are the positives) are device
+    tensors; the per-image arrays may live anywhere.  Raises ValueError where metrics_eval does (one pixel class only,
+    non-finite scores) and where the reference's normalisation divides by zero (all scores equal)."""
+    import numpy as np
+
+    engine.require_gpu(pixel_preds, "metrics_eval_device")
+    engine.require_gpu(pixel_label, "metrics_eval_device")
+    dev = pixel_preds.device
+    n_img = pixel_preds.shape[0]
+    pp = pixel_preds.to(torch.float32).contiguous()
+    pl = pixel_label if pixel_label.dtype == torch.uint8 else (pixel_label != 0).to(torch.uint8)
+    pixel = engine.curve_metrics(pp, pl, per_image=pp.numel() // n_img)
+    image_label = np.asarray(image_label.cpu() if torch.is_tensor(image_label) else image_label)
+    if image_label.max() != image_label.min():
+        ip = torch.as_tensor(image_preds).to(device=dev, dtype=torch.float32).contiguous()
+        rng, _ = engine.metrics_range(ip)
+        r = engine.metrics_range_host(rng)
+        if r["nonfinite"] or r["max"] == r["min"]:
+            raise ValueError("metrics_eval_device: image scores are not finite or all equal")
+        ip = engine.metrics_normalise(ip, rng)
+        if ip.dim() == 2 and ip.shape[1] == 2:
+            ip = ip[:, 0]
+        ip = ip.reshape(-1)
+        score = pixel.image_max * 0.5 + ip * 0.5 if domain != "Medical" else pixel.image_max
+        il = torch.as_tensor(image_label.reshape(-1) != 0).to(device=dev, dtype=torch.uint8)
+        image = engine.curve_metrics(score, il, normalise=False)
+        image_auc, image_ap = image.auroc, image.ap
+    else:
+        image_auc = image_ap = 0
+    return {"class name": class_names, "pixel AUC": round(pixel.auroc, 4) * 100, "pixel AP": round(pixel.ap, 4) * 100,
+            "image AUC": round(image_auc, 4) * 100, "image AP": round(image_ap, 4) * 100}
+
+
 def visualize(*args, **kwargs):
     """The reference's heat-map writer (forward_utils.py:316-360: cv2 colour maps + file output) is outside this
     build (OUT OF SCOPE).  The name exists so that `from forward_utils import visualize`

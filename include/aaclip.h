@@ -456,6 +456,51 @@ int aaclip_augment_geometric(const float* image, const float* mask, int B, int S
                              const int32_t* shift, const int32_t* flags, float* image_out, float* mask_out,
                              void* stream);
 
+/* Exact AUROC and average precision of one class on the device (csrc/metrics.hip): what sklearn's roc_auc_score and
+ * average_precision_score return for the min-max normalised scores of reference forward_utils.py:233-308 -- the same
+ * tie groups and definitions, no histogram.  n = number of scores, 2 .. 2^31 - 1 (1 .. for aaclip_metrics_normalise).
+ * No floating-point atomics, every floating-point sum in an order fixed by n and the number of tie groups: two calls
+ * give the same bits.  All checks precede the first launch, the workspace size last; errors carry the entry's name.
+ * Every *_workspace_bytes is 0 for a refused n and monotonic in n.  scores / keys 4-byte, records and workspaces 8-byte
+ * aligned; scores, labels, outputs, records and the workspace of a call must not overlap one another (checked).
+ *   aaclip_metrics_range: record <- {min, max, number of non-finite scores (left out of min and max), number of
+ *   non-zero labels (0 when labels is NULL)} in two stages (per-workgroup partials, one workgroup folds them in index
+ *   order).  per_image > 0 (n a multiple of it): image_max[n / per_image] <- the maximum of every image; 0: none.
+ *   aaclip_metrics_normalise: out = (x - min) / (max - min) in fp32, an IEEE subtraction and a correctly rounded
+ *   division (numpy's bits; where min is a zero and the scores hold zeros of both signs, a normalised zero may carry
+ *   the other sign than numpy's), when the record's max != 1.0f; otherwise out = x (reference forward_utils.py:246-253).
+ *   The record is read on the device.  out == scores is allowed.  The map is monotone, so the image maxima of the raw
+ *   scores go through the same call to become the maxima of the normalised images (:277).
+ *   aaclip_metrics_sort: keys[n] <- the ascending order-preserving uint32 images of the scores (-0.0 counts as +0.0),
+ *   by a stable LSD radix sort of four 8-bit passes.  packed = 1: for scores in [0, 1] (bit pattern below 2^30) the
+ *   key is bits << 1 | (label != 0) and labels_sorted is not used; *out_of_range <- the number of scores outside
+ *   [0, 1], for which the result is void.  packed = 0: any finite scores; key = bits ^ (sign ? ~0 : 1 << 31) and
+ *   labels_sorted[n] <- the labels in the keys' order.  One workgroup takes aaclip_metrics_sort_group_items() keys.
+ *   aaclip_metrics_curve: from the sorted keys, record <- {num, P, N, groups, ap}: P / N positives / negatives, groups
+ *   = distinct scores, and over the groups from the top, with (tp, fp) the counts down to and including a group and
+ *   (tp0, fp0) those above it: num = sum (fp - fp0)(tp + tp0), an exact integer with AUROC = num / (2 P N);
+ *   ap = sum ((tp - tp0) / P)(tp / (tp + fp)) in fp64.  P = 0 gives a NaN ap; the caller checks the classes first. */
+typedef struct aaclip_metrics_range_record {
+  float min, max;
+  unsigned long long nonfinite, positives;
+} aaclip_metrics_range_record;
+typedef struct aaclip_metrics_curve_record {
+  unsigned long long num, P, N, groups;
+  double ap;
+} aaclip_metrics_curve_record;
+size_t aaclip_metrics_range_workspace_bytes(long n, long per_image);
+int aaclip_metrics_range(const float* scores, const uint8_t* labels, long n, long per_image, float* image_max,
+                         void* record, void* ws, size_t ws_bytes, void* stream);
+int aaclip_metrics_normalise(const float* scores, float* out, long n, const void* range_record, void* stream);
+size_t aaclip_metrics_sort_workspace_bytes(long n);
+long aaclip_metrics_sort_group_items(void);
+int aaclip_metrics_sort(const float* scores, const uint8_t* labels, long n, int packed, uint32_t* keys,
+                        uint8_t* labels_sorted, unsigned long long* out_of_range, void* ws, size_t ws_bytes,
+                        void* stream);
+size_t aaclip_metrics_curve_workspace_bytes(long n);
+int aaclip_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
+                         size_t ws_bytes, void* stream);
+
 /* Text embedding: x[i*T+t] = token_embedding[tokens[i,t]] + positional_embedding[t].
  * Replaces reference model/adapter.py:277-281 (model/model.py:192-194).  Token ids outside [0, vocab) are CLAMPED
  * to 0 / vocab - 1 (the reference's nn.Embedding raises instead); D a multiple of 4. */
