@@ -721,6 +721,19 @@ def _long_rows(L: int, long_rows: Optional[bool]) -> bool:
     return L > ATTN_BWD_SHORT_MAX_L if long_rows is None else bool(long_rows)
 
 
+def _backward_route(L: int, long_rows: Optional[bool], precision: str) -> str:
+    """The key of _ATTN_BWD / _BLOCK_BWD: "bf16x3" at any L, else "long" or "short" by _long_rows."""
+    return "bf16x3" if precision == "bf16x3" else "long" if _long_rows(L, long_rows) else "short"
+
+
+_ATTN_BWD = {   # route -> (entry, its workspace-size function or None, error tag)
+    "short": ("aaclip_attention_backward", None, "attention_backward"),
+    "long": ("aaclip_attention_backward_long", "aaclip_attention_backward_long_workspace_bytes", "attention_backward_long"),
+    "bf16x3": ("aaclip_attention_backward_long_bf16x3", "aaclip_attention_backward_long_bf16x3_workspace_bytes",
+               "attention_backward_long_bf16x3"),
+}
+
+
 def attention_backward(qkv: torch.Tensor, d_ctx: torch.Tensor, B: int, L: int, heads: int, causal: bool,
                        dq_scale: float = 1.0, long_rows: Optional[bool] = None, precision: str = "fp32") -> torch.Tensor:
     """packed fp32 q|k|v rows [B*L, 3*H*64] (q pre-scaled) + d ctx [B*L, H*64] -> d qkv: aaclip_attention_backward for
@@ -731,21 +744,13 @@ def attention_backward(qkv: torch.Tensor, d_ctx: torch.Tensor, B: int, L: int, h
     qkv, d_ctx = _f32c(qkv), _f32c(d_ctx)
     out = torch.empty_like(qkv)
     lib = _lib.load()
-    if precision == "bf16x3":
-        ws = Workspace.get(qkv.device, lib.aaclip_attention_backward_long_bf16x3_workspace_bytes(int(B), int(L), int(heads)))
-        _lib.check(lib.aaclip_attention_backward_long_bf16x3(qkv.data_ptr(), d_ctx.data_ptr(), out.data_ptr(), B, L, heads,
-                                                             int(causal), float(dq_scale), ws.data_ptr(), ws.numel(),
-                                                             _stream(qkv.device)), "attention_backward_long_bf16x3")
-        return out
-    if _long_rows(L, long_rows):
-        ws = Workspace.get(qkv.device, lib.aaclip_attention_backward_long_workspace_bytes(int(B), int(L), int(heads)))
-        _lib.check(lib.aaclip_attention_backward_long(qkv.data_ptr(), d_ctx.data_ptr(), out.data_ptr(), B, L, heads,
-                                                      int(causal), float(dq_scale), ws.data_ptr(), ws.numel(),
-                                                      _stream(qkv.device)), "attention_backward_long")
-        return out
-    _lib.check(lib.aaclip_attention_backward(qkv.data_ptr(), d_ctx.data_ptr(), out.data_ptr(), B, L, heads,
-                                             int(causal), float(dq_scale), _stream(qkv.device)),
-               "attention_backward")
+    entry, ws_bytes, tag = _ATTN_BWD[_backward_route(L, long_rows, precision)]
+    ws_args = ()
+    if ws_bytes is not None:
+        ws = Workspace.get(qkv.device, getattr(lib, ws_bytes)(int(B), int(L), int(heads)))
+        ws_args = (ws.data_ptr(), ws.numel())
+    _lib.check(getattr(lib, entry)(qkv.data_ptr(), d_ctx.data_ptr(), out.data_ptr(), B, L, heads, int(causal),
+                                   float(dq_scale), *ws_args, _stream(qkv.device)), tag)
     return out
 
 
@@ -775,43 +780,47 @@ def adapter_mix_backward(u: torch.Tensor, z: torch.Tensor, d_y: torch.Tensor, we
     return d_z, d_u
 
 
-def pack_block_transposed(block, adapter_weight: Optional[torch.Tensor]) -> Tuple[BlockWeights, list]:
-    """The `wt` argument of aaclip_block_backward: fp32 transposes [in, out] of the block's matrix weights."""
+# The weight structs of the block backward beside pack_block's: per field the (dtype code, WeightCache kind) of its copy
+_MATRICES = ("qkv_w", "out_w", "fc_w", "proj_w")
+_BLOCK_PACKS = {
+    "transposed": {f: (F32, "transpose") for f in _MATRICES + ("adapter_w",)},
+    "split3": dict({f: (BF16, "split3") for f in _MATRICES}, qkv_w=(BF16, "split3_q"), qkv_b=(F32, "scale_q")),
+    "split3_transposed": dict({f: (BF16, "split3_t") for f in _MATRICES}, adapter_w=(F32, "transpose")),
+}
+
+
+def _pack_block_copies(block, adapter_weight: Optional[torch.Tensor], pack: str) -> Tuple[BlockWeights, list]:
+    params = dict(qkv_w=block.attn.in_proj_weight, qkv_b=block.attn.in_proj_bias, out_w=block.attn.out_proj.weight,
+                  fc_w=block.mlp.c_fc.weight, proj_w=block.mlp.c_proj.weight, adapter_w=adapter_weight)
     refs: list = []
     w = BlockWeights()
-    w.qkv_w = _keep(refs, CACHE.get(block.attn.in_proj_weight, F32, "transpose"))
-    w.out_w = _keep(refs, CACHE.get(block.attn.out_proj.weight, F32, "transpose"))
-    w.fc_w = _keep(refs, CACHE.get(block.mlp.c_fc.weight, F32, "transpose"))
-    w.proj_w = _keep(refs, CACHE.get(block.mlp.c_proj.weight, F32, "transpose"))
-    if adapter_weight is not None:
-        w.adapter_w = _keep(refs, CACHE.get(adapter_weight, F32, "transpose"))
+    for field, (code, kind) in _BLOCK_PACKS[pack].items():
+        if field != "adapter_w" or adapter_weight is not None:
+            setattr(w, field, _keep(refs, CACHE.get(params[field], code, kind)))
     return w, refs
+
+
+def pack_block_transposed(block, adapter_weight: Optional[torch.Tensor]) -> Tuple[BlockWeights, list]:
+    """The `wt` argument of aaclip_block_backward: fp32 transposes [in, out] of the block's matrix weights."""
+    return _pack_block_copies(block, adapter_weight, "transposed")
 
 
 def pack_block_split3(block) -> Tuple[BlockWeights, list]:
-    """The `w3` argument of aaclip_block_backward_long_bf16x3: the stacked bf16 weights [N, 3K], in_proj (weight and
-    fp32 bias) with its q rows times 1/8."""
-    refs: list = []
-    w = BlockWeights()
-    w.qkv_w = _keep(refs, CACHE.get(block.attn.in_proj_weight, BF16, "split3_q"))
-    w.qkv_b = _keep(refs, CACHE.get(block.attn.in_proj_bias, F32, "scale_q"))
-    w.out_w = _keep(refs, CACHE.get(block.attn.out_proj.weight, BF16, "split3"))
-    w.fc_w = _keep(refs, CACHE.get(block.mlp.c_fc.weight, BF16, "split3"))
-    w.proj_w = _keep(refs, CACHE.get(block.mlp.c_proj.weight, BF16, "split3"))
-    return w, refs
+    """The `w3` argument: the stacked bf16 weights [N, 3K], in_proj (weight and fp32 bias) with its q rows times 1/8."""
+    return _pack_block_copies(block, None, "split3")
 
 
 def pack_block_split3_transposed(block, adapter_weight: Optional[torch.Tensor]) -> Tuple[BlockWeights, list]:
     """The `wt3` argument: the stacked bf16 transposes [in, 3 * out]; the adapter's transpose stays fp32."""
-    refs: list = []
-    w = BlockWeights()
-    w.qkv_w = _keep(refs, CACHE.get(block.attn.in_proj_weight, BF16, "split3_t"))
-    w.out_w = _keep(refs, CACHE.get(block.attn.out_proj.weight, BF16, "split3_t"))
-    w.fc_w = _keep(refs, CACHE.get(block.mlp.c_fc.weight, BF16, "split3_t"))
-    w.proj_w = _keep(refs, CACHE.get(block.mlp.c_proj.weight, BF16, "split3_t"))
-    if adapter_weight is not None:
-        w.adapter_w = _keep(refs, CACHE.get(adapter_weight, F32, "transpose"))
-    return w, refs
+    return _pack_block_copies(block, adapter_weight, "split3_transposed")
+
+
+_BLOCK_BWD = {   # route -> (entry, its workspace-size function, error tag)
+    "short": ("aaclip_block_backward", "aaclip_text_backward_workspace_bytes", "block_backward"),
+    "long": ("aaclip_block_backward_long", "aaclip_block_backward_long_workspace_bytes", "block_backward"),
+    "bf16x3": ("aaclip_block_backward_long_bf16x3", "aaclip_block_backward_long_bf16x3_workspace_bytes",
+               "block_backward_bf16x3"),
+}
 
 
 def block_backward(x_in: torch.Tensor, block, B: int, L: int, heads: int, d_out: torch.Tensor, causal: bool = False,
@@ -827,31 +836,21 @@ def block_backward(x_in: torch.Tensor, block, B: int, L: int, heads: int, d_out:
         raise ValueError("block_backward: x_in and d_out must be contiguous fp32")
     D = x_in.shape[1]
     F = block.mlp.c_fc.weight.shape[0]
+    route = _backward_route(L, long_rows, precision)
+    entry, ws_bytes, tag = _BLOCK_BWD[route]
     w, refs = pack_block(block, F32, adapter_weight)
-    wt, refs_t = (pack_block_transposed(block, adapter_weight) if need_input_grad and precision == "fp32"
-                  else (BlockWeights(), []))
+    w3, refs3 = pack_block_split3(block) if route == "bf16x3" else (None, [])
+    pack_t = pack_block_split3_transposed if route == "bf16x3" else pack_block_transposed
+    wt, refs_t = pack_t(block, adapter_weight) if need_input_grad else (BlockWeights(), [])
+    structs = [w, wt] if w3 is None else [w, w3, wt]
     d_in = (d_out if in_place else torch.empty_like(d_out)) if need_input_grad else None
     d_aw = torch.empty(D, D, dtype=torch.float32, device=x_in.device) if adapter_weight is not None else None
-    if precision == "bf16x3":
-        w3, refs3 = pack_block_split3(block)
-        wt3, refs_t = pack_block_split3_transposed(block, adapter_weight) if need_input_grad else (BlockWeights(), [])
-        ws = Workspace.get(x_in.device, lib.aaclip_block_backward_long_bf16x3_workspace_bytes(int(B), int(L), int(D), int(F)))
-        _lib.check(lib.aaclip_block_backward_long_bf16x3(
-            x_in.data_ptr(), C.byref(w), C.byref(w3), C.byref(wt3), float(mix), B, L, D, heads, F,
-            ATTN_CAUSAL if causal else ATTN_FULL, d_out.data_ptr(), _ptr(d_in), _ptr(d_aw), ws.data_ptr(), ws.numel(),
-            _stream(x_in.device)), "block_backward_bf16x3")
-        del refs, refs3, refs_t
-        return d_in, d_aw
-    if _long_rows(L, long_rows):
-        ws = Workspace.get(x_in.device, lib.aaclip_block_backward_long_workspace_bytes(int(B), int(L), int(D), int(F)))
-        entry = lib.aaclip_block_backward_long
-    else:
-        ws = text_backward_workspace(x_in.device, B * L, D, F)
-        entry = lib.aaclip_block_backward
-    _lib.check(entry(x_in.data_ptr(), C.byref(w), C.byref(wt), float(mix), B, L, D, heads, F,
-                     ATTN_CAUSAL if causal else ATTN_FULL, d_out.data_ptr(), _ptr(d_in), _ptr(d_aw),
-                     ws.data_ptr(), ws.numel(), _stream(x_in.device)), "block_backward")
-    del refs, refs_t
+    dims = (B * L, D, F) if route == "short" else (B, L, D, F)
+    ws = Workspace.get(x_in.device, getattr(lib, ws_bytes)(*map(int, dims)))
+    _lib.check(getattr(lib, entry)(x_in.data_ptr(), *map(C.byref, structs), float(mix), B, L, D, heads, F,
+                                   ATTN_CAUSAL if causal else ATTN_FULL, d_out.data_ptr(), _ptr(d_in), _ptr(d_aw),
+                                   ws.data_ptr(), ws.numel(), _stream(x_in.device)), tag)
+    del refs, refs3, refs_t   # they kept the tensors behind the structs' pointers alive until the call was issued
     return d_in, d_aw
 
 

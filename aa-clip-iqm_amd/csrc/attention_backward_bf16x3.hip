@@ -1,57 +1,30 @@
-// Attention backward for any sequence length in the three-term bf16 arithmetic (bf16x3.h): launch_attention_backward_long's
-// contract and pass structure (attention_backward.hip: statistics, then dk | dv, then dq; same formulas, same masking,
-// nothing of size L x L in memory, no atomics), with all five products on v_mfma_f32_32x32x16_bf16 as
+// Attention backward for any sequence length in the three-term bf16 arithmetic (bf16x3.h): the policy of
+// attention_backward_passes.h (the formulas and the three passes are there; launch_attention_backward_long's contract),
+// with all five products on v_mfma_f32_32x32x16_bf16 as
 //   X.Y = Xl.Yh + Xh.Yl + Xh.Yh   (hi = bf16(v), lo = bf16(v - hi); fp32 accumulation, the two small terms first).
-// The statistics m, 1 / sum and delta, the exponent and ds = p (dp - delta) are fp32.
 //   attn3_split_kernel  writes the hi and lo planes of q, k, v and d_ctx once, per (image, head) as [L][64] bf16 (a 32-row
 //                       tile of a plane is 4 KiB of consecutive memory); the passes then never convert an input again.
-//   attn3_stats_kernel  a wave owns 32 queries and walks the key tiles: s^T = K q^T and dp^T = V dctx^T, 12 MFMAs each.
-//   attn3_dkv_kernel    a wave owns 32 keys and walks the query tiles: s = Q k^T, dp = Dctx v^T, then dv^T += Dctx^T p and
-//                       dk^T += Q^T ds with p and ds split in registers -- an accumulator of a score MFMA has its column
-//                       on the lane and its rows in the registers, so registers 8 s .. 8 s + 7 are the B fragment of k-step
-//                       s of the next MFMA as they stand (rows {0..3, 8..11} + 4 h + 16 s); the A fragment for those rows
-//                       comes from the same LDS tile by ds_read_b64_tr_b16, as attention.hip reads V for P.V.
-//   attn3_dq_kernel     a wave owns 32 queries and walks the key tiles: s^T, dp^T as in pass 1, dq^T += K^T ds.
-// Every output element is summed by one wave, over the tiles in ascending order and inside a tile in the order above:
-// two calls give the same bits.  p of pass 2 and of pass 3 agree to rounding only (the small terms swap roles).
+//   pass 1, pass 3      s^T = K q^T and dp^T = V dctx^T, 12 MFMAs each; pass 3 then dq^T += K^T ds.
+//   pass 2              s = Q k^T, dp = Dctx v^T, then dv^T += Dctx^T p and dk^T += Q^T ds with p and ds split in
+//                       registers -- an accumulator of a score MFMA has its column on the lane and its rows in the
+//                       registers, so registers 8 s .. 8 s + 7 are the B fragment of k-step s of the next MFMA as they
+//                       stand (rows {0..3, 8..11} + 4 h + 16 s); the A fragment for those rows comes from the same LDS
+//                       tile by ds_read_b64_tr_b16, as attention.hip reads V for P.V.
+// p of pass 2 and of pass 3 agree to rounding only (the small terms swap roles).
 // LDS: a stage is four 32-row planes (x hi, x lo, y hi, y lo) of 128-byte rows in common.h's tile image (tile_off: both
 // the row reads of a score product and the transposed reads of a gradient product are conflict-free on it), 16 KiB; two
 // stages, plus 3 x 32 statistics per stage in pass 2: 33 536 bytes.  Registers (pass 2, the largest): own rows 64,
 // dk | dv 64, s | dp 32, the split p and ds 32, the tile in flight 16.
 // Per 32 x 32 tile a wave issues 24 (pass 1), 48 (pass 2) and 36 (pass 3) MFMAs of 32 cycles against 64, 128 and 96 of
 // 64 cycles in the fp32 kernels.
+#include "attention_backward_passes.h"
 #include "bf16x3.h"
-#include "common.h"
 
 namespace aaclip {
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float M_START = -1e30f;             // finite: a fully masked tile must not produce inf - inf
 constexpr int PLANE = 4096;                   // bytes of a 32-row plane in LDS
-constexpr int STAGE = 4 * PLANE;
-
-AACLIP_DEV int mfma_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
-
-AACLIP_DEV void xswap(float& a, float& b) { asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
-AACLIP_DEV float half_sum(float v) {   // v of lane (r, 0) + v of lane (r, 1), in that order on both halves
-  float a = v, c = v;
-  xswap(a, c);
-  return a + c;
-}
-AACLIP_DEV float half_max(float v) {
-  float a = v, c = v;
-  xswap(a, c);
-  return fmaxf(a, c);
-}
-
-AACLIP_DEV float attn3_p(float s, float m, float linv) { return __builtin_amdgcn_exp2f(s * LOG2E - m) * linv; }
-
-// The eight planes of the workspace, each [B][H][L][64] bf16
-struct Planes {
-  const bf16* p[8];   // q hi, q lo, k hi, k lo, v hi, v lo, dctx hi, dctx lo
-};
 
 // row `row` of the hi and lo planes as the B fragments of a score product: element j of k-step ks is d = 16 ks + 8 h + j
 struct OwnRow {
@@ -151,8 +124,66 @@ AACLIP_DEV void grad3(const char* th, const char* tl, const Offsets& of, const f
     }
   }
 }
-
 }  // namespace
+
+struct AttnBwdBf16x3 {
+  static constexpr int STAGE_BYTES = 4 * PLANE;
+  static constexpr int ENTRY_NOPS[3] = {2, 63, 2};   // loops at 904, 1380 and 1656 bytes from the entry
+  // The eight planes of the workspace, each [B][H][L][64] bf16: q hi, q lo, k hi, k lo, v hi, v lo, dctx hi, dctx lo
+  struct Args {
+    const bf16* p[8];
+  };
+  const bf16* pl[8];   // field f of this (image, head): hi pl[2 f], lo pl[2 f + 1]
+  Offsets of;
+  int D, r, h;
+  AACLIP_DEV AttnBwdBf16x3(const Args& a, int b, int head, int L, int H, int lane)
+      : D(H * 64), r(lane & 31), h(lane >> 5) {
+    const long hb = ((long)b * H + head) * L * 64;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) pl[i] = a.p[i] + hb;
+    of.init(lane);
+  }
+
+  struct Own : OwnRow {
+    AACLIP_DEV void load(const AttnBwdBf16x3& v, int f, int row) { OwnRow::load(v.pl[2 * f], v.pl[2 * f + 1], row, v.h); }
+  };
+  struct Tile : Tile4 {
+    AACLIP_DEV void load(const AttnBwdBf16x3& v, int fa, int fb, int t0, int L, int tid) {
+      Tile4::load(v.pl[2 * fa], v.pl[2 * fa + 1], v.pl[2 * fb], v.pl[2 * fb + 1], t0, L, tid);
+    }
+  };
+
+  AACLIP_DEV f32x16 score(const char* st, int which, const Own& own) const {
+    return score3(st + 2 * which * PLANE, st + (2 * which + 1) * PLANE, of, own);
+  }
+  AACLIP_DEV void grad_dkv(const char* st, const f32x16& p, const f32x16& ds, f32x16 (&dk)[2], f32x16 (&dv)[2]) const {
+    grad3(st + 2 * PLANE, st + 3 * PLANE, of, p, dv);   // dv^T[d][key] += sum_q dctx[q][d] p[q][key]
+    grad3(st, st + PLANE, of, ds, dk);                  // dk^T[d][key] += sum_q q[q][d] ds[q][key]
+  }
+  AACLIP_DEV void grad_dq(const char* st, const f32x16& ds, f32x16 (&dq)[2]) const { grad3(st, st + PLANE, of, ds, dq); }
+
+  // dk[db][e] = dk[key r][d = 32 db + (e, h)]: registers 4 g .. 4 g + 3 are d = 32 db + 8 g + 4 h ..
+  AACLIP_DEV void store_dkv(float* __restrict__ dqkv, int b, int L, int head, int key0, const f32x16 (&dk)[2],
+                            const f32x16 (&dv)[2]) const {
+    const int kj = key0 + r;
+    if (kj < L) {
+      float* out = dqkv + ((long)b * L + kj) * (3L * D) + head * 64;
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          f32x4 a, c;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            a[j] = dk[db][4 * g + j];
+            c[j] = dv[db][4 * g + j];
+          }
+          *(f32x4*)(out + D + db * 32 + 8 * g + 4 * h) = a;
+          *(f32x4*)(out + 2 * D + db * 32 + 8 * g + 4 * h) = c;
+        }
+    }
+  }
+};
 
 // ------------------------------------------------------------------------------------------------ pre-pass: the planes
 __global__ __launch_bounds__(256) void attn3_split_kernel(const float* __restrict__ qkv, const float* __restrict__ dctx,
@@ -181,242 +212,6 @@ __global__ __launch_bounds__(256) void attn3_split_kernel(const float* __restric
   *(bf16x8*)(dst + plane) = lo;
 }
 
-// ------------------------------------------------------------------------------------------------ pass 1: statistics
-__global__ __launch_bounds__(256) void attn3_stats_kernel(Planes pl, float* __restrict__ stats, int L, int H, int causal) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, h = lane >> 5;
-  const int head = blockIdx.y, b = blockIdx.z;
-  const long hb = ((long)b * H + head) * L * 64;
-  const bf16 *qh = pl.p[0] + hb, *ql = pl.p[1] + hb, *kh = pl.p[2] + hb, *kl = pl.p[3] + hb;
-  const bf16 *vh = pl.p[4] + hb, *vl = pl.p[5] + hb, *dh = pl.p[6] + hb, *dl = pl.p[7] + hb;
-  const int q0 = blockIdx.x * 128 + wave * 32;
-  const int qi = q0 + r;
-  const int qrow = qi < L ? qi : L - 1;
-  OwnRow qo, go;
-  qo.load(qh, ql, qrow, h);
-  go.load(dh, dl, qrow, h);
-  Offsets of;
-  of.init(lane);
-  float m = M_START, l = 0.f, dsum = 0.f;
-  int last_q = blockIdx.x * 128 + 127;
-  if (last_q > L - 1) last_q = L - 1;
-  const int nkt = causal ? (last_q / 32 + 1) : ((L + 31) / 32);
-
-  Tile4 tp;
-  tp.load(kh, kl, vh, vl, 0, L, tid);
-  tp.store(smem, tid);
-  __syncthreads();
-  for (int kt = 0; kt < nkt; ++kt) {
-    const char* st = smem + (kt & 1) * STAGE;
-    const int k0 = kt * 32;
-    if (kt + 1 < nkt) tp.load(kh, kl, vh, vl, k0 + 32, L, tid);
-    if (q0 < L && !(causal && k0 > q0 + 31)) {
-      f32x16 s = score3(st, st + PLANE, of, qo);
-      const f32x16 dp = score3(st + 2 * PLANE, st + 3 * PLANE, of, go);
-      float mt = M_START;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int key = k0 + mfma_row(e, h);
-        const bool dead = (key >= L) || (causal && key > qi);
-        s[e] = dead ? -INFINITY : s[e] * LOG2E;
-        mt = fmaxf(mt, s[e]);
-      }
-      const float mn = fmaxf(m, half_max(mt));
-      const float alpha = __builtin_amdgcn_exp2f(m - mn);
-      float rs = 0.f, rd = 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const float p = __builtin_amdgcn_exp2f(s[e] - mn);   // a dead key: 2^-inf = 0
-        rs += p;
-        rd = fmaf(p, dp[e], rd);
-      }
-      l = l * alpha + half_sum(rs);
-      dsum = dsum * alpha + half_sum(rd);
-      m = mn;
-    }
-    if (kt + 1 < nkt) tp.store(smem + ((kt & 1) ^ 1) * STAGE, tid);   // the other stage: everyone left it one barrier ago
-    __syncthreads();
-  }
-  if (qi < L && h == 0) {
-    const size_t n = (size_t)gridDim.z * H * L;
-    const size_t at = ((size_t)b * H + head) * L + qi;
-    const float linv = 1.0f / l;
-    stats[at] = m;
-    stats[n + at] = linv;
-    stats[2 * n + at] = dsum * linv;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ pass 2: dk, dv
-__global__ __launch_bounds__(256) void attn3_dkv_kernel(Planes pl, const float* __restrict__ stats,
-                                                        float* __restrict__ dqkv, int L, int H, int causal) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
-  __shared__ float St[2][3][32];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, h = lane >> 5;
-  const int head = blockIdx.y, b = blockIdx.z;
-  const int D = H * 64;
-  const long ld = 3L * D;
-  const long hb = ((long)b * H + head) * L * 64;
-  const bf16 *qh = pl.p[0] + hb, *ql = pl.p[1] + hb, *kh = pl.p[2] + hb, *kl = pl.p[3] + hb;
-  const bf16 *vh = pl.p[4] + hb, *vl = pl.p[5] + hb, *dh = pl.p[6] + hb, *dl = pl.p[7] + hb;
-  const size_t nstat = (size_t)gridDim.z * H * L;
-  const float* sbase = stats + ((size_t)b * H + head) * L;
-  const int key0 = blockIdx.x * 128 + wave * 32;
-  const int kj = key0 + r;
-  const int krow = kj < L ? kj : L - 1;
-  OwnRow ko, vo;
-  ko.load(kh, kl, krow, h);
-  vo.load(vh, vl, krow, h);
-  Offsets of;
-  of.init(lane);
-  f32x16 dk[2], dv[2];
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) dk[db][e] = dv[db][e] = 0.f;
-  const int nqt = (L + 31) / 32;
-  const int qt0 = causal ? blockIdx.x * 4 : 0;   // the diagonal tile of this workgroup's first wave
-
-  Tile4 tp;
-  float sreg = 0.f;
-  auto load_stats = [&](int t0) {
-    if (tid < 96) {
-      int row = t0 + (tid & 31);
-      row = row < L ? row : L - 1;
-      sreg = sbase[(size_t)(tid >> 5) * nstat + row];
-    }
-  };
-  auto store_stats = [&](int st) {
-    if (tid < 96) St[st][tid >> 5][tid & 31] = sreg;
-  };
-  tp.load(qh, ql, dh, dl, qt0 * 32, L, tid);
-  load_stats(qt0 * 32);
-  tp.store(smem + (qt0 & 1) * STAGE, tid);
-  store_stats(qt0 & 1);
-  __syncthreads();
-  for (int qt = qt0; qt < nqt; ++qt) {
-    const int sti = qt & 1;
-    const char* st = smem + sti * STAGE;
-    const int t0 = qt * 32;
-    if (qt + 1 < nqt) {
-      tp.load(qh, ql, dh, dl, t0 + 32, L, tid);
-      load_stats(t0 + 32);
-    }
-    if (key0 < L && !(causal && t0 + 31 < key0)) {
-      f32x16 p = score3(st, st + PLANE, of, ko);                      // s[query (e, h)][key r]
-      f32x16 ds = score3(st + 2 * PLANE, st + 3 * PLANE, of, vo);     // dp
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = mfma_row(e, h);
-        const int q = t0 + row;
-        const bool dead = (q >= L) || (causal && kj > q);
-        const float pe = dead ? 0.f : attn3_p(p[e], St[sti][0][row], St[sti][1][row]);
-        p[e] = pe;
-        ds[e] = pe * (ds[e] - St[sti][2][row]);
-      }
-      grad3(st + 2 * PLANE, st + 3 * PLANE, of, p, dv);   // dv^T[d][key] += sum_q dctx[q][d] p[q][key]
-      grad3(st, st + PLANE, of, ds, dk);                  // dk^T[d][key] += sum_q q[q][d] ds[q][key]
-    }
-    if (qt + 1 < nqt) {
-      tp.store(smem + (sti ^ 1) * STAGE, tid);
-      store_stats(sti ^ 1);
-    }
-    __syncthreads();
-  }
-  // dk[db][e] = dk[key r][d = 32 db + (e, h)]: registers 4 g .. 4 g + 3 are d = 32 db + 8 g + 4 h ..
-  if (kj < L) {
-    float* out = dqkv + ((long)b * L + kj) * ld + head * 64;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f32x4 a, c;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          a[j] = dk[db][4 * g + j];
-          c[j] = dv[db][4 * g + j];
-        }
-        *(f32x4*)(out + D + db * 32 + 8 * g + 4 * h) = a;
-        *(f32x4*)(out + 2 * D + db * 32 + 8 * g + 4 * h) = c;
-      }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ pass 3: dq
-__global__ __launch_bounds__(256) void attn3_dq_kernel(Planes pl, const float* __restrict__ stats,
-                                                       float* __restrict__ dqkv, int L, int H, int causal,
-                                                       float dq_scale) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, h = lane >> 5;
-  const int head = blockIdx.y, b = blockIdx.z;
-  const int D = H * 64;
-  const long ld = 3L * D;
-  const long hb = ((long)b * H + head) * L * 64;
-  const bf16 *qh = pl.p[0] + hb, *ql = pl.p[1] + hb, *kh = pl.p[2] + hb, *kl = pl.p[3] + hb;
-  const bf16 *vh = pl.p[4] + hb, *vl = pl.p[5] + hb, *dh = pl.p[6] + hb, *dl = pl.p[7] + hb;
-  const int q0 = blockIdx.x * 128 + wave * 32;
-  const int qi = q0 + r;
-  const int qrow = qi < L ? qi : L - 1;
-  OwnRow qo, go;
-  qo.load(qh, ql, qrow, h);
-  go.load(dh, dl, qrow, h);
-  Offsets of;
-  of.init(lane);
-  const size_t nstat = (size_t)gridDim.z * H * L;
-  const size_t at = ((size_t)b * H + head) * L + qrow;
-  const float m = stats[at], linv = stats[nstat + at], delta = stats[2 * nstat + at];
-  f32x16 dq[2];
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) dq[db][e] = 0.f;
-  int last_q = blockIdx.x * 128 + 127;
-  if (last_q > L - 1) last_q = L - 1;
-  const int nkt = causal ? (last_q / 32 + 1) : ((L + 31) / 32);
-
-  Tile4 tp;
-  tp.load(kh, kl, vh, vl, 0, L, tid);
-  tp.store(smem, tid);
-  __syncthreads();
-  for (int kt = 0; kt < nkt; ++kt) {
-    const char* st = smem + (kt & 1) * STAGE;
-    const int k0 = kt * 32;
-    if (kt + 1 < nkt) tp.load(kh, kl, vh, vl, k0 + 32, L, tid);
-    if (q0 < L && !(causal && k0 > q0 + 31)) {
-      f32x16 ds = score3(st, st + PLANE, of, qo);                          // s[key (e, h)][query r]
-      const f32x16 dp = score3(st + 2 * PLANE, st + 3 * PLANE, of, go);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int key = k0 + mfma_row(e, h);
-        const bool dead = (key >= L) || (causal && key > qi);
-        const float pe = dead ? 0.f : attn3_p(ds[e], m, linv);
-        ds[e] = pe * (dp[e] - delta);
-      }
-      grad3(st, st + PLANE, of, ds, dq);   // dq^T[d][query] += sum_key k[key][d] ds[key][query]
-    }
-    if (kt + 1 < nkt) tp.store(smem + ((kt & 1) ^ 1) * STAGE, tid);
-    __syncthreads();
-  }
-  if (qi < L) {
-    float* dst = dqkv + ((long)b * L + qi) * ld + head * 64;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f32x4 v;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = dq[db][4 * g + j] * dq_scale;
-        *(f32x4*)(dst + db * 32 + 8 * g + 4 * h) = v;
-      }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ host side
 // the row statistics (3 * B * H * L floats), then the eight planes of B * H * L * 64 bf16
 size_t attention_backward_long_bf16x3_ws_bytes(int B, int L, int H) {
@@ -429,14 +224,14 @@ void launch_attention_backward_long_bf16x3(const float* qkv, const float* dctx, 
   float* stats = (float*)ws;
   bf16* planes = (bf16*)((char*)ws + attention_backward_long_ws_bytes(B, L, H));
   const long plane = (long)B * H * L * 64;
-  Planes pl;
+  AttnBwdBf16x3::Args pl;
   for (int i = 0; i < 8; ++i) pl.p[i] = planes + i * plane;
   const long n = (long)B * L * H * 32;
   hipLaunchKernelGGL(attn3_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, qkv, dctx, planes, n, L, H);
   const dim3 g((L + 127) / 128, H, B);
-  hipLaunchKernelGGL(attn3_stats_kernel, g, dim3(256), 0, s, pl, stats, L, H, causal);
-  hipLaunchKernelGGL(attn3_dkv_kernel, g, dim3(256), 0, s, pl, stats, dqkv, L, H, causal);
-  hipLaunchKernelGGL(attn3_dq_kernel, g, dim3(256), 0, s, pl, stats, dqkv, L, H, causal, dq_scale);
+  hipLaunchKernelGGL(attn_bwd_stats_kernel<AttnBwdBf16x3>, g, dim3(256), 0, s, pl, stats, L, H, causal);
+  hipLaunchKernelGGL(attn_bwd_dkv_kernel<AttnBwdBf16x3>, g, dim3(256), 0, s, pl, stats, dqkv, L, H, causal);
+  hipLaunchKernelGGL(attn_bwd_dq_kernel<AttnBwdBf16x3>, g, dim3(256), 0, s, pl, stats, dqkv, L, H, causal, dq_scale);
 }
 
 }  // namespace aaclip

@@ -18,6 +18,12 @@ static int fail(int code, const char* msg) {
   snprintf(g_err, sizeof(g_err), "%s", msg);
   return code;
 }
+// "<entry>: <msg>" as a REQUIRE message, for a name known only at run time (a body that several entries share)
+static const char* in(const char* entry, const char* msg) {
+  static thread_local char text[256];
+  snprintf(text, sizeof(text), "%s: %s", entry, msg);
+  return text;
+}
 #define REQUIRE(cond, msg) \
   do {                     \
     if (!(cond)) return fail(-1, msg); \
@@ -27,7 +33,7 @@ static int fail(int code, const char* msg) {
   do {                                                                          \
     const void* ptrs_[] = {__VA_ARGS__};                                        \
     for (const void* p_ : ptrs_)                                                \
-      if ((uintptr_t)p_ & 15) return fail(-1, what ": pointers must be 16-byte aligned"); \
+      if ((uintptr_t)p_ & 15) return fail(-1, in(what, "pointers must be 16-byte aligned")); \
   } while (0)
 #define REQUIRE_ROW_WIDTH(D) \
   do {                       \
@@ -946,97 +952,124 @@ int aaclip_adapter_mix_backward(const float* u, const float* z, const float* d_y
   return finish("adapter_mix_backward");
 }
 
-// The body of aaclip_block_backward and aaclip_block_backward_long: they differ in the length check, in the workspace
-// (the long form appends the attention statistics to the text-backward layout) and in which attention backward runs.
-static int block_backward_body(bool long_rows, const float* x_in, const aaclip_block_weights* w,
-                               const aaclip_block_weights* wt, float mix, int B, int L, int D, int H, int F, int attn_mode,
-                               const float* d_out, float* d_in, float* d_adapter_w, void* ws, size_t ws_bytes,
-                               void* stream) {
-  REQUIRE(x_in && w && wt && d_out && ws, "block_backward: null pointer");
-  REQUIRE(w->struct_bytes == sizeof(aaclip_block_weights) && wt->struct_bytes == sizeof(aaclip_block_weights),
-          "block_backward: aaclip_block_weights.struct_bytes does not match this library");
+// one buffer for every split3 A operand of the bf16x3 block: each is read by the product right behind the pass that
+// writes it
+static size_t bf16x3_rows_bytes(long rows, int D, int F) {
+  return up256((size_t)rows * 3 * (size_t)(F > 3 * D ? F : 3 * D) * 2);
+}
+
+// The body of aaclip_block_backward, aaclip_block_backward_long and aaclip_block_backward_long_bf16x3 (`name` is the
+// entry's prefix in error texts).  The routes differ in two places.  The workspace tail and the attention backward: the
+// long form appends the attention statistics to the text-backward layout, bf16x3 its split3 buffer a3 and the
+// statistics and planes.  And how one product of the block proper is issued (`product` below): an fp32 GEMM on the
+// fp32 rows against `wp` = w / `wt`, or the split3 pass into a3 and a bf16 GEMM over K' = 3K against the stacked
+// weights `wp` = w3 / `wt` = wt3 (w3's in_proj carries the q scale).  The recomputed forward attention, the adapter's
+// three products and every row op are fp32 on every route.
+enum { BLOCK_BWD_SHORT, BLOCK_BWD_LONG, BLOCK_BWD_LONG_BF16X3 };
+static int block_backward_body(int route, const char* name, const float* x_in, const aaclip_block_weights* w,
+                               const aaclip_block_weights* wp, const aaclip_block_weights* wt, float mix, int B, int L,
+                               int D, int H, int F, int attn_mode, const float* d_out, float* d_in, float* d_adapter_w,
+                               void* ws, size_t ws_bytes, void* stream) {
+  const bool bf16x3 = route == BLOCK_BWD_LONG_BF16X3;
+  REQUIRE(x_in && w && wp && wt && d_out && ws, in(name, "null pointer"));
+  REQUIRE(w->struct_bytes == sizeof(aaclip_block_weights) && wp->struct_bytes == sizeof(aaclip_block_weights) &&
+              wt->struct_bytes == sizeof(aaclip_block_weights),
+          in(name, "aaclip_block_weights.struct_bytes does not match this library"));
   REQUIRE(attn_mode == AACLIP_ATTN_FULL || attn_mode == AACLIP_ATTN_CAUSAL,
-          "block_backward: attn_mode must be AACLIP_ATTN_FULL or AACLIP_ATTN_CAUSAL");
-  REQUIRE(B > 0 && L > 0, "block_backward: empty batch");
-  REQUIRE(D == 64 * H, "block_backward: D must equal 64*H (head dim 64)");
+          in(name, "attn_mode must be AACLIP_ATTN_FULL or AACLIP_ATTN_CAUSAL"));
+  REQUIRE(B > 0 && L > 0, in(name, "empty batch"));
+  REQUIRE(D == 64 * H, in(name, "D must equal 64*H (head dim 64)"));
   REQUIRE_ROW_WIDTH(D);
-  REQUIRE(F > 0 && F % 128 == 0, "block_backward: F must be a multiple of 128");
-  if (const char* m = long_rows ? attention_backward_long_check(B, L, H) : attention_backward_check(B, L, H))
+  REQUIRE(F > 0 && F % 128 == 0, in(name, "F must be a multiple of 128"));
+  if (const char* m = route == BLOCK_BWD_SHORT ? attention_backward_check(B, L, H) : attention_backward_long_check(B, L, H))
     return fail(-1, m);
   const long rows = (long)B * L;
-  REQUIRE(rows < (1L << 31) / 4, "block_backward: too many rows");
-  REQUIRE(w->ln1_w && w->ln1_b && w->qkv_w && w->qkv_b && w->out_w && w->out_b && w->ln2_w && w->ln2_b && w->fc_w &&
-              w->fc_b && w->proj_w && w->proj_b,
-          "block_backward: null weight pointer");
+  REQUIRE(rows < (1L << 31) / 4, in(name, "too many rows"));
+  REQUIRE(w->ln1_w && w->ln1_b && w->out_b && w->ln2_w && w->ln2_b && w->fc_b && w->proj_b,
+          in(name, "null weight pointer"));
+  REQUIRE(wp->qkv_w && wp->qkv_b && wp->out_w && wp->fc_w && wp->proj_w,
+          in(name, bf16x3 ? "null stacked weight pointer" : "null weight pointer"));
   const bool adapter = w->adapter_w != nullptr;
-  REQUIRE(adapter || d_in, "block_backward: nothing to compute (no adapter and d_in is NULL)");
-  REQUIRE(!adapter || d_adapter_w, "block_backward: d_adapter_w is required for a block with an adapter");
+  REQUIRE(adapter || d_in, in(name, "nothing to compute (no adapter and d_in is NULL)"));
+  REQUIRE(!adapter || d_adapter_w, in(name, "d_adapter_w is required for a block with an adapter"));
   REQUIRE(!d_in || (wt->qkv_w && wt->out_w && wt->fc_w && wt->proj_w && (!adapter || wt->adapter_w)),
-          "block_backward: null transposed weight pointer");
+          in(name, "null transposed weight pointer"));
   const TbLayout l = tb_layout(rows, D, F);
-  REQUIRE(ws_bytes >= l.total + (long_rows ? attention_backward_long_ws_bytes(B, L, H) : 0),
-          "block_backward: workspace too small");
-  REQUIRE_ALIGNED16("block_backward", x_in, d_out, d_in, d_adapter_w, ws, w->ln1_w, w->ln2_w, w->adapter_w);
+  const size_t a3_bytes = bf16x3 ? bf16x3_rows_bytes(rows, D, F) : 0;
+  const size_t attn_bytes = bf16x3                     ? attention_backward_long_bf16x3_ws_bytes(B, L, H)
+                            : route == BLOCK_BWD_LONG ? attention_backward_long_ws_bytes(B, L, H)
+                                                      : 0;
+  REQUIRE(ws_bytes >= l.total + a3_bytes + attn_bytes, in(name, "workspace too small"));
+  REQUIRE_ALIGNED16(name, x_in, d_out, d_in, d_adapter_w, ws, w->ln1_w, w->ln2_w, w->adapter_w);
+  if (bf16x3)   // the stacked 16-bit weights; the fp32 routes never asked this of theirs
+    REQUIRE_ALIGNED16(name, wp->qkv_w, wp->out_w, wp->fc_w, wp->proj_w, wt->qkv_w, wt->out_w, wt->fc_w, wt->proj_w,
+                      wt->adapter_w);
   hipStream_t s = (hipStream_t)stream;
   char* base = (char*)ws;
   float *h = (float*)(base + l.h), *qkv = (float*)(base + l.qkv), *ctx = (float*)(base + l.ctx);
   float *x1 = (float*)(base + l.x1), *f = (float*)(base + l.f), *g = (float*)(base + l.g), *x2 = (float*)(base + l.x2);
   float *z = (float*)(base + l.z), *dx = (float*)(base + l.dx), *dqkv = (float*)(base + l.dqkv);
   float* tmp = (float*)(base + l.tmp);
+  void* a3 = base + l.total;
+  void* attn_ws = base + l.total + a3_bytes;
   const int M = (int)rows;
   const int causal = attn_mode == AACLIP_ATTN_CAUSAL;
   const float qscale = 0.125f;
-  // ---- the block's internals again, in fp32, from its input (aaclip_block's arithmetic)
+  // out[M, N] (fp32) = A[M, K] . W[N, K]^T (+ bias (+ resid)), the first q_cols columns times qscale.  bf16x3: in three
+  // terms, W is [N, 3K] bf16 and carries the scale, a3 receives A's split3 rows (A == NULL: a3 holds them already)
+  auto product = [&](const float* A, const void* W, const void* bias, float* out, int N, int K, const float* resid,
+                     int q_cols) {
+    if (bf16x3 && A) launch_split3_rows(A, a3, rows, K, s);
+    GemmParams p = bf16x3 ? gemm_params(a3, 3L * K, W, (const float*)bias, out, N, M, N, 3 * K)
+                          : gemm_params(A, K, W, (const float*)bias, out, N, M, N, K);
+    p.resid = resid;
+    if (!bf16x3 && q_cols) { p.scale_cols = q_cols; p.scale = qscale; }
+    if (bf16x3) launch_gemm(AACLIP_BF16, resid ? EPI_BIAS_RESID : EPI_ACT_F32, p, s);
+    else launch_gemm(AACLIP_F32, resid ? EPI_BIAS_RESID : bias ? EPI_BIAS : EPI_ACT_F32, p, s);
+  };
+  // ---- the block's internals again from its input (aaclip_block's arithmetic), qkv with q scaled
   launch_layernorm(AACLIP_F32, x_in, w->ln1_w, w->ln1_b, h, rows, D, 1e-5f, s);
-  GemmParams p = gemm_params(h, D, w->qkv_w, w->qkv_b, qkv, 3 * D, M, 3 * D, D);
-  p.scale_cols = D; p.scale = qscale;
-  launch_gemm(AACLIP_F32, EPI_BIAS, p, s);
+  product(h, wp->qkv_w, wp->qkv_b, qkv, 3 * D, D, nullptr, D);
   launch_attention(AACLIP_F32, qkv, ctx, B, L, H, causal, 0, s);
-  p = gemm_params(ctx, D, w->out_w, w->out_b, x1, D, M, D, D);
-  p.resid = x_in;
-  launch_gemm(AACLIP_F32, EPI_BIAS_RESID, p, s);
+  product(ctx, wp->out_w, w->out_b, x1, D, D, x_in, 0);
   launch_layernorm(AACLIP_F32, x1, w->ln2_w, w->ln2_b, h, rows, D, 1e-5f, s);
-  p = gemm_params(h, D, w->fc_w, w->fc_b, f, F, M, F, D);
-  launch_gemm(AACLIP_F32, EPI_BIAS, p, s);
+  product(h, wp->fc_w, w->fc_b, f, F, D, nullptr, 0);
   const float* dy = d_out;   // gradient of the stream after the MLP half
   if (adapter) {
-    launch_gelu_forward(f, g, rows * F, s);
-    p = gemm_params(g, F, w->proj_w, w->proj_b, x2, D, M, D, F);
-    p.resid = x1;
-    launch_gemm(AACLIP_F32, EPI_BIAS_RESID, p, s);
-    p = gemm_params(x2, D, w->adapter_w, nullptr, z, D, M, D, D);
+    if (bf16x3) launch_gelu_forward_split3(f, a3, rows, F, s);
+    else launch_gelu_forward(f, g, rows * F, s);
+    product(bf16x3 ? nullptr : g, wp->proj_w, w->proj_b, x2, D, F, x1, 0);
+    GemmParams p = gemm_params(x2, D, w->adapter_w, nullptr, z, D, M, D, D);
     launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
     launch_adapter_mix_backward(x2, z, d_out, z, dx, rows, D, mix, s);   // z <- dz, dx <- the direct d x2
     launch_wgrad(z, D, x2, D, d_adapter_w, rows, D, D, base + l.wg, s);
-    if (!d_in) return finish("block_backward");
+    if (!d_in) return finish(name);
     p = gemm_params(z, D, wt->adapter_w, nullptr, tmp, D, M, D, D);
     launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
     launch_add_rows(dx, tmp, dx, rows * D, s);
     dy = dx;
   }
   // ---- x2 = x1 + c_proj(gelu(f)),  f = c_fc(ln_2 x1)
-  p = gemm_params(dy, D, wt->proj_w, nullptr, g, F, M, F, D);
-  launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
-  launch_gelu_backward(f, g, g, rows * F, s);
-  p = gemm_params(g, F, wt->fc_w, nullptr, tmp, D, M, D, F);
-  launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+  product(dy, wt->proj_w, nullptr, g, F, D, nullptr, 0);
+  if (bf16x3) launch_gelu_backward_split3(f, g, a3, rows, F, s);
+  else launch_gelu_backward(f, g, g, rows * F, s);
+  product(bf16x3 ? nullptr : g, wt->fc_w, nullptr, tmp, D, F, nullptr, 0);
   launch_layernorm_backward(x1, w->ln2_w, tmp, dy, dx, nullptr, rows, D, 1e-5f, s);   // dx <- d x1
   // ---- x1 = x_in + out_proj(attention(qkv)),  qkv = in_proj(ln_1 x_in), q scaled
-  p = gemm_params(dx, D, wt->out_w, nullptr, tmp, D, M, D, D);
-  launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
-  if (long_rows) launch_attention_backward_long(qkv, tmp, dqkv, B, L, H, causal, qscale, base + l.total, s);
+  product(dx, wt->out_w, nullptr, tmp, D, D, nullptr, 0);
+  if (bf16x3) launch_attention_backward_long_bf16x3(qkv, tmp, dqkv, B, L, H, causal, qscale, attn_ws, s);
+  else if (route == BLOCK_BWD_LONG) launch_attention_backward_long(qkv, tmp, dqkv, B, L, H, causal, qscale, attn_ws, s);
   else launch_attention_backward(qkv, tmp, dqkv, B, L, H, causal, qscale, s);
-  p = gemm_params(dqkv, 3 * D, wt->qkv_w, nullptr, tmp, D, M, D, 3 * D);
-  launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
+  product(dqkv, wt->qkv_w, nullptr, tmp, D, 3 * D, nullptr, 0);
   launch_layernorm_backward(x_in, w->ln1_w, tmp, dx, d_in, nullptr, rows, D, 1e-5f, s);
-  return finish("block_backward");
+  return finish(name);
 }
 
 int aaclip_block_backward(const float* x_in, const aaclip_block_weights* w, const aaclip_block_weights* wt, float mix,
                           int B, int L, int D, int H, int F, int attn_mode, const float* d_out, float* d_in,
                           float* d_adapter_w, void* ws, size_t ws_bytes, void* stream) {
-  return block_backward_body(false, x_in, w, wt, mix, B, L, D, H, F, attn_mode, d_out, d_in, d_adapter_w, ws, ws_bytes,
-                             stream);
+  return block_backward_body(BLOCK_BWD_SHORT, "block_backward", x_in, w, w, wt, mix, B, L, D, H, F, attn_mode, d_out,
+                             d_in, d_adapter_w, ws, ws_bytes, stream);
 }
 
 size_t aaclip_block_backward_long_workspace_bytes(int B, int L, int D, int F) {
@@ -1047,8 +1080,8 @@ size_t aaclip_block_backward_long_workspace_bytes(int B, int L, int D, int F) {
 int aaclip_block_backward_long(const float* x_in, const aaclip_block_weights* w, const aaclip_block_weights* wt,
                                float mix, int B, int L, int D, int H, int F, int attn_mode, const float* d_out,
                                float* d_in, float* d_adapter_w, void* ws, size_t ws_bytes, void* stream) {
-  return block_backward_body(true, x_in, w, wt, mix, B, L, D, H, F, attn_mode, d_out, d_in, d_adapter_w, ws, ws_bytes,
-                             stream);
+  return block_backward_body(BLOCK_BWD_LONG, "block_backward", x_in, w, w, wt, mix, B, L, D, H, F, attn_mode, d_out,
+                             d_in, d_adapter_w, ws, ws_bytes, stream);
 }
 
 // ---- The three-term bf16 backward of the visual blocks (bf16x3.h; include/aaclip.h, "bf16x3")
@@ -1077,11 +1110,6 @@ int aaclip_attention_backward_long_bf16x3(const float* qkv, const float* d_ctx, 
   return finish("attention_backward_long_bf16x3");
 }
 
-// one buffer for every split3 A operand of the block: each is read by the product right behind the pass that writes it
-static size_t bf16x3_rows_bytes(long rows, int D, int F) {
-  return up256((size_t)rows * 3 * (size_t)(F > 3 * D ? F : 3 * D) * 2);
-}
-
 size_t aaclip_block_backward_long_bf16x3_workspace_bytes(int B, int L, int D, int F) {
   if (B <= 0 || L <= 0 || D <= 0 || F < 0) return 0;
   const long rows = (long)B * L;
@@ -1089,96 +1117,12 @@ size_t aaclip_block_backward_long_bf16x3_workspace_bytes(int B, int L, int D, in
          attention_backward_long_bf16x3_ws_bytes(B, L, (D + 63) / 64);
 }
 
-// block_backward_body(long_rows) step for step; the eight products of the block proper are bf16 GEMMs over K' = 3K on
-// split3 rows against the stacked weights, the attention backward is the bf16x3 one.  The recomputed forward attention,
-// the adapter's three products and every row op are the fp32 kernels of block_backward_body.
 int aaclip_block_backward_long_bf16x3(const float* x_in, const aaclip_block_weights* w, const aaclip_block_weights* w3,
                                       const aaclip_block_weights* wt3, float mix, int B, int L, int D, int H, int F,
                                       int attn_mode, const float* d_out, float* d_in, float* d_adapter_w, void* ws,
                                       size_t ws_bytes, void* stream) {
-  REQUIRE(x_in && w && w3 && wt3 && d_out && ws, "block_backward_bf16x3: null pointer");
-  REQUIRE(w->struct_bytes == sizeof(aaclip_block_weights) && w3->struct_bytes == sizeof(aaclip_block_weights) &&
-              wt3->struct_bytes == sizeof(aaclip_block_weights),
-          "block_backward_bf16x3: aaclip_block_weights.struct_bytes does not match this library");
-  REQUIRE(attn_mode == AACLIP_ATTN_FULL || attn_mode == AACLIP_ATTN_CAUSAL,
-          "block_backward_bf16x3: attn_mode must be AACLIP_ATTN_FULL or AACLIP_ATTN_CAUSAL");
-  REQUIRE(B > 0 && L > 0, "block_backward_bf16x3: empty batch");
-  REQUIRE(D == 64 * H, "block_backward_bf16x3: D must equal 64*H (head dim 64)");
-  REQUIRE_ROW_WIDTH(D);
-  REQUIRE(F > 0 && F % 128 == 0, "block_backward_bf16x3: F must be a multiple of 128");
-  if (const char* m = attention_backward_long_check(B, L, H)) return fail(-1, m);
-  const long rows = (long)B * L;
-  REQUIRE(rows < (1L << 31) / 4, "block_backward_bf16x3: too many rows");
-  REQUIRE(w->ln1_w && w->ln1_b && w->out_b && w->ln2_w && w->ln2_b && w->fc_b && w->proj_b,
-          "block_backward_bf16x3: null weight pointer");
-  REQUIRE(w3->qkv_w && w3->qkv_b && w3->out_w && w3->fc_w && w3->proj_w,
-          "block_backward_bf16x3: null stacked weight pointer");
-  const bool adapter = w->adapter_w != nullptr;
-  REQUIRE(adapter || d_in, "block_backward_bf16x3: nothing to compute (no adapter and d_in is NULL)");
-  REQUIRE(!adapter || d_adapter_w, "block_backward_bf16x3: d_adapter_w is required for a block with an adapter");
-  REQUIRE(!d_in || (wt3->qkv_w && wt3->out_w && wt3->fc_w && wt3->proj_w && (!adapter || wt3->adapter_w)),
-          "block_backward_bf16x3: null transposed weight pointer");
-  const TbLayout l = tb_layout(rows, D, F);
-  const size_t a3_bytes = bf16x3_rows_bytes(rows, D, F);
-  REQUIRE(ws_bytes >= l.total + a3_bytes + attention_backward_long_bf16x3_ws_bytes(B, L, H),
-          "block_backward_bf16x3: workspace too small");
-  REQUIRE_ALIGNED16("block_backward_bf16x3", x_in, d_out, d_in, d_adapter_w, ws, w->ln1_w, w->ln2_w, w->adapter_w,
-                    w3->qkv_w, w3->out_w, w3->fc_w, w3->proj_w, wt3->qkv_w, wt3->out_w, wt3->fc_w, wt3->proj_w,
-                    wt3->adapter_w);
-  hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)ws;
-  float *h = (float*)(base + l.h), *qkv = (float*)(base + l.qkv), *ctx = (float*)(base + l.ctx);
-  float *x1 = (float*)(base + l.x1), *f = (float*)(base + l.f), *g = (float*)(base + l.g), *x2 = (float*)(base + l.x2);
-  float *z = (float*)(base + l.z), *dx = (float*)(base + l.dx), *dqkv = (float*)(base + l.dqkv);
-  float* tmp = (float*)(base + l.tmp);
-  void* a3 = base + l.total;
-  void* attn_ws = base + l.total + a3_bytes;
-  const int M = (int)rows;
-  const int causal = attn_mode == AACLIP_ATTN_CAUSAL;
-  // out[M, N] (fp32) = A[M, K] . W[N, K]^T (+ bias) in three terms: a3 holds A's split3 rows, W3 is [N, 3K] bf16
-  auto product = [&](const void* W3, const float* bias, float* out, int N, int K, const float* resid) {
-    GemmParams p = gemm_params(a3, 3L * K, W3, bias, out, N, M, N, 3 * K);
-    p.resid = resid;
-    launch_gemm(AACLIP_BF16, resid ? EPI_BIAS_RESID : EPI_ACT_F32, p, s);
-  };
-  // ---- the block's internals again from its input; qkv comes out with q scaled: w3->qkv_w and w3->qkv_b carry 1/8
-  launch_layernorm(AACLIP_F32, x_in, w->ln1_w, w->ln1_b, h, rows, D, 1e-5f, s);
-  launch_split3_rows(h, a3, rows, D, s);
-  product(w3->qkv_w, (const float*)w3->qkv_b, qkv, 3 * D, D, nullptr);
-  launch_attention(AACLIP_F32, qkv, ctx, B, L, H, causal, 0, s);
-  launch_split3_rows(ctx, a3, rows, D, s);
-  product(w3->out_w, (const float*)w->out_b, x1, D, D, x_in);
-  launch_layernorm(AACLIP_F32, x1, w->ln2_w, w->ln2_b, h, rows, D, 1e-5f, s);
-  launch_split3_rows(h, a3, rows, D, s);
-  product(w3->fc_w, (const float*)w->fc_b, f, F, D, nullptr);
-  const float* dy = d_out;   // gradient of the stream after the MLP half
-  if (adapter) {
-    launch_gelu_forward_split3(f, a3, rows, F, s);
-    product(w3->proj_w, (const float*)w->proj_b, x2, D, F, x1);
-    GemmParams p = gemm_params(x2, D, w->adapter_w, nullptr, z, D, M, D, D);
-    launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
-    launch_adapter_mix_backward(x2, z, d_out, z, dx, rows, D, mix, s);   // z <- dz, dx <- the direct d x2
-    launch_wgrad(z, D, x2, D, d_adapter_w, rows, D, D, base + l.wg, s);
-    if (!d_in) return finish("block_backward_bf16x3");
-    p = gemm_params(z, D, wt3->adapter_w, nullptr, tmp, D, M, D, D);
-    launch_gemm(AACLIP_F32, EPI_ACT_F32, p, s);
-    launch_add_rows(dx, tmp, dx, rows * D, s);
-    dy = dx;
-  }
-  // ---- x2 = x1 + c_proj(gelu(f)),  f = c_fc(ln_2 x1)
-  launch_split3_rows(dy, a3, rows, D, s);
-  product(wt3->proj_w, nullptr, g, F, D, nullptr);
-  launch_gelu_backward_split3(f, g, a3, rows, F, s);
-  product(wt3->fc_w, nullptr, tmp, D, F, nullptr);
-  launch_layernorm_backward(x1, w->ln2_w, tmp, dy, dx, nullptr, rows, D, 1e-5f, s);   // dx <- d x1
-  // ---- x1 = x_in + out_proj(attention(qkv)),  qkv = in_proj(ln_1 x_in), q scaled
-  launch_split3_rows(dx, a3, rows, D, s);
-  product(wt3->out_w, nullptr, tmp, D, D, nullptr);
-  launch_attention_backward_long_bf16x3(qkv, tmp, dqkv, B, L, H, causal, 0.125f, attn_ws, s);
-  launch_split3_rows(dqkv, a3, rows, 3 * D, s);
-  product(wt3->qkv_w, nullptr, tmp, D, 3 * D, nullptr);
-  launch_layernorm_backward(x_in, w->ln1_w, tmp, dx, d_in, nullptr, rows, D, 1e-5f, s);
-  return finish("block_backward_bf16x3");
+  return block_backward_body(BLOCK_BWD_LONG_BF16X3, "block_backward_bf16x3", x_in, w, w3, wt3, mix, B, L, D, H, F,
+                             attn_mode, d_out, d_in, d_adapter_w, ws, ws_bytes, stream);
 }
 
 int aaclip_row_head_backward(const float* x, const int32_t* tokens, const float* ln_w, const float* ln_b,

@@ -343,6 +343,32 @@ def test_gemm_k_loop_has_no_waterfall_loops(tmp_path):
         assert not any(op.startswith("scratch_") for op in loop), f"half tile, EPI {epi} NP {np_}: spill in the K loop"
 
 
+def test_bf16x3_attention_backward_tile_loops_start_where_measured(tmp_path):
+    """AttnBwdBf16x3::ENTRY_NOPS pads the three pass kernels so that their tile loops start 904, 1380 and 1656 bytes
+    behind the kernel's entry, the distances they were timed at ("Timing").  The pad is right only for the
+    code the compiler emits before each loop; a drift must fail here, not cost its 1 % unseen.  The loop's head is the
+    nearest target of a backward branch."""
+    import re
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    objdump = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "llvm-objdump")
+    if not (os.path.exists(hipcc) and os.path.exists(objdump)):
+        pytest.skip("hipcc / llvm-objdump not available")
+    src = os.path.join(REPO, "aa-clip-iqm_amd", "csrc", "attention_backward_bf16x3.hip")
+    obj = str(tmp_path / "attention_backward_bf16x3.co")
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
+                           "--cuda-device-only", "--no-gpu-bundle-output", "-c", src, "-o", obj], stderr=subprocess.DEVNULL)
+    text = subprocess.run([objdump, "-d", obj], capture_output=True, text=True, check=True).stdout
+    heads = {}   # pass -> smallest offset a branch behind it jumps back to
+    branch = r"branch\S*\s+\d+\s+// ([0-9A-F]+): [0-9A-F]+ <\w*attn_bwd_(\w+?)_kernelI\w+\+0x([0-9a-f]+)>"
+    for at, kernel, off in re.findall(branch, text):
+        base = int(re.search(rf"^([0-9a-f]+) <\w*attn_bwd_{kernel}_kernelI", text, re.M).group(1), 16)
+        if int(off, 16) < int(at, 16) - base:
+            heads[kernel] = min(heads.get(kernel, 1 << 30), int(off, 16))
+    assert heads == {"stats": 904, "dkv": 1380, "dq": 1656}
+
+
 def test_tower_run_plans_one_call_with_tap_buffers(monkeypatch):
     """Host logic of Transformer.run (no GPU: engine.run_blocks is replaced by a recorder): the whole tower is ONE
     aaclip_blocks_taps call with one output buffer per block; a tapped buffer is never written again (the block behind
