@@ -12,7 +12,7 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AACLIP_LIB") or os.path.join(_HERE, "libaaclip_hip.so")   # AACLIP_LIB: experiment builds
-ABI_VERSION = 9   # include/aaclip.h AACLIP_ABI_VERSION this binding was written against
+ABI_VERSION = 10   # include/aaclip.h AACLIP_ABI_VERSION this binding was written against
 
 F32, F16, BF16, F16X2 = 0, 1, 2, 3   # F16X2: split fp16 (hi + lo pairs), include/aaclip.h
 EXACT16_QKV, EXACT16_OUT, EXACT16_FC, EXACT16_PROJ, EXACT16_ADAPTER = 1, 2, 4, 8, 16
@@ -35,6 +35,17 @@ class BlockWeights(C.Structure):
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         self.struct_bytes = C.sizeof(BlockWeights)
+
+
+class GemmFusedArgs(C.Structure):
+    """struct aaclip_gemm_fused_args (include/aaclip.h): the fields of a product that only the block path sets.
+    struct_bytes is filled in on construction; the library refuses any other size."""
+    _fields_ = [("struct_bytes", _sz), ("resid", _vp), ("out16", _vp), ("stats_out", _vp), ("row_ab", _vp),
+                ("col_s", _vp), ("w_exact16", _i), ("out_qk8", _i), ("out_no_hi8", _i)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_bytes = C.sizeof(GemmFusedArgs)
 
 
 # name -> (restype, argtypes); every symbol include/aaclip.h declares
@@ -104,6 +115,12 @@ SIGNATURES = {
     "aaclip_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "aaclip_attention_log2q": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "aaclip_adapter_mix": (_i, [_vp, _vp, _l, _i, _f, _vp]),
+    "aaclip_gemm_fused": (_i, [_i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _f, C.POINTER(GemmFusedArgs), _vp]),
+    "aaclip_ln_stats_finalize": (_i, [_vp, _vp, _l, _i, _f, _vp]),
+    "aaclip_adapter_mix_fold": (_i, [_i, _vp, _vp, _l, _i, _f, _vp, _vp, _vp]),
+    "aaclip_attention_split": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "aaclip_layernorm_split": (_i, [_vp, _vp, _vp, _vp, _l, _i, _f, _i, _vp]),
+    "aaclip_split_rows": (_i, [_vp, _vp, _l, _i, _i, _vp]),
     "aaclip_small_attention": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "aaclip_cross_rows_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "aaclip_cross_rows": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),

@@ -219,6 +219,103 @@ int aaclip_adapter_mix(float* x, const float* a, long rows, int D, float weight,
   return finish("adapter_mix");
 }
 
+// The forms of the building blocks that only aaclip_block(s) selects, one entry each (include/aaclip.h, "The block
+// path's forms of the building blocks").  Every refusal precedes the first launch.
+int aaclip_gemm_fused(int dtype, int epi, const void* A, long lda, const void* W, const float* bias, void* out, long ldc,
+                      int M, int N, int K, int act, int scale_cols, float scale, const aaclip_gemm_fused_args* f,
+                      void* stream) {
+  REQUIRE(f, "gemm_fused: null argument struct");
+  REQUIRE(f->struct_bytes == sizeof(aaclip_gemm_fused_args),
+          "gemm_fused: aaclip_gemm_fused_args.struct_bytes does not match this library (binding generated from another "
+          "include/aaclip.h revision?)");
+  REQUIRE(dtype_ok(dtype), "gemm_fused: bad dtype");
+  REQUIRE(epi >= AACLIP_EPI_BIAS && epi <= AACLIP_EPI_ACT_F32, "gemm_fused: bad epilogue");
+  REQUIRE(f->w_exact16 >= 0 && f->w_exact16 <= 1 && f->out_no_hi8 >= 0 && f->out_no_hi8 <= 1 && f->out_qk8 >= 0,
+          "gemm_fused: w_exact16 and out_no_hi8 are 0 or 1, out_qk8 is a column count");
+  GemmParams p = gemm_params(A, lda, W, bias, out, ldc, M, N, K);
+  p.scale_cols = scale_cols; p.scale = scale; p.act = act;
+  p.resid = f->resid; p.out16 = f->out16; p.stats_out = f->stats_out; p.row_ab = f->row_ab; p.col_s = f->col_s;
+  p.w_exact16 = f->w_exact16; p.out_qk8 = f->out_qk8; p.out_no_hi8 = f->out_no_hi8;
+  const char* m = gemm_check(dtype, epi, p);
+  if (m) return fail(-1, m);
+  const bool plain16 = dtype == AACLIP_F16 || dtype == AACLIP_BF16;
+  REQUIRE(!p.resid || epi == EPI_BIAS_RESID, "gemm_fused: resid belongs to the residual epilogue");
+  REQUIRE(!p.resid || !((uintptr_t)p.resid & 15), "gemm_fused: resid must be 16-byte aligned");
+  REQUIRE((p.out16 != nullptr) == (p.stats_out != nullptr), "gemm_fused: out16 and stats_out are given together");
+  REQUIRE(!p.out16 || (epi == EPI_BIAS_RESID && plain16 && gemm_routes_to_256t(dtype, p)),
+          "gemm_fused: out16 / stats_out need the residual epilogue of an fp16 / bf16 product that runs a 256-row-tile "
+          "kernel (M >= 4096, N a multiple of 256, GEMM variant other than 1)");
+  REQUIRE(!p.out16 || !(((uintptr_t)p.out16 | (uintptr_t)p.stats_out) & 7), "gemm_fused: out16 / stats_out must be 8-byte aligned");
+  REQUIRE((p.row_ab != nullptr) == (p.col_s != nullptr), "gemm_fused: row_ab and col_s are given together");
+  REQUIRE(!p.row_ab || ((epi == EPI_BIAS || epi == EPI_BIAS_GELU) && plain16 && gemm_routes_to_256t(dtype, p)),
+          "gemm_fused: row_ab / col_s need the bias or GELU epilogue of an fp16 / bf16 product that runs a 256-row-tile "
+          "kernel (M >= 4096, N a multiple of 256, GEMM variant other than 1)");
+  REQUIRE(!p.row_ab || (!((uintptr_t)p.row_ab & 7) && !((uintptr_t)p.col_s & 15)),
+          "gemm_fused: row_ab must be 8-byte, col_s 16-byte aligned");
+  REQUIRE(!p.w_exact16 || (dtype == AACLIP_F16X2 && K % 256 == 0),
+          "gemm_fused: w_exact16 (3-plane weight) needs split fp16 and K a multiple of 256");
+  REQUIRE(!p.out_no_hi8 || (dtype == AACLIP_F16X2 && epi == EPI_BIAS_GELU),
+          "gemm_fused: out_no_hi8 belongs to the GELU epilogue of a split fp16 product");
+  if (p.out_qk8) {
+    REQUIRE(epi == EPI_BIAS && dtype == AACLIP_F16X2 && gemm_split_routes_to_256t(p),
+            "gemm_fused: out_qk8 needs the bias epilogue of a split fp16 product that runs the 256-row-tile kernel "
+            "(M >= 4096, N a multiple of 256, GEMM variant other than 1)");
+    REQUIRE(p.out_qk8 % 64 == 0 && p.out_qk8 <= N, "gemm_fused: out_qk8 must be a multiple of 64 and at most N");
+  }
+  launch_gemm(dtype, epi, p, (hipStream_t)stream);
+  return finish("gemm_fused");
+}
+
+int aaclip_ln_stats_finalize(const float* partials, float* row_ab, long rows, int D, float eps, void* stream) {
+  REQUIRE(partials && row_ab, "ln_stats_finalize: null pointer");
+  REQUIRE(!(((uintptr_t)partials | (uintptr_t)row_ab) & 7), "ln_stats_finalize: pointers must be 8-byte aligned");
+  REQUIRE(rows > 0 && rows < (1L << 27), "ln_stats_finalize: rows must be in 1 .. 2^27 - 1");
+  REQUIRE_ROW_WIDTH(D);
+  launch_ln_stats_finalize(partials, row_ab, rows, D / 64, D, eps, (hipStream_t)stream);
+  return finish("ln_stats_finalize");
+}
+
+int aaclip_adapter_mix_fold(int dtype, float* x, const float* a, long rows, int D, float weight, void* out16,
+                            float* row_ab, void* stream) {
+  REQUIRE(dtype == AACLIP_F16 || dtype == AACLIP_BF16, "adapter_mix_fold: fp16 or bf16 rows only");
+  REQUIRE(x && a && out16 && row_ab && rows > 0, "adapter_mix_fold: bad arguments");
+  REQUIRE(!(((uintptr_t)x | (uintptr_t)a) & 15) && !(((uintptr_t)out16 | (uintptr_t)row_ab) & 7),
+          "adapter_mix_fold: x and a must be 16-byte, out16 and row_ab 8-byte aligned");
+  REQUIRE_ROW_WIDTH(D);
+  launch_adapter_mix_fold(dtype, x, a, rows, D, weight, out16, row_ab, (hipStream_t)stream);
+  return finish("adapter_mix_fold");
+}
+
+int aaclip_attention_split(const void* qkv, void* ctx, int B, int L, int H, int causal, int log2q, int qk8, int hi8,
+                           void* stream) {
+  REQUIRE(qkv && ctx, "attention_split: null pointer");
+  REQUIRE(B > 0 && L > 0 && H > 0, "attention_split: empty problem");
+  REQUIRE(B <= 65535 && H <= 65535, "attention_split: grid limit");
+  REQUIRE((long)L * 3 * 64 * H * 4 < (1L << 31), "attention_split: L * 3 * 64 * H * 4 must stay below 2^31 (32-bit row offsets)");
+  REQUIRE((long)((L + 255) / 256) * H * B < (1L << 30), "attention_split: too many workgroups");
+  REQUIRE(!qk8 || (log2q && attention_qk8_applicable(L, causal)),
+          "attention_split: the e4m3 record form (qk8) needs q in log2 units, L >= 512 and no causal mask");
+  launch_attention(AACLIP_F16X2, qkv, ctx, B, L, H, causal, log2q != 0, (hipStream_t)stream, hi8 != 0, qk8 != 0);
+  return finish("attention_split");
+}
+
+int aaclip_layernorm_split(const float* x, const float* w, const float* b, void* out, long rows, int D, float eps,
+                           int hi8, void* stream) {
+  REQUIRE(x && w && b && out, "layernorm_split: null pointer");
+  REQUIRE(rows > 0, "layernorm_split: rows must be positive");
+  REQUIRE_ROW_WIDTH(D);
+  launch_layernorm(AACLIP_F16X2, x, w, b, out, rows, D, eps, (hipStream_t)stream, hi8 != 0);
+  return finish("layernorm_split");
+}
+
+int aaclip_split_rows(const float* src, void* dst, long rows, int D, int hi8, void* stream) {
+  REQUIRE(src && dst, "split_rows: null pointer");
+  REQUIRE(!(((uintptr_t)src | (uintptr_t)dst) & 15), "split_rows: pointers must be 16-byte aligned");
+  REQUIRE(rows > 0 && D > 0 && D % 8 == 0, "split_rows: rows must be positive, D a positive multiple of 8");
+  launch_split_rows(src, dst, rows, D, (hipStream_t)stream, hi8 != 0);
+  return finish("split_rows");
+}
+
 int aaclip_small_attention(int kv_dtype, const float* q, const void* k, const void* v, float* out, int B, int nq, int Lk,
                            int H, int hd, float scale, void* stream) {
   REQUIRE(plain_dtype_ok(kv_dtype), "small_attention: bad dtype (fp32, fp16 or bf16)");

@@ -375,8 +375,14 @@ const char* gemm_check(int dtype, int epi, const GemmParams& p) {
   if (dtype == AACLIP_F16X2) {
     if (p.K % 128) return "gemm: split fp16 products take K tiles in pairs: K must be a multiple of 128";
     if (p.lda < 2L * p.K) return "gemm: split8 rows of A hold 4 bytes per element: lda (in halves) must be >= 2K";
-    if ((epi == EPI_BIAS || epi == EPI_BIAS_GELU) && p.ldc < 2L * p.N)
+    // an out_qk8 row is N fp16 + one 128-byte record per 64 columns below out_qk8 (gemm256t.hip: the record of column
+    // group g starts 2N + 128 g bytes into the row): N + out_qk8 halves
+    if (p.out_qk8 > 0 && epi == EPI_BIAS) {
+      if (p.ldc < (long)p.N + p.out_qk8)
+        return "gemm: out_qk8 rows hold N fp16 and 2 bytes per column below out_qk8: ldc (in halves) must be >= N + out_qk8";
+    } else if ((epi == EPI_BIAS || epi == EPI_BIAS_GELU) && p.ldc < 2L * p.N) {
       return "gemm: split output rows hold 4 bytes per element: ldc (in halves) must be >= 2N";
+    }
     if ((long)p.K >= (1L << 20)) return "gemm: K too large for the split kernels";
   }
   if (epi < 0 || epi > EPI_PATCH) return "gemm: unknown epilogue";

@@ -35,7 +35,8 @@ struct GemmParams {
   // rows too ([M, >= 2N], ldc = row stride, lo plane N columns after the hi plane).
   int w_exact16;
   int out_qk8;                // EPI_BIAS, split fp16, 256-tile kernel only: > 0 = the output is the attention kernel's
-                              // [hi: N fp16][per 64 columns below out_qk8: lo8 64 B | hi8 64 B] record (ldc >= (N + out_qk8 / 2) halves... see gemm256t.hip)
+                              // [hi: N fp16][per 64 columns below out_qk8: lo8 64 B | hi8 64 B] record: 2N + 2 out_qk8 bytes, so
+                              // ldc >= N + out_qk8 halves (gemm_check; the QKV product: N = 3D, out_qk8 = 2D, ldc = 5D)
   int out_no_hi8;             // EPI_BIAS_GELU, split fp16: the consumer's weight is exact in fp16 -- skip the hi8 plane
 };
 

@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define AACLIP_ABI_VERSION 9   /* 9: attention and block backward for rows of any length (the *_long entry points) */
+#define AACLIP_ABI_VERSION 10   /* 10: the block path's forms of the building blocks (aaclip_gemm_fused and the entries beside it) */
 
 enum { AACLIP_F32 = 0, AACLIP_F16 = 1, AACLIP_BF16 = 2, AACLIP_F16X2 = 3 };
 enum { AACLIP_ACT_NONE = 0, AACLIP_ACT_LEAKY = 1, AACLIP_ACT_RELU = 2,
@@ -547,6 +547,59 @@ int aaclip_attention(int dtype, const void* qkv, void* ctx, int B, int L, int H,
  * (one v_exp_f32 per score, no per-score multiply); exported so that it can be tested and timed on its own. */
 int aaclip_attention_log2q(int dtype, const void* qkv, void* ctx, int B, int L, int H, int causal, void* stream);
 int aaclip_adapter_mix(float* x, const float* a, long rows, int D, float weight, void* stream);
+
+/* The block path's forms of the building blocks (ABI version >= 10): what aaclip_block(s) selects on fields and flags
+ * that the entries above cannot set, exported so that each form is tested per element on its own.  Every check
+ * precedes the first launch; a field that the kernel this call would run does not implement is REFUSED (rc < 0,
+ * aaclip_last_error, nothing launched), never ignored.  Errors carry the entry's name as prefix.
+ *
+ * aaclip_gemm_fused = aaclip_gemm plus the fields of the struct below; with all of them zero it is aaclip_gemm:
+ *   resid      AACLIP_EPI_BIAS_RESID: the residual is READ here ([M, ldc] fp32, left untouched) instead of from `out`.
+ *   out16, stats_out (together)  AACLIP_EPI_BIAS_RESID, fp16 / bf16, a 256-row-tile kernel (M >= 4096, N a multiple of
+ *              256, ldc a multiple of 8, GEMM variant other than 1): out16 [M, N] <- the new rows rounded to dtype;
+ *              stats_out [M][N / 64][2] <- (sum, sum of squares) of those ROUNDED values per 64-column slice.
+ *   row_ab, col_s (together)     AACLIP_EPI_BIAS / AACLIP_EPI_BIAS_GELU, same kernels: row_ab [M][2] = (a, b) per row,
+ *              col_s [N]; the epilogue's input becomes fmaf(a_m, acc, b_m * s_n) (+ bias_n): LayerNorm folded into the
+ *              product, with (a, b) = (rstd, -mean * rstd) and s = the row sums of the gamma-scaled weight.
+ *   w_exact16  AACLIP_F16X2, K a multiple of 256: W is [N, 3K] bytes (no lo plane; the weight is exact in fp16).
+ *   out_qk8    AACLIP_EPI_BIAS, AACLIP_F16X2, the 256-row-tile kernel: a multiple of 64, <= N.  The output row is
+ *              [N fp16: hi][per 64 columns below out_qk8: lo8 64 B | hi8 64 B] = N + out_qk8 halves (ldc >= that): the
+ *              [q k v hi | q8 | k8] records of aaclip_attention_split(qk8) for N = 3 * 64 H, out_qk8 = 2 * 64 H.
+ *              Columns >= out_qk8 are rounded to fp16 (no correction).
+ *   out_no_hi8 AACLIP_EPI_BIAS_GELU, AACLIP_F16X2: the hi8 plane of the split8 output rows is not written (for a
+ *              consumer whose weight is exact in fp16, which never reads it).
+ * aaclip_ln_stats_finalize: partials [rows][D / 64][2] (stats_out) -> row_ab [rows][2] = (rstd, -mean * rstd) with the
+ *   one-pass biased variance max(q / D - mean^2, 0) in fp32.  Its relative error grows with mean(x^2) / (var + eps)
+ *   (DESIGN.md 3c).  D a supported row width, rows < 2^27.
+ * aaclip_adapter_mix_fold: aaclip_adapter_mix (x bit-identical) that also writes out16 [rows, D] = the new rows in dtype
+ *   (fp16 / bf16) and row_ab [rows][2] of those rounded values, eps 1e-5.
+ * aaclip_attention_split: aaclip_attention / _log2q (log2q != 0) for AACLIP_F16X2 with the launcher's flags: hi8 = 0
+ *   leaves the hi8 plane of the context rows unwritten; qk8 != 0 reads [q k v hi | q8 | k8] records of 10 * 64 H bytes
+ *   (refused unless log2q, L >= 512 and not causal).
+ * aaclip_layernorm_split / aaclip_split_rows: aaclip_layernorm(AACLIP_F16X2) / fp32 [rows, D] -> split8 rows [rows, 4D]
+ *   bytes, with hi8 = 0 leaving the hi8 plane unwritten. */
+typedef struct aaclip_gemm_fused_args {
+  size_t struct_bytes;    /* sizeof(aaclip_gemm_fused_args) as the caller compiled it; any other value is refused */
+  const float* resid;
+  void* out16;
+  float* stats_out;
+  const float* row_ab;
+  const float* col_s;
+  int w_exact16;
+  int out_qk8;
+  int out_no_hi8;
+} aaclip_gemm_fused_args;
+int aaclip_gemm_fused(int dtype, int epi, const void* A, long lda, const void* W, const float* bias, void* out, long ldc,
+                      int M, int N, int K, int act, int scale_cols, float scale, const aaclip_gemm_fused_args* f,
+                      void* stream);
+int aaclip_ln_stats_finalize(const float* partials, float* row_ab, long rows, int D, float eps, void* stream);
+int aaclip_adapter_mix_fold(int dtype, float* x, const float* a, long rows, int D, float weight, void* out16,
+                            float* row_ab, void* stream);
+int aaclip_attention_split(const void* qkv, void* ctx, int B, int L, int H, int causal, int log2q, int qk8, int hi8,
+                           void* stream);
+int aaclip_layernorm_split(const float* x, const float* w, const float* b, void* out, long rows, int D, float eps,
+                           int hi8, void* stream);
+int aaclip_split_rows(const float* src, void* dst, long rows, int D, int hi8, void* stream);
 
 /* ---- IQM side branch (reference model/iqm.py, the glue of model/adapter.py:186-269 and the IQM maps of
  * test_last.py:102-147).  Its matrix products -- class_query_mlp, query_adapters,

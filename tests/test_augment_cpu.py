@@ -25,7 +25,7 @@ def test_symbols_and_abi():
     lib = _lib.load()
     for name in NEW_SYMBOLS:
         assert name in _lib.SIGNATURES and getattr(lib, name) is not None
-    assert lib.aaclip_version() == 9
+    assert lib.aaclip_version() == 10
     header = open(os.path.join(os.path.dirname(__file__), "..", "include", "aaclip.h")).read()
     for name in NEW_SYMBOLS:
         assert name + "(" in header

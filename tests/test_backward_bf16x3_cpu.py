@@ -64,12 +64,12 @@ def test_library_exports_the_new_symbols():
     for name in NEW_SYMBOLS:
         assert hasattr(lib, name), name
         assert name in _lib.SIGNATURES, name
-    assert _lib.load().aaclip_version() == 9 == _lib.ABI_VERSION
+    assert _lib.load().aaclip_version() == 10 == _lib.ABI_VERSION
     with open(os.path.join(os.path.dirname(PKG), "include", "aaclip.h")) as f:
         header = f.read()
     for name in NEW_SYMBOLS:
         assert name + "(" in header, name
-    assert "#define AACLIP_ABI_VERSION 9 " in header
+    assert "#define AACLIP_ABI_VERSION 10 " in header
 
 
 def test_workspace_sizes():

@@ -28,7 +28,7 @@ def test_symbols_and_abi_version():
         assert re.search(r"\b%s\(" % name, header)
     assert callable(engine.cross_rows_levels_backward)
     in_header = int(re.search(r"#define\s+AACLIP_ABI_VERSION\s+(\d+)", header).group(1))
-    assert in_header == 9 and lib.aaclip_version() == 9 and _lib.ABI_VERSION == 9
+    assert in_header == 10 and lib.aaclip_version() == 10 and _lib.ABI_VERSION == 10
 
 
 def test_cpu_tensors_raise():

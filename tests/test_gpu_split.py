@@ -164,9 +164,10 @@ def test_gemm_split_epilogues(dev, shape):
     o32 = torch.empty(M, N, dtype=torch.float32, device=dev)
     _gemm(lib, dev, _lib.EPI_ACT_F32, Ad, Wd, None, o32, K, act=1)
     assert_close(o32, O.leaky_relu(acc), ea, er, "leaky")
-    # a weight that is exact in fp16 (its lo plane is all zero): same function of the rounded weight.  (The 3-plane
-    # 'exact' form, which skips the weight-lo tile, is selected by aaclip_block_weights.exact16 and is exercised by
-    # test_full_b4_fp16_native_weights; the generic aaclip_gemm entry point always takes 4-plane weights.)
+    # a weight that is exact in fp16 (its lo plane is all zero): same function of the rounded weight.  (aaclip_gemm
+    # always takes 4-plane weights; the 3-plane 'exact' form, which skips the weight-lo tile, is aaclip_gemm_fused's
+    # w_exact16, pinned bit for bit on both tile sizes by tests/test_gpu_fused_epilogues.py
+    # test_three_plane_weights_exact_integers.)
     Wh = W.half().float()
     W4 = engine.split_rows(Wh.to(dev), weight=True)
     _gemm(lib, dev, _lib.EPI_ACT_F32, Ad, W4, None, o32, K)

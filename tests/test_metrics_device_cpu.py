@@ -95,7 +95,7 @@ def test_symbols_and_abi():
     header = open(os.path.join(os.path.dirname(__file__), "..", "include", "aaclip.h")).read()
     for name in NEW_SYMBOLS:
         assert name in _lib.SIGNATURES and getattr(lib, name) is not None and name + "(" in header
-    assert lib.aaclip_version() == 9 == _lib.ABI_VERSION
+    assert lib.aaclip_version() == 10 == _lib.ABI_VERSION
     assert lib.aaclip_metrics_sort_group_items() % 64 == 0 and lib.aaclip_metrics_sort_group_items() > 0
 
 
