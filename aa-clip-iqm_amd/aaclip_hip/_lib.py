@@ -21,7 +21,7 @@ ACT_GELU = 3   # aaclip_act_backward only
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_ACT_F32 = 0, 1, 2, 3
 SEG_LOSS_FOCAL, SEG_LOSS_DICE0, SEG_LOSS_DICE1, SEG_LOSS_ALL = 1, 2, 4, 7
 
-_vp, _i, _l, _f, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
+_vp, _i, _l, _f, _sz, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t, C.c_double
 
 
 class BlockWeights(C.Structure):
@@ -109,6 +109,12 @@ SIGNATURES = {
     "aaclip_metrics_sort": (_i, [_vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "aaclip_metrics_curve_workspace_bytes": (_sz, [_l]),
     "aaclip_metrics_curve": (_i, [_vp, _vp, _l, _i, _vp, _vp, _sz, _vp]),
+    "aaclip_metrics_regions_workspace_bytes": (_sz, [_l, _l, _l]),
+    "aaclip_metrics_regions": (_i, [_vp, _l, _l, _l, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aaclip_metrics_sort_pairs_workspace_bytes": (_sz, [_l]),
+    "aaclip_metrics_sort_pairs": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
+    "aaclip_metrics_pro_curve_workspace_bytes": (_sz, [_l]),
+    "aaclip_metrics_pro_curve": (_i, [_vp, _vp, _l, _vp, _d, _vp, _vp, _sz, _vp]),
     "aaclip_row_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp] + [_i] * 6 + [_vp, _sz, _vp]),
     "aaclip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _l, _i, _f, _vp]),
     "aaclip_gemm": (_i, [_i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _f, _vp]),

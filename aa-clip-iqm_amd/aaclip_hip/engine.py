@@ -1216,6 +1216,119 @@ def curve_metrics(scores: torch.Tensor, labels: torch.Tensor, per_image: int = 0
 
 
 # ------------------------------------------------------------------------------------------------
+# per-region overlap (AUPRO) of one class on the device (csrc/regions.hip; forward_utils.pro_eval_device)
+PRO_RECORD_WORDS = 5            # int64 words: aupro (fp64 bits), regions, normal pixels, groups, y at the limit (fp64 bits)
+ProMetrics = collections.namedtuple("ProMetrics", "aupro regions normal groups")
+
+
+def _mask_images(mask: torch.Tensor, what: str):
+    """uint8 device mask [N, H, W] (or [N, 1, H, W], or [H, W]) -> (contiguous mask, images, H, W)"""
+    require_gpu(mask, what)
+    if mask.dtype != torch.uint8 or mask.dim() < 2:
+        raise ValueError(f"{what} expects a uint8 mask of [images, H, W]")
+    H, W = int(mask.shape[-2]), int(mask.shape[-1])
+    n = mask.numel()
+    if H < 1 or W < 1 or not 2 <= n <= METRICS_MAX_N:
+        raise ValueError(f"{what}: 2 .. 2^31 - 1 pixels in images of at least 1 x 1, got {tuple(mask.shape)}")
+    return mask.contiguous(), n // (H * W), H, W
+
+
+def metrics_regions(mask: torch.Tensor, connectivity: int = 8):
+    """-> (region, area, record): the connected components of the non-zero pixels of every image of the uint8 mask
+    [N, H, W].  region (int32, mask's shape; read it as uint32): 0 for a normal pixel, else 1 + the flat index of the
+    first pixel, in row-major order over the whole tensor, of the pixel's component; area (int32): the component's
+    pixel count, 0 for a normal pixel; record: int64 [3] on the device = regions, anomalous pixels, normal pixels."""
+    mask, images, H, W = _mask_images(mask, "metrics_regions")
+    if connectivity not in (4, 8):
+        raise ValueError(f"metrics_regions: connectivity must be 4 or 8, got {connectivity}")
+    dev = mask.device
+    lib = _lib.load()
+    region = torch.empty(mask.shape, dtype=torch.int32, device=dev)
+    area = torch.empty(mask.shape, dtype=torch.int32, device=dev)
+    record = torch.empty(3, dtype=torch.int64, device=dev)
+    ws = Workspace.get(dev, lib.aaclip_metrics_regions_workspace_bytes(images, H, W))
+    _lib.check(lib.aaclip_metrics_regions(mask.data_ptr(), images, H, W, connectivity, region.data_ptr(), area.data_ptr(),
+                                          record.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "metrics_regions")
+    return region, area, record
+
+
+def metrics_sort_pairs(scores: torch.Tensor, values: torch.Tensor):
+    """-> (keys, values_sorted): the ascending unpacked keys of the fp32 scores as int32 [n] (read them as uint32) and
+    the int32 values in their order; equal keys keep their input order."""
+    scores, _ = _metrics_inputs(scores, None, "metrics_sort_pairs")
+    require_gpu(values, "metrics_sort_pairs")
+    if values.dtype != torch.int32 or values.numel() != scores.numel() or values.device != scores.device:
+        raise ValueError("metrics_sort_pairs expects int32 values of the scores' size and device")
+    values = values.contiguous().view(-1)
+    n, dev = scores.numel(), scores.device
+    lib = _lib.load()
+    keys = torch.empty(n, dtype=torch.int32, device=dev)
+    values_sorted = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = Workspace.get(dev, lib.aaclip_metrics_sort_pairs_workspace_bytes(n))
+    _lib.check(lib.aaclip_metrics_sort_pairs(scores.data_ptr(), values.data_ptr(), n, keys.data_ptr(),
+                                             values_sorted.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+               "metrics_sort_pairs")
+    return keys, values_sorted
+
+
+def metrics_pro_curve(keys: torch.Tensor, areas_sorted: torch.Tensor, regions_record: torch.Tensor, fpr_limit: float,
+                      record: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sorted (key, area) pairs and the record of metrics_regions -> the device record (int64 [PRO_RECORD_WORDS]: aupro
+    bits, regions, normal pixels, groups, bits of y at the limit)."""
+    require_gpu(keys, "metrics_pro_curve")
+    n, dev = keys.numel(), keys.device
+    if keys.dtype != torch.int32 or keys.dim() != 1 or not keys.is_contiguous() or not 2 <= n <= METRICS_MAX_N:
+        raise ValueError("metrics_pro_curve expects the int32 [n] keys of metrics_sort_pairs")
+    if (areas_sorted.dtype != torch.int32 or areas_sorted.shape != keys.shape or not areas_sorted.is_contiguous()
+            or areas_sorted.device != dev):
+        raise ValueError("metrics_pro_curve expects the int32 [n] sorted areas of metrics_sort_pairs")
+    if regions_record.dtype != torch.int64 or regions_record.numel() != 3 or regions_record.device != dev:
+        raise ValueError("metrics_pro_curve expects the int64 [3] record of metrics_regions")
+    if not 0.0 < float(fpr_limit) <= 1.0:
+        raise ValueError(f"metrics_pro_curve: fpr_limit must lie in (0, 1], got {fpr_limit}")
+    if record is None:
+        record = torch.zeros(PRO_RECORD_WORDS, dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    ws = Workspace.get(dev, lib.aaclip_metrics_pro_curve_workspace_bytes(n))
+    _lib.check(lib.aaclip_metrics_pro_curve(keys.data_ptr(), areas_sorted.data_ptr(), n, regions_record.data_ptr(),
+                                            float(fpr_limit), record.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+               "metrics_pro_curve")
+    return record
+
+
+def pro_metrics(scores: torch.Tensor, mask: torch.Tensor, fpr_limit: float = 0.3, connectivity: int = 8,
+                normalise: bool = True) -> ProMetrics:
+    """The per-region overlap curve of the min-max normalised scores integrated up to the false-positive rate fpr_limit
+    and divided by it (AUPRO), exactly, on the device: forward_utils.pro_eval's definition over every distinct score.
+    scores fp32 and mask uint8 (non-zero = anomalous) [N, H, W].  -> ProMetrics(aupro, regions, normal, groups).
+    Raises ValueError before anything is sorted when the mask holds no region or no normal pixel, when a score is not
+    finite or when max == min; normalise=False takes the scores as they are (equal scores are then one tie group)."""
+    mask, images, H, W = _mask_images(mask, "pro_metrics")
+    scores, _ = _metrics_inputs(scores, None, "pro_metrics")
+    if scores.numel() != mask.numel() or scores.device != mask.device:
+        raise ValueError("pro_metrics: scores and mask must have one size and device")
+    if not 0.0 < float(fpr_limit) <= 1.0:
+        raise ValueError(f"pro_metrics: fpr_limit must lie in (0, 1], got {fpr_limit}")
+    n = scores.numel()
+    _, area, regions_record = metrics_regions(mask, connectivity)
+    rng, _ = metrics_range(scores)
+    R, _, normal = (int(v) for v in regions_record.cpu())
+    r = metrics_range_host(rng)
+    if R == 0 or normal == 0:
+        raise ValueError(f"pro_metrics: {R} regions and {normal} normal pixels; the PRO curve needs both")
+    if r["nonfinite"]:
+        raise ValueError(f"pro_metrics: {r['nonfinite']} of {n} scores are not finite")
+    if normalise and r["max"] == r["min"]:
+        raise ValueError("pro_metrics: all scores are equal (max == min): the min-max normalisation divides by zero")
+    norm = metrics_normalise(scores, rng) if normalise else scores
+    keys, areas_sorted = metrics_sort_pairs(norm, area)
+    del norm, area
+    h = metrics_pro_curve(keys, areas_sorted, regions_record, fpr_limit).cpu()
+    assert int(h[1]) == R and int(h[2]) == normal, (h, R, normal)
+    return ProMetrics(float(h[0:1].view(torch.float64)), R, normal, int(h[3]))
+
+
+# ------------------------------------------------------------------------------------------------
 # IQM side branch (reference model/iqm.py, model/adapter.py:186-269, test_last.py:102-147): thin wrappers of the C ABI
 def gemm(code: int, epi: int, a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor,
          act: int = 0) -> torch.Tensor:

@@ -1513,6 +1513,86 @@ int aaclip_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, lon
   return finish("metrics_curve");
 }
 
+// ---- per-region overlap, AUPRO (regions.hip; the pair sort is metrics.hip's)
+static inline long regions_pixels(long images, long H, long W) {   // 0 where the product is refused
+  if (images < 1 || H < 1 || W < 1 || H > 2147483647L || W > 2147483647L || images > 2147483647L) return 0;
+  if (H > 2147483647L / W || images > 2147483647L / (H * W)) return 0;
+  const long n = images * H * W;
+  return metrics_n_ok(n) ? n : 0;
+}
+
+size_t aaclip_metrics_regions_workspace_bytes(long images, long H, long W) {
+  const long n = regions_pixels(images, H, W);
+  return n ? up256(metrics_regions_ws_bytes(n)) : 0;
+}
+
+int aaclip_metrics_regions(const uint8_t* mask, long images, long H, long W, int connectivity, uint32_t* region,
+                           uint32_t* area, void* record, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(mask && region && area && record && ws, "metrics_regions: null pointer");
+  REQUIRE(connectivity == 4 || connectivity == 8, "metrics_regions: connectivity must be 4 or 8");
+  const long n = regions_pixels(images, H, W);
+  REQUIRE(n != 0, "metrics_regions: images, H, W must be positive with 2 .. 2^31 - 1 pixels in all");
+  REQUIRE((((uintptr_t)region | (uintptr_t)area) & 3) == 0 && (((uintptr_t)record | (uintptr_t)ws) & 7) == 0,
+          "metrics_regions: region / area must be 4-byte, record / workspace 8-byte aligned");
+  const size_t need = aaclip_metrics_regions_workspace_bytes(images, H, W), n4 = (size_t)n * 4;
+  REQUIRE(!ranges_overlap(ws, need, mask, (size_t)n) && !ranges_overlap(ws, need, region, n4) &&
+              !ranges_overlap(ws, need, area, n4) && !ranges_overlap(ws, need, record, 24) &&
+              !ranges_overlap(region, n4, mask, (size_t)n) && !ranges_overlap(area, n4, mask, (size_t)n) &&
+              !ranges_overlap(region, n4, area, n4) && !ranges_overlap(record, 24, mask, (size_t)n) &&
+              !ranges_overlap(record, 24, region, n4) && !ranges_overlap(record, 24, area, n4),
+          "metrics_regions: mask, outputs, record and workspace must not overlap one another");
+  REQUIRE(ws_bytes >= need, "metrics_regions: workspace too small");
+  launch_metrics_regions(mask, n, (int)H, (int)W, connectivity, region, area, record, ws, (hipStream_t)stream);
+  return finish("metrics_regions");
+}
+
+size_t aaclip_metrics_sort_pairs_workspace_bytes(long n) {
+  return metrics_n_ok(n) ? up256(metrics_sort_pairs_ws_bytes(n)) : 0;
+}
+
+int aaclip_metrics_sort_pairs(const float* scores, const uint32_t* values, long n, uint32_t* keys,
+                              uint32_t* values_sorted, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(scores && values && keys && values_sorted && ws, "metrics_sort_pairs: null pointer");
+  REQUIRE(metrics_n_ok(n), "metrics_sort_pairs: n must be 2 .. 2^31 - 1");
+  REQUIRE((((uintptr_t)scores | (uintptr_t)values | (uintptr_t)keys | (uintptr_t)values_sorted) & 3) == 0 &&
+              ((uintptr_t)ws & 7) == 0,
+          "metrics_sort_pairs: scores / values / keys must be 4-byte, the workspace 8-byte aligned");
+  const size_t need = aaclip_metrics_sort_pairs_workspace_bytes(n), n4 = (size_t)n * 4;
+  REQUIRE(!ranges_overlap(keys, n4, scores, n4) && !ranges_overlap(keys, n4, values, n4) &&
+              !ranges_overlap(values_sorted, n4, scores, n4) && !ranges_overlap(values_sorted, n4, values, n4),
+          "metrics_sort_pairs: the outputs must not overlap the inputs");
+  REQUIRE(!ranges_overlap(ws, need, scores, n4) && !ranges_overlap(ws, need, values, n4) &&
+              !ranges_overlap(ws, need, keys, n4) && !ranges_overlap(ws, need, values_sorted, n4) &&
+              !ranges_overlap(keys, n4, values_sorted, n4),
+          "metrics_sort_pairs: inputs, outputs and workspace must not overlap one another");
+  REQUIRE(ws_bytes >= need, "metrics_sort_pairs: workspace too small");
+  launch_metrics_sort_pairs(scores, values, n, keys, values_sorted, ws, (hipStream_t)stream);
+  return finish("metrics_sort_pairs");
+}
+
+size_t aaclip_metrics_pro_curve_workspace_bytes(long n) {
+  return metrics_n_ok(n) ? up256(metrics_pro_curve_ws_bytes(n)) : 0;
+}
+
+int aaclip_metrics_pro_curve(const uint32_t* keys, const uint32_t* areas_sorted, long n, const void* regions_record,
+                             double fpr_limit, void* record, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(keys && areas_sorted && regions_record && record && ws, "metrics_pro_curve: null pointer");
+  REQUIRE(metrics_n_ok(n), "metrics_pro_curve: n must be 2 .. 2^31 - 1");
+  REQUIRE(fpr_limit > 0.0 && fpr_limit <= 1.0, "metrics_pro_curve: fpr_limit must lie in (0, 1]");
+  REQUIRE((((uintptr_t)keys | (uintptr_t)areas_sorted) & 3) == 0 &&
+              (((uintptr_t)regions_record | (uintptr_t)record | (uintptr_t)ws) & 7) == 0,
+          "metrics_pro_curve: keys / areas must be 4-byte, records / workspace 8-byte aligned");
+  const size_t need = aaclip_metrics_pro_curve_workspace_bytes(n), n4 = (size_t)n * 4;
+  REQUIRE(!ranges_overlap(ws, need, keys, n4) && !ranges_overlap(ws, need, areas_sorted, n4) &&
+              !ranges_overlap(ws, need, record, 40) && !ranges_overlap(ws, need, regions_record, 24) &&
+              !ranges_overlap(record, 40, keys, n4) && !ranges_overlap(record, 40, areas_sorted, n4) &&
+              !ranges_overlap(record, 40, regions_record, 24),
+          "metrics_pro_curve: keys, areas, records and workspace must not overlap one another");
+  REQUIRE(ws_bytes >= need, "metrics_pro_curve: workspace too small");
+  launch_metrics_pro_curve(keys, areas_sorted, n, regions_record, fpr_limit, record, ws, (hipStream_t)stream);
+  return finish("metrics_pro_curve");
+}
+
 int aaclip_text_embed(const int32_t* tokens, const float* table, const float* pos, float* x, int n, int T, int D,
                       int vocab, void* stream) {
   REQUIRE(tokens && table && pos && x, "text_embed: null pointer");

@@ -277,5 +277,15 @@ void launch_metrics_sort(const float* scores, const uint8_t* labels, long n, int
 size_t metrics_curve_ws_bytes(long n);
 void launch_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
                           hipStream_t s);
+size_t metrics_sort_pairs_ws_bytes(long n);
+void launch_metrics_sort_pairs(const float* scores, const uint32_t* values, long n, uint32_t* keys,
+                               uint32_t* values_sorted, void* ws, hipStream_t s);
+// ---- regions.hip : per-region overlap (AUPRO): connected components with canonical ids and areas, the PRO curve
+size_t metrics_regions_ws_bytes(long n);
+void launch_metrics_regions(const uint8_t* mask, long n, int H, int W, int connectivity, uint32_t* region,
+                            uint32_t* area, void* record, void* ws, hipStream_t s);
+size_t metrics_pro_curve_ws_bytes(long n);
+void launch_metrics_pro_curve(const uint32_t* keys, const uint32_t* areas_sorted, long n, const void* regions_record,
+                              double fpr_limit, void* record, void* ws, hipStream_t s);
 
 }  // namespace aaclip

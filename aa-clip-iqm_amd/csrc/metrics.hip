@@ -253,10 +253,12 @@ __global__ __launch_bounds__(MT) void sort_scan_apply_kernel(uint32_t* __restric
   }
 }
 
+// V: what travels beside the key -- the label byte of aaclip_metrics_sort, the 32-bit value of aaclip_metrics_sort_pairs
+template <typename V>
 __global__ __launch_bounds__(MT) void sort_scatter_kernel(const uint32_t* __restrict__ keys_in,
                                                           uint32_t* __restrict__ keys_out,
-                                                          const uint8_t* __restrict__ lab_in,
-                                                          uint8_t* __restrict__ lab_out, long n, int shift,
+                                                          const V* __restrict__ lab_in,
+                                                          V* __restrict__ lab_out, long n, int shift,
                                                           const uint32_t* __restrict__ table, long chunks) {
   __shared__ uint32_t first[SORT_WAVES][256];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -298,6 +300,29 @@ __global__ __launch_bounds__(MT) void sort_scatter_kernel(const uint32_t* __rest
   }
 }
 
+// The four passes: keys ping-pong between `keys` and keys_b and are back in `keys` at the end; what travels beside them
+// (nothing when v_in is null) starts in v_in, ping-pongs between v_b and v_out and ends in v_out.
+template <typename V>
+static void sort_passes(uint32_t* keys, uint32_t* keys_b, const V* v_in, V* v_out, V* v_b, uint32_t* table,
+                        uint32_t* seg_sum, long n, hipStream_t s) {
+  const long chunks = metrics_sort_chunks(n);
+  const long seg_len = (chunks + SCAN_SEGMENTS - 1) / SCAN_SEGMENTS;
+  const int segments = (int)((chunks + seg_len - 1) / seg_len);
+  const unsigned groups = (unsigned)((chunks + SORT_WAVES - 1) / SORT_WAVES);
+  for (int pass = 0; pass < 4; ++pass) {
+    const uint32_t* src = pass & 1 ? keys_b : keys;
+    uint32_t* dst = pass & 1 ? keys : keys_b;
+    const V* vsrc = !v_in ? nullptr : (pass == 0 ? v_in : (pass & 1 ? v_b : v_out));
+    V* vdst = !v_in ? nullptr : (pass & 1 ? v_out : v_b);
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(groups), dim3(MT), 0, s, src, n, 8 * pass, table, chunks);
+    hipLaunchKernelGGL(sort_scan_sum_kernel, dim3(segments), dim3(MT), 0, s, table, chunks, seg_len, seg_sum);
+    hipLaunchKernelGGL(sort_scan_base_kernel, dim3(1), dim3(MT), 0, s, seg_sum, segments);
+    hipLaunchKernelGGL(sort_scan_apply_kernel, dim3(segments), dim3(MT), 0, s, table, chunks, seg_len, seg_sum);
+    hipLaunchKernelGGL(sort_scatter_kernel<V>, dim3(groups), dim3(MT), 0, s, src, dst, vsrc, vdst, n, 8 * pass, table,
+                       chunks);
+  }
+}
+
 size_t metrics_sort_ws_bytes(long n) {
   const long chunks = metrics_sort_chunks(n);
   return up256_bytes((size_t)n * 4) + up256_bytes((size_t)n) + (size_t)chunks * 1024 + (size_t)SCAN_SEGMENTS * 1024;
@@ -307,33 +332,40 @@ size_t metrics_sort_ws_bytes(long n) {
 // The keys start in `keys` and are back there after the fourth pass; so are the labels in `labels_sorted`.
 void launch_metrics_sort(const float* scores, const uint8_t* labels, long n, int packed, uint32_t* keys,
                          uint8_t* labels_sorted, unsigned long long* out_of_range, void* ws, hipStream_t s) {
-  const long chunks = metrics_sort_chunks(n);
   char* p = (char*)ws;
   uint32_t* keys_b = (uint32_t*)p;
   p += up256_bytes((size_t)n * 4);
   uint8_t* lab_b = (uint8_t*)p;
   p += up256_bytes((size_t)n);
   uint32_t* table = (uint32_t*)p;
-  p += (size_t)chunks * 1024;
+  p += (size_t)metrics_sort_chunks(n) * 1024;
   uint32_t* seg_sum = (uint32_t*)p;
-  const long seg_len = (chunks + SCAN_SEGMENTS - 1) / SCAN_SEGMENTS;
-  const int segments = (int)((chunks + seg_len - 1) / seg_len);
-  const unsigned groups = (unsigned)((chunks + SORT_WAVES - 1) / SORT_WAVES);
   (void)hipMemsetAsync(out_of_range, 0, sizeof(u64), s);
   hipLaunchKernelGGL(metrics_keys_kernel, dim3((unsigned)((n + MT - 1) / MT)), dim3(MT), 0, s, scores, labels, n, packed,
                      keys, out_of_range);
-  for (int pass = 0; pass < 4; ++pass) {
-    const uint32_t* src = pass & 1 ? keys_b : keys;
-    uint32_t* dst = pass & 1 ? keys : keys_b;
-    const uint8_t* lsrc = packed ? nullptr : (pass == 0 ? labels : (pass & 1 ? lab_b : labels_sorted));
-    uint8_t* ldst = packed ? nullptr : (pass & 1 ? labels_sorted : lab_b);
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(groups), dim3(MT), 0, s, src, n, 8 * pass, table, chunks);
-    hipLaunchKernelGGL(sort_scan_sum_kernel, dim3(segments), dim3(MT), 0, s, table, chunks, seg_len, seg_sum);
-    hipLaunchKernelGGL(sort_scan_base_kernel, dim3(1), dim3(MT), 0, s, seg_sum, segments);
-    hipLaunchKernelGGL(sort_scan_apply_kernel, dim3(segments), dim3(MT), 0, s, table, chunks, seg_len, seg_sum);
-    hipLaunchKernelGGL(sort_scatter_kernel, dim3(groups), dim3(MT), 0, s, src, dst, lsrc, ldst, n, 8 * pass, table,
-                       chunks);
-  }
+  sort_passes<uint8_t>(keys, keys_b, packed ? nullptr : labels, labels_sorted, lab_b, table, seg_sum, n, s);
+}
+
+size_t metrics_sort_pairs_ws_bytes(long n) {
+  const long chunks = metrics_sort_chunks(n);
+  return 2 * up256_bytes((size_t)n * 4) + (size_t)chunks * 1024 + (size_t)SCAN_SEGMENTS * 1024;
+}
+
+// The same four passes with a 32-bit value beside the unpacked key.
+// ws: [keys B: n uint32] [values B: n uint32] [table: chunks x 256 uint32] [segment sums: 256 x 256 uint32]
+void launch_metrics_sort_pairs(const float* scores, const uint32_t* values, long n, uint32_t* keys,
+                               uint32_t* values_sorted, void* ws, hipStream_t s) {
+  char* p = (char*)ws;
+  uint32_t* keys_b = (uint32_t*)p;
+  p += up256_bytes((size_t)n * 4);
+  uint32_t* val_b = (uint32_t*)p;
+  p += up256_bytes((size_t)n * 4);
+  uint32_t* table = (uint32_t*)p;
+  p += (size_t)metrics_sort_chunks(n) * 1024;
+  uint32_t* seg_sum = (uint32_t*)p;
+  hipLaunchKernelGGL(metrics_keys_kernel, dim3((unsigned)((n + MT - 1) / MT)), dim3(MT), 0, s, scores,
+                     (const uint8_t*)nullptr, n, 0, keys, (u64*)nullptr);
+  sort_passes<uint32_t>(keys, keys_b, values, values_sorted, val_b, table, seg_sum, n, s);
 }
 
 // ---------------------------------------------------------------------------------------------------- curve

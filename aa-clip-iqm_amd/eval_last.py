@@ -12,6 +12,12 @@ the same names and arguments:
                                           which keeps precedence -- the IQM branch from the "iqm_branch" entry that
                                           train.train_image_adapter writes into image_adapter_<epoch>.pth; test_last.py
                                           evaluates the branch with its seeded initialisation after training
+  evaluate_rows(..., device_metrics=False, fpr_limit=None)
+                                          the loop behind evaluate(device_metrics=True), for either metrics path; a
+                                          number as fpr_limit adds the column "pixel AUPRO": the per-region overlap curve
+                                          integrated up to that false-positive rate (forward_utils.pro_eval on the host,
+                                          pro_eval_device on the GPU).  eval_aupro.py is the script with the --aupro flag;
+                                          this script's arguments and evaluate() stay test_last's plus --device_metrics
   main(argv)                              the arguments and steps of test_last.main plus --device_metrics
 
 python eval_last.py --save_path ... [--device_metrics] [every argument of test_last.py]
@@ -31,7 +37,9 @@ import test_last as TL
 from aaclip_hip import engine
 from aaclip_hip.shard import gather_predictions, shard_range
 from dataset import DOMAINS
-from forward_utils import calculate_anomaly_map, image_score, metrics_eval_device
+from forward_utils import calculate_anomaly_map, image_score, metrics_eval, metrics_eval_device
+
+AUPRO_COL = "pixel AUPRO"
 
 
 def get_predictions(model, class_text_embeddings: torch.Tensor, test_loader, device, img_size: int,
@@ -65,13 +73,22 @@ def get_predictions(model, class_text_embeddings: torch.Tensor, test_loader, dev
 def evaluate(model, image_datasets: Dict[str, torch.utils.data.Dataset], text_embeddings: Dict[str, torch.Tensor],
              device, img_size: int, dataset: str, batch_size: int = 32, loader_kwargs=None, logger=None,
              use_iqm: bool = True, device_metrics: bool = False) -> List[dict]:
-    """test_last.evaluate; device_metrics: the class's masks, maps and image scores stay on the GPU, the row comes from
-    metrics_eval_device, and the tensors are released before the next class.  Under torch.distributed the shards are
-    gathered as host arrays exactly as in test_last.evaluate (so the gloo rehearsal path keeps working) and the
-    gathered arrays of a class are uploaded once."""
+    """test_last.evaluate; device_metrics: evaluate_rows with the metrics on the GPU"""
     if not device_metrics:
         return TL.evaluate(model, image_datasets, text_embeddings, device, img_size, dataset, batch_size=batch_size,
                            loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm)
+    return evaluate_rows(model, image_datasets, text_embeddings, device, img_size, dataset, batch_size=batch_size,
+                         loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm, device_metrics=True)
+
+
+def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], text_embeddings: Dict[str, torch.Tensor],
+                  device, img_size: int, dataset: str, batch_size: int = 32, loader_kwargs=None, logger=None,
+                  use_iqm: bool = True, device_metrics: bool = False, fpr_limit=None) -> List[dict]:
+    """The per-class loop of test_last.evaluate for either metrics path.  device_metrics: the class's masks, maps and
+    image scores stay on the GPU, the row comes from metrics_eval_device, and the tensors are released before the next
+    class.  Under torch.distributed the shards are gathered as host arrays exactly as in test_last.evaluate (so the
+    gloo rehearsal path keeps working) and the gathered arrays of a class are uploaded once.  fpr_limit: a
+    false-positive rate in (0, 1] adds "pixel AUPRO" to every row and to the average; None leaves the rows as they are."""
     import torch.distributed as dist
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
@@ -86,7 +103,7 @@ def evaluate(model, image_datasets: Dict[str, torch.utils.data.Dataset], text_em
             with torch.no_grad():
                 masks, labels, preds, preds_image, _ = get_predictions(
                     model=model, class_text_embeddings=text_embeddings[class_name], test_loader=loader, device=device,
-                    img_size=img_size, dataset=dataset, use_iqm=use_iqm, on_device=world == 1)
+                    img_size=img_size, dataset=dataset, use_iqm=use_iqm, on_device=device_metrics and world == 1)
         else:   # more ranks than images of this class
             masks = np.zeros((0, 1, img_size, img_size), np.float32)
             labels, preds_image = np.zeros((0,), np.int64), np.zeros((0,), np.float32)
@@ -96,16 +113,29 @@ def evaluate(model, image_datasets: Dict[str, torch.utils.data.Dataset], text_em
             masks, labels, preds, preds_image = gather_predictions(
                 ((masks != 0).astype(np.uint8), labels.astype(np.int64), preds.astype(np.float32),
                  preds_image.astype(np.float32)), total, device=gdev)
-            masks = torch.from_numpy(np.ascontiguousarray(masks)).to(device)
-            preds = torch.from_numpy(np.ascontiguousarray(preds)).to(device)
-        rows.append(metrics_eval_device(masks, labels, preds, preds_image, class_name, domain=DOMAINS[dataset]))
+            if device_metrics:
+                masks = torch.from_numpy(np.ascontiguousarray(masks)).to(device)
+                preds = torch.from_numpy(np.ascontiguousarray(preds)).to(device)
+            else:
+                masks = masks.astype(np.float32)
+        row_of = metrics_eval_device if device_metrics else metrics_eval
+        rows.append(row_of(masks, labels, preds, preds_image, class_name, domain=DOMAINS[dataset], fpr_limit=fpr_limit))
         del masks, preds, preds_image          # released before the next class is evaluated
         if logger:
             logger.info("%s", rows[-1])
-    avg = {c: float(np.mean([r[c] for r in rows])) for c in TL.NUMERIC_COLS}
+    avg = {c: float(np.mean([r[c] for r in rows])) for c in TL.NUMERIC_COLS + ([AUPRO_COL] if fpr_limit is not None else [])}
     avg["class name"] = "Average"
     rows.append(avg)
     return rows
+
+
+def format_table(rows: List[dict]) -> str:
+    """test_last.format_table, with the AUPRO column behind it where the rows carry one"""
+    table = TL.format_table(rows)
+    if not rows or AUPRO_COL not in rows[0]:
+        return table
+    extra = [f"{AUPRO_COL:>14s}"] + [f"{r[AUPRO_COL]:>14.2f}" for r in rows]
+    return "\n".join(line + "  " + cell for line, cell in zip(table.split("\n"), extra))
 
 
 def load_adapters(model, save_path: str, logger=None) -> bool:
@@ -177,14 +207,21 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None):
     """The steps of test_last.main with this module's load_adapters and evaluate."""
+    return run(build_parser(), argv)
+
+
+def run(parser: argparse.ArgumentParser, argv=None):
+    """main() for a parser that may carry further arguments: `aupro` (eval_aupro.py), a false-positive rate or None"""
     from dataset import get_dataset
     from forward_utils import get_adapted_text_embedding
     from model.adapter import AdaptedCLIP
     from model.clip import create_model
-    parser = build_parser()
     args = parser.parse_args(argv)
+    aupro = getattr(args, "aupro", None)
     if args.iqm_hidden_size != 768:
         parser.error("--iqm_hidden_size must be 768 (the visual features' width; see test_last.py)")
+    if aupro is not None and not 0.0 < aupro <= 1.0:
+        parser.error("--aupro takes a false-positive rate in (0, 1]")
     TL.setup_seed(args.seed)
     os.makedirs(args.save_path, exist_ok=True)
     logger = logging.getLogger(__name__)
@@ -214,10 +251,11 @@ def main(argv=None):
                                  device_preprocess=args.device_preprocess)
     with torch.no_grad():
         text_embeddings = get_adapted_text_embedding(model if adapt_text else clip_model, args.dataset, device)
-    rows = evaluate(model, image_datasets, text_embeddings, device, args.img_size, args.dataset,
-                    batch_size=args.image_batch_size, loader_kwargs={"num_workers": 4, "pin_memory": True},
-                    logger=logger, use_iqm=args.iqm == "on", device_metrics=args.device_metrics)
-    table = TL.format_table(rows)
+    where = (model, image_datasets, text_embeddings, device, args.img_size, args.dataset)
+    how = dict(batch_size=args.image_batch_size, loader_kwargs={"num_workers": 4, "pin_memory": True}, logger=logger,
+               use_iqm=args.iqm == "on", device_metrics=args.device_metrics)
+    rows = evaluate(*where, **how) if aupro is None else evaluate_rows(*where, **how, fpr_limit=aupro)
+    table = format_table(rows)
     logger.info("final results:\n%s", table)
     if int(os.environ.get("RANK", "0")) == 0:
         print(table)

@@ -125,14 +125,114 @@ def image_score(det_feature: torch.Tensor, text_feature: torch.Tensor) -> torch.
 
 # ------------------------------------------------------------------------------------------------
 # evaluation harness counterpart (host side: numpy + sklearn, like the reference)
-def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names, domain):
+def _pro_curve_area(pixel_label, pixel_preds, fpr_limit, connectivity):
+    """Steps 1 and 3-5 of pro_eval on scores that are normalised already: [N, H, W] arrays -> (aupro, R, N_ok, groups)"""
+    import numpy as np
+    from scipy import ndimage
+
+    if connectivity not in (4, 8):
+        raise ValueError(f"pro_eval: connectivity must be 4 or 8, got {connectivity}")
+    if not 0.0 < float(fpr_limit) <= 1.0:
+        raise ValueError(f"pro_eval: fpr_limit must lie in (0, 1], got {fpr_limit}")
+    structure = np.ones((3, 3), int) if connectivity == 8 else ndimage.generate_binary_structure(2, 1)
+    area = np.zeros(pixel_label.shape, np.int64)
+    regions = 0
+    for k in range(pixel_label.shape[0]):
+        lab, count = ndimage.label(pixel_label[k] != 0, structure=structure)
+        area[k] = np.bincount(lab.reshape(-1), minlength=count + 1)[lab] * (lab != 0)
+        regions += count
+    area = area.reshape(-1)
+    n_ok = int(np.count_nonzero(area == 0))
+    if regions == 0 or n_ok == 0:
+        raise ValueError(f"pro_eval: {regions} regions and {n_ok} normal pixels; the PRO curve needs both")
+    scores = pixel_preds.reshape(-1)
+    order = np.argsort(scores, kind="stable")[::-1]
+    scores, area = scores[order], area[order]
+    end = np.ones(scores.size, bool)                       # last element of its tie group, walking down (-0 == +0)
+    end[:-1] = scores[:-1] != scores[1:]
+    weight = np.divide(1.0, area.astype(np.float64), out=np.zeros(area.size, np.float64), where=area != 0)
+    fp = np.cumsum(area == 0)[end]
+    x = np.concatenate([[0.0], fp.astype(np.float64) / float(n_ok)])
+    y = np.concatenate([[0.0], np.minimum(1.0, np.cumsum(weight)[end] / float(regions))])
+    k = int(np.count_nonzero(x <= fpr_limit))              # x ascends: the points up to the limit are a prefix
+    total = float(np.sum(0.5 * (x[1:k] - x[:k - 1]) * (y[1:k] + y[:k - 1])))
+    if k < x.size and x[k - 1] < fpr_limit:
+        y_limit = y[k - 1] + (y[k] - y[k - 1]) * ((fpr_limit - x[k - 1]) / (x[k] - x[k - 1]))
+        total += 0.5 * (fpr_limit - x[k - 1]) * (y_limit + y[k - 1])
+    return float(total / fpr_limit), regions, n_ok, int(end.sum())
+
+
+def _pro_shapes(pixel_label, pixel_preds):
+    """maps [N, H, W] ([N, 1, H, W] and square [N, pixels] as in metrics_eval) and the labels in the same shape"""
+    import numpy as np
+    if pixel_preds.ndim == 4 and pixel_preds.shape[1] == 1:
+        pixel_preds = pixel_preds[:, 0]
+    elif pixel_preds.ndim == 2:
+        side = int(pixel_preds.shape[1] ** 0.5)
+        if side * side == pixel_preds.shape[1]:
+            pixel_preds = pixel_preds.reshape(pixel_preds.shape[0], side, side)
+    if pixel_preds.ndim != 3 or pixel_label.size != pixel_preds.size:
+        raise ValueError(f"pro_eval: maps of [N, H, W] and as many labels, got {pixel_preds.shape} and {pixel_label.shape}")
+    return pixel_label.reshape(pixel_preds.shape), pixel_preds
+
+
+def pro_eval(pixel_label, pixel_preds, fpr_limit=0.3, connectivity=8):
+    """The per-region overlap curve integrated up to the false-positive rate fpr_limit, divided by it (AUPRO), of one
+    class on the host, over every distinct score -- no threshold grid.  The definition the device path is measured
+    against (engine.pro_metrics):
+      1. the connected components (scipy.ndimage.label; connectivity 8 = the 3x3 structure of the MVTec evaluation, or
+         4) of the non-zero labels of every image on its own: R regions, area(p) = the size of p's region, N_ok normal
+         pixels; R = 0 or N_ok = 0 raises ValueError
+      2. the scores are min-max normalised as metrics_eval does it (in their own dtype, skipped when max == 1);
+         non-finite scores and max == min raise ValueError
+      3. over the groups of equal scores from the highest down: fp = normal pixels so far, S = fp64 sum of 1 / area over
+         the anomalous pixels so far, the point (fp / N_ok, min(1, S / R)), with (0, 0) in front
+      4. the trapezoids of the points with x <= fpr_limit, plus the one up to the linearly interpolated point at
+         fpr_limit when the next point lies beyond it and the last one below it
+      5. divided by fpr_limit.
+    -> the unrounded AUPRO (float)."""
+    return pro_eval_record(pixel_label, pixel_preds, fpr_limit, connectivity)[0]
+
+
+def pro_eval_record(pixel_label, pixel_preds, fpr_limit=0.3, connectivity=8):
+    """pro_eval with its integers: -> (aupro, regions, normal pixels, tie groups)"""
+    import numpy as np
+    pixel_preds = np.asarray(pixel_preds)
+    pixel_label = np.asarray(pixel_label)
+    if not np.isfinite(pixel_preds).all():
+        raise ValueError("pro_eval: the scores are not all finite")
+    if pixel_preds.max() == pixel_preds.min():
+        raise ValueError("pro_eval: all scores are equal (max == min): the min-max normalisation divides by zero")
+    if pixel_preds.max() != 1:
+        pixel_preds = (pixel_preds - pixel_preds.min()) / (pixel_preds.max() - pixel_preds.min())
+    pixel_label, pixel_preds = _pro_shapes(pixel_label, pixel_preds)
+    return _pro_curve_area(pixel_label, pixel_preds, fpr_limit, connectivity)
+
+
+def pro_eval_device(pixel_label, pixel_preds, fpr_limit=0.3, connectivity=8):
+    """pro_eval on the GPU (csrc/regions.hip through engine.pro_metrics): device tensors, fp32 maps [N, H, W] (or
+    [N, 1, H, W]) and labels whose non-zero entries are the anomalous pixels; the same definition and ValueErrors."""
+    engine.require_gpu(pixel_preds, "pro_eval_device")
+    engine.require_gpu(pixel_label, "pro_eval_device")
+    pp = pixel_preds.to(torch.float32).contiguous()
+    if pp.dim() == 4 and pp.shape[1] == 1:
+        pp = pp[:, 0]
+    if pp.dim() != 3 or pixel_label.numel() != pp.numel():
+        raise ValueError(f"pro_eval_device: maps of [N, H, W] and as many labels, got {tuple(pp.shape)} and "
+                         f"{tuple(pixel_label.shape)}")
+    pl = pixel_label if pixel_label.dtype == torch.uint8 else (pixel_label != 0).to(torch.uint8)
+    return engine.pro_metrics(pp, pl.reshape(pp.shape), fpr_limit=fpr_limit, connectivity=connectivity).aupro
+
+
+def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, fpr_limit=None):
     """Pixel / image AUROC and AP of one class, reference forward_utils.py:233-308:
     global min-max normalisation of maps and image scores (:246-253), per-image maximum of
     the normalised map (:277), Industrial score = 0.5*max_pixel + 0.5*image score, Medical =
     max_pixel (:279-282), sklearn roc_auc_score / average_precision_score (:288-296).
     `image_preds` is the per-image score vector [N] (this build computes the intended
     (det . t_abnormal + 1)/2 score; the reference's [N,2] broadcast quirk, of which it keeps
-    column 0, is documented in DESIGN.md and accepted here too)."""
+    column 0, is documented in DESIGN.md and accepted here too).
+    fpr_limit: None returns the reference's dict; a number adds "pixel AUPRO", pro_eval up to that false-positive rate."""
     import numpy as np
     from sklearn.metrics import average_precision_score, roc_auc_score
 
@@ -167,17 +267,21 @@ def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names
         image_ap = average_precision_score(il, image_preds.reshape(-1))
     else:
         image_auc = image_ap = 0
-    return {"class name": class_names, "pixel AUC": round(pixel_auc, 4) * 100, "pixel AP": round(pixel_ap, 4) * 100,
-            "image AUC": round(image_auc, 4) * 100, "image AP": round(image_ap, 4) * 100}
+    row = {"class name": class_names, "pixel AUC": round(pixel_auc, 4) * 100, "pixel AP": round(pixel_ap, 4) * 100,
+           "image AUC": round(image_auc, 4) * 100, "image AP": round(image_ap, 4) * 100}
+    if fpr_limit is not None:      # the maps are normalised above: max == 1 now, or they were taken as they are
+        row["pixel AUPRO"] = round(_pro_curve_area(*_pro_shapes(pixel_label, pixel_preds), fpr_limit, 8)[0], 4) * 100
+    return row
 
 
-def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, class_names, domain):
+def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, fpr_limit=None):
     """metrics_eval with the sort and the curve sums on the GPU (csrc/metrics.hip through engine.curve_metrics): the same
     arguments, shape handling, domain rule, `image_label.max() != image_label.min()` rule, result dict and rounding, and
     the same numbers -- sklearn's tie groups and definitions, an integer AUROC numerator, an fp64 AP sum.
     pixel_preds (fp32) and pixel_label (uint8 0 / 1, or anything whose non-zero entries are the positives) are device
     tensors; the per-image arrays may live anywhere.  Raises ValueError where metrics_eval does (one pixel class only,
-    non-finite scores) and where the reference's normalisation divides by zero (all scores equal)."""
+    non-finite scores) and where the reference's normalisation divides by zero (all scores equal).
+    fpr_limit: as in metrics_eval, with "pixel AUPRO" from engine.pro_metrics (a labelling, a second sort, the PRO curve)."""
     import numpy as np
 
     engine.require_gpu(pixel_preds, "metrics_eval_device")
@@ -204,8 +308,11 @@ def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, clas
         image_auc, image_ap = image.auroc, image.ap
     else:
         image_auc = image_ap = 0
-    return {"class name": class_names, "pixel AUC": round(pixel.auroc, 4) * 100, "pixel AP": round(pixel.ap, 4) * 100,
-            "image AUC": round(image_auc, 4) * 100, "image AP": round(image_ap, 4) * 100}
+    row = {"class name": class_names, "pixel AUC": round(pixel.auroc, 4) * 100, "pixel AP": round(pixel.ap, 4) * 100,
+           "image AUC": round(image_auc, 4) * 100, "image AP": round(image_ap, 4) * 100}
+    if fpr_limit is not None:
+        row["pixel AUPRO"] = round(pro_eval_device(pl, pp, fpr_limit=fpr_limit), 4) * 100
+    return row
 
 
 def visualize(*args, **kwargs):

@@ -501,6 +501,47 @@ size_t aaclip_metrics_curve_workspace_bytes(long n);
 int aaclip_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* Per-region overlap (AUPRO) of one class on the device (csrc/regions.hip, the pair sort in csrc/metrics.hip): the PRO
+ * curve over every distinct threshold, integrated up to a false-positive rate fpr_limit and divided by it -- exact, no
+ * threshold grid.  The conventions are those of the entries above (checks before the first launch, the workspace size
+ * last, *_workspace_bytes 0 for refused sizes and monotonic, overlap checks, no floating-point atomics, floating-point
+ * sums in an order fixed by the sizes).  This ABI number is unchanged: the entries are additions.
+ *   aaclip_metrics_regions: mask u8 [images * H * W], non-zero = anomalous; n = images * H * W in 2 .. 2^31 - 1.  The
+ *   connected components (connectivity 8: the 3x3 structure of the MVTec evaluation, or 4) of every image on its own:
+ *   nothing joins across images or across the row wrap.  region[p] <- 0 for a normal pixel, else 1 + the flat index in
+ *   the whole buffer of the first pixel, in row-major order, of p's component; area[p] <- the component's pixel count, 0
+ *   for a normal pixel; record <- {regions, anomalous pixels, normal pixels}.  A union-find on a 32-bit parent array
+ *   whose entries are only ever lowered, by an integer atomic minimum (parent[i] <= i: every find / union loop is
+ *   bounded by its start index), read inside the loops by relaxed atomic loads; areas by integer atomic adds at the
+ *   root.  Minima and integer sums: the result does not depend on the order of execution.
+ *   aaclip_metrics_sort_pairs: aaclip_metrics_sort's stable sort with its unpacked key (any finite scores, -0.0 as
+ *   +0.0) and a 32-bit value beside it: keys[n] ascending, values_sorted[n] in their order, equal keys in input order.
+ *   aaclip_metrics_pro_curve: keys / areas_sorted from the pair sort of (normalised scores, area); area 0 marks a
+ *   normal pixel.  Tie groups from the highest key down; after group g, fp_g = normal pixels so far, S_g = the fp64
+ *   sum of 1.0 / area over the anomalous pixels so far, x_g = fp_g / N_ok, y_g = min(1, S_g / R), (x, y) = (0, 0) in
+ *   front; R is read on the device from regions_record (the record of aaclip_metrics_regions), N_ok is the number of
+ *   zero areas.  Area = the trapezoids of the groups with x_g <= fpr_limit plus, for the first group beyond it whose
+ *   predecessor lies below it, the trapezoid up to the linearly interpolated point at fpr_limit.
+ *   record <- {aupro = area / fpr_limit, R, N_ok, groups, y at the limit}.  fpr_limit in (0, 1].  R = 0 or N_ok = 0
+ *   give a NaN aupro; the caller checks the regions record first. */
+typedef struct aaclip_metrics_regions_record {
+  unsigned long long regions, anomalous, normal;
+} aaclip_metrics_regions_record;
+typedef struct aaclip_metrics_pro_record {
+  double aupro;
+  unsigned long long regions, normal, groups;
+  double y_limit;
+} aaclip_metrics_pro_record;
+size_t aaclip_metrics_regions_workspace_bytes(long images, long H, long W);
+int aaclip_metrics_regions(const uint8_t* mask, long images, long H, long W, int connectivity, uint32_t* region,
+                           uint32_t* area, void* record, void* ws, size_t ws_bytes, void* stream);
+size_t aaclip_metrics_sort_pairs_workspace_bytes(long n);
+int aaclip_metrics_sort_pairs(const float* scores, const uint32_t* values, long n, uint32_t* keys,
+                              uint32_t* values_sorted, void* ws, size_t ws_bytes, void* stream);
+size_t aaclip_metrics_pro_curve_workspace_bytes(long n);
+int aaclip_metrics_pro_curve(const uint32_t* keys, const uint32_t* areas_sorted, long n, const void* regions_record,
+                             double fpr_limit, void* record, void* ws, size_t ws_bytes, void* stream);
+
 /* Text embedding: x[i*T+t] = token_embedding[tokens[i,t]] + positional_embedding[t].
  * Replaces reference model/adapter.py:277-281 (model/model.py:192-194).  Token ids outside [0, vocab) are CLAMPED
  * to 0 / vocab - 1 (the reference's nn.Embedding raises instead); D a multiple of 4. */
