@@ -109,6 +109,10 @@ SIGNATURES = {
     "aaclip_metrics_sort": (_i, [_vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "aaclip_metrics_curve_workspace_bytes": (_sz, [_l]),
     "aaclip_metrics_curve": (_i, [_vp, _vp, _l, _i, _vp, _vp, _sz, _vp]),
+    "aaclip_metrics_f1max_workspace_bytes": (_sz, [_l]),
+    "aaclip_metrics_f1max": (_i, [_vp, _vp, _l, _i, _vp, _vp, _sz, _vp]),
+    "aaclip_metrics_threshold_workspace_bytes": (_sz, [_l, _l]),
+    "aaclip_metrics_threshold": (_i, [_vp, _vp, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "aaclip_metrics_regions_workspace_bytes": (_sz, [_l, _l, _l]),
     "aaclip_metrics_regions": (_i, [_vp, _l, _l, _l, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "aaclip_metrics_sort_pairs_workspace_bytes": (_sz, [_l]),

@@ -1170,6 +1170,47 @@ def metrics_curve(keys: torch.Tensor, labels_sorted: Optional[torch.Tensor], pac
     return record
 
 
+def _curve_record_arg(record: Optional[torch.Tensor], what: str) -> None:
+    if record is not None and (record.dtype != torch.int64 or record.numel() != CURVE_RECORD_WORDS or not record.is_cuda
+                               or not record.is_contiguous()):
+        raise ValueError(f"{what}: record must be a contiguous int64 [{CURVE_RECORD_WORDS}] device tensor")
+
+
+def _sorted_curve(scores: torch.Tensor, labels: torch.Tensor, per_image: int, record: Optional[torch.Tensor],
+                  normalise: bool, what: str, f1_record: Optional[torch.Tensor] = None):
+    """The body of curve_metrics and f1max_metrics: the range, the checks, ONE sort, the curve sums and -- when
+    f1_record (int64 [F1MAX_RECORD_WORDS], device) is given -- the F1-max argmax over the same sorted keys.
+    -> (CurveMetrics, range record on the device, the f1max record on the host or None)"""
+    n = scores.numel()
+    rng, image_max = metrics_range(scores, labels, per_image)
+    r = metrics_range_host(rng)
+    if r["nonfinite"]:
+        raise ValueError(f"{what}: {r['nonfinite']} of {n} scores are not finite")
+    if normalise and r["max"] == r["min"]:
+        raise ValueError(f"{what}: all scores are equal (max == min): the min-max normalisation divides by zero")
+    if r["positives"] == 0 or r["positives"] == n:
+        raise ValueError(f"{what}: only one class present in the labels; AUROC and AP are not defined")
+    norm = metrics_normalise(scores, rng) if normalise else scores
+    if normalise and image_max is not None:
+        metrics_normalise(image_max, rng, out=image_max)
+    # the label rides in the key where every sorted score lies in [0, 1]: normalised, or passed through inside it
+    packed = (normalise and r["max"] != 1.0) or (r["min"] >= 0.0 and r["max"] <= 1.0)
+    if record is None:
+        record = torch.zeros(CURVE_RECORD_WORDS, dtype=torch.int64, device=scores.device)
+    keys, labels_sorted, _ = metrics_sort(norm, labels, packed, out_of_range=record[CURVE_RECORD_WORDS - 1:])
+    del norm
+    metrics_curve(keys, labels_sorted, packed, record)
+    if f1_record is not None:
+        metrics_f1max(keys, labels_sorted, packed, f1_record)
+    h = record.cpu()
+    num, P, N, groups, _, outside = (int(v) for v in h)
+    if outside:
+        raise RuntimeError(f"{what}: {outside} normalised scores fell outside [0, 1]")
+    assert P == r["positives"] and P + N == n, (P, N, r, n)
+    curve = CurveMetrics(num / (2 * P * N), float(h[4:5].view(torch.float64)), P, N, image_max, num, groups)
+    return curve, rng, (None if f1_record is None else f1_record.cpu())
+
+
 def curve_metrics(scores: torch.Tensor, labels: torch.Tensor, per_image: int = 0,
                   record: Optional[torch.Tensor] = None, normalise: bool = True) -> CurveMetrics:
     """sklearn's roc_auc_score and average_precision_score of the min-max normalised scores (reference
@@ -1185,34 +1226,119 @@ def curve_metrics(scores: torch.Tensor, labels: torch.Tensor, per_image: int = 0
     scores, labels = _metrics_inputs(scores, labels, "curve_metrics")
     if labels is None:
         raise ValueError("curve_metrics needs labels")
-    if record is not None and (record.dtype != torch.int64 or record.numel() != CURVE_RECORD_WORDS or not record.is_cuda
-                               or not record.is_contiguous()):
-        raise ValueError(f"curve_metrics: record must be a contiguous int64 [{CURVE_RECORD_WORDS}] device tensor")
-    n = scores.numel()
-    rng, image_max = metrics_range(scores, labels, per_image)
-    r = metrics_range_host(rng)
-    if r["nonfinite"]:
-        raise ValueError(f"curve_metrics: {r['nonfinite']} of {n} scores are not finite")
-    if normalise and r["max"] == r["min"]:
-        raise ValueError("curve_metrics: all scores are equal (max == min): the min-max normalisation divides by zero")
-    if r["positives"] == 0 or r["positives"] == n:
-        raise ValueError("curve_metrics: only one class present in the labels; AUROC and AP are not defined")
-    norm = metrics_normalise(scores, rng) if normalise else scores
-    if normalise and image_max is not None:
-        metrics_normalise(image_max, rng, out=image_max)
-    # the label rides in the key where every sorted score lies in [0, 1]: normalised, or passed through inside it
-    packed = (normalise and r["max"] != 1.0) or (r["min"] >= 0.0 and r["max"] <= 1.0)
-    if record is None:
-        record = torch.zeros(CURVE_RECORD_WORDS, dtype=torch.int64, device=scores.device)
-    keys, labels_sorted, _ = metrics_sort(norm, labels, packed, out_of_range=record[CURVE_RECORD_WORDS - 1:])
-    del norm
-    metrics_curve(keys, labels_sorted, packed, record)
+    _curve_record_arg(record, "curve_metrics")
+    return _sorted_curve(scores, labels, per_image, record, normalise, "curve_metrics")[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# exact F1-max and its operating point (csrc/metrics.hip; forward_utils.f1max_eval_device), masks at a threshold
+F1MAX_RECORD_WORDS = 7          # int64 words: tp, fp, P, N, groups, start index, key (low half) | fp32 threshold bits (high)
+THRESHOLD_RECORD_WORDS = 4      # int64 words: tp, fp, fn, tn
+F1Max = collections.namedtuple("F1Max", "f1 threshold tp fp fn precision recall groups")
+
+
+def f1max_from_counts(tp: int, fp: int, P: int, threshold: float, groups: int) -> F1Max:
+    """The F1Max of integer counts: f1 = 2 tp / (2 tp + fp + fn) is ONE division of Python integers, so the host and the
+    device path, which agree on the integers, agree on its bits."""
+    tp, fp, fn = int(tp), int(fp), int(P) - int(tp)
+    return F1Max(2 * tp / (2 * tp + fp + fn), float(threshold), tp, fp, fn, tp / (tp + fp) if tp + fp else 0.0,
+                 tp / (tp + fn), int(groups))
+
+
+def f1max_record_host(record: torch.Tensor) -> dict:
+    """The f1max record on the host (one synchronising copy of 56 bytes)."""
     h = record.cpu()
-    num, P, N, groups, _, outside = (int(v) for v in h)
-    if outside:
-        raise RuntimeError(f"curve_metrics: {outside} normalised scores fell outside [0, 1]")
-    assert P == r["positives"] and P + N == n, (P, N, r, n)
-    return CurveMetrics(num / (2 * P * N), float(h[4:5].view(torch.float64)), P, N, image_max, num, groups)
+    tp, fp, P, N, groups, start, last = (int(v) for v in h)
+    return {"tp": tp, "fp": fp, "P": P, "N": N, "groups": groups, "start": start, "key": last & 0xFFFFFFFF,
+            "threshold": float(h[6:7].view(torch.float32)[1])}
+
+
+def metrics_f1max(keys: torch.Tensor, labels_sorted: Optional[torch.Tensor], packed: bool,
+                  record: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sorted keys (metrics_sort's) -> the device record of aaclip_metrics_f1max (int64 [F1MAX_RECORD_WORDS];
+    f1max_record_host reads it): the tie group with the largest F1, the higher score among exactly equal ones."""
+    require_gpu(keys, "metrics_f1max")
+    if keys.dtype != torch.int32 or keys.dim() != 1 or not keys.is_contiguous() or not 2 <= keys.numel() <= METRICS_MAX_N:
+        raise ValueError("metrics_f1max expects the int32 [n] keys of metrics_sort")
+    if not packed and (labels_sorted is None or labels_sorted.dtype != torch.uint8 or labels_sorted.numel() != keys.numel()
+                       or not labels_sorted.is_contiguous() or labels_sorted.device != keys.device):
+        raise ValueError("metrics_f1max: keys without a packed label need the uint8 [n] labels of metrics_sort")
+    n, dev = keys.numel(), keys.device
+    if record is None:
+        record = torch.zeros(F1MAX_RECORD_WORDS, dtype=torch.int64, device=dev)
+    elif (record.dtype != torch.int64 or record.numel() != F1MAX_RECORD_WORDS or record.device != dev
+          or not record.is_contiguous()):
+        raise ValueError(f"metrics_f1max: record must be a contiguous int64 [{F1MAX_RECORD_WORDS}] tensor on the keys' device")
+    lib = _lib.load()
+    ws = Workspace.get(dev, lib.aaclip_metrics_f1max_workspace_bytes(n))
+    _lib.check(lib.aaclip_metrics_f1max(keys.data_ptr(), None if packed else labels_sorted.data_ptr(), n,
+                                        int(bool(packed)), record.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+               "metrics_f1max")
+    return record
+
+
+def threshold_record(threshold: float, dev: torch.device) -> torch.Tensor:
+    """A device f1max record that carries nothing but the fp32 threshold (what metrics_threshold reads)"""
+    host = torch.zeros(F1MAX_RECORD_WORDS, dtype=torch.int64)
+    host[6:7].view(torch.float32)[1] = float(threshold)
+    return host.to(dev)
+
+
+def metrics_threshold(scores: torch.Tensor, threshold, labels: Optional[torch.Tensor] = None, per_image: int = 0,
+                      range_record: Optional[torch.Tensor] = None, mask: bool = True, totals: bool = True):
+    """-> (mask, image_counts, totals) of the fp32 scores at a threshold: mask uint8 in scores' shape, 1 where the
+    score -- normalised on the fly with range_record (metrics_range's) when that is given -- is >= the threshold;
+    image_counts int32 [n / per_image, 4] = tp, fp, fn, tn of every image when labels and per_image > 0 are given,
+    else None; totals int64 [4] on the device = tp, fp, fn, tn (without labels: fp = flagged, tn = the rest).
+    threshold: the device record of metrics_f1max (read on the device, nothing synchronises) or a number.
+    mask=False / totals=False leave that output out (None)."""
+    shape = scores.shape
+    scores, labels = _metrics_inputs(scores, labels, "metrics_threshold")
+    n, dev = scores.numel(), scores.device
+    if per_image < 0 or (per_image and n % per_image):
+        raise ValueError(f"metrics_threshold: {n} scores are no multiple of per_image = {per_image}")
+    if torch.is_tensor(threshold):
+        if (threshold.dtype != torch.int64 or threshold.numel() != F1MAX_RECORD_WORDS or threshold.device != dev
+                or not threshold.is_contiguous()):
+            raise ValueError("metrics_threshold: a tensor threshold must be the int64 record of metrics_f1max on the "
+                             "scores' device")
+        f1_record = threshold
+    else:
+        f1_record = threshold_record(threshold, dev)
+    if range_record is not None and (range_record.dtype != torch.int64 or range_record.numel() != 3
+                                     or range_record.device != dev):
+        raise ValueError("metrics_threshold: range_record must be the int64 [3] record of metrics_range")
+    counts = labels is not None and per_image > 0
+    if not (mask or totals or counts):
+        raise ValueError("metrics_threshold: nothing to compute (no mask, no totals, no per-image counts)")
+    lib = _lib.load()
+    out_mask = torch.empty(n, dtype=torch.uint8, device=dev) if mask else None
+    out_counts = torch.empty(n // per_image, 4, dtype=torch.int32, device=dev) if counts else None
+    out_totals = torch.empty(THRESHOLD_RECORD_WORDS, dtype=torch.int64, device=dev) if totals else None
+    ws = Workspace.get(dev, lib.aaclip_metrics_threshold_workspace_bytes(n, per_image))
+    _lib.check(lib.aaclip_metrics_threshold(scores.data_ptr(), _ptr(labels), n, per_image, _ptr(range_record),
+                                            f1_record.data_ptr(), _ptr(out_mask), _ptr(out_counts), _ptr(out_totals),
+                                            ws.data_ptr(), ws.numel(), _stream(dev)), "metrics_threshold")
+    return (out_mask.view(shape) if mask else None), out_counts, out_totals
+
+
+def f1max_metrics(scores: torch.Tensor, labels: torch.Tensor, per_image: int = 0, normalise: bool = True,
+                  records: Optional[dict] = None):
+    """curve_metrics and the exact F1-max from ONE sort: -> (CurveMetrics, F1Max(f1, threshold, tp, fp, fn, precision,
+    recall, groups)).  F1-max is the largest 2 tp / (2 tp + fp + fn) over every distinct threshold, compared in integers;
+    among thresholds of exactly equal F1 the highest; threshold is in the units that were sorted (normalised ones when
+    normalise) and predicted = score >= threshold.  The arguments, checks and ValueErrors are curve_metrics'.
+    records: a dict that receives the device records "range" and "f1max" (what metrics_threshold takes)."""
+    scores, labels = _metrics_inputs(scores, labels, "f1max_metrics")
+    if labels is None:
+        raise ValueError("f1max_metrics needs labels")
+    f1_record = torch.zeros(F1MAX_RECORD_WORDS, dtype=torch.int64, device=scores.device)
+    curve, rng, h = _sorted_curve(scores, labels, per_image, None, normalise, "f1max_metrics", f1_record)
+    tp, fp, P, N, groups = (int(v) for v in h[:5])
+    assert (P, N, groups) == (curve.P, curve.N, curve.groups), (h, curve)
+    if records is not None:
+        records["range"], records["f1max"] = rng, f1_record
+    return curve, f1max_from_counts(tp, fp, P, float(h[6:7].view(torch.float32)[1]), groups)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1513,6 +1513,62 @@ int aaclip_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, lon
   return finish("metrics_curve");
 }
 
+// ---- exact F1-max and the masks at a threshold (metrics.hip)
+size_t aaclip_metrics_f1max_workspace_bytes(long n) { return metrics_n_ok(n) ? up256(metrics_f1max_ws_bytes(n)) : 0; }
+
+int aaclip_metrics_f1max(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
+                         size_t ws_bytes, void* stream) {
+  REQUIRE(keys && record && ws, "metrics_f1max: null pointer");
+  REQUIRE(packed == 0 || packed == 1, "metrics_f1max: packed must be 0 or 1");
+  REQUIRE(packed || labels_sorted, "metrics_f1max: labels_sorted is required when the label is not packed into the key");
+  REQUIRE(metrics_n_ok(n), "metrics_f1max: n must be 2 .. 2^31 - 1");
+  REQUIRE(((uintptr_t)keys & 3) == 0 && (((uintptr_t)record | (uintptr_t)ws) & 7) == 0,
+          "metrics_f1max: keys must be 4-byte, record / workspace 8-byte aligned");
+  const size_t need = aaclip_metrics_f1max_workspace_bytes(n), rec = sizeof(aaclip_metrics_f1max_record);
+  REQUIRE(!ranges_overlap(ws, need, keys, (size_t)n * 4) && !ranges_overlap(ws, need, record, rec) &&
+              !ranges_overlap(record, rec, keys, (size_t)n * 4) &&
+              !(labels_sorted && (ranges_overlap(ws, need, labels_sorted, (size_t)n) ||
+                                  ranges_overlap(record, rec, labels_sorted, (size_t)n))),
+          "metrics_f1max: keys, labels, record and workspace must not overlap one another");
+  REQUIRE(ws_bytes >= need, "metrics_f1max: workspace too small");
+  launch_metrics_f1max(keys, labels_sorted, n, packed, record, ws, (hipStream_t)stream);
+  return finish("metrics_f1max");
+}
+
+size_t aaclip_metrics_threshold_workspace_bytes(long n, long per_image) {
+  if (!metrics_n_ok(n) || per_image < 0 || (per_image > 0 && n % per_image != 0)) return 0;
+  return up256(metrics_threshold_ws_bytes(n, per_image));
+}
+
+int aaclip_metrics_threshold(const float* scores, const uint8_t* labels, long n, long per_image,
+                             const void* range_record, const void* f1max_record, uint8_t* mask,
+                             uint32_t* image_counts, void* totals, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(scores && f1max_record && ws, "metrics_threshold: null pointer");
+  REQUIRE(mask || image_counts || totals, "metrics_threshold: no output (mask, image_counts and totals are all null)");
+  REQUIRE(metrics_n_ok(n), "metrics_threshold: n must be 2 .. 2^31 - 1");
+  REQUIRE(per_image >= 0 && (per_image == 0 || n % per_image == 0),
+          "metrics_threshold: n must be a multiple of per_image");
+  REQUIRE(!image_counts || (labels && per_image > 0), "metrics_threshold: per-image counts need labels and per_image > 0");
+  REQUIRE((((uintptr_t)scores | (uintptr_t)image_counts) & 3) == 0 &&
+              (((uintptr_t)range_record | (uintptr_t)f1max_record | (uintptr_t)totals | (uintptr_t)ws) & 7) == 0,
+          "metrics_threshold: scores / image_counts must be 4-byte, records / totals / workspace 8-byte aligned");
+  const size_t need = aaclip_metrics_threshold_workspace_bytes(n, per_image), n4 = (size_t)n * 4;
+  const size_t f1 = sizeof(aaclip_metrics_f1max_record), tot = sizeof(aaclip_metrics_threshold_record);
+  const size_t cnt = image_counts ? (size_t)(n / per_image) * 16 : 0;
+  // every written buffer (mask, image_counts, totals, workspace) against every other buffer of the call
+  const void* bufs[8] = {mask, image_counts, totals, ws, scores, labels, range_record, f1max_record};
+  const size_t lens[8] = {(size_t)n, cnt, tot, need, n4, (size_t)n, 24, f1};
+  bool clash = false;
+  for (int a = 0; a < 4; ++a)
+    for (int b = a + 1; b < 8; ++b)
+      clash = clash || (bufs[a] && bufs[b] && ranges_overlap(bufs[a], lens[a], bufs[b], lens[b]));
+  REQUIRE(!clash, "metrics_threshold: scores, labels, records, outputs and workspace must not overlap one another");
+  REQUIRE(ws_bytes >= need, "metrics_threshold: workspace too small");
+  launch_metrics_threshold(scores, labels, n, per_image, range_record, f1max_record, mask, image_counts, totals, ws,
+                           (hipStream_t)stream);
+  return finish("metrics_threshold");
+}
+
 // ---- per-region overlap, AUPRO (regions.hip; the pair sort is metrics.hip's)
 static inline long regions_pixels(long images, long H, long W) {   // 0 where the product is refused
   if (images < 1 || H < 1 || W < 1 || H > 2147483647L || W > 2147483647L || images > 2147483647L) return 0;

@@ -277,6 +277,13 @@ void launch_metrics_sort(const float* scores, const uint8_t* labels, long n, int
 size_t metrics_curve_ws_bytes(long n);
 void launch_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
                           hipStream_t s);
+size_t metrics_f1max_ws_bytes(long n);                 // F1-max: the curve's first phases, then an integer argmax
+void launch_metrics_f1max(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
+                          hipStream_t s);
+size_t metrics_threshold_ws_bytes(long n, long per_image);
+void launch_metrics_threshold(const float* scores, const uint8_t* labels, long n, long per_image,
+                              const void* range_record, const void* f1max_record, uint8_t* mask,
+                              uint32_t* image_counts, void* totals, void* ws, hipStream_t s);
 size_t metrics_sort_pairs_ws_bytes(long n);
 void launch_metrics_sort_pairs(const float* scores, const uint32_t* values, long n, uint32_t* keys,
                                uint32_t* values_sorted, void* ws, hipStream_t s);

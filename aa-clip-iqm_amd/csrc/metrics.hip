@@ -4,6 +4,9 @@
 //   keys       an order-preserving uint32 image of every score; the 0 / 1 label in bit 0 where the scores lie in [0, 1]
 //   sort       stable LSD radix sort, four passes of 8-bit digits
 //   curve      tie groups of the sorted keys -> integer AUROC numerator and the fp64 AP sum
+// and, from the same sorted keys and the curve's own first phases (forward_utils.f1max_eval_device):
+//   f1max      the tie group with the largest F1, an integer argmax -> counts, start index, key and fp32 threshold
+//   threshold  raw scores -> uint8 masks and tp / fp / fn / tn per image and in all at a threshold read on the device
 // The numbers are sklearn's roc_auc_score / average_precision_score: the same tie groups and the same definitions.
 // No floating-point atomics; every floating-point sum runs in an order fixed by n alone, so two calls give the same bits.
 #include "common.h"
@@ -532,16 +535,19 @@ __global__ void curve_final_kernel(const u64* __restrict__ part_num, const doubl
   rec->num = num, rec->P = P, rec->N = (u64)n - P, rec->groups = tot >> 32, rec->ap = ap;
 }
 
-size_t metrics_curve_ws_bytes(long n) {
-  return up256_bytes((size_t)metrics_curve_tiles(n) * 8) + 256 + up256_bytes((size_t)n * 8) +
-         2 * up256_bytes((size_t)metrics_curve_blocks(n) * 8);
+// The phases that aaclip_metrics_curve and aaclip_metrics_f1max share: tile sums, their scan, the mark list.
+// ws: [tile sums: tiles x 8] [total: 8] [marks: n x 8] [rest: what the entry's own reduction needs]
+struct CurveMarks {
+  const u64* total;   // groups << 32 | positives
+  const u64* marks;   // marks[g] = i << 32 | E, ascending
+  char* rest;
+};
+static size_t curve_marks_ws_bytes(long n) {
+  return up256_bytes((size_t)metrics_curve_tiles(n) * 8) + 256 + up256_bytes((size_t)n * 8);
 }
-
-// ws: [tile sums: tiles x 8] [total: 8] [marks: n x 8] [partial numerators] [partial AP sums]
-void launch_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
-                          hipStream_t s) {
+static CurveMarks launch_curve_marks(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* ws,
+                                     hipStream_t s) {
   const long tiles = metrics_curve_tiles(n);
-  const int parts = (int)metrics_curve_blocks(n);
   char* p = (char*)ws;
   u64* tile_sum = (u64*)p;
   p += up256_bytes((size_t)tiles * 8);
@@ -549,17 +555,261 @@ void launch_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, lo
   p += 256;
   u64* marks = (u64*)p;
   p += up256_bytes((size_t)n * 8);
-  u64* part_num = (u64*)p;
-  p += up256_bytes((size_t)parts * 8);
-  double* part_ap = (double*)p;
   hipLaunchKernelGGL(curve_tile_sum_kernel, dim3((unsigned)tiles), dim3(MT), 0, s, keys, labels_sorted, n, packed,
                      tile_sum);
   hipLaunchKernelGGL(curve_tile_scan_kernel, dim3(1), dim3(MT), 0, s, tile_sum, tiles, total);
   hipLaunchKernelGGL(curve_mark_kernel, dim3((unsigned)tiles), dim3(MT), 0, s, keys, labels_sorted, n, packed, tile_sum,
                      marks);
-  hipLaunchKernelGGL(curve_group_kernel, dim3(parts), dim3(MT), 0, s, marks, total, n, part_num, part_ap);
-  hipLaunchKernelGGL(curve_final_kernel, dim3(1), dim3(64), 0, s, part_num, part_ap, parts, total, n,
+  return CurveMarks{total, marks, p};
+}
+
+size_t metrics_curve_ws_bytes(long n) {
+  return curve_marks_ws_bytes(n) + 2 * up256_bytes((size_t)metrics_curve_blocks(n) * 8);
+}
+
+// rest: [partial numerators] [partial AP sums]
+void launch_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
+                          hipStream_t s) {
+  const int parts = (int)metrics_curve_blocks(n);
+  const CurveMarks m = launch_curve_marks(keys, labels_sorted, n, packed, ws, s);
+  u64* part_num = (u64*)m.rest;
+  double* part_ap = (double*)(m.rest + up256_bytes((size_t)parts * 8));
+  hipLaunchKernelGGL(curve_group_kernel, dim3(parts), dim3(MT), 0, s, m.marks, m.total, n, part_num, part_ap);
+  hipLaunchKernelGGL(curve_final_kernel, dim3(1), dim3(64), 0, s, part_num, part_ap, parts, m.total, n,
                      (CurveRecord*)record);
+}
+
+// ---------------------------------------------------------------------------------------------------- F1-max
+// After the group that starts at ascending index i (walking down from the top, everything from i on is flagged):
+// tp = P - E, m = n - i, F1 = 2 tp / (m + P).  A CANDIDATE is (tp, d = m + P, i); a beats b when tp_a d_b > tp_b d_a
+// -- tp < 2^31 and d < 2^32, so the products are exact in uint64 -- and, at equal products, when i_a > i_b (the higher
+// score).  (ratio, i) is a strict total order over the groups: whichever way they are shared out and folded, the same
+// one wins.  d = 0 marks "no candidate" (a real d is at least 1).  Integers only, no atomics.
+struct F1Candidate {
+  u64 tp, d, i;
+};
+struct F1MaxRecord {   // include/aaclip.h aaclip_metrics_f1max_record
+  u64 tp, fp, P, N, groups, start;
+  uint32_t key;
+  float threshold;
+};
+
+AACLIP_DEV bool f1_beats(const F1Candidate& a, const F1Candidate& b) {
+  if (a.d == 0) return false;
+  if (b.d == 0) return true;
+  const u64 l = a.tp * b.d, r = b.tp * a.d;
+  return l > r || (l == r && a.i > b.i);
+}
+
+// the workgroup's best candidate, valid in thread 0
+AACLIP_DEV F1Candidate f1_block_best(F1Candidate best, u64* s_tp, u64* s_d, u64* s_i) {
+  const int t = threadIdx.x;
+  s_tp[t] = best.tp, s_d[t] = best.d, s_i[t] = best.i;
+  __syncthreads();
+  for (int o = MT / 2; o > 0; o >>= 1) {
+    if (t < o) {
+      const F1Candidate mine{s_tp[t], s_d[t], s_i[t]}, other{s_tp[t + o], s_d[t + o], s_i[t + o]};
+      if (f1_beats(other, mine)) s_tp[t] = other.tp, s_d[t] = other.d, s_i[t] = other.i;
+    }
+    __syncthreads();
+  }
+  return F1Candidate{s_tp[0], s_d[0], s_i[0]};
+}
+
+// Workgroup b takes a contiguous share of the groups, a thread every 256th of them.
+__global__ __launch_bounds__(MT) void f1max_group_kernel(const u64* __restrict__ marks, const u64* __restrict__ total,
+                                                         long n, F1Candidate* __restrict__ partial) {
+  __shared__ u64 s_tp[MT], s_d[MT], s_i[MT];
+  const u64 tot = *total;
+  const long G = (long)(tot >> 32);
+  const u64 P = tot & 0xFFFFFFFFull;
+  const long per = (G + gridDim.x - 1) / gridDim.x;
+  const long g0 = (long)blockIdx.x * per, g1 = g0 + per < G ? g0 + per : G;
+  F1Candidate best{0, 0, 0};
+  for (long g = g0 + threadIdx.x; g < g1; g += MT) {
+    const u64 a = marks[g];
+    const u64 i = a >> 32, E = a & 0xFFFFFFFFull;
+    const F1Candidate c{P - E, ((u64)n - i) + P, i};
+    if (f1_beats(c, best)) best = c;
+  }
+  best = f1_block_best(best, s_tp, s_d, s_i);
+  if (threadIdx.x == 0) partial[blockIdx.x] = best;
+}
+
+// one workgroup over the partials; thread 0 writes the record
+__global__ __launch_bounds__(MT) void f1max_final_kernel(const F1Candidate* __restrict__ partial, int parts,
+                                                         const u64* __restrict__ total, long n,
+                                                         const uint32_t* __restrict__ keys, int packed,
+                                                         F1MaxRecord* __restrict__ rec) {
+  __shared__ u64 s_tp[MT], s_d[MT], s_i[MT];
+  F1Candidate best{0, 0, 0};
+  for (int j = threadIdx.x; j < parts; j += MT) {
+    const F1Candidate c = partial[j];
+    if (f1_beats(c, best)) best = c;
+  }
+  best = f1_block_best(best, s_tp, s_d, s_i);
+  if (threadIdx.x != 0) return;
+  const u64 tot = *total;
+  const u64 P = tot & 0xFFFFFFFFull;
+  const u64 start = best.i < (u64)n ? best.i : 0;   // i < n whenever the marks are those of these keys
+  const uint32_t k = keys[start];
+  const uint32_t score = packed ? k >> 1 : k;
+  const uint32_t bits = packed ? score : ((score >> 31) ? score ^ 0x80000000u : ~score);
+  rec->tp = best.tp, rec->fp = (best.d - P) - best.tp, rec->P = P, rec->N = (u64)n - P, rec->groups = tot >> 32;
+  rec->start = start, rec->key = score, rec->threshold = __uint_as_float(bits);
+}
+
+size_t metrics_f1max_ws_bytes(long n) {
+  return curve_marks_ws_bytes(n) + up256_bytes((size_t)metrics_curve_blocks(n) * sizeof(F1Candidate));
+}
+
+// rest: [partial candidates]
+void launch_metrics_f1max(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
+                          hipStream_t s) {
+  const int parts = (int)metrics_curve_blocks(n);
+  const CurveMarks m = launch_curve_marks(keys, labels_sorted, n, packed, ws, s);
+  F1Candidate* partial = (F1Candidate*)m.rest;
+  hipLaunchKernelGGL(f1max_group_kernel, dim3(parts), dim3(MT), 0, s, m.marks, m.total, n, partial);
+  hipLaunchKernelGGL(f1max_final_kernel, dim3(1), dim3(MT), 0, s, partial, parts, m.total, n, keys, packed,
+                     (F1MaxRecord*)record);
+}
+
+// ------------------------------------------------------------------------------------------------- threshold
+// flagged = (v >= threshold), v the raw score or the score normalised as metrics_normalise_kernel does it.  Segments and
+// workgroups per segment are those of the range kernels.  Within a segment the elements in front of the first 16-byte
+// aligned score (at most 3) and behind the last whole quad (at most 3) are taken one by one by the segment's first
+// workgroup; the quads in between are read with one 128-bit load each, their four mask bytes stored as one word where
+// the mask's address at the quad is 4-byte aligned (the same for every quad of a segment), byte by byte otherwise; the
+// labels likewise.  Counts are integers: stage 1 leaves {tp, fp, fn, tn} per workgroup, stage 2 folds them.
+struct ThresholdRecord {   // include/aaclip.h aaclip_metrics_threshold_record
+  u64 tp, fp, fn, tn;
+};
+
+AACLIP_DEV float threshold_value(float x, bool norm, float mn, float mx) { return norm ? __fdiv_rn(x - mn, mx - mn) : x; }
+
+AACLIP_DEV void threshold_count(bool flag, bool pos, uint32_t& tp, uint32_t& fp, uint32_t& fn, uint32_t& tn) {
+  tp += flag && pos, fp += flag && !pos, fn += !flag && pos, tn += !flag && !pos;
+}
+
+__global__ __launch_bounds__(MT) void metrics_threshold_kernel(const float* __restrict__ scores,
+                                                               const uint8_t* __restrict__ labels, long seg_len,
+                                                               int blocks, const RangeRecord* __restrict__ range,
+                                                               const F1MaxRecord* __restrict__ f1,
+                                                               uint8_t* __restrict__ mask, uint4* __restrict__ partial) {
+  __shared__ uint32_t s_c[4][MT];
+  const long seg = blockIdx.x / blocks;
+  const int blk = blockIdx.x % blocks, t = threadIdx.x;
+  const long base = seg * seg_len;
+  const float thr = f1->threshold;
+  float mn = 0.0f, mx = 1.0f;
+  if (range) mn = range->mn, mx = range->mx;
+  const bool norm = range && mx != 1.0f;
+  // head: elements in front of the first 16-byte aligned score of the segment
+  long head = (long)(((16 - ((uintptr_t)(scores + base) & 15)) & 15) >> 2);
+  if (head > seg_len) head = seg_len;
+  const long quads = (seg_len - head) >> 2;
+  const long tail0 = head + 4 * quads;   // first element behind the quads
+  uint32_t tp = 0, fp = 0, fn = 0, tn = 0;
+  if (blk == 0) {
+    long i = -1;
+    if (t < head) i = t;
+    else if (t - head < seg_len - tail0) i = tail0 + (t - head);
+    if (i >= 0) {
+      const bool flag = threshold_value(scores[base + i], norm, mn, mx) >= thr;
+      if (mask) mask[base + i] = flag ? 1 : 0;
+      threshold_count(flag, labels && labels[base + i] != 0, tp, fp, fn, tn);
+    }
+  }
+  const float4* q4 = reinterpret_cast<const float4*>(scores + base + head);
+  const bool mask_word = mask && ((uintptr_t)(mask + base + head) & 3) == 0;
+  const bool label_word = labels && ((uintptr_t)(labels + base + head) & 3) == 0;
+  for (long q = (long)blk * MT + t; q < quads; q += (long)blocks * MT) {
+    const float4 x = q4[q];
+    const long e = base + head + 4 * q;
+    uint32_t lab = 0;   // the four label bytes, element 0 in the low byte
+    if (label_word) {
+      lab = *reinterpret_cast<const uint32_t*>(labels + e);
+    } else if (labels) {
+      lab = (uint32_t)labels[e] | ((uint32_t)labels[e + 1] << 8) | ((uint32_t)labels[e + 2] << 16) |
+            ((uint32_t)labels[e + 3] << 24);
+    }
+    const bool f0 = threshold_value(x.x, norm, mn, mx) >= thr, f1b = threshold_value(x.y, norm, mn, mx) >= thr;
+    const bool f2 = threshold_value(x.z, norm, mn, mx) >= thr, f3 = threshold_value(x.w, norm, mn, mx) >= thr;
+    if (mask_word) {
+      *reinterpret_cast<uint32_t*>(mask + e) =
+          (uint32_t)f0 | ((uint32_t)f1b << 8) | ((uint32_t)f2 << 16) | ((uint32_t)f3 << 24);
+    } else if (mask) {
+      mask[e] = f0, mask[e + 1] = f1b, mask[e + 2] = f2, mask[e + 3] = f3;
+    }
+    threshold_count(f0, (lab & 0xFFu) != 0, tp, fp, fn, tn);
+    threshold_count(f1b, (lab & 0xFF00u) != 0, tp, fp, fn, tn);
+    threshold_count(f2, (lab & 0xFF0000u) != 0, tp, fp, fn, tn);
+    threshold_count(f3, (lab & 0xFF000000u) != 0, tp, fp, fn, tn);
+  }
+  s_c[0][t] = tp, s_c[1][t] = fp, s_c[2][t] = fn, s_c[3][t] = tn;
+  __syncthreads();
+  for (int o = MT / 2; o > 0; o >>= 1) {
+    if (t < o) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) s_c[c][t] += s_c[c][t + o];
+    }
+    __syncthreads();
+  }
+  if (t == 0) partial[blockIdx.x] = make_uint4(s_c[0][0], s_c[1][0], s_c[2][0], s_c[3][0]);
+}
+
+// one workgroup: every image's counts from its workgroups in index order, and the totals over all partials
+__global__ __launch_bounds__(MT) void metrics_threshold_fold_kernel(const uint4* __restrict__ partial, long segs,
+                                                                    int blocks, uint32_t* __restrict__ image_counts,
+                                                                    ThresholdRecord* __restrict__ totals) {
+  __shared__ u64 s_c[4][MT];
+  const int t = threadIdx.x;
+  if (image_counts)
+    for (long s = t; s < segs; s += MT) {
+      uint32_t tp = 0, fp = 0, fn = 0, tn = 0;
+      for (int b = 0; b < blocks; ++b) {
+        const uint4 p = partial[s * blocks + b];
+        tp += p.x, fp += p.y, fn += p.z, tn += p.w;
+      }
+      uint32_t* out = image_counts + 4 * s;   // 4-byte aligned only
+      out[0] = tp, out[1] = fp, out[2] = fn, out[3] = tn;
+    }
+  if (!totals) return;   // the same for every thread
+  u64 tp = 0, fp = 0, fn = 0, tn = 0;
+  const long all = segs * blocks;
+  for (long j = t; j < all; j += MT) {
+    const uint4 p = partial[j];
+    tp += p.x, fp += p.y, fn += p.z, tn += p.w;
+  }
+  s_c[0][t] = tp, s_c[1][t] = fp, s_c[2][t] = fn, s_c[3][t] = tn;
+  __syncthreads();
+  for (int o = MT / 2; o > 0; o >>= 1) {
+    if (t < o) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) s_c[c][t] += s_c[c][t + o];
+    }
+    __syncthreads();
+  }
+  if (t == 0) *totals = ThresholdRecord{s_c[0][0], s_c[1][0], s_c[2][0], s_c[3][0]};
+}
+
+size_t metrics_threshold_ws_bytes(long n, long per_image) {
+  return (size_t)metrics_range_partials(n, per_image) * sizeof(uint4);
+}
+
+// ws: [partials: segments x workgroups per segment x {tp, fp, fn, tn} uint32]
+void launch_metrics_threshold(const float* scores, const uint8_t* labels, long n, long per_image,
+                              const void* range_record, const void* f1max_record, uint8_t* mask,
+                              uint32_t* image_counts, void* totals, void* ws, hipStream_t s) {
+  const long seg_len = per_image > 0 ? per_image : n;
+  const long segs = n / seg_len;
+  const int blocks = (int)metrics_range_blocks(seg_len);
+  uint4* partial = (uint4*)ws;
+  hipLaunchKernelGGL(metrics_threshold_kernel, dim3((unsigned)(segs * blocks)), dim3(MT), 0, s, scores, labels, seg_len,
+                     blocks, (const RangeRecord*)range_record, (const F1MaxRecord*)f1max_record, mask, partial);
+  if (image_counts || totals)
+    hipLaunchKernelGGL(metrics_threshold_fold_kernel, dim3(1), dim3(MT), 0, s, partial, segs, blocks, image_counts,
+                       (ThresholdRecord*)totals);
 }
 
 }  // namespace aaclip

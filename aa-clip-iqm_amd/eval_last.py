@@ -18,6 +18,9 @@ the same names and arguments:
                                           integrated up to that false-positive rate (forward_utils.pro_eval on the host,
                                           pro_eval_device on the GPU).  eval_aupro.py is the script with the --aupro flag;
                                           this script's arguments and evaluate() stay test_last's plus --device_metrics
+                                          f1_max=True adds "pixel F1-max" and "image F1-max", the best F1 over every
+                                          threshold (forward_utils.f1max_eval / engine.f1max_metrics); eval_metrics.py is
+                                          the script with the --f1max flag
   main(argv)                              the arguments and steps of test_last.main plus --device_metrics
 
 python eval_last.py --save_path ... [--device_metrics] [every argument of test_last.py]
@@ -37,9 +40,11 @@ import test_last as TL
 from aaclip_hip import engine
 from aaclip_hip.shard import gather_predictions, shard_range
 from dataset import DOMAINS
-from forward_utils import calculate_anomaly_map, image_score, metrics_eval, metrics_eval_device
+from forward_utils import (IMAGE_F1_COL, PIXEL_F1_COL, calculate_anomaly_map, image_score, metrics_eval,
+                           metrics_eval_device)
 
 AUPRO_COL = "pixel AUPRO"
+F1_COLS = [PIXEL_F1_COL, IMAGE_F1_COL]
 
 
 def get_predictions(model, class_text_embeddings: torch.Tensor, test_loader, device, img_size: int,
@@ -83,12 +88,16 @@ def evaluate(model, image_datasets: Dict[str, torch.utils.data.Dataset], text_em
 
 def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], text_embeddings: Dict[str, torch.Tensor],
                   device, img_size: int, dataset: str, batch_size: int = 32, loader_kwargs=None, logger=None,
-                  use_iqm: bool = True, device_metrics: bool = False, fpr_limit=None) -> List[dict]:
+                  use_iqm: bool = True, device_metrics: bool = False, fpr_limit=None, f1_max: bool = False,
+                  details: Dict[str, dict] = None, return_masks: bool = False) -> List[dict]:
     """The per-class loop of test_last.evaluate for either metrics path.  device_metrics: the class's masks, maps and
     image scores stay on the GPU, the row comes from metrics_eval_device, and the tensors are released before the next
     class.  Under torch.distributed the shards are gathered as host arrays exactly as in test_last.evaluate (so the
     gloo rehearsal path keeps working) and the gathered arrays of a class are uploaded once.  fpr_limit: a
-    false-positive rate in (0, 1] adds "pixel AUPRO" to every row and to the average; None leaves the rows as they are."""
+    false-positive rate in (0, 1] adds "pixel AUPRO" to every row and to the average; None leaves the rows as they are.
+    f1_max: adds "pixel F1-max" and "image F1-max" likewise (forward_utils.f1max_eval; on the GPU from the sort that
+    serves AUROC / AP).  details: with f1_max, a dict that receives, per class name, what metrics_eval's `details`
+    receives: the thresholds of the operating points and, with return_masks=True, the class's predicted uint8 masks."""
     import torch.distributed as dist
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
@@ -119,23 +128,31 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
             else:
                 masks = masks.astype(np.float32)
         row_of = metrics_eval_device if device_metrics else metrics_eval
-        rows.append(row_of(masks, labels, preds, preds_image, class_name, domain=DOMAINS[dataset], fpr_limit=fpr_limit))
+        extra = {}
+        if f1_max:
+            extra["f1_max"] = True
+            if details is not None:
+                extra["details"] = details[class_name] = {"masks": bool(return_masks)}
+        rows.append(row_of(masks, labels, preds, preds_image, class_name, domain=DOMAINS[dataset], fpr_limit=fpr_limit,
+                           **extra))
         del masks, preds, preds_image          # released before the next class is evaluated
         if logger:
             logger.info("%s", rows[-1])
-    avg = {c: float(np.mean([r[c] for r in rows])) for c in TL.NUMERIC_COLS + ([AUPRO_COL] if fpr_limit is not None else [])}
+    cols = TL.NUMERIC_COLS + ([AUPRO_COL] if fpr_limit is not None else []) + (F1_COLS if f1_max else [])
+    avg = {c: float(np.mean([r[c] for r in rows])) for c in cols}
     avg["class name"] = "Average"
     rows.append(avg)
     return rows
 
 
 def format_table(rows: List[dict]) -> str:
-    """test_last.format_table, with the AUPRO column behind it where the rows carry one"""
+    """test_last.format_table, with the AUPRO column and the two F1-max columns behind it where the rows carry them"""
     table = TL.format_table(rows)
-    if not rows or AUPRO_COL not in rows[0]:
-        return table
-    extra = [f"{AUPRO_COL:>14s}"] + [f"{r[AUPRO_COL]:>14.2f}" for r in rows]
-    return "\n".join(line + "  " + cell for line, cell in zip(table.split("\n"), extra))
+    for col in [AUPRO_COL] + F1_COLS:
+        if rows and col in rows[0]:
+            extra = [f"{col:>14s}"] + [f"{r[col]:>14.2f}" for r in rows]
+            table = "\n".join(line + "  " + cell for line, cell in zip(table.split("\n"), extra))
+    return table
 
 
 def load_adapters(model, save_path: str, logger=None) -> bool:
@@ -211,13 +228,14 @@ def main(argv=None):
 
 
 def run(parser: argparse.ArgumentParser, argv=None):
-    """main() for a parser that may carry further arguments: `aupro` (eval_aupro.py), a false-positive rate or None"""
+    """main() for a parser that may carry further arguments: `aupro` (eval_aupro.py), a false-positive rate or None,
+    and `f1max` (eval_metrics.py), which adds the F1-max columns and logs every class's thresholds"""
     from dataset import get_dataset
     from forward_utils import get_adapted_text_embedding
     from model.adapter import AdaptedCLIP
     from model.clip import create_model
     args = parser.parse_args(argv)
-    aupro = getattr(args, "aupro", None)
+    aupro, f1_max = getattr(args, "aupro", None), bool(getattr(args, "f1max", False))
     if args.iqm_hidden_size != 768:
         parser.error("--iqm_hidden_size must be 768 (the visual features' width; see test_last.py)")
     if aupro is not None and not 0.0 < aupro <= 1.0:
@@ -254,7 +272,14 @@ def run(parser: argparse.ArgumentParser, argv=None):
     where = (model, image_datasets, text_embeddings, device, args.img_size, args.dataset)
     how = dict(batch_size=args.image_batch_size, loader_kwargs={"num_workers": 4, "pin_memory": True}, logger=logger,
                use_iqm=args.iqm == "on", device_metrics=args.device_metrics)
-    rows = evaluate(*where, **how) if aupro is None else evaluate_rows(*where, **how, fpr_limit=aupro)
+    if f1_max:
+        details = {}
+        rows = evaluate_rows(*where, **how, fpr_limit=aupro, f1_max=True, details=details)
+        for name, d in details.items():
+            logger.info("%s: pixel threshold %.9g, image threshold %s (normalised units)", name, d["pixel threshold"],
+                        d["image threshold"])
+    else:
+        rows = evaluate(*where, **how) if aupro is None else evaluate_rows(*where, **how, fpr_limit=aupro)
     table = format_table(rows)
     logger.info("final results:\n%s", table)
     if int(os.environ.get("RANK", "0")) == 0:

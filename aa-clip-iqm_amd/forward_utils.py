@@ -224,7 +224,60 @@ def pro_eval_device(pixel_label, pixel_preds, fpr_limit=0.3, connectivity=8):
     return engine.pro_metrics(pp, pl.reshape(pp.shape), fpr_limit=fpr_limit, connectivity=connectivity).aupro
 
 
-def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, fpr_limit=None):
+def f1max_eval(labels, scores):
+    """The exact F1-max of one class on the host and its operating point -- the definition the device path is measured
+    against (engine.f1max_metrics).  labels 0 / non-zero and scores of one size, taken as they are (metrics_eval hands
+    in the normalised ones):
+      1. a stable descending argsort; a tie group ends where the next score differs (-0.0 == +0.0)
+      2. after group g: tp_g = positives with a score >= the group's, m_g = all elements with one,
+         F1_g = 2 tp_g / (m_g + P) with P the number of positives (= 2pr / (p + r) wherever that is defined)
+      3. the maximum over the groups; a beats b iff tp_a (m_b + P) > tp_b (m_a + P) -- the groups whose fp64 F1 lies
+         within 1e-9 of the fp64 maximum are compared in Python integers, so this is exact at any size -- and among groups
+         of exactly equal F1 the one with the highest score wins (fewest elements flagged)
+      4. threshold = that group's score, predicted = score >= threshold.
+    Raises ValueError when the labels hold one class only or a score is not finite.
+    -> engine.F1Max(f1, threshold, tp, fp, fn, precision, recall, groups)"""
+    import numpy as np
+    scores = np.asarray(scores).reshape(-1)
+    positive = np.asarray(labels).reshape(-1) != 0
+    if scores.size != positive.size:
+        raise ValueError(f"f1max_eval: {positive.size} labels for {scores.size} scores")
+    P = int(np.count_nonzero(positive))
+    if P == 0 or P == positive.size:
+        raise ValueError("f1max_eval: only one class present in the labels; F1 is not defined")
+    if not np.isfinite(scores).all():
+        raise ValueError("f1max_eval: the scores are not all finite")
+    order = np.argsort(scores, kind="stable")[::-1]
+    scores, positive = scores[order], positive[order]
+    end = np.ones(scores.size, bool)                       # last element of its tie group, walking down
+    end[:-1] = scores[:-1] != scores[1:]
+    tp = np.cumsum(positive, dtype=np.int64)[end]
+    m = np.flatnonzero(end).astype(np.int64) + 1
+    f1 = 2.0 * tp.astype(np.float64) / (m + P).astype(np.float64)
+    best = None
+    for g in np.flatnonzero(f1 >= f1.max() - 1e-9):        # ascending g = descending score: the first of equals stays
+        cand = (int(tp[g]), int(m[g]) + P, int(g))
+        if best is None or cand[0] * best[1] > best[0] * cand[1]:
+            best = cand
+    g = best[2]
+    threshold = scores[np.flatnonzero(end)[g]] + scores.dtype.type(0)      # -0.0 + 0.0 = +0.0, as the keys treat it
+    return engine.f1max_from_counts(best[0], int(m[g]) - best[0], P, float(threshold), int(end.sum()))
+
+
+def f1max_eval_device(labels, scores):
+    """f1max_eval on the GPU (csrc/metrics.hip through engine.f1max_metrics): device tensors, fp32 scores taken as they
+    are and labels whose non-zero entries are the positives; the same definition, ValueErrors and F1Max."""
+    engine.require_gpu(scores, "f1max_eval_device")
+    engine.require_gpu(labels, "f1max_eval_device")
+    lab = labels if labels.dtype == torch.uint8 else (labels != 0).to(torch.uint8)
+    return engine.f1max_metrics(scores.to(torch.float32).contiguous(), lab, normalise=False)[1]
+
+
+PIXEL_F1_COL, IMAGE_F1_COL = "pixel F1-max", "image F1-max"
+
+
+def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, fpr_limit=None,
+                 f1_max=False, details=None):
     """Pixel / image AUROC and AP of one class, reference forward_utils.py:233-308:
     global min-max normalisation of maps and image scores (:246-253), per-image maximum of
     the normalised map (:277), Industrial score = 0.5*max_pixel + 0.5*image score, Medical =
@@ -232,7 +285,11 @@ def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names
     `image_preds` is the per-image score vector [N] (this build computes the intended
     (det . t_abnormal + 1)/2 score; the reference's [N,2] broadcast quirk, of which it keeps
     column 0, is documented in DESIGN.md and accepted here too).
-    fpr_limit: None returns the reference's dict; a number adds "pixel AUPRO", pro_eval up to that false-positive rate."""
+    fpr_limit: None returns the reference's dict; a number adds "pixel AUPRO", pro_eval up to that false-positive rate.
+    f1_max: True adds "pixel F1-max" and "image F1-max" (f1max_eval of the normalised pixels and of the combined image
+    scores; the image one is 0 where image AUC is); details: a dict that then receives "pixel threshold" and "image
+    threshold" (None where the column is 0), in normalised units, and -- when it holds a true "masks" on entry -- the
+    uint8 predicted masks `normalised map >= pixel threshold` under "masks"."""
     import numpy as np
     from sklearn.metrics import average_precision_score, roc_auc_score
 
@@ -271,17 +328,35 @@ def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names
            "image AUC": round(image_auc, 4) * 100, "image AP": round(image_ap, 4) * 100}
     if fpr_limit is not None:      # the maps are normalised above: max == 1 now, or they were taken as they are
         row["pixel AUPRO"] = round(_pro_curve_area(*_pro_shapes(pixel_label, pixel_preds), fpr_limit, 8)[0], 4) * 100
+    if f1_max:
+        pixel_f1 = f1max_eval(pl, pp)
+        image_f1 = f1max_eval(image_label.reshape(-1), image_preds.reshape(-1)) if image_label.max() != image_label.min() else None
+        _f1_columns(row, details, pixel_f1, image_f1)
+        if details is not None and details.get("masks") is True:
+            details["masks"] = (pixel_preds >= pixel_preds.dtype.type(pixel_f1.threshold)).astype(np.uint8)
     return row
 
 
-def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, fpr_limit=None):
+def _f1_columns(row, details, pixel_f1, image_f1):
+    row[PIXEL_F1_COL] = round(pixel_f1.f1, 4) * 100
+    row[IMAGE_F1_COL] = round(image_f1.f1 if image_f1 is not None else 0, 4) * 100
+    if details is not None:
+        details["pixel threshold"] = pixel_f1.threshold
+        details["image threshold"] = None if image_f1 is None else image_f1.threshold
+
+
+def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, fpr_limit=None,
+                        f1_max=False, details=None):
     """metrics_eval with the sort and the curve sums on the GPU (csrc/metrics.hip through engine.curve_metrics): the same
     arguments, shape handling, domain rule, `image_label.max() != image_label.min()` rule, result dict and rounding, and
     the same numbers -- sklearn's tie groups and definitions, an integer AUROC numerator, an fp64 AP sum.
     pixel_preds (fp32) and pixel_label (uint8 0 / 1, or anything whose non-zero entries are the positives) are device
     tensors; the per-image arrays may live anywhere.  Raises ValueError where metrics_eval does (one pixel class only,
     non-finite scores) and where the reference's normalisation divides by zero (all scores equal).
-    fpr_limit: as in metrics_eval, with "pixel AUPRO" from engine.pro_metrics (a labelling, a second sort, the PRO curve)."""
+    fpr_limit: as in metrics_eval, with "pixel AUPRO" from engine.pro_metrics (a labelling, a second sort, the PRO curve).
+    f1_max, details: as in metrics_eval; the columns come from engine.f1max_metrics, that is from the ONE sort that
+    serves AUROC / AP already, and details["masks"] is a device tensor from engine.metrics_threshold, which normalises
+    the raw maps on the fly and reads the threshold from the device record."""
     import numpy as np
 
     engine.require_gpu(pixel_preds, "metrics_eval_device")
@@ -290,7 +365,11 @@ def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, clas
     n_img = pixel_preds.shape[0]
     pp = pixel_preds.to(torch.float32).contiguous()
     pl = pixel_label if pixel_label.dtype == torch.uint8 else (pixel_label != 0).to(torch.uint8)
-    pixel = engine.curve_metrics(pp, pl, per_image=pp.numel() // n_img)
+    records, pixel_f1, image_f1 = {}, None, None
+    if f1_max:
+        pixel, pixel_f1 = engine.f1max_metrics(pp, pl, per_image=pp.numel() // n_img, records=records)
+    else:
+        pixel = engine.curve_metrics(pp, pl, per_image=pp.numel() // n_img)
     image_label = np.asarray(image_label.cpu() if torch.is_tensor(image_label) else image_label)
     if image_label.max() != image_label.min():
         ip = torch.as_tensor(image_preds).to(device=dev, dtype=torch.float32).contiguous()
@@ -304,7 +383,10 @@ def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, clas
         ip = ip.reshape(-1)
         score = pixel.image_max * 0.5 + ip * 0.5 if domain != "Medical" else pixel.image_max
         il = torch.as_tensor(image_label.reshape(-1) != 0).to(device=dev, dtype=torch.uint8)
-        image = engine.curve_metrics(score, il, normalise=False)
+        if f1_max:
+            image, image_f1 = engine.f1max_metrics(score, il, normalise=False)
+        else:
+            image = engine.curve_metrics(score, il, normalise=False)
         image_auc, image_ap = image.auroc, image.ap
     else:
         image_auc = image_ap = 0
@@ -312,6 +394,12 @@ def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, clas
            "image AUC": round(image_auc, 4) * 100, "image AP": round(image_ap, 4) * 100}
     if fpr_limit is not None:
         row["pixel AUPRO"] = round(pro_eval_device(pl, pp, fpr_limit=fpr_limit), 4) * 100
+    if f1_max:
+        _f1_columns(row, details, pixel_f1, image_f1)
+        if details is not None and details.get("masks") is True:
+            shaped = pp[:, 0] if pp.dim() == 4 and pp.shape[1] == 1 else pp
+            details["masks"] = engine.metrics_threshold(shaped, records["f1max"], range_record=records["range"],
+                                                        totals=False)[0]
     return row
 
 

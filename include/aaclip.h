@@ -542,6 +542,42 @@ size_t aaclip_metrics_pro_curve_workspace_bytes(long n);
 int aaclip_metrics_pro_curve(const uint32_t* keys, const uint32_t* areas_sorted, long n, const void* regions_record,
                              double fpr_limit, void* record, void* ws, size_t ws_bytes, void* stream);
 
+/* Exact F1-max of one class and its operating point on the device (csrc/metrics.hip), and the masks at a threshold.  The
+ * conventions are those of the entries above (checks before the first launch, the workspace size last,
+ * *_workspace_bytes 0 for refused sizes and monotonic, overlap checks); integers only, no atomics: any order of
+ * execution gives the same record.  This ABI number is unchanged: the entries are additions.
+ *   aaclip_metrics_f1max: the arguments of aaclip_metrics_curve (sorted keys, packed or with labels_sorted) and its
+ *   first phases (tile sums, scan, the list of tie-group starts).  After the group that starts at ascending index i,
+ *   walking down from the highest score: tp = positives at or above its score, m = n - i elements at or above it,
+ *   F1 = 2 tp / (m + P).  The winner is the group with the largest F1, compared as tp_a (m_b + P) > tp_b (m_a + P) in
+ *   unsigned 64-bit integers (tp < 2^31, m + P < 2^32: exact); among groups of exactly equal F1 the one with the
+ *   highest score.  record <- {tp, fp = m - tp, P, N, groups, start = i, key = the score part of keys[i] (packed: the
+ *   key >> 1, which is the fp32 bit pattern), threshold = the fp32 score decoded from it}; predicted = score >=
+ *   threshold.  P = 0 leaves tp = 0 and the lowest group; the caller checks the classes first.
+ *   aaclip_metrics_threshold: flagged = (v >= threshold) for every raw score, with v = the score, or, when range_record
+ *   (the record of aaclip_metrics_range) is given, the score normalised on the fly with aaclip_metrics_normalise's
+ *   arithmetic and its max != 1.0f decision; IEEE comparison, so -0.0 counts as +0.0 and a NaN is never flagged.  The
+ *   threshold is read on the device from f1max_record (an aaclip_metrics_f1max_record, of which only `threshold` is
+ *   used: no host round trip after aaclip_metrics_f1max).  Outputs, each may be NULL but not all three: mask u8 [n] (1 =
+ *   flagged); image_counts u32 [n / per_image][4] = tp, fp, fn, tn of every image (needs labels and per_image > 0);
+ *   totals <- {tp, fp, fn, tn} over all n -- with labels NULL every label counts as 0: fp = flagged, tn = the rest.
+ *   Two stages: per-workgroup integer partials, one workgroup folds them in index order.  per_image 0: one segment. */
+typedef struct aaclip_metrics_f1max_record {
+  unsigned long long tp, fp, P, N, groups, start;
+  unsigned int key;
+  float threshold;
+} aaclip_metrics_f1max_record;
+typedef struct aaclip_metrics_threshold_record {
+  unsigned long long tp, fp, fn, tn;
+} aaclip_metrics_threshold_record;
+size_t aaclip_metrics_f1max_workspace_bytes(long n);
+int aaclip_metrics_f1max(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
+                         size_t ws_bytes, void* stream);
+size_t aaclip_metrics_threshold_workspace_bytes(long n, long per_image);
+int aaclip_metrics_threshold(const float* scores, const uint8_t* labels, long n, long per_image,
+                             const void* range_record, const void* f1max_record, uint8_t* mask,
+                             uint32_t* image_counts, void* totals, void* ws, size_t ws_bytes, void* stream);
+
 /* Text embedding: x[i*T+t] = token_embedding[tokens[i,t]] + positional_embedding[t].
  * Replaces reference model/adapter.py:277-281 (model/model.py:192-194).  Token ids outside [0, vocab) are CLAMPED
  * to 0 / vocab - 1 (the reference's nn.Embedding raises instead); D a multiple of 4. */
