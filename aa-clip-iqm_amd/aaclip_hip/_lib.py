@@ -48,6 +48,31 @@ class GemmFusedArgs(C.Structure):
         self.struct_bytes = C.sizeof(GemmFusedArgs)
 
 
+OPTIM_MAX_GROUPS = 8     # include/aaclip.h AACLIP_OPTIM_MAX_GROUPS
+OPTIM_CHUNK, OPTIM_TABLE_TENSORS, OPTIM_TABLE_BLOCKS = 16384, 24, 640   # csrc/optim_pack.h
+
+
+class OptimTensor(C.Structure):
+    """struct aaclip_optim_tensor (include/aaclip.h)"""
+    _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("n", _l), ("group", _i)]
+
+
+class OptimTensors(C.Structure):
+    """struct aaclip_optim_tensors (include/aaclip.h): a host array of OptimTensor.  struct_bytes is filled in on
+    construction; the library refuses any other size."""
+    _fields_ = [("struct_bytes", _sz), ("items", C.POINTER(OptimTensor)), ("count", _l)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_bytes = C.sizeof(OptimTensors)
+
+
+class OptimGroup(C.Structure):
+    """struct aaclip_optim_group (include/aaclip.h)"""
+    _fields_ = [("lr", _d), ("beta1", _d), ("beta2", _d), ("eps", _d), ("weight_decay", _d), ("decoupled", _i),
+                ("step", _l)]
+
+
 # name -> (restype, argtypes); every symbol include/aaclip.h declares
 SIGNATURES = {
     "aaclip_version": (_i, []),
@@ -119,6 +144,9 @@ SIGNATURES = {
     "aaclip_metrics_sort_pairs": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
     "aaclip_metrics_pro_curve_workspace_bytes": (_sz, [_l]),
     "aaclip_metrics_pro_curve": (_i, [_vp, _vp, _l, _vp, _d, _vp, _vp, _sz, _vp]),
+    "aaclip_optim_grad_norm_workspace_bytes": (_sz, [C.POINTER(OptimTensors)]),
+    "aaclip_optim_grad_norm": (_i, [C.POINTER(OptimTensors), _f, _vp, _vp, _sz, _vp]),
+    "aaclip_optim_adam_step": (_i, [C.POINTER(OptimTensors), C.POINTER(OptimGroup), _i, _vp, _vp]),
     "aaclip_row_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp] + [_i] * 6 + [_vp, _sz, _vp]),
     "aaclip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _l, _i, _f, _vp]),
     "aaclip_gemm": (_i, [_i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _f, _vp]),

@@ -1775,3 +1775,126 @@ def iqm_map(seg_tokens: Sequence[torch.Tensor], queries: torch.Tensor, img_size:
     _lib.check(lib.aaclip_iqm_map(arr, len(segs), q.data_ptr(), _ptr(bs), out.data_ptr(), B, g, E, img_size, float(w_base),
                                   float(w_iqm), ws.data_ptr(), ws.numel(), _stream(out.device)), "iqm_map")
     return out
+
+
+# ------------------------------------------------------------------------------- fused optimizer step (csrc/optim.hip)
+OPTIM_RECORD_FLOATS = 2          # fp32 words of aaclip_optim_record: total_norm, clip_coef
+OPTIM_MAX_GROUPS = _lib.OPTIM_MAX_GROUPS
+
+
+def _optim_tensor(t: torch.Tensor, what: str, like: Optional[torch.Tensor] = None) -> None:
+    """the optimizer kernels take fp32, contiguous tensors on one GPU as they are: nothing is cast or copied"""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{what}: expected a tensor, got {type(t).__name__}")
+    require_gpu(t, what)
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what}: {t.dtype} tensor; parameters, gradients and optimizer state are fp32 in this library")
+    if t.is_sparse or t.layout != torch.strided or not t.is_contiguous():
+        raise ValueError(f"{what}: the tensor must be dense and contiguous")
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise ValueError(f"{what}: shape {tuple(t.shape)} on {t.device} does not match its parameter's "
+                         f"{tuple(like.shape)} on {like.device}")
+
+
+class OptimPack:
+    """A tensor list in the form the library reads (struct aaclip_optim_tensors), checked once and reusable from step to
+    step: params / grads / exp_avgs / exp_avg_sqs (equally long lists of fp32, contiguous tensors on one GPU; all but
+    grads may be None for a list that only optim_grad_norm reads) and group_of (index into the groups of
+    optim_adam_step per tensor).  set_grad(i, g) swaps one gradient without rebuilding the list."""
+
+    def __init__(self, params, grads, exp_avgs=None, exp_avg_sqs=None, group_of=None, what="optim"):
+        grads = list(grads)
+        full = params is not None
+        if full:
+            params, exp_avgs, exp_avg_sqs, group_of = list(params), list(exp_avgs), list(exp_avg_sqs), list(group_of)
+            if not (len(params) == len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(group_of)):
+                raise ValueError(f"{what}: params, grads, exp_avgs, exp_avg_sqs and group_of must be equally long")
+            for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
+                _optim_tensor(p, what)
+                for t in (g, m, v):
+                    _optim_tensor(t, what, like=p)
+        else:
+            for g in grads:
+                _optim_tensor(g, what)
+        self.params, self.grads, self.exp_avgs, self.exp_avg_sqs = params, grads, exp_avgs, exp_avg_sqs
+        self.group_of = [int(k) for k in group_of] if full else [0] * len(grads)
+        self.device = grads[0].device if grads else None
+        if any(g.device != self.device for g in grads):
+            raise ValueError(f"{what}: the tensors must be on one device")
+        if full:
+            rows = [(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), k)
+                    for p, g, m, v, k in zip(params, grads, exp_avgs, exp_avg_sqs, self.group_of)]
+        else:
+            rows = [(None, g.data_ptr(), None, None, g.numel(), 0) for g in grads]
+        self.items = (_lib.OptimTensor * max(len(rows), 1))(*rows)
+        self.struct = _lib.OptimTensors(items=self.items, count=len(rows))
+        self.norm_workspace_bytes = int(_lib.load().aaclip_optim_grad_norm_workspace_bytes(C.byref(self.struct)))
+
+    def __len__(self):
+        return len(self.grads)
+
+    def set_grad(self, i: int, g: torch.Tensor) -> None:
+        """the caller has checked g (fp32, contiguous, the parameter's shape and device)"""
+        self.grads[i] = g
+        self.items[i].g = g.data_ptr()
+
+
+def _optim_record_ok(record: torch.Tensor, dev) -> bool:
+    return (record.dtype == torch.float32 and record.numel() == OPTIM_RECORD_FLOATS and record.is_contiguous()
+            and (dev is None or record.device == dev))
+
+
+def optim_grad_norm(grads, max_norm: float, record: Optional[torch.Tensor] = None,
+                    workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> record, fp32 [2] on the device: the 2-norm over all of `grads` (a list of tensors, or an OptimPack) and
+    clip_coef = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_'s formula).  Per-chunk fp64 sums in
+    workspace slots, one workgroup adds them: no atomics, the same inputs give the same bits.  The gradients are only
+    read, nothing comes back to the host.  record / workspace: buffers to reuse (fp32 [2]; uint8 of at least
+    pack.norm_workspace_bytes bytes); allocated when None."""
+    pack = grads if isinstance(grads, OptimPack) else OptimPack(None, grads, what="optim_grad_norm")
+    if not float(max_norm) > 0.0:
+        raise ValueError(f"optim_grad_norm: max_norm must be above 0, got {max_norm}")
+    if pack.device is None and record is None:
+        raise ValueError("optim_grad_norm: no gradients and no record to tell the device from")
+    dev = pack.device if pack.device is not None else record.device
+    need = pack.norm_workspace_bytes
+    if record is None:
+        record = torch.empty(OPTIM_RECORD_FLOATS, dtype=torch.float32, device=dev)
+    elif not _optim_record_ok(record, dev):
+        raise ValueError("optim_grad_norm: record must be a contiguous fp32 [2] tensor on the gradients' device")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or workspace.numel() < need:
+        raise ValueError(f"optim_grad_norm: workspace must be a uint8 tensor of at least {need} bytes on {dev}")
+    _lib.check(_lib.load().aaclip_optim_grad_norm(C.byref(pack.struct), float(max_norm), record.data_ptr(),
+                                                  workspace.data_ptr(), workspace.numel(), _stream(dev)),
+               "optim_grad_norm")
+    return record
+
+
+def optim_adam_step(params, grads=None, exp_avgs=None, exp_avg_sqs=None, group_of=None, groups=(),
+                    record: Optional[torch.Tensor] = None) -> None:
+    """One Adam / AdamW step of every tensor in place, in as few launches as the list needs (24 tensors and 640 chunks of
+    16384 elements per launch).  params .. group_of: lists (group_of[i]: index into `groups` of tensor i), or an
+    OptimPack in place of params.  groups: up to OPTIM_MAX_GROUPS dicts {"lr", "beta1", "beta2", "eps", "weight_decay",
+    "decoupled" (True: AdamW), "step" (the step being taken, >= 1)}.  record: the device record of optim_grad_norm,
+    whose clip_coef scales every gradient as it is read (the gradients in memory stay as they are); None: no clipping.
+    Arithmetic: include/aaclip.h aaclip_optim_adam_step."""
+    groups = list(groups)
+    if not 1 <= len(groups) <= OPTIM_MAX_GROUPS:
+        raise ValueError(f"optim_adam_step: 1 .. {OPTIM_MAX_GROUPS} groups per call, got {len(groups)}")
+    pack = params if isinstance(params, OptimPack) else OptimPack(params, grads, exp_avgs, exp_avg_sqs, group_of,
+                                                                  "optim_adam_step")
+    if pack.params is None:
+        raise ValueError("optim_adam_step: the pack holds gradients only")
+    if any(not 0 <= k < len(groups) for k in pack.group_of):
+        raise ValueError(f"optim_adam_step: a group index lies outside the {len(groups)} groups")
+    if not len(pack):
+        return
+    if record is not None and not _optim_record_ok(record, pack.device):
+        raise ValueError("optim_adam_step: record must be the fp32 [2] record of optim_grad_norm on the parameters' device")
+    cg = (_lib.OptimGroup * len(groups))(*[
+        (float(h["lr"]), float(h["beta1"]), float(h["beta2"]), float(h["eps"]), float(h["weight_decay"]),
+         1 if h["decoupled"] else 0, int(h["step"])) for h in groups])
+    _lib.check(_lib.load().aaclip_optim_adam_step(C.byref(pack.struct), cg, len(groups), _ptr(record),
+                                                  _stream(pack.device)), "optim_adam_step")

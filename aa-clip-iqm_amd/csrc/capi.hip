@@ -1569,6 +1569,95 @@ int aaclip_metrics_threshold(const float* scores, const uint8_t* labels, long n,
   return finish("metrics_threshold");
 }
 
+// ---- fused Adam / AdamW step and its gradient norm (optim.hip)
+// the checks the entries share; need: 0 = the counts alone (workspace size), 1 = g as well (grad norm), 2 = p, g, m, v
+// and the group index.  nullptr = fine
+static const char* optim_tensors_check(const aaclip_optim_tensors* t, int need, int n_groups) {
+  if (!t) return "tensors is null";
+  if (t->struct_bytes != sizeof(aaclip_optim_tensors)) return "tensors->struct_bytes is not sizeof(aaclip_optim_tensors)";
+  if (t->count < 0) return "tensors->count is negative";
+  if (t->count > 0 && !t->items) return "tensors->items is null";
+  for (long i = 0; i < t->count; ++i) {
+    const aaclip_optim_tensor& it = t->items[i];
+    if (it.n < 0) return "a tensor has n < 0";
+    if (it.n > OPTIM_MAX_ELEMS) return "a tensor has more than 2^27 * 16384 elements";
+    if (need == 2 && (it.group < 0 || it.group >= n_groups)) return "a tensor's group index is out of range";
+    if (it.n == 0 || need == 0) continue;
+    if (!it.g || (need == 2 && (!it.p || !it.m || !it.v))) return "a tensor with n > 0 has a null pointer";
+    uintptr_t bits = (uintptr_t)it.g;
+    if (need == 2) bits |= (uintptr_t)it.p | (uintptr_t)it.m | (uintptr_t)it.v;
+    if (bits & 3) return "a tensor's pointers must be 4-byte aligned";
+  }
+  return nullptr;
+}
+
+// the element counts as optim_pack.h walks them; the caller frees
+static long* optim_counts(const aaclip_optim_tensors* t) {
+  long* counts = (long*)malloc(sizeof(long) * (size_t)(t->count > 0 ? t->count : 1));
+  for (long i = 0; counts && i < t->count; ++i) counts[i] = t->items[i].n;
+  return counts;
+}
+
+size_t aaclip_optim_grad_norm_workspace_bytes(const aaclip_optim_tensors* tensors) {
+  if (optim_tensors_check(tensors, 0, 0)) return 0;
+  long chunks = 0;
+  for (long i = 0; i < tensors->count; ++i) chunks += optim_chunks(tensors->items[i].n);
+  return up256(optim_grad_norm_ws_bytes(chunks));
+}
+
+int aaclip_optim_grad_norm(const aaclip_optim_tensors* tensors, float max_norm, void* record, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  if (const char* m = optim_tensors_check(tensors, 1, 0)) return fail(-1, in("optim_grad_norm", m));
+  REQUIRE(max_norm > 0.0f, "optim_grad_norm: max_norm must be above 0");
+  REQUIRE(record && workspace, "optim_grad_norm: null pointer");
+  REQUIRE((((uintptr_t)record | (uintptr_t)workspace) & 7) == 0,
+          "optim_grad_norm: record and workspace must be 8-byte aligned");
+  const size_t need = aaclip_optim_grad_norm_workspace_bytes(tensors);
+  REQUIRE(workspace_bytes >= need, "optim_grad_norm: workspace too small");
+  REQUIRE(!ranges_overlap(workspace, need, record, sizeof(aaclip_optim_record)),
+          "optim_grad_norm: record and workspace must not overlap");
+  long* counts = optim_counts(tensors);
+  if (!counts) return fail(-3, "optim_grad_norm: out of memory");
+  launch_optim_grad_norm(tensors->items, counts, tensors->count, max_norm, record, workspace, (hipStream_t)stream);
+  free(counts);
+  return finish("optim_grad_norm");
+}
+
+int aaclip_optim_adam_step(const aaclip_optim_tensors* tensors, const aaclip_optim_group* groups, int n_groups,
+                           const void* record_or_null, void* stream) {
+  REQUIRE(groups, "optim_adam_step: groups is null");
+  REQUIRE(n_groups >= 1 && n_groups <= AACLIP_OPTIM_MAX_GROUPS, "optim_adam_step: n_groups must be 1 .. 8");
+  if (const char* m = optim_tensors_check(tensors, 2, n_groups)) return fail(-1, in("optim_adam_step", m));
+  REQUIRE(((uintptr_t)record_or_null & 7) == 0, "optim_adam_step: record must be 8-byte aligned");
+  OptimGroupScalars scalars[AACLIP_OPTIM_MAX_GROUPS];
+  for (int i = 0; i < n_groups; ++i) {
+    const aaclip_optim_group& g = groups[i];
+    REQUIRE(g.step >= 1, "optim_adam_step: step must be at least 1");
+    REQUIRE(g.lr >= 0.0 && g.lr < INFINITY && g.eps >= 0.0 && g.eps < INFINITY && g.weight_decay >= 0.0 &&
+                g.weight_decay < INFINITY,
+            "optim_adam_step: lr, eps and weight_decay must be finite and not negative");
+    REQUIRE(g.beta1 >= 0.0 && g.beta1 < 1.0 && g.beta2 >= 0.0 && g.beta2 < 1.0,
+            "optim_adam_step: the betas must lie in [0, 1)");
+    REQUIRE(g.decoupled == 0 || g.decoupled == 1, "optim_adam_step: decoupled must be 0 or 1");
+    // fp64 on the host, rounded once
+    const double bc1 = 1.0 - pow(g.beta1, (double)g.step), bc2 = 1.0 - pow(g.beta2, (double)g.step);
+    OptimGroupScalars& h = scalars[i];
+    h.beta1 = (float)g.beta1, h.one_minus_beta1 = (float)(1.0 - g.beta1);
+    h.beta2 = (float)g.beta2, h.one_minus_beta2 = (float)(1.0 - g.beta2);
+    h.step_size = (float)(g.lr / bc1);
+    h.sqrt_bc2 = (float)sqrt(bc2);
+    h.eps = (float)g.eps;
+    h.coupled = !g.decoupled && g.weight_decay != 0.0;
+    h.weight_decay = h.coupled ? (float)g.weight_decay : 0.0f;
+    h.decay = g.decoupled ? (float)(1.0 - g.lr * g.weight_decay) : 1.0f;
+  }
+  long* counts = optim_counts(tensors);
+  if (!counts) return fail(-3, "optim_adam_step: out of memory");
+  launch_optim_adam_step(tensors->items, counts, tensors->count, scalars, n_groups, record_or_null, (hipStream_t)stream);
+  free(counts);
+  return finish("optim_adam_step");
+}
+
 // ---- per-region overlap, AUPRO (regions.hip; the pair sort is metrics.hip's)
 static inline long regions_pixels(long images, long H, long W) {   // 0 where the product is refused
   if (images < 1 || H < 1 || W < 1 || H > 2147483647L || W > 2147483647L || images > 2147483647L) return 0;

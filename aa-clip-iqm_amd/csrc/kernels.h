@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "../../include/aaclip.h"
+#include "optim_pack.h"
 
 namespace aaclip {
 
@@ -294,5 +295,22 @@ void launch_metrics_regions(const uint8_t* mask, long n, int H, int W, int conne
 size_t metrics_pro_curve_ws_bytes(long n);
 void launch_metrics_pro_curve(const uint32_t* keys, const uint32_t* areas_sorted, long n, const void* regions_record,
                               double fpr_limit, void* record, void* ws, hipStream_t s);
+
+// ---- multi-tensor optimizer (optim.hip; the launch packing is optim_pack.h)
+struct OptimGroupScalars {   // one group's hyper-parameters as the kernel reads them: formed in fp64, rounded once
+  float beta1, one_minus_beta1, beta2, one_minus_beta2;
+  float step_size;           // lr / (1 - beta1^step)
+  float sqrt_bc2;            // sqrt(1 - beta2^step)
+  float eps;
+  float weight_decay;        // coupled: g += weight_decay * p
+  float decay;               // decoupled: p *= 1 - lr * weight_decay; exactly 1 otherwise
+  int coupled;
+};
+size_t optim_grad_norm_ws_bytes(long chunks);
+// items: the caller's list; counts[i] = items[i].n (what optim_pack.h walks); record: aaclip_optim_record on the device
+void launch_optim_grad_norm(const aaclip_optim_tensor* items, const long* counts, long tensors, float max_norm,
+                            void* record, void* ws, hipStream_t s);
+void launch_optim_adam_step(const aaclip_optim_tensor* items, const long* counts, long tensors,
+                            const OptimGroupScalars* groups, int n_groups, const void* record, hipStream_t s);
 
 }  // namespace aaclip

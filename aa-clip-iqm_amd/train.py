@@ -39,6 +39,10 @@ trains that very forward (aaclip_hip.autograd.iqm_train_form, IqmQueriesFolded; 
 aaclip_cross_rows_levels_backward): the queries the loss sees are the bits test_last.py evaluates.  It raises
 NotImplementedError before any launch on a model whose forward does not fold (fp32, --relu, a tower neither 768 nor
 1024 wide).
+
+The optimizers are torch's.  `run` also reads two attributes that this parser never sets and train_fused.py's does:
+`fused_optimizer` builds both from aaclip_hip.optim (FusedAdam / FusedAdamW: one multi-tensor HIP step, checkpoints in
+torch's layout either way), and `clip_grad_norm` then clips the stage-2 step inside optimizer.step().
 """
 from __future__ import annotations
 
@@ -319,10 +323,18 @@ def run(args, model_factory=create_model, levels=(6, 12, 18, 24)):
         p.requires_grad_(False)
     for p in list(model.text_adapter.parameters()) + image_params + iqm_params:
         p.requires_grad_(True)
-    text_optimizer = torch.optim.Adam(model.text_adapter.parameters(), lr=args.text_lr, betas=(0.5, 0.999))
-    image_optimizer = torch.optim.AdamW([{"params": image_params, "lr": args.image_lr, "weight_decay": 1e-4},
-                                         {"params": iqm_params, "lr": args.image_lr * 0.1, "weight_decay": 1e-3}],
-                                        betas=(0.9, 0.999))
+    adam, adamw, clip = torch.optim.Adam, torch.optim.AdamW, {}
+    if getattr(args, "fused_optimizer", False):          # train_fused.py; the state and checkpoints keep torch's layout
+        from aaclip_hip import optim
+        adam, adamw = optim.FusedAdam, optim.FusedAdamW
+        # the reference clips in stage 2 alone (train.py:214, on gradients it then discards); here inside step()
+        clip = {"max_grad_norm": getattr(args, "clip_grad_norm", None)}
+    elif getattr(args, "clip_grad_norm", None) is not None:
+        raise ValueError("train.run: clip_grad_norm needs fused_optimizer (the clipping lives inside its step())")
+    text_optimizer = adam(model.text_adapter.parameters(), lr=args.text_lr, betas=(0.5, 0.999))
+    image_optimizer = adamw([{"params": image_params, "lr": args.image_lr, "weight_decay": 1e-4},
+                             {"params": iqm_params, "lr": args.image_lr * 0.1, "weight_decay": 1e-3}],
+                            betas=(0.9, 0.999), **clip)
     image_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(image_optimizer, T_max=args.image_epoch, eta_min=1e-6)
     # resume (train.py:356-375)
     text_start_epoch = 0
@@ -371,13 +383,18 @@ def run(args, model_factory=create_model, levels=(6, 12, 18, 24)):
                                img_size=args.img_size, logger=logger)
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
+def host_threads():
+    """the reference's thread settings (train.py:27-34)"""
     for name in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS", "VECLIB_MAXIMUM_THREADS",
                  "NUMEXPR_NUM_THREADS"):
         os.environ[name] = str(HOST_THREADS)
     torch.set_num_threads(HOST_THREADS)
     os.environ["TOKENIZERS_PARALLELISM"] = "false"
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    host_threads()
     return run(args)
 
 

@@ -578,6 +578,57 @@ int aaclip_metrics_threshold(const float* scores, const uint8_t* labels, long n,
                              const void* range_record, const void* f1max_record, uint8_t* mask,
                              uint32_t* image_counts, void* totals, void* ws, size_t ws_bytes, void* stream);
 
+/* Fused Adam / AdamW step over a list of tensors, and the gradient norm that clips it (csrc/optim.hip).  fp32
+ * parameters, gradients and state only.  One launch serves up to 24 tensors and 640 chunks of 16384 elements; its table
+ * travels by value in the kernel arguments, so a call copies nothing to the device, allocates nothing and waits for
+ * nothing.  Every argument check happens before the first launch and a bad argument returns -1: a null struct, a
+ * struct_bytes other than sizeof, count < 0, items null with count > 0, n < 0 or n > 2^27 * 16384, a null or not
+ * 4-byte aligned pointer of a tensor with n > 0, a group index outside [0, n_groups), n_groups outside
+ * 1 .. AACLIP_OPTIM_MAX_GROUPS, step < 1, a negative or non-finite lr / eps / weight_decay, a beta outside [0, 1), decoupled
+ * other than 0 / 1, max_norm not above 0, record / workspace null or not 8-byte aligned, a workspace too small.
+ * Tensors with n == 0 are skipped.  This ABI number is unchanged: the entries are additions.
+ *   aaclip_optim_grad_norm: only g and n of every tensor are read.  Stage 1, one workgroup per chunk: the sum of g^2
+ *   over the chunk in fp64, stored in the workspace slot of that chunk (no atomics).  Stage 2, one workgroup: the slots
+ *   added in fp64 in a fixed order; record <- {total_norm = fp32(sqrt(sum)), clip_coef = min(1, max_norm / (total_norm
+ *   + 1e-6))} in fp32, torch.nn.utils.clip_grad_norm_'s formula.  The same inputs give the same bits.  A NaN or inf
+ *   gradient gives a NaN or inf norm and a NaN or 0 coefficient; nothing is skipped.
+ *   aaclip_optim_adam_step: per element, in fp32 with every operation rounded on its own,
+ *     g' = g * coef (+ weight_decay * p when decoupled == 0);  p' = p * (1 - lr * weight_decay) when decoupled == 1
+ *     m = beta1 * m + (1 - beta1) * g';  v = beta2 * v + (1 - beta2) * g' * g'
+ *     p = p' - (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps)),  bc1 = 1 - beta1^step, bc2 = 1 - beta2^step
+ *   coef = record->clip_coef read on the device (no host round trip after aaclip_optim_grad_norm), or 1 when record is
+ *   NULL.  1 - beta, 1 - lr * weight_decay, lr / bc1 and sqrt(bc2) are formed on the host in fp64 and rounded once to
+ *   fp32.  UNLIKE clip_grad_norm_, the gradients in memory are not rescaled: g is read only.  16-byte loads and stores
+ *   where p, g, m and v of a tensor are all 16-byte aligned, 4-byte ones otherwise, with the same arithmetic: a
+ *   tensor's result does not depend on its alignment, on its place in the list or on the other tensors. */
+#define AACLIP_OPTIM_MAX_GROUPS 8
+typedef struct aaclip_optim_tensor {
+  void* p;          /* parameter, fp32 [n], updated in place */
+  const void* g;    /* gradient, fp32 [n], read only */
+  void* m;          /* exp_avg, fp32 [n], updated in place */
+  void* v;          /* exp_avg_sq, fp32 [n], updated in place */
+  long n;
+  int group;        /* index into the groups of aaclip_optim_adam_step; ignored by aaclip_optim_grad_norm */
+} aaclip_optim_tensor;
+typedef struct aaclip_optim_tensors {
+  size_t struct_bytes;               /* sizeof(aaclip_optim_tensors) */
+  const aaclip_optim_tensor* items;  /* HOST array */
+  long count;
+} aaclip_optim_tensors;
+typedef struct aaclip_optim_group {
+  double lr, beta1, beta2, eps, weight_decay;
+  int decoupled;    /* 1: AdamW, 0: Adam (the decay joins the gradient) */
+  long step;        /* the step being taken, 1 for the first */
+} aaclip_optim_group;
+typedef struct aaclip_optim_record {
+  float total_norm, clip_coef;
+} aaclip_optim_record;
+size_t aaclip_optim_grad_norm_workspace_bytes(const aaclip_optim_tensors* tensors);   /* 0 for a refused list */
+int aaclip_optim_grad_norm(const aaclip_optim_tensors* tensors, float max_norm, void* record, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int aaclip_optim_adam_step(const aaclip_optim_tensors* tensors, const aaclip_optim_group* groups, int n_groups,
+                           const void* record_or_null, void* stream);
+
 /* Text embedding: x[i*T+t] = token_embedding[tokens[i,t]] + positional_embedding[t].
  * Replaces reference model/adapter.py:277-281 (model/model.py:192-194).  Token ids outside [0, vocab) are CLAMPED
  * to 0 / vocab - 1 (the reference's nn.Embedding raises instead); D a multiple of 4. */
