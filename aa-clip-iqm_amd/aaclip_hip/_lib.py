@@ -140,6 +140,8 @@ SIGNATURES = {
     "aaclip_metrics_threshold": (_i, [_vp, _vp, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "aaclip_metrics_regions_workspace_bytes": (_sz, [_l, _l, _l]),
     "aaclip_metrics_regions": (_i, [_vp, _l, _l, _l, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aaclip_region_table_workspace_bytes": (_sz, [_l, _l, _l]),
+    "aaclip_region_table": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _l, _l, _l, _l, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "aaclip_metrics_sort_pairs_workspace_bytes": (_sz, [_l]),
     "aaclip_metrics_sort_pairs": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
     "aaclip_metrics_pro_curve_workspace_bytes": (_sz, [_l]),

@@ -1455,6 +1455,135 @@ def pro_metrics(scores: torch.Tensor, mask: torch.Tensor, fpr_limit: float = 0.3
 
 
 # ------------------------------------------------------------------------------------------------
+# defect instances at an operating point (csrc/region_table.hip; forward_utils.defects_eval_device)
+REGION_ROW_WORDS = 12           # int32 words of a row, in REGION_ROW_FIELDS' order; `peak` holds fp32 bits
+REGION_ROW_FIELDS = ("image", "label", "first", "area", "x0", "y0", "x1", "y1", "peak_x", "peak_y", "peak", "overlap")
+REGION_TABLE_RECORD_WORDS = 4   # int64 words: rows kept, regions seen, kept regions with overlap > 0, rows dropped
+DEFECTS_RECORD_WORDS = 6        # int64 words: predicted regions, predicted hit, gt regions, gt hit, images, images with >= 1
+RegionTable = collections.namedtuple("RegionTable", "rows image_offsets record kept_mask")
+Defects = collections.namedtuple("Defects", "predicted truth record mask")
+
+
+def region_table(region: torch.Tensor, area: torch.Tensor, scores: torch.Tensor, other: Optional[torch.Tensor] = None,
+                 range_record: Optional[torch.Tensor] = None, min_area: int = 1, kept_mask: bool = False,
+                 regions=None) -> RegionTable:
+    """-> RegionTable(rows, image_offsets, record, kept_mask), device tensors: the regions of metrics_regions (its
+    `region` and `area`, [N, H, W]) with at least min_area pixels as rows int32 [R, 12] (REGION_ROW_FIELDS) in canonical
+    order -- ascending (image, first pixel), scipy's label order; image_offsets int32 [N + 1], the rows in front of
+    every image; record int64 [4] = rows kept, regions seen, kept regions that overlap `other`, rows dropped.
+    scores fp32 of the same size: `peak` is the largest score of the region, normalised on the fly with range_record
+    (metrics_range's) when that is given, (peak_x, peak_y) the lowest flat index that attains it.  other: a uint8 mask of
+    the same size whose non-zero pixels are counted in `overlap`.  kept_mask=True also returns the uint8 mask of the
+    kept regions' pixels.
+    regions: the record of metrics_regions (one synchronising copy of 24 bytes sizes `rows`) or the region count as a
+    number; None takes the most regions the images can hold (every other pixel), which is safe and large.  `rows` is cut to
+    the rows kept (with the record and min_area = 1 that is every row, and nothing more is read back).  Raises
+    RuntimeError if the record reports dropped rows (a count that was too small)."""
+    require_gpu(region, "region_table")
+    shape, dev = region.shape, region.device
+    if region.dtype != torch.int32 or region.dim() < 2 or not 2 <= region.numel() <= METRICS_MAX_N:
+        raise ValueError("region_table expects the int32 [images, H, W] region map of metrics_regions")
+    n, H, W = region.numel(), int(shape[-2]), int(shape[-1])
+    images = n // (H * W)
+    for name, t, dt in (("area", area, torch.int32), ("scores", scores, torch.float32), ("other", other, torch.uint8)):
+        if t is not None and (t.dtype != dt or t.numel() != n or t.device != dev):
+            raise ValueError(f"region_table: {name} must be a {dt} tensor of the region map's size and device")
+    if range_record is not None and (range_record.dtype != torch.int64 or range_record.numel() != 3
+                                     or range_record.device != dev):
+        raise ValueError("region_table: range_record must be the int64 [3] record of metrics_range")
+    if int(min_area) < 1:
+        raise ValueError(f"region_table: min_area must be at least 1, got {min_area}")
+    exact = torch.is_tensor(regions)
+    if exact:
+        if regions.dtype != torch.int64 or regions.numel() != 3:
+            raise ValueError("region_table: regions must be the int64 [3] record of metrics_regions or a number")
+        capacity = int(regions.cpu()[0])
+    else:
+        capacity = images * ((H * W + 1) // 2) if regions is None else int(regions)
+    if capacity < 0:
+        raise ValueError(f"region_table: a negative region count, {capacity}")
+    region, area, scores = region.contiguous(), area.contiguous(), scores.contiguous()
+    other = None if other is None else other.contiguous()
+    lib = _lib.load()
+    rows = torch.empty(capacity, REGION_ROW_WORDS, dtype=torch.int32, device=dev)
+    offsets = torch.empty(images + 1, dtype=torch.int32, device=dev)
+    record = torch.empty(REGION_TABLE_RECORD_WORDS, dtype=torch.int64, device=dev)
+    kept = torch.empty(shape, dtype=torch.uint8, device=dev) if kept_mask else None
+    ws = Workspace.get(dev, lib.aaclip_region_table_workspace_bytes(images, H, W))
+    _lib.check(lib.aaclip_region_table(region.data_ptr(), area.data_ptr(), scores.data_ptr(), _ptr(range_record),
+                                       _ptr(other), images, H, W, int(min_area), capacity,
+                                       rows.data_ptr() if capacity else None, offsets.data_ptr(), _ptr(kept),
+                                       record.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "region_table")
+    if not (exact and int(min_area) == 1):      # with the regions record and no filter every row is written: R = capacity
+        h = record.cpu()
+        if int(h[3]):
+            raise RuntimeError(f"region_table: {int(h[3])} of {int(h[0])} rows were dropped: the region count "
+                               f"{capacity} is too small for this region map")
+        rows = rows[:int(h[0])]
+    return RegionTable(rows, offsets, record, kept)
+
+
+def region_rows_per_image(rows, image_offsets) -> list:
+    """Host arrays of a region table (rows int32 [R, 12], offsets [N + 1]) -> a list per image of dicts with
+    REGION_ROW_FIELDS' keys (without "image"), `peak` as a float, in canonical order."""
+    import numpy as np
+    rows = np.asarray(rows).reshape(-1, REGION_ROW_WORDS)
+    peaks = np.ascontiguousarray(rows[:, 10]).view(np.float32)
+    names = [(c, k) for c, k in enumerate(REGION_ROW_FIELDS) if k not in ("image", "peak")]
+    out = []
+    for i in range(len(image_offsets) - 1):
+        span = range(int(image_offsets[i]), int(image_offsets[i + 1]))
+        assert all(int(rows[j, 0]) == i for j in span), "a row outside its image's offsets"
+        out.append([dict({k: int(rows[j, c]) for c, k in names}, peak=float(peaks[j])) for j in span])
+    return out
+
+
+def region_table_host(table: RegionTable) -> list:
+    """The device table on the host (region_rows_per_image of it); raises if the record reports dropped rows."""
+    record = table.record.cpu()
+    if int(record[3]):
+        raise RuntimeError(f"region_table_host: {int(record[3])} rows were dropped")
+    return region_rows_per_image(table.rows.cpu().numpy()[:int(record[0])], table.image_offsets.cpu().numpy())
+
+
+def defects_at_threshold(scores: torch.Tensor, threshold, range_record: Optional[torch.Tensor], gt_mask=None,
+                         min_area: int = 1, connectivity: int = 8) -> Defects:
+    """The defect instances of fp32 maps [N, H, W] at an operating point, on the device: metrics_threshold gives the
+    predicted mask (threshold: the device record of metrics_f1max, read on the device, or a number; scores normalised on
+    the fly with range_record when given), metrics_regions labels it, region_table lists the regions of at least
+    min_area pixels with other = gt_mask.  With gt_mask (uint8, non-zero = anomalous) the ground truth is labelled too
+    and tabulated against the KEPT predicted mask, which says which true regions were found.
+    -> Defects(predicted, truth, record, mask): two RegionTables (truth None without gt_mask), the device record int64
+    [6] = predicted regions, predicted regions that touch ground truth, gt regions, gt regions that were hit, images,
+    images with at least one predicted region; mask = the kept predicted uint8 mask."""
+    require_gpu(scores, "defects_at_threshold")
+    if scores.dtype != torch.float32 or scores.dim() < 2:
+        raise ValueError("defects_at_threshold expects fp32 maps of [images, H, W]")
+    dev, shape = scores.device, scores.shape
+    if gt_mask is not None:
+        require_gpu(gt_mask, "defects_at_threshold")
+        if gt_mask.dtype != torch.uint8 or gt_mask.numel() != scores.numel() or gt_mask.device != dev:
+            raise ValueError("defects_at_threshold: gt_mask must be a uint8 tensor of the maps' size and device")
+        gt_mask = gt_mask.contiguous().view(shape)
+    predicted_mask = metrics_threshold(scores, threshold, range_record=range_record, totals=False)[0]
+    region, area, regions_record = metrics_regions(predicted_mask, connectivity)
+    predicted = region_table(region, area, scores, other=gt_mask, range_record=range_record, min_area=min_area,
+                             kept_mask=True, regions=regions_record)
+    del region, area
+    images = predicted.image_offsets.numel() - 1
+    with_any = (predicted.image_offsets[1:] != predicted.image_offsets[:-1]).sum()
+    record = torch.zeros(DEFECTS_RECORD_WORDS, dtype=torch.int64, device=dev)
+    record[0], record[1], record[4], record[5] = predicted.record[0], predicted.record[2], images, with_any
+    truth = None
+    if gt_mask is not None:
+        region, area, regions_record = metrics_regions(gt_mask, connectivity)
+        truth = region_table(region, area, scores, other=predicted.kept_mask, range_record=range_record,
+                             regions=regions_record)
+        record[2], record[3] = truth.record[0], truth.record[2]
+    return Defects(predicted, truth, record, predicted.kept_mask)
+
+
+# ------------------------------------------------------------------------------------------------
 # IQM side branch (reference model/iqm.py, model/adapter.py:186-269, test_last.py:102-147): thin wrappers of the C ABI
 def gemm(code: int, epi: int, a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor,
          act: int = 0) -> torch.Tensor:

@@ -1738,6 +1738,42 @@ int aaclip_metrics_pro_curve(const uint32_t* keys, const uint32_t* areas_sorted,
   return finish("metrics_pro_curve");
 }
 
+// ---- the table of the regions (region_table.hip)
+size_t aaclip_region_table_workspace_bytes(long images, long H, long W) {
+  const long n = regions_pixels(images, H, W);
+  return n ? up256(region_table_ws_bytes(n, images)) : 0;
+}
+
+int aaclip_region_table(const uint32_t* region, const uint32_t* area, const float* scores, const void* range_record,
+                        const uint8_t* other, long images, long H, long W, long min_area, long capacity, void* rows,
+                        int32_t* image_offsets, uint8_t* kept_mask, void* record, void* ws, size_t ws_bytes,
+                        void* stream) {
+  REQUIRE(region && area && scores && image_offsets && record && ws, "region_table: null pointer");
+  const long n = regions_pixels(images, H, W);
+  REQUIRE(n != 0, "region_table: images, H, W must be positive with 2 .. 2^31 - 1 pixels in all");
+  REQUIRE(min_area >= 1, "region_table: min_area must be at least 1");
+  REQUIRE(capacity >= 0, "region_table: capacity must not be negative");
+  REQUIRE(capacity == 0 || rows, "region_table: rows is null with capacity > 0");
+  REQUIRE((((uintptr_t)region | (uintptr_t)area | (uintptr_t)scores | (uintptr_t)image_offsets) & 3) == 0 &&
+              (((uintptr_t)range_record | (uintptr_t)rows | (uintptr_t)record | (uintptr_t)ws) & 7) == 0,
+          "region_table: region / area / scores / image_offsets must be 4-byte, rows / records / workspace 8-byte aligned");
+  const size_t need = aaclip_region_table_workspace_bytes(images, H, W), n4 = (size_t)n * 4;
+  const size_t row_bytes = rows ? (size_t)(capacity < n ? capacity : n) * sizeof(aaclip_region_row) : 0;
+  // every written buffer (rows, image_offsets, kept_mask, record, workspace) against every other buffer of the call
+  const void* bufs[10] = {rows, image_offsets, kept_mask, record, ws, region, area, scores, range_record, other};
+  const size_t lens[10] = {row_bytes, (size_t)(images + 1) * 4, (size_t)n, sizeof(aaclip_region_table_record), need,
+                           n4, n4, n4, 24, (size_t)n};
+  bool clash = false;
+  for (int a = 0; a < 5; ++a)
+    for (int b = a + 1; b < 10; ++b)
+      clash = clash || (bufs[a] && bufs[b] && lens[a] && lens[b] && ranges_overlap(bufs[a], lens[a], bufs[b], lens[b]));
+  REQUIRE(!clash, "region_table: inputs, outputs, records and workspace must not overlap one another");
+  REQUIRE(ws_bytes >= need, "region_table: workspace too small");
+  launch_region_table(region, area, scores, range_record, other, images, (int)H, (int)W, min_area, capacity, rows,
+                      image_offsets, kept_mask, record, ws, (hipStream_t)stream);
+  return finish("region_table");
+}
+
 int aaclip_text_embed(const int32_t* tokens, const float* table, const float* pos, float* x, int n, int T, int D,
                       int vocab, void* stream) {
   REQUIRE(tokens && table && pos && x, "text_embed: null pointer");

@@ -295,6 +295,11 @@ void launch_metrics_regions(const uint8_t* mask, long n, int H, int W, int conne
 size_t metrics_pro_curve_ws_bytes(long n);
 void launch_metrics_pro_curve(const uint32_t* keys, const uint32_t* areas_sorted, long n, const void* regions_record,
                               double fpr_limit, void* record, void* ws, hipStream_t s);
+// ---- region_table.hip : one row per region of launch_metrics_regions: box, peak, overlap with a second mask
+size_t region_table_ws_bytes(long n, long images);
+void launch_region_table(const uint32_t* region, const uint32_t* area, const float* scores, const void* range_record,
+                         const uint8_t* other, long images, int H, int W, long min_area, long capacity, void* rows,
+                         int32_t* image_offsets, uint8_t* kept_mask, void* record, void* ws, hipStream_t s);
 
 // ---- multi-tensor optimizer (optim.hip; the launch packing is optim_pack.h)
 struct OptimGroupScalars {   // one group's hyper-parameters as the kernel reads them: formed in fp64, rounded once

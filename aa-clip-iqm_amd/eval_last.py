@@ -21,6 +21,9 @@ the same names and arguments:
                                           f1_max=True adds "pixel F1-max" and "image F1-max", the best F1 over every
                                           threshold (forward_utils.f1max_eval / engine.f1max_metrics); eval_metrics.py is
                                           the script with the --f1max flag
+                                          defects=MIN_AREA (with f1_max) adds the region-level columns of the defect
+                                          instances at the pixel F1-max threshold (forward_utils.defects_eval /
+                                          engine.defects_at_threshold); eval_defects.py is the script with --defects
   main(argv)                              the arguments and steps of test_last.main plus --device_metrics
 
 python eval_last.py --save_path ... [--device_metrics] [every argument of test_last.py]
@@ -40,7 +43,7 @@ import test_last as TL
 from aaclip_hip import engine
 from aaclip_hip.shard import gather_predictions, shard_range
 from dataset import DOMAINS
-from forward_utils import (IMAGE_F1_COL, PIXEL_F1_COL, calculate_anomaly_map, image_score, metrics_eval,
+from forward_utils import (DEFECT_COLS, IMAGE_F1_COL, PIXEL_F1_COL, calculate_anomaly_map, image_score, metrics_eval,
                            metrics_eval_device)
 
 AUPRO_COL = "pixel AUPRO"
@@ -89,7 +92,7 @@ def evaluate(model, image_datasets: Dict[str, torch.utils.data.Dataset], text_em
 def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], text_embeddings: Dict[str, torch.Tensor],
                   device, img_size: int, dataset: str, batch_size: int = 32, loader_kwargs=None, logger=None,
                   use_iqm: bool = True, device_metrics: bool = False, fpr_limit=None, f1_max: bool = False,
-                  details: Dict[str, dict] = None, return_masks: bool = False) -> List[dict]:
+                  details: Dict[str, dict] = None, return_masks: bool = False, defects=None) -> List[dict]:
     """The per-class loop of test_last.evaluate for either metrics path.  device_metrics: the class's masks, maps and
     image scores stay on the GPU, the row comes from metrics_eval_device, and the tensors are released before the next
     class.  Under torch.distributed the shards are gathered as host arrays exactly as in test_last.evaluate (so the
@@ -97,8 +100,13 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
     false-positive rate in (0, 1] adds "pixel AUPRO" to every row and to the average; None leaves the rows as they are.
     f1_max: adds "pixel F1-max" and "image F1-max" likewise (forward_utils.f1max_eval; on the GPU from the sort that
     serves AUROC / AP).  details: with f1_max, a dict that receives, per class name, what metrics_eval's `details`
-    receives: the thresholds of the operating points and, with return_masks=True, the class's predicted uint8 masks."""
+    receives: the thresholds of the operating points and, with return_masks=True, the class's predicted uint8 masks;
+    beside them the class's "file_names", "labels" and raw "image scores" in the order of the maps.
+    defects: None, or a min_area (needs f1_max): metrics_eval's keyword -- the three region-level columns of
+    forward_utils.DEFECT_COLS in every row and in the average, the per-image lists of defects under details[class]."""
     import torch.distributed as dist
+    if defects is not None and not f1_max:
+        raise ValueError("evaluate_rows: defects needs f1_max=True (the regions are those at the pixel F1-max threshold)")
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
     rows = []
@@ -110,13 +118,13 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
         if len(image_dataset) > 0:
             loader = torch.utils.data.DataLoader(image_dataset, batch_size=batch_size, shuffle=False, **(loader_kwargs or {}))
             with torch.no_grad():
-                masks, labels, preds, preds_image, _ = get_predictions(
+                masks, labels, preds, preds_image, file_names = get_predictions(
                     model=model, class_text_embeddings=text_embeddings[class_name], test_loader=loader, device=device,
                     img_size=img_size, dataset=dataset, use_iqm=use_iqm, on_device=device_metrics and world == 1)
         else:   # more ranks than images of this class
             masks = np.zeros((0, 1, img_size, img_size), np.float32)
             labels, preds_image = np.zeros((0,), np.int64), np.zeros((0,), np.float32)
-            preds = np.zeros((0, img_size, img_size), np.float32)
+            preds, file_names = np.zeros((0, img_size, img_size), np.float32), []
         if world > 1:
             gdev = device if dist.get_backend() == "nccl" else None
             masks, labels, preds, preds_image = gather_predictions(
@@ -131,14 +139,25 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
         extra = {}
         if f1_max:
             extra["f1_max"] = True
+            if defects is not None:
+                extra["defects"] = defects
             if details is not None:
-                extra["details"] = details[class_name] = {"masks": bool(return_masks)}
+                if world > 1:
+                    shards = [None] * world
+                    dist.all_gather_object(shards, list(file_names))
+                    file_names = [name for shard in shards for name in shard]
+                scores = preds_image.detach().cpu().numpy() if torch.is_tensor(preds_image) else np.asarray(preds_image)
+                extra["details"] = details[class_name] = {
+                    "masks": bool(return_masks), "file_names": list(file_names),
+                    "labels": [int(v) for v in np.asarray(labels).reshape(-1)],
+                    "image scores": [float(v) for v in scores.reshape(len(file_names), -1)[:, 0]] if file_names else []}
         rows.append(row_of(masks, labels, preds, preds_image, class_name, domain=DOMAINS[dataset], fpr_limit=fpr_limit,
                            **extra))
         del masks, preds, preds_image          # released before the next class is evaluated
         if logger:
             logger.info("%s", rows[-1])
-    cols = TL.NUMERIC_COLS + ([AUPRO_COL] if fpr_limit is not None else []) + (F1_COLS if f1_max else [])
+    cols = (TL.NUMERIC_COLS + ([AUPRO_COL] if fpr_limit is not None else []) + (F1_COLS if f1_max else []) +
+            (DEFECT_COLS if defects is not None else []))
     avg = {c: float(np.mean([r[c] for r in rows])) for c in cols}
     avg["class name"] = "Average"
     rows.append(avg)
@@ -227,15 +246,19 @@ def main(argv=None):
     return run(build_parser(), argv)
 
 
-def run(parser: argparse.ArgumentParser, argv=None):
+def run(parser: argparse.ArgumentParser, argv=None, table=None, finish=None):
     """main() for a parser that may carry further arguments: `aupro` (eval_aupro.py), a false-positive rate or None,
-    and `f1max` (eval_metrics.py), which adds the F1-max columns and logs every class's thresholds"""
+    `f1max` (eval_metrics.py), which adds the F1-max columns and logs every class's thresholds, and `defects`
+    (eval_defects.py), a minimum area or None, which implies f1max and adds the region-level columns.  table: the
+    function that formats the rows (format_table); finish(args, rows, details): called after the evaluation when the
+    F1-max path ran."""
     from dataset import get_dataset
     from forward_utils import get_adapted_text_embedding
     from model.adapter import AdaptedCLIP
     from model.clip import create_model
     args = parser.parse_args(argv)
-    aupro, f1_max = getattr(args, "aupro", None), bool(getattr(args, "f1max", False))
+    defects = getattr(args, "defects", None)
+    aupro, f1_max = getattr(args, "aupro", None), bool(getattr(args, "f1max", False)) or defects is not None
     if args.iqm_hidden_size != 768:
         parser.error("--iqm_hidden_size must be 768 (the visual features' width; see test_last.py)")
     if aupro is not None and not 0.0 < aupro <= 1.0:
@@ -274,13 +297,16 @@ def run(parser: argparse.ArgumentParser, argv=None):
                use_iqm=args.iqm == "on", device_metrics=args.device_metrics)
     if f1_max:
         details = {}
-        rows = evaluate_rows(*where, **how, fpr_limit=aupro, f1_max=True, details=details)
+        extra = {} if defects is None else {"defects": defects}
+        rows = evaluate_rows(*where, **how, fpr_limit=aupro, f1_max=True, details=details, **extra)
         for name, d in details.items():
             logger.info("%s: pixel threshold %.9g, image threshold %s (normalised units)", name, d["pixel threshold"],
                         d["image threshold"])
+        if finish is not None:
+            finish(args, rows, details)
     else:
         rows = evaluate(*where, **how) if aupro is None else evaluate_rows(*where, **how, fpr_limit=aupro)
-    table = format_table(rows)
+    table = (table or format_table)(rows)
     logger.info("final results:\n%s", table)
     if int(os.environ.get("RANK", "0")) == 0:
         print(table)

@@ -2,6 +2,7 @@
 (reference forward_utils.py:138-216), executed by the HIP path."""
 from __future__ import annotations
 
+import collections
 from typing import Sequence
 
 import torch
@@ -274,10 +275,136 @@ def f1max_eval_device(labels, scores):
 
 
 PIXEL_F1_COL, IMAGE_F1_COL = "pixel F1-max", "image F1-max"
+DEFECT_COLS = ["region recall", "region precision", "false regions / image"]
+HostRegionTable = collections.namedtuple("HostRegionTable", "rows image_offsets record kept_mask")
+
+
+def region_table_host(mask, scores, other=None, min_area=1, connectivity=8):
+    """The table of the connected regions of a mask on the host -- the definition the device path is measured against
+    (engine.region_table).  mask [N, H, W] (non-zero = set), scores of the same shape, taken as they are, other an
+    optional second mask:
+      1. scipy.ndimage.label of every image on its own (connectivity 8 = the 3x3 structure, or 4): its label numbers
+         are the order of the regions' first pixels in row-major order
+      2. per region: area, the bounding box of find_objects (x0 / y0 inclusive, x1 / y1 exclusive), the number of its
+         pixels where other is non-zero, and over its pixels IN ROW-MAJOR ORDER peak = np.max and the position of the
+         FIRST np.argmax -- the lowest flat index among equal scores; -0.0 counts as +0.0.  scipy's maximum_position
+         is not used: on a constant region it returns the last pixel, not the first
+      3. regions of fewer than min_area pixels get no row; the labels of the others stay what they were.
+    -> HostRegionTable(rows int32 [R, 12] in engine.REGION_ROW_FIELDS' order with the fp32 bits of the peak, image_offsets
+    int32 [N + 1], record (kept, regions, kept regions with overlap > 0, 0), kept_mask uint8)."""
+    import numpy as np
+    from scipy import ndimage
+
+    mask, scores = np.asarray(mask), np.asarray(scores)
+    if mask.ndim != 3 or scores.shape != mask.shape or (other is not None and np.asarray(other).shape != mask.shape):
+        raise ValueError(f"region_table_host: a mask of [N, H, W], scores and other in its shape, got {mask.shape}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"region_table_host: connectivity must be 4 or 8, got {connectivity}")
+    if int(min_area) < 1:
+        raise ValueError(f"region_table_host: min_area must be at least 1, got {min_area}")
+    other = None if other is None else np.asarray(other) != 0
+    structure = np.ones((3, 3), int) if connectivity == 8 else ndimage.generate_binary_structure(2, 1)
+    N, H, W = mask.shape
+    rows, offsets, regions, hit = [], [0], 0, 0
+    kept_mask = np.zeros(mask.shape, np.uint8)
+    for k in range(N):
+        lab, count = ndimage.label(mask[k] != 0, structure=structure)
+        regions += count
+        areas = np.bincount(lab.reshape(-1), minlength=count + 1)
+        for j, box in enumerate(ndimage.find_objects(lab), start=1):
+            area = int(areas[j])
+            if area < min_area:
+                continue
+            inside = lab[box] == j
+            ys, xs = np.nonzero(inside)                       # row-major order
+            values = scores[k][box][inside] + scores.dtype.type(0)      # -0.0 + 0.0 = +0.0
+            at = int(np.argmax(values))                       # the first of equal maxima
+            y0, x0 = box[0].start, box[1].start
+            overlap = int(np.count_nonzero(other[k][box][inside])) if other is not None else 0
+            hit += overlap > 0
+            rows.append((k, j, (y0 + int(ys[0])) * W + x0 + int(xs[0]), area, x0, y0, box[1].stop, box[0].stop,
+                         x0 + int(xs[at]), y0 + int(ys[at]), int(np.float32(values[at]).view(np.uint32)), overlap))
+            kept_mask[k][box][inside] = 1
+        offsets.append(len(rows))
+    table = np.array(rows, dtype=np.int64).reshape(-1, 12).astype(np.uint32).view(np.int32)
+    return HostRegionTable(table, np.array(offsets, np.int32), (len(rows), regions, hit, 0), kept_mask)
+
+
+region_rows_per_image = engine.region_rows_per_image
+
+
+def defects_from_record(record):
+    """The three region-level columns from the six integers {predicted regions, predicted hit, gt regions, gt hit,
+    images, images with a predicted region}: each ONE division of Python integers, so the host and the device path,
+    which agree on the integers, agree on the bits."""
+    predicted, predicted_hit, truth, truth_hit, images, _ = (int(v) for v in record)
+    return {"region recall": truth_hit / truth if truth else 0.0,
+            "region precision": predicted_hit / predicted if predicted else 0.0,
+            "false regions / image": (predicted - predicted_hit) / images}
+
+
+def _defect_shapes(masks, preds, what):
+    if preds.ndim == 4 and preds.shape[1] == 1:
+        preds = preds[:, 0]
+    if preds.ndim != 3 or masks.size != preds.size:
+        raise ValueError(f"{what}: maps of [N, H, W] and as many labels, got {preds.shape} and {masks.shape}")
+    return masks.reshape(preds.shape), preds
+
+
+def defects_eval(masks, preds, threshold, min_area=1):
+    """The defect instances of one class at an operating point, on the host (8-connectivity): predicted = preds >=
+    threshold (preds are taken as they are: metrics_eval hands in the normalised maps), its regions of at least min_area
+    pixels tabulated against the ground truth `masks`, and the ground-truth regions against the KEPT predicted pixels.
+    -> a dict: "region recall" = gt regions with >= 1 kept predicted pixel / gt regions, "region precision" = kept
+    predicted regions with >= 1 gt pixel / kept predicted regions (0.0 without any), "false regions / image" = kept
+    predicted regions without a gt pixel / images; "record" = the six integers of defects_from_record; "predicted" and
+    "truth" = the per-image lists of region_rows_per_image; "kept mask" = the predicted mask without small regions."""
+    import numpy as np
+    masks, preds = _defect_shapes(np.asarray(masks), np.asarray(preds), "defects_eval")
+    predicted = region_table_host(preds >= preds.dtype.type(threshold), preds, other=masks, min_area=min_area)
+    truth = region_table_host(masks, preds, other=predicted.kept_mask)
+    with_any = int(np.count_nonzero(np.diff(predicted.image_offsets)))
+    record = (predicted.record[0], predicted.record[2], truth.record[0], truth.record[2], preds.shape[0], with_any)
+    out = defects_from_record(record)
+    out.update(record=record, predicted=region_rows_per_image(predicted.rows, predicted.image_offsets),
+               truth=region_rows_per_image(truth.rows, truth.image_offsets))
+    out["kept mask"] = predicted.kept_mask
+    return out
+
+
+def defects_eval_device(masks, preds, threshold, min_area=1, range_record=None):
+    """defects_eval on the GPU (csrc/region_table.hip through engine.defects_at_threshold): fp32 device maps [N, H, W],
+    labels whose non-zero entries are the anomalous pixels; threshold a number or the device record of
+    engine.metrics_f1max; range_record (engine.metrics_range's) normalises raw maps on the fly.  The same dict, with
+    "kept mask" a device tensor."""
+    engine.require_gpu(preds, "defects_eval_device")
+    engine.require_gpu(masks, "defects_eval_device")
+    pp = preds.to(torch.float32).contiguous()
+    if pp.dim() == 4 and pp.shape[1] == 1:
+        pp = pp[:, 0]
+    if pp.dim() != 3 or masks.numel() != pp.numel():
+        raise ValueError(f"defects_eval_device: maps of [N, H, W] and as many labels, got {tuple(pp.shape)} and "
+                         f"{tuple(masks.shape)}")
+    gt = masks if masks.dtype == torch.uint8 else (masks != 0).to(torch.uint8)
+    d = engine.defects_at_threshold(pp, threshold, range_record, gt_mask=gt.reshape(pp.shape), min_area=min_area)
+    record = tuple(int(v) for v in d.record.cpu())
+    out = defects_from_record(record)
+    out.update(record=record, predicted=engine.region_table_host(d.predicted), truth=engine.region_table_host(d.truth))
+    out["kept mask"] = d.mask
+    return out
+
+
+def _defect_columns(row, details, d, want_masks):
+    for col in DEFECT_COLS:
+        row[col] = d[col]
+    if details is not None:
+        details["defects"] = d["predicted"]
+        if want_masks:
+            details["kept masks"] = d["kept mask"]
 
 
 def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, fpr_limit=None,
-                 f1_max=False, details=None):
+                 f1_max=False, details=None, defects=None):
     """Pixel / image AUROC and AP of one class, reference forward_utils.py:233-308:
     global min-max normalisation of maps and image scores (:246-253), per-image maximum of
     the normalised map (:277), Industrial score = 0.5*max_pixel + 0.5*image score, Medical =
@@ -289,9 +416,15 @@ def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names
     f1_max: True adds "pixel F1-max" and "image F1-max" (f1max_eval of the normalised pixels and of the combined image
     scores; the image one is 0 where image AUC is); details: a dict that then receives "pixel threshold" and "image
     threshold" (None where the column is 0), in normalised units, and -- when it holds a true "masks" on entry -- the
-    uint8 predicted masks `normalised map >= pixel threshold` under "masks"."""
+    uint8 predicted masks `normalised map >= pixel threshold` under "masks".
+    defects: None, or a min_area >= 1 (needs f1_max=True): adds DEFECT_COLS -- "region recall", "region precision", "false
+    regions / image" of defects_eval at the pixel threshold -- and puts the per-image lists of the kept predicted regions
+    under details["defects"] and, where "masks" was asked for, the filtered masks under details["kept masks"]."""
     import numpy as np
     from sklearn.metrics import average_precision_score, roc_auc_score
+
+    if defects is not None and not f1_max:
+        raise ValueError("metrics_eval: defects needs f1_max=True (the regions are those at its pixel threshold)")
 
     # arithmetic stays in the callers' dtype (float32 arrays in test_last.py), as in the reference: the min-max
     # normalisation decides which pixels tie, and ties decide AUROC / AP digits
@@ -332,8 +465,11 @@ def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names
         pixel_f1 = f1max_eval(pl, pp)
         image_f1 = f1max_eval(image_label.reshape(-1), image_preds.reshape(-1)) if image_label.max() != image_label.min() else None
         _f1_columns(row, details, pixel_f1, image_f1)
-        if details is not None and details.get("masks") is True:
+        want_masks = details is not None and details.get("masks") is True
+        if want_masks:
             details["masks"] = (pixel_preds >= pixel_preds.dtype.type(pixel_f1.threshold)).astype(np.uint8)
+        if defects is not None:
+            _defect_columns(row, details, defects_eval(pixel_label, pixel_preds, pixel_f1.threshold, defects), want_masks)
     return row
 
 
@@ -346,7 +482,7 @@ def _f1_columns(row, details, pixel_f1, image_f1):
 
 
 def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, fpr_limit=None,
-                        f1_max=False, details=None):
+                        f1_max=False, details=None, defects=None):
     """metrics_eval with the sort and the curve sums on the GPU (csrc/metrics.hip through engine.curve_metrics): the same
     arguments, shape handling, domain rule, `image_label.max() != image_label.min()` rule, result dict and rounding, and
     the same numbers -- sklearn's tie groups and definitions, an integer AUROC numerator, an fp64 AP sum.
@@ -356,9 +492,13 @@ def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, clas
     fpr_limit: as in metrics_eval, with "pixel AUPRO" from engine.pro_metrics (a labelling, a second sort, the PRO curve).
     f1_max, details: as in metrics_eval; the columns come from engine.f1max_metrics, that is from the ONE sort that
     serves AUROC / AP already, and details["masks"] is a device tensor from engine.metrics_threshold, which normalises
-    the raw maps on the fly and reads the threshold from the device record."""
+    the raw maps on the fly and reads the threshold from the device record.
+    defects: as in metrics_eval, through engine.defects_at_threshold: the threshold and the range stay on the device, the
+    lists come from the region tables and details["kept masks"] is a device tensor."""
     import numpy as np
 
+    if defects is not None and not f1_max:
+        raise ValueError("metrics_eval_device: defects needs f1_max=True (the regions are those at its pixel threshold)")
     engine.require_gpu(pixel_preds, "metrics_eval_device")
     engine.require_gpu(pixel_label, "metrics_eval_device")
     dev = pixel_preds.device
@@ -396,10 +536,18 @@ def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, clas
         row["pixel AUPRO"] = round(pro_eval_device(pl, pp, fpr_limit=fpr_limit), 4) * 100
     if f1_max:
         _f1_columns(row, details, pixel_f1, image_f1)
-        if details is not None and details.get("masks") is True:
-            shaped = pp[:, 0] if pp.dim() == 4 and pp.shape[1] == 1 else pp
+        want_masks = details is not None and details.get("masks") is True
+        shaped = pp[:, 0] if pp.dim() == 4 and pp.shape[1] == 1 else pp
+        if want_masks:
             details["masks"] = engine.metrics_threshold(shaped, records["f1max"], range_record=records["range"],
                                                         totals=False)[0]
+        if defects is not None:
+            if shaped.dim() == 2:                       # [N, pixels] -> [N, side, side], as metrics_eval reshapes it
+                side = int(shaped.shape[1] ** 0.5)
+                if side * side == shaped.shape[1]:
+                    shaped = shaped.reshape(shaped.shape[0], side, side)
+            _defect_columns(row, details, defects_eval_device(pl, shaped, records["f1max"], defects,
+                                                              range_record=records["range"]), want_masks)
     return row
 
 

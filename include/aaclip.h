@@ -578,6 +578,48 @@ int aaclip_metrics_threshold(const float* scores, const uint8_t* labels, long n,
                              const void* range_record, const void* f1max_record, uint8_t* mask,
                              uint32_t* image_counts, void* totals, void* ws, size_t ws_bytes, void* stream);
 
+/* The table of the regions of one class on the device (csrc/region_table.hip; the code it shares with a host program is
+ * csrc/region_table.h): what a user reads off an operating point -- which image every defect is in, where, how large, how
+ * strong -- from the outputs of aaclip_metrics_regions on the predicted masks of aaclip_metrics_threshold.  The
+ * conventions are those of the entries above (checks before the first launch, the workspace size last,
+ * *_workspace_bytes 0 for refused sizes and monotonic, overlap checks); integer minima, maxima and sums only, no
+ * floating-point atomics: a second call gives the same bytes.  This ABI number is unchanged: the entries are additions.
+ *   aaclip_region_table: region / area u32 [images * H * W] as aaclip_metrics_regions leaves them, scores fp32 of the
+ *   same size (finite), other u8 of the same size or NULL (non-zero = set).  One aaclip_region_row for every region
+ *   with area >= min_area (min_area >= 1), in canonical order: ascending (image, first), the order of the region ids
+ *   and of scipy.ndimage.label's numbers.
+ *     image           index of the image
+ *     label           1-based number of the region among ALL regions of its image, before the min_area filter
+ *     first           flat index within the image of the region's first pixel in row-major order
+ *     area            pixel count
+ *     x0, y0, x1, y1  bounding box, x0 / y0 inclusive, x1 / y1 exclusive (scipy.ndimage.find_objects' slices)
+ *     peak            fp32 bits of the largest compared score of the region; the compared score of a pixel is scores[p],
+ *                     or with range_record (the record of aaclip_metrics_range) scores[p] normalised on the fly with
+ *                     aaclip_metrics_normalise's arithmetic and its max != 1.0f decision; -0.0 counts as +0.0
+ *     peak_x, peak_y  the pixel of the LOWEST flat index among those that attain the peak
+ *     overlap         the region's pixels where other is non-zero; 0 when other is NULL
+ *   image_offsets i32 [images + 1]: rows in front of image i; image_offsets[images] = the rows kept.  kept_mask u8
+ *   [images * H * W] or NULL: 1 exactly on the pixels of kept regions.  record <- {rows kept, regions seen, kept regions
+ *   with overlap > 0, rows dropped for lack of capacity}.  When more rows are kept than `capacity`, the first `capacity`
+ *   rows in canonical order are written and nothing behind rows[capacity] is touched; kept, the offsets, kept_mask and
+ *   the overlap count stay the true ones and dropped = kept - capacity.  rows may be NULL when capacity is 0.
+ *   Row numbers and labels come from scans over the root flags (region[p] == p + 1).  A pixel's share travels as one
+ *   64-bit word, order-preserving score key << 32 | (0xFFFFFFFF - flat index in the image), whose integer maximum is
+ *   the peak with the lowest-index rule; lanes of a wave that follow one another in a region are folded first, then the
+ *   workgroup's runs of one row in the LDS, then one integer atomic per field at the row.
+ *   Alignment: region / area / scores / image_offsets 4 bytes; rows, the records and the workspace 8 bytes. */
+typedef struct aaclip_region_row {
+  uint32_t image, label, first, area, x0, y0, x1, y1, peak_x, peak_y, peak, overlap;
+} aaclip_region_row;
+typedef struct aaclip_region_table_record {
+  unsigned long long kept, regions, hit, dropped;
+} aaclip_region_table_record;
+size_t aaclip_region_table_workspace_bytes(long images, long H, long W);
+int aaclip_region_table(const uint32_t* region, const uint32_t* area, const float* scores, const void* range_record,
+                        const uint8_t* other, long images, long H, long W, long min_area, long capacity, void* rows,
+                        int32_t* image_offsets, uint8_t* kept_mask, void* record, void* ws, size_t ws_bytes,
+                        void* stream);
+
 /* Fused Adam / AdamW step over a list of tensors, and the gradient norm that clips it (csrc/optim.hip).  fp32
  * parameters, gradients and state only.  One launch serves up to 24 tensors and 640 chunks of 16384 elements; its table
  * travels by value in the kernel arguments, so a call copies nothing to the device, allocates nothing and waits for
