@@ -19,6 +19,7 @@ EXACT16_QKV, EXACT16_OUT, EXACT16_FC, EXACT16_PROJ, EXACT16_ADAPTER = 1, 2, 4, 8
 ACT_NONE, ACT_LEAKY, ACT_RELU = 0, 1, 2
 ACT_GELU = 3   # aaclip_act_backward only
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_ACT_F32 = 0, 1, 2, 3
+SUPPORT_FP32, SUPPORT_FP16 = 0, 1   # include/aaclip.h AACLIP_SUPPORT_*
 SEG_LOSS_FOCAL, SEG_LOSS_DICE0, SEG_LOSS_DICE1, SEG_LOSS_ALL = 1, 2, 4, 7
 
 _vp, _i, _l, _f, _sz, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t, C.c_double
@@ -149,6 +150,10 @@ SIGNATURES = {
     "aaclip_optim_grad_norm_workspace_bytes": (_sz, [C.POINTER(OptimTensors)]),
     "aaclip_optim_grad_norm": (_i, [C.POINTER(OptimTensors), _f, _vp, _vp, _sz, _vp]),
     "aaclip_optim_adam_step": (_i, [C.POINTER(OptimTensors), C.POINTER(OptimGroup), _i, _vp, _vp]),
+    "aaclip_support_nearest_workspace_bytes": (_sz, [_l, _l, _i, _i]),
+    "aaclip_support_nearest": (_i, [_vp, _l, _vp, _l, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "aaclip_support_bank_rows": (_i, [_vp, _l, _i, _i, _vp, _vp]),
+    "aaclip_support_map": (_i, [C.POINTER(_vp), _i, _vp, _f, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "aaclip_row_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp] + [_i] * 6 + [_vp, _sz, _vp]),
     "aaclip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _l, _i, _f, _vp]),
     "aaclip_gemm": (_i, [_i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _f, _vp]),

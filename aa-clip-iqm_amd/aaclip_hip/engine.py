@@ -1906,6 +1906,129 @@ def iqm_map(seg_tokens: Sequence[torch.Tensor], queries: torch.Tensor, img_size:
     return out
 
 
+# ------------------------------------------------------------------------------- few-shot support bank (csrc/support.hip)
+SUPPORT_FP32, SUPPORT_FP16 = _lib.SUPPORT_FP32, _lib.SUPPORT_FP16
+SUPPORT_FORMS = {"fp16": SUPPORT_FP16, "fp32": SUPPORT_FP32}
+SUPPORT_OPERAND_EXP = 4          # csrc/support_pack.h: the fp16 form's bank rows are fp16(v * 2^4)
+SupportBank = collections.namedtuple("SupportBank", "rows form patches shots")
+SupportBank.__doc__ = """rows: per tap level the bank [N, E] in the form's layout (fp16 of v * 2^4, or fp32), N = shots *
+patches in (shot, patch) order; form: SUPPORT_FP16 / SUPPORT_FP32; patches: rows per image; shots: images in the bank."""
+
+
+def support_form(form) -> int:
+    """'fp16' / 'fp32' (or the code itself) -> SUPPORT_FP16 / SUPPORT_FP32"""
+    if isinstance(form, str):
+        form = SUPPORT_FORMS.get(form.lower())
+    if form not in (SUPPORT_FP16, SUPPORT_FP32):
+        raise ValueError("support form must be 'fp16' or 'fp32'")
+    return int(form)
+
+
+def support_bank_rows(rows: torch.Tensor, form) -> torch.Tensor:
+    """fp32 rows [N, E] -> the bank of one level in the form's layout (aaclip_support_bank_rows)"""
+    form = support_form(form)
+    r = _f32c(rows)
+    require_gpu(r, "support_bank_rows")
+    if r.dim() != 2:
+        raise ValueError("support_bank_rows expects rows of [N, E]")
+    N, E = r.shape
+    out = torch.empty(N, E, dtype=torch.float16 if form == SUPPORT_FP16 else torch.float32, device=r.device)
+    _lib.check(_lib.load().aaclip_support_bank_rows(r.data_ptr(), N, E, form, out.data_ptr(), _stream(r.device)),
+               "support_bank_rows")
+    return out
+
+
+def support_bank(seg_tokens_per_image_batch, form) -> SupportBank:
+    """The bank of k normal images: seg_tokens_per_image_batch is a sequence of batches, each the per-level list of unit
+    fp32 seg tokens [b, P, E] that AdaptedCLIP.forward returns (one batch's list is accepted too).  The images are
+    concatenated in order, so bank row shot * P + patch is that patch of that image."""
+    form = support_form(form)
+    batches = list(seg_tokens_per_image_batch)
+    if not batches:
+        raise ValueError("support_bank: no images")
+    if torch.is_tensor(batches[0]):
+        batches = [batches]
+    levels = len(batches[0])
+    if levels < 1 or any(len(b) != levels for b in batches):
+        raise ValueError("support_bank: every batch must hold the same tap levels")
+    require_gpu(batches[0][0], "support_bank")
+    P, E = batches[0][0].shape[1:]
+    shots = sum(int(b[0].shape[0]) for b in batches)
+    rows = []
+    for l in range(levels):
+        parts = [_f32c(b[l]) for b in batches]
+        if any(p.dim() != 3 or tuple(p.shape[1:]) != (P, E) for p in parts):
+            raise ValueError("support_bank: seg tokens must be [b, P, E] with one P and E")
+        rows.append(support_bank_rows(torch.cat(parts, dim=0).reshape(shots * P, E), form))
+    return SupportBank(rows, form, int(P), shots)
+
+
+def support_nearest(q: torch.Tensor, bank_level: torch.Tensor, form=None, want_idx: bool = True):
+    """-> (cos fp32 [M], idx int32 [M]): for every row of q ([M, E], or [B, P, E] taken as B * P rows) the largest inner
+    product with a row of bank_level (one entry of SupportBank.rows; the form is read off its dtype unless given) and
+    the lowest bank row that attains it.  want_idx=False returns idx = None."""
+    form = (SUPPORT_FP16 if bank_level.dtype == torch.float16 else SUPPORT_FP32) if form is None else support_form(form)
+    qq = _f32c(q)
+    require_gpu(qq, "support_nearest")
+    require_gpu(bank_level, "support_nearest")
+    qq = qq.reshape(-1, qq.shape[-1])
+    M, E = qq.shape
+    want = torch.float16 if form == SUPPORT_FP16 else torch.float32
+    if bank_level.dim() != 2 or bank_level.shape[1] != E or bank_level.dtype != want or bank_level.device != qq.device:
+        raise ValueError(f"support_nearest: the bank must be a {want} tensor [N, {E}] on the queries' device")
+    bank_level = bank_level.contiguous()
+    lib = _lib.load()
+    dev = qq.device
+    cos = torch.empty(M, dtype=torch.float32, device=dev)
+    idx = torch.empty(M, dtype=torch.int32, device=dev) if want_idx else None
+    N = bank_level.shape[0]
+    ws = Workspace.get(dev, max(256, lib.aaclip_support_nearest_workspace_bytes(M, N, E, form)))
+    _lib.check(lib.aaclip_support_nearest(qq.data_ptr(), M, bank_level.data_ptr(), N, E, form, cos.data_ptr(), _ptr(idx),
+                                          ws.data_ptr(), ws.numel(), _stream(dev)), "support_nearest")
+    return cos, idx
+
+
+def support_map_from_cos(cos_levels: Sequence[torch.Tensor], B: int, img_size: int, ksize: int, sigma: float,
+                         base: Optional[torch.Tensor] = None, weight: float = 50.0) -> torch.Tensor:
+    """The map stage alone: per level best_cos [B * g * g] -> [B, S, S] = base + weight * sum over levels of
+    upsample(blur(1 - best_cos)) with anomaly_map's blur, upsample and level order (aaclip_support_map)."""
+    cs = [_f32c(c).reshape(-1) for c in cos_levels]
+    require_gpu(cs[0], "support_map")
+    dev = cs[0].device
+    P = cs[0].numel() // B
+    g = int(round(P ** 0.5))
+    if g * g != P or any(c.numel() != B * P for c in cs):
+        raise ValueError(f"support_map: {cs[0].numel()} cosines are not {B} square grids")
+    out = torch.empty(B, img_size, img_size, dtype=torch.float32, device=dev)
+    bs = _f32c(base) if base is not None else None
+    if bs is not None and (bs.shape != out.shape or bs.device != dev):
+        raise ValueError("base map must be [B, S, S] on the tokens' device")
+    ws = Workspace.get(dev, len(cs) * B * P * 4 + 256)
+    arr = (C.c_void_p * len(cs))(*[c.data_ptr() for c in cs])
+    _lib.check(_lib.load().aaclip_support_map(arr, len(cs), _ptr(bs), float(weight), out.data_ptr(), B, g, img_size,
+                                              int(ksize), float(sigma), ws.data_ptr(), ws.numel(), _stream(dev)),
+               "support_map")
+    return out
+
+
+def support_map(seg_tokens: Sequence[torch.Tensor], bank: SupportBank, img_size: int, ksize: int, sigma: float,
+                base: Optional[torch.Tensor] = None, weight: float = 50.0, nearest: Optional[list] = None) -> torch.Tensor:
+    """-> [B, S, S] = base + weight * sum over levels of upsample(blur(d_l)), d_l = 1 - (largest cosine of every patch to
+    the level's bank rows) on the g x g grid, not clamped; base=None counts as 0.  nearest: a list that receives the
+    int32 [B, P] index of the nearest bank row per level (shot, patch = divmod(index, bank.patches))."""
+    segs = list(seg_tokens)
+    if len(segs) != len(bank.rows):
+        raise ValueError(f"support_map: {len(segs)} levels of tokens for a bank of {len(bank.rows)}")
+    B, P = segs[0].shape[:2]
+    cos = []
+    for s, rows in zip(segs, bank.rows):
+        c, i = support_nearest(s, rows, bank.form, want_idx=nearest is not None)
+        cos.append(c)
+        if nearest is not None:
+            nearest.append(i.reshape(B, P))
+    return support_map_from_cos(cos, B, img_size, ksize, sigma, base, weight)
+
+
 # ------------------------------------------------------------------------------- fused optimizer step (csrc/optim.hip)
 OPTIM_RECORD_FLOATS = 2          # fp32 words of aaclip_optim_record: total_norm, clip_coef
 OPTIM_MAX_GROUPS = _lib.OPTIM_MAX_GROUPS

@@ -1774,6 +1774,68 @@ int aaclip_region_table(const uint32_t* region, const uint32_t* area, const floa
   return finish("region_table");
 }
 
+// ---- few-shot support bank (support.hip)
+static const char* support_shape_check(long M, long N, int E, int form) {
+  if (form != AACLIP_SUPPORT_FP16 && form != AACLIP_SUPPORT_FP32) return "form must be AACLIP_SUPPORT_FP16 or AACLIP_SUPPORT_FP32";
+  if (M < 1 || N < 1 || M > 0x7FFFFFFFl || N > 0x7FFFFFFFl) return "M and N must be 1 .. 2^31 - 1";
+  if (E < 64 || E > 1024 || E % 32 != 0) return "E must be a multiple of 32 in 64 .. 1024";
+  return nullptr;
+}
+
+size_t aaclip_support_nearest_workspace_bytes(long M, long N, int E, int form) {
+  return support_shape_check(M, N, E, form) ? 0 : support_ws_bytes(M);
+}
+
+int aaclip_support_nearest(const float* q, long M, const void* bank, long N, int E, int form, float* best_cos,
+                           int* best_idx, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(q && bank && best_cos && ws, "support_nearest: null pointer");
+  if (const char* m = support_shape_check(M, N, E, form)) return fail(-1, in("support_nearest", m));
+  REQUIRE_ALIGNED16("support_nearest", q, bank);
+  REQUIRE((((uintptr_t)best_cos | (uintptr_t)best_idx) & 3) == 0 && ((uintptr_t)ws & 7) == 0,
+          "support_nearest: best_cos / best_idx must be 4-byte, the workspace 8-byte aligned");
+  const size_t need = support_ws_bytes(M);
+  REQUIRE(ws_bytes >= need, "support_nearest: workspace too small");
+  const size_t qb = (size_t)M * E * 4, bb = (size_t)N * E * (form == AACLIP_SUPPORT_FP16 ? 2 : 4), ob = (size_t)M * 4;
+  const void* bufs[5] = {best_cos, best_idx, ws, q, bank};
+  const size_t lens[5] = {ob, ob, need, qb, bb};
+  bool clash = false;
+  for (int a = 0; a < 3; ++a)
+    for (int b = a + 1; b < 5; ++b) clash = clash || (bufs[a] && bufs[b] && ranges_overlap(bufs[a], lens[a], bufs[b], lens[b]));
+  REQUIRE(!clash, "support_nearest: outputs and workspace must not overlap one another or the inputs");
+  launch_support_nearest(q, M, bank, N, E, form, best_cos, best_idx, ws, (hipStream_t)stream);
+  return finish("support_nearest");
+}
+
+int aaclip_support_bank_rows(const float* rows, long N, int E, int form, void* bank, void* stream) {
+  REQUIRE(rows && bank, "support_bank_rows: null pointer");
+  if (const char* m = support_shape_check(1, N, E, form)) return fail(-1, in("support_bank_rows", m));
+  REQUIRE_ALIGNED16("support_bank_rows", rows, bank);
+  const size_t rb = (size_t)N * E * 4, bb = (size_t)N * E * (form == AACLIP_SUPPORT_FP16 ? 2 : 4);
+  REQUIRE(!ranges_overlap(rows, rb, bank, bb), "support_bank_rows: rows and bank must not overlap");
+  launch_support_bank_rows(rows, N, E, form, bank, (hipStream_t)stream);
+  return finish("support_bank_rows");
+}
+
+int aaclip_support_map(const float* const* best_cos, int NL, const float* base, float weight, float* out, int B, int g,
+                       int S, int ksize, float sigma, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(best_cos && out && ws, "support_map: null pointer");
+  REQUIRE(NL >= 1 && NL <= 4, "support_map: 1..4 levels");
+  REQUIRE(map_shape_ok(B, g, S), "support_map: bad shape (grid <= 40)");
+  REQUIRE(ksize >= 1 && ksize <= 15 && ksize / 2 < g, "support_map: kernel size must be 1..15 and < 2*grid");
+  REQUIRE(sigma > 0.f, "support_map: sigma must be positive");
+  const long BP = (long)B * g * g, n = (long)B * S * S;
+  REQUIRE(ws_bytes >= (size_t)NL * BP * 4, "support_map: workspace too small");
+  REQUIRE(base == nullptr || !ranges_overlap(base, (size_t)n * 4, out, (size_t)n * 4),
+          "support_map: base must not overlap out");
+  for (int l = 0; l < NL; ++l) REQUIRE(best_cos[l], "support_map: null level pointer");
+  hipStream_t s = (hipStream_t)stream;
+  float* pre = (float*)ws;
+  for (int l = 0; l < NL; ++l) launch_support_dist(best_cos[l], pre + (size_t)l * BP, BP, s);
+  launch_blur_upsample(pre, out, B, g, S, NL, ksize, sigma, s);
+  launch_support_add(base, weight, out, n, s);
+  return finish("support_map");
+}
+
 int aaclip_text_embed(const int32_t* tokens, const float* table, const float* pos, float* x, int n, int T, int D,
                       int vocab, void* stream) {
   REQUIRE(tokens && table && pos && x, "text_embed: null pointer");

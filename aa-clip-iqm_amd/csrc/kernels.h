@@ -301,6 +301,14 @@ void launch_region_table(const uint32_t* region, const uint32_t* area, const flo
                          const uint8_t* other, long images, int H, int W, long min_area, long capacity, void* rows,
                          int32_t* image_offsets, uint8_t* kept_mask, void* record, void* ws, hipStream_t s);
 
+// ---- support.hip : nearest bank row of every query row (the candidate word, tiling and workspace are support_pack.h)
+size_t support_ws_bytes(long M);
+void launch_support_nearest(const float* q, long M, const void* bank, long N, int E, int form, float* best_cos,
+                            int* best_idx, void* ws, hipStream_t s);
+void launch_support_bank_rows(const float* rows, long N, int E, int form, void* bank, hipStream_t s);
+void launch_support_dist(const float* cosine, float* d, long n, hipStream_t s);              // d = 1 - cosine
+void launch_support_add(const float* base, float weight, float* out, long n, hipStream_t s);   // out = base + weight * out
+
 // ---- multi-tensor optimizer (optim.hip; the launch packing is optim_pack.h)
 struct OptimGroupScalars {   // one group's hyper-parameters as the kernel reads them: formed in fp64, rounded once
   float beta1, one_minus_beta1, beta2, one_minus_beta2;

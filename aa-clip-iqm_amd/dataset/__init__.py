@@ -81,6 +81,25 @@ class BaseSingleClassDataset(Dataset):
     def __len__(self):
         return len(self.meta)
 
+    def _with_meta(self, meta):
+        """a dataset of the same settings over the given entries"""
+        import copy
+        other = copy.copy(self)
+        other.meta = list(meta)
+        other.normal_meta = [m for m in other.meta if m["label"] == 0]
+        return other
+
+    def support_split(self, k: int):
+        """-> (support_dataset, eval_dataset) of the k-shot protocol: the support set is the first k entries of
+        normal_meta in file order, and those images are REMOVED from the evaluated set (a test image that is in the
+        bank has distance 0 to itself); the other entries keep their order.  k larger than the number of normal images
+        (or below 1) raises ValueError."""
+        if not 1 <= int(k) <= len(self.normal_meta):
+            raise ValueError(f"support_split: k = {k}, but the class has {len(self.normal_meta)} normal images")
+        support = self.normal_meta[:int(k)]
+        taken = {id(m) for m in support}
+        return self._with_meta(support), self._with_meta([m for m in self.meta if id(m) not in taken])
+
     def __getitem__(self, idx):
         meta = self.meta[idx]
         img = Image.open(os.path.join(self.data_path, meta["image_path"])).convert("RGB")

@@ -24,6 +24,9 @@ the same names and arguments:
                                           defects=MIN_AREA (with f1_max) adds the region-level columns of the defect
                                           instances at the pixel F1-max threshold (forward_utils.defects_eval /
                                           engine.defects_at_threshold); eval_defects.py is the script with --defects
+                                          support={class: engine.SupportBank} adds the few-shot memory-bank term to the
+                                          text-anchor map before the IQM fusion (forward_utils.support_anomaly_map;
+                                          support_banks builds the banks); eval_support.py is the script with --support
   main(argv)                              the arguments and steps of test_last.main plus --device_metrics
 
 python eval_last.py --save_path ... [--device_metrics] [every argument of test_last.py]
@@ -43,8 +46,8 @@ import test_last as TL
 from aaclip_hip import engine
 from aaclip_hip.shard import gather_predictions, shard_range
 from dataset import DOMAINS
-from forward_utils import (DEFECT_COLS, IMAGE_F1_COL, PIXEL_F1_COL, calculate_anomaly_map, image_score, metrics_eval,
-                           metrics_eval_device)
+from forward_utils import (DEFECT_COLS, IMAGE_F1_COL, PIXEL_F1_COL, SUPPORT_WEIGHT, calculate_anomaly_map, image_score,
+                           metrics_eval, metrics_eval_device, support_anomaly_map)
 
 AUPRO_COL = "pixel AUPRO"
 F1_COLS = [PIXEL_F1_COL, IMAGE_F1_COL]
@@ -78,6 +81,48 @@ def get_predictions(model, class_text_embeddings: torch.Tensor, test_loader, dev
             torch.cat(preds_image, dim=0), file_names)
 
 
+def get_predictions_support(model, class_text_embeddings: torch.Tensor, test_loader, device, img_size: int,
+                            dataset: str = "MVTec", use_iqm: bool = True, on_device: bool = False, support=None,
+                            support_weight: float = SUPPORT_WEIGHT, nearest: list = None):
+    """get_predictions with the class's few-shot bank (its signature is test_last's plus on_device and stays so; this is
+    the function with the further keywords).  support: an engine.SupportBank, or None, which is get_predictions itself.
+    With a bank the text-anchor map becomes calculate_anomaly_map(...) + support_weight * (the nearest-patch distance to
+    the bank, blurred, upsampled and summed over the levels like the text map: forward_utils.support_anomaly_map) BEFORE
+    the IQM fusion, which is unchanged.  nearest: a list that then receives, per batch, the per-level int32 [b, P]
+    indices of the nearest bank rows.  on_device as in get_predictions."""
+    if support is None:
+        return get_predictions(model, class_text_embeddings, test_loader, device, img_size, dataset, use_iqm, on_device)
+    masks, labels, preds, preds_image, file_names = [], [], [], [], []
+    domain = DOMAINS[dataset]
+    for input_data in test_loader:
+        image = input_data["image"].to(device, non_blocking=True)
+        assert len(set(input_data["class_name"])) == 1, "mixed class not supported"
+        if on_device:
+            masks.append((input_data["mask"].to(device, non_blocking=True) != 0).to(torch.uint8))
+        else:
+            masks.append(np.asarray(input_data["mask"].cpu().numpy()))
+        labels.append(np.asarray(torch.as_tensor(input_data["label"]).cpu().numpy()))
+        file_names.extend(input_data["file_name"])
+        if image.dtype == torch.uint8:
+            image = engine.preprocess(image, img_size)
+        epoch_text_feature = class_text_embeddings.unsqueeze(0).repeat(image.size(0), 1, 1) if use_iqm else None
+        patch_features, det_feature, iqm_outputs = model(image, text_embeddings=epoch_text_feature)
+        score = image_score(det_feature, class_text_embeddings)
+        final_map = calculate_anomaly_map(patch_features, class_text_embeddings, img_size, domain=domain)
+        batch_nearest = [] if nearest is not None else None
+        final_map = support_anomaly_map(patch_features, support, img_size, domain=domain, base=final_map,
+                                        weight=support_weight, nearest=batch_nearest)
+        if nearest is not None:
+            nearest.append(batch_nearest)
+        if iqm_outputs is not None:
+            final_map = engine.iqm_map(patch_features, iqm_outputs.last_hidden_state, img_size, base=final_map,
+                                       w_base=TL.TEXT_WEIGHT, w_iqm=TL.IQM_WEIGHT)
+        preds_image.append(score.float() if on_device else score.cpu().numpy())
+        preds.append(final_map if on_device else final_map.cpu().numpy())
+    cat = (lambda v: torch.cat(v, dim=0)) if on_device else (lambda v: np.concatenate(v, axis=0))
+    return cat(masks), np.concatenate(labels, axis=0), cat(preds), cat(preds_image), file_names
+
+
 def evaluate(model, image_datasets: Dict[str, torch.utils.data.Dataset], text_embeddings: Dict[str, torch.Tensor],
              device, img_size: int, dataset: str, batch_size: int = 32, loader_kwargs=None, logger=None,
              use_iqm: bool = True, device_metrics: bool = False) -> List[dict]:
@@ -92,7 +137,8 @@ def evaluate(model, image_datasets: Dict[str, torch.utils.data.Dataset], text_em
 def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], text_embeddings: Dict[str, torch.Tensor],
                   device, img_size: int, dataset: str, batch_size: int = 32, loader_kwargs=None, logger=None,
                   use_iqm: bool = True, device_metrics: bool = False, fpr_limit=None, f1_max: bool = False,
-                  details: Dict[str, dict] = None, return_masks: bool = False, defects=None) -> List[dict]:
+                  details: Dict[str, dict] = None, return_masks: bool = False, defects=None, support=None,
+                  support_weight: float = SUPPORT_WEIGHT) -> List[dict]:
     """The per-class loop of test_last.evaluate for either metrics path.  device_metrics: the class's masks, maps and
     image scores stay on the GPU, the row comes from metrics_eval_device, and the tensors are released before the next
     class.  Under torch.distributed the shards are gathered as host arrays exactly as in test_last.evaluate (so the
@@ -103,7 +149,12 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
     receives: the thresholds of the operating points and, with return_masks=True, the class's predicted uint8 masks;
     beside them the class's "file_names", "labels" and raw "image scores" in the order of the maps.
     defects: None, or a min_area (needs f1_max): metrics_eval's keyword -- the three region-level columns of
-    forward_utils.DEFECT_COLS in every row and in the average, the per-image lists of defects under details[class]."""
+    forward_utils.DEFECT_COLS in every row and in the average, the per-image lists of defects under details[class].
+    support: None, or {class name: engine.SupportBank} (forward_utils.build_support_bank of the class's k normal images;
+    under torch.distributed every rank builds the same bank itself): get_predictions_support's keyword for every class, weighted
+    by support_weight.  With details and return_masks=True, details[class]["support nearest"] is then a list per tap
+    level of int32 arrays [N, P, 2]: (shot, patch) = divmod(index of the nearest bank row, P) for every patch of every
+    evaluated image -- which good patch it was compared with.  support=None changes nothing."""
     import torch.distributed as dist
     if defects is not None and not f1_max:
         raise ValueError("evaluate_rows: defects needs f1_max=True (the regions are those at the pixel F1-max threshold)")
@@ -117,14 +168,19 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
             image_dataset = torch.utils.data.Subset(image_dataset, list(range(b, e)))
         if len(image_dataset) > 0:
             loader = torch.utils.data.DataLoader(image_dataset, batch_size=batch_size, shuffle=False, **(loader_kwargs or {}))
+            bank = {} if support is None else {"support": support[class_name], "support_weight": support_weight}
+            nearest = [] if bank and details is not None and return_masks else None
+            if nearest is not None:
+                bank["nearest"] = nearest
+            predict = get_predictions_support if bank else get_predictions
             with torch.no_grad():
-                masks, labels, preds, preds_image, file_names = get_predictions(
+                masks, labels, preds, preds_image, file_names = predict(
                     model=model, class_text_embeddings=text_embeddings[class_name], test_loader=loader, device=device,
-                    img_size=img_size, dataset=dataset, use_iqm=use_iqm, on_device=device_metrics and world == 1)
+                    img_size=img_size, dataset=dataset, use_iqm=use_iqm, on_device=device_metrics and world == 1, **bank)
         else:   # more ranks than images of this class
             masks = np.zeros((0, 1, img_size, img_size), np.float32)
             labels, preds_image = np.zeros((0,), np.int64), np.zeros((0,), np.float32)
-            preds, file_names = np.zeros((0, img_size, img_size), np.float32), []
+            preds, file_names, nearest = np.zeros((0, img_size, img_size), np.float32), [], None
         if world > 1:
             gdev = device if dist.get_backend() == "nccl" else None
             masks, labels, preds, preds_image = gather_predictions(
@@ -151,6 +207,8 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
                     "masks": bool(return_masks), "file_names": list(file_names),
                     "labels": [int(v) for v in np.asarray(labels).reshape(-1)],
                     "image scores": [float(v) for v in scores.reshape(len(file_names), -1)[:, 0]] if file_names else []}
+                if support is not None and return_masks:
+                    details[class_name]["support nearest"] = _support_nearest_pairs(nearest, support[class_name], world)
         rows.append(row_of(masks, labels, preds, preds_image, class_name, domain=DOMAINS[dataset], fpr_limit=fpr_limit,
                            **extra))
         del masks, preds, preds_image          # released before the next class is evaluated
@@ -162,6 +220,45 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
     avg["class name"] = "Average"
     rows.append(avg)
     return rows
+
+
+def _support_nearest_pairs(nearest, bank, world):
+    """per batch, per level int32 [b, P] device indices -> per level int32 [N, P, 2] host arrays of (shot, patch); under
+    torch.distributed the shards are joined in rank order"""
+    levels = len(bank.rows)
+    out = []
+    for l in range(levels):
+        parts = [b[l].cpu().numpy() for b in (nearest or [])]
+        idx = np.concatenate(parts, axis=0) if parts else np.zeros((0, bank.patches), np.int32)
+        out.append(np.stack(np.divmod(idx, bank.patches), axis=-1).astype(np.int32))
+    if world > 1:
+        import torch.distributed as dist
+        shards = [None] * world
+        dist.all_gather_object(shards, out)
+        out = [np.concatenate([s[l] for s in shards], axis=0) for l in range(levels)]
+    return out
+
+
+def support_banks(model, image_datasets, k: int, device, img_size: int, form=None, support_datasets=None,
+                  batch_size: int = 32):
+    """The k-shot protocol for every class: -> ({class name: engine.SupportBank}, {class name: evaluated dataset}).
+    Without support_datasets the class's first k normal images feed the bank and leave the evaluated set
+    (BaseSingleClassDataset.support_split); with them -- datasets of another metadata file, such as MVTec's train/good --
+    their first k normal images feed it and the evaluated set stays whole.  Every process that calls this builds the same
+    banks: k images per class, no communication."""
+    from forward_utils import build_support_bank
+    banks, evaluated = {}, {}
+    for class_name, ds in image_datasets.items():
+        if support_datasets is None:
+            shots, evaluated[class_name] = ds.support_split(k)
+        else:
+            shots, evaluated[class_name] = support_datasets[class_name].support_split(k)[0], ds
+        batches = []
+        for b in torch.utils.data.DataLoader(shots, batch_size=batch_size, shuffle=False):
+            image = b["image"].to(device)
+            batches.append(engine.preprocess(image, img_size) if image.dtype == torch.uint8 else image)
+        banks[class_name] = build_support_bank(model, batches, form)
+    return banks, evaluated
 
 
 def format_table(rows: List[dict]) -> str:
@@ -249,7 +346,9 @@ def main(argv=None):
 def run(parser: argparse.ArgumentParser, argv=None, table=None, finish=None):
     """main() for a parser that may carry further arguments: `aupro` (eval_aupro.py), a false-positive rate or None,
     `f1max` (eval_metrics.py), which adds the F1-max columns and logs every class's thresholds, and `defects`
-    (eval_defects.py), a minimum area or None, which implies f1max and adds the region-level columns.  table: the
+    (eval_defects.py), a minimum area or None, which implies f1max and adds the region-level columns, and `support`
+    (eval_support.py), a number of shots or None, with `support_weight`, `support_form` and `support_meta` beside it: the
+    banks of support_banks are built after the text embeddings and every class is evaluated with its bank.  table: the
     function that formats the rows (format_table); finish(args, rows, details): called after the evaluation when the
     F1-max path ran."""
     from dataset import get_dataset
@@ -292,12 +391,25 @@ def run(parser: argparse.ArgumentParser, argv=None, table=None, finish=None):
                                  device_preprocess=args.device_preprocess)
     with torch.no_grad():
         text_embeddings = get_adapted_text_embedding(model if adapt_text else clip_model, args.dataset, device)
+    shots, bank = getattr(args, "support", None), {}
+    if shots is not None:
+        support_sets = None
+        if getattr(args, "support_meta", None):
+            from dataset import DATA_PATH, BaseSingleClassDataset
+            support_sets = {c: BaseSingleClassDataset(DATA_PATH[args.dataset], args.support_meta, args.img_size, c,
+                                                      device_preprocess=args.device_preprocess) for c in image_datasets}
+        banks, image_datasets = support_banks(model, image_datasets, shots, device, args.img_size,
+                                              form=getattr(args, "support_form", None), support_datasets=support_sets,
+                                              batch_size=args.image_batch_size)
+        bank = {"support": banks, "support_weight": getattr(args, "support_weight", SUPPORT_WEIGHT)}
+        logger.info("support banks: %d shots per class, form %s, weight %s", shots,
+                    "fp16" if next(iter(banks.values())).form == engine.SUPPORT_FP16 else "fp32", bank["support_weight"])
     where = (model, image_datasets, text_embeddings, device, args.img_size, args.dataset)
     how = dict(batch_size=args.image_batch_size, loader_kwargs={"num_workers": 4, "pin_memory": True}, logger=logger,
                use_iqm=args.iqm == "on", device_metrics=args.device_metrics)
     if f1_max:
         details = {}
-        extra = {} if defects is None else {"defects": defects}
+        extra = dict(bank) if defects is None else dict(bank, defects=defects)
         rows = evaluate_rows(*where, **how, fpr_limit=aupro, f1_max=True, details=details, **extra)
         for name, d in details.items():
             logger.info("%s: pixel threshold %.9g, image threshold %s (normalised units)", name, d["pixel threshold"],
@@ -305,7 +417,8 @@ def run(parser: argparse.ArgumentParser, argv=None, table=None, finish=None):
         if finish is not None:
             finish(args, rows, details)
     else:
-        rows = evaluate(*where, **how) if aupro is None else evaluate_rows(*where, **how, fpr_limit=aupro)
+        rows = (evaluate(*where, **how) if aupro is None and not bank else
+                evaluate_rows(*where, **how, fpr_limit=aupro, **bank))
     table = (table or format_table)(rows)
     logger.info("final results:\n%s", table)
     if int(os.environ.get("RANK", "0")) == 0:

@@ -116,6 +116,109 @@ def calculate_anomaly_map(patch_features: Sequence[torch.Tensor], epoch_text_fea
     return engine.anomaly_map(list(patch_features), epoch_text_feature, img_size, ksize, sigma)
 
 
+# ------------------------------------------------------------------------------------------------
+# few-shot support bank: the memory-bank score of k known-good images, added to the text-anchor map without training
+SUPPORT_WEIGHT = 50.0   # derived, not tuned: the text map is 50 * (cos_1 - cos_0) + 0.5 per level (csrc/anomaly_map.hip),
+#                         so one unit of cosine distance to the bank weighs as much as one unit of anchor-cosine difference
+
+
+def _map_domain(domain):
+    return (1.0, 7) if domain == "Industrial" else (1.5, 9)     # sigma, ksize: calculate_anomaly_map's
+
+
+def build_support_bank(model, images, form=None) -> engine.SupportBank:
+    """The bank of the normal images `images` ([k, 3, S, S] normalised, or a sequence of such batches): the model's unit
+    seg tokens of every tap level, in image order.  form: 'fp16' / 'fp32'; None picks fp32
+    for a precision="fp32" model and fp16 otherwise.  Runs under no_grad with text_embeddings=None (the IQM branch has no
+    part in the bank)."""
+    if form is None:
+        code = engine.dtype_code(getattr(getattr(model, "clipmodel", model), "precision", "fp32"))
+        form = "fp32" if code == _lib.F32 else "fp16"
+    batches = [images] if torch.is_tensor(images) else list(images)
+    dev = next(model.parameters()).device
+    tokens = []
+    with torch.no_grad():
+        for image in batches:
+            if image.dtype == torch.uint8:
+                raise ValueError("build_support_bank takes normalised images (engine.preprocess turns raw frames into them)")
+            patch_features, _, _ = model(image.to(dev), text_embeddings=None)
+            tokens.append([p.float() for p in patch_features])
+    return engine.support_bank(tokens, form)
+
+
+def support_anomaly_map(patch_features: Sequence[torch.Tensor], bank, img_size, domain="Industrial", base=None,
+                        weight=SUPPORT_WEIGHT, nearest=None):
+    """-> [B, S, S] = base + weight * sum over levels of upsample(blur(1 - nearest cosine to the bank)), with the blur,
+    align-corners upsample and level order of calculate_anomaly_map for the domain (engine.support_map).  base: the
+    text-anchor map, or None for the support term alone.  nearest: a list that receives per level the int32 [B, P] index
+    of the nearest bank row."""
+    sigma, ksize = _map_domain(domain)
+    return engine.support_map(list(patch_features), bank, img_size, ksize, sigma, base=base, weight=weight, nearest=nearest)
+
+
+def _blur_upsample_host(pre, S, ksize, sigma):
+    """numpy fp64: [B, g, g] -> [B, S, S], the Gaussian blur (normalised taps exp(-x^2 / 2 sigma^2), reflect border,
+    rows then columns) and the bilinear align_corners=True upsample of csrc/anomaly_map.hip"""
+    import numpy as np
+    B, g, _ = pre.shape
+    r = ksize // 2
+    x = np.arange(ksize, dtype=np.float64) - r + (0.0 if ksize % 2 else 0.5)
+    taps = np.exp(-(x * x) / (2.0 * sigma * sigma))
+    taps /= taps.sum()
+    if ksize > 1:
+        at = np.arange(g)[:, None] + np.arange(ksize)[None, :] - r
+        at = np.abs(at)
+        at = np.where(at >= g, 2 * (g - 1) - at, at)                    # torch 'reflect'
+        pre = np.einsum("byxk,k->byx", pre[:, :, at], taps)             # along x
+        pre = np.einsum("bykx,k->byx", pre[:, at, :], taps)             # along y
+    scale = (g - 1) / (S - 1) if S > 1 else 0.0
+    s = scale * np.arange(S, dtype=np.float64)
+    i0 = np.minimum(s.astype(np.int64), g - 1)
+    i1 = np.minimum(i0 + 1, g - 1)
+    l1 = s - i0
+    l0 = 1.0 - l1
+    rows = l0[None, :, None] * pre[:, i0, :] + l1[None, :, None] * pre[:, i1, :]
+    return l0[None, None, :] * rows[:, :, i0] + l1[None, None, :] * rows[:, :, i1]
+
+
+def support_anomaly_map_host(patch_features, bank_features, img_size, domain="Industrial", base=None,
+                             weight=SUPPORT_WEIGHT, best_cos=None, nearest=None):
+    """The host definition support_anomaly_map is measured against, in numpy: per level the fp64 cosines of every patch
+    row ([B, P, E]) to every bank row (bank_features: per level [shots, P, E] or [N, E], fp32 rows as they are), their
+    maximum per patch, d = 1 - max on the g x g grid (not clamped), then the blur, the align-corners upsample and the
+    level sum in level order, and base + weight * sum; -> fp64 [B, S, S].  best_cos: per level [B * P] cosines to use
+    instead of the brute force (the device's own, to check the map stage alone).  nearest: a list that receives per level
+    the int64 [B, P] lowest index of the nearest bank row."""
+    import numpy as np
+    sigma, ksize = _map_domain(domain)
+    total = None
+    for l, f in enumerate(patch_features):
+        f = np.asarray(f.detach().cpu() if torch.is_tensor(f) else f)
+        B, P, E = f.shape
+        g = int(round(P ** 0.5))
+        if g * g != P:
+            raise ValueError(f"{P} patches is not a square grid")
+        if best_cos is not None:
+            best = np.asarray(best_cos[l], np.float64).reshape(B * P)
+        else:
+            b = bank_features[l]
+            b = np.asarray(b.detach().cpu() if torch.is_tensor(b) else b, np.float64).reshape(-1, E).T
+            best, idx = np.empty(B * P), np.empty(B * P, np.int64)
+            q = f.reshape(B * P, E)
+            for r0 in range(0, B * P, 512):
+                c = q[r0:r0 + 512].astype(np.float64) @ b
+                idx[r0:r0 + 512] = np.argmax(c, axis=1)
+                best[r0:r0 + 512] = c.max(axis=1)
+            if nearest is not None:
+                nearest.append(idx.reshape(B, P))
+        up = _blur_upsample_host((1.0 - best).reshape(B, g, g), img_size, ksize, sigma)
+        total = up if total is None else total + up
+    out = weight * total
+    if base is not None:
+        out = np.asarray(base.detach().cpu() if torch.is_tensor(base) else base, np.float64) + out
+    return out
+
+
 def image_score(det_feature: torch.Tensor, text_feature: torch.Tensor) -> torch.Tensor:
     """Per-image anomaly score (det_b . t_abnormal + 1)/2 -> [B].  Deliberate
     deviation from test_last.py:90-91, whose [B,768]@[B,768,2] broadcast yields

@@ -620,6 +620,36 @@ int aaclip_region_table(const uint32_t* region, const uint32_t* area, const floa
                         int32_t* image_offsets, uint8_t* kept_mask, void* record, void* ws, size_t ws_bytes,
                         void* stream);
 
+/* Few-shot support bank (csrc/support.hip; the code it shares with a host program is csrc/support_pack.h): the
+ * nearest bank row of every query row, for the memory-bank score built from k known-good images.  The conventions are
+ * those of the entries above (checks before the first launch, *_workspace_bytes 0 for refused sizes, overlap checks,
+ * only kernels and one memset enqueued on the caller's stream).  This ABI number is unchanged: the entries are additions.
+ *   aaclip_support_nearest: best_cos[m] = max over j of <q_m, bank_j>, best_idx[m] = the LOWEST j that attains it
+ *   (best_idx may be NULL).  q fp32 [M, E]; bank [N, E] as aaclip_support_bank_rows wrote it for the same form.
+ *   M, N in 1 .. 2^31 - 1, E a multiple of 32 in 64 .. 1024, inputs finite.  The M x N cosines stay in MFMA
+ *   accumulators; a row's candidates travel as 64-bit words, order-preserving key of the cosine << 32 |
+ *   (0xFFFFFFFF - j), merged by an integer maximum (no floating-point atomics): a second call gives the same bytes,
+ *   and -0.0 counts as +0.0.  Padding rows of the last tiles are never compared and never written.
+ *     AACLIP_SUPPORT_FP16  both operands are multiplied by 2^4 (exact) and rounded to fp16, the products run on
+ *                          v_mfma_f32_16x16x32_f16 with an fp32 accumulator that is multiplied by 2^-8 (exact).  For
+ *                          rows of norm <= 1: |best_cos - exact| <= 2u + u^2 + E * 2^-24 < 1.1e-3, u = 2^-11.  Components
+ *                          of magnitude >= 4094 overflow fp16: the form is meant for unit rows.
+ *     AACLIP_SUPPORT_FP32  fp32 operands on v_mfma_f32_32x32x2_f32 (a k-ordered fmaf chain per cosine).
+ *   aaclip_support_bank_rows: rows fp32 [N, E] -> bank: fp16 [N, E] of rows * 2^4 (FP16, N * E * 2 bytes) or a copy
+ *   (FP32, N * E * 4 bytes).
+ *   aaclip_support_map: out [B, S, S] = base + weight * sum over levels of upsample(blur(1 - best_cos[l])), with
+ *   aaclip_anomaly_map's blur, align-corners upsample and level order; best_cos[l] fp32 [B * g * g]; base [B, S, S] or
+ *   NULL (= 0), not overlapping out; the distance is not clamped.  Workspace: NL * B * g * g * 4 bytes.
+ *   Alignment: q, rows and bank 16 bytes; best_cos, best_idx 4 bytes; the workspace 8 bytes. */
+#define AACLIP_SUPPORT_FP32 0
+#define AACLIP_SUPPORT_FP16 1
+size_t aaclip_support_nearest_workspace_bytes(long M, long N, int E, int form);
+int aaclip_support_nearest(const float* q, long M, const void* bank, long N, int E, int form, float* best_cos,
+                           int* best_idx, void* ws, size_t ws_bytes, void* stream);
+int aaclip_support_bank_rows(const float* rows, long N, int E, int form, void* bank, void* stream);
+int aaclip_support_map(const float* const* best_cos, int NL, const float* base, float weight, float* out, int B, int g,
+                       int S, int ksize, float sigma, void* ws, size_t ws_bytes, void* stream);
+
 /* Fused Adam / AdamW step over a list of tensors, and the gradient norm that clips it (csrc/optim.hip).  fp32
  * parameters, gradients and state only.  One launch serves up to 24 tensors and 640 chunks of 16384 elements; its table
  * travels by value in the kernel arguments, so a call copies nothing to the device, allocates nothing and waits for
