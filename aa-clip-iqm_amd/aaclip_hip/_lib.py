@@ -154,6 +154,10 @@ SIGNATURES = {
     "aaclip_support_nearest": (_i, [_vp, _l, _vp, _l, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "aaclip_support_bank_rows": (_i, [_vp, _l, _i, _i, _vp, _vp]),
     "aaclip_support_map": (_i, [C.POINTER(_vp), _i, _vp, _f, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "aaclip_coreset_rows": (_i, [_vp, _l, _i, _vp, _vp, _vp]),
+    "aaclip_coreset_unit_rows": (_i, [_vp, _l, _i, _vp, _vp]),
+    "aaclip_coreset_select_workspace_bytes": (_sz, [_l, _i, _l]),
+    "aaclip_coreset_select": (_i, [_vp, _vp, _l, _i, _l, _l, _vp, _vp, _vp, _vp, _sz, _vp]),
     "aaclip_row_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp] + [_i] * 6 + [_vp, _sz, _vp]),
     "aaclip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _l, _i, _f, _vp]),
     "aaclip_gemm": (_i, [_i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _f, _vp]),

@@ -2029,6 +2029,133 @@ def support_map(seg_tokens: Sequence[torch.Tensor], bank: SupportBank, img_size:
     return support_map_from_cos(cos, B, img_size, ksize, sigma, base, weight)
 
 
+# ------------------------------------------------------------------------------- coreset of the bank (csrc/coreset.hip)
+CORESET_SCALE_EXP = 14           # csrc/coreset_pack.h: rows are quantised to int16 of v * 2^14
+CORESET_NORM2_LIMIT = 1 << 29    # the selection's precondition on every norm2
+CoresetBank = collections.namedtuple("CoresetBank", "rows form patches shots index radius2 dim")
+CoresetBank.__doc__ = """SupportBank's fields with SupportBank's meaning -- rows holds only the kept rows, patches and
+shots describe the FULL bank -- and: index: per level an int32 device tensor, for each kept row its row in the full bank,
+in pick order; radius2: per level the host uint32 array of covering radii squared (entry t with t picks, in units of
+2^-28: radius2 / 2^29 is the cosine distance on unit rows); dim: the width the selection ran on (0: the rows' own)."""
+
+
+def coreset_rows(rows: torch.Tensor):
+    """fp32 rows [N, E] -> (q int16 [N, E] = clamp(rint(v * 2^14), -32767, 32767), norm2 int32 [N] = sum q^2)
+    (aaclip_coreset_rows)"""
+    r = _f32c(rows)
+    require_gpu(r, "coreset_rows")
+    if r.dim() != 2:
+        raise ValueError("coreset_rows expects rows of [N, E]")
+    N, E = r.shape
+    q = torch.empty(N, E, dtype=torch.int16, device=r.device)
+    norm2 = torch.empty(N, dtype=torch.int32, device=r.device)
+    _lib.check(_lib.load().aaclip_coreset_rows(r.data_ptr(), N, E, q.data_ptr(), norm2.data_ptr(), _stream(r.device)),
+               "coreset_rows")
+    return q, norm2
+
+
+def coreset_unit_rows(rows: torch.Tensor) -> torch.Tensor:
+    """fp32 rows [N, E] -> rows / max(|row|, 1e-12) (aaclip_coreset_unit_rows)"""
+    r = _f32c(rows)
+    require_gpu(r, "coreset_unit_rows")
+    if r.dim() != 2:
+        raise ValueError("coreset_unit_rows expects rows of [N, E]")
+    out = torch.empty_like(r)
+    _lib.check(_lib.load().aaclip_coreset_unit_rows(r.data_ptr(), r.shape[0], r.shape[1], out.data_ptr(), _stream(r.device)),
+               "coreset_unit_rows")
+    return out
+
+
+def coreset_select(q: torch.Tensor, norm2: torch.Tensor, n: int, start: int = 0):
+    """Greedy k-center selection of n of the N quantised rows, from row `start` (aaclip_coreset_select) ->
+    (picks int32 [n], radius2 [n + 1], min_d2 [N]), device tensors; radius2 and min_d2 hold uint32 values in int32
+    storage (view the host copies as numpy uint32).  Raises ValueError when a norm2 is 2^29 or more: the dot products would leave int32."""
+    require_gpu(q, "coreset_select")
+    require_gpu(norm2, "coreset_select")
+    if q.dim() != 2 or q.dtype != torch.int16 or norm2.dtype != torch.int32 or norm2.shape != (q.shape[0],) or \
+            norm2.device != q.device:
+        raise ValueError("coreset_select takes q int16 [N, E] and norm2 int32 [N] of coreset_rows on one device")
+    q, norm2 = q.contiguous(), norm2.contiguous()
+    N, E = q.shape
+    if N and (int(norm2.max()) >= CORESET_NORM2_LIMIT or int(norm2.min()) < 0):
+        raise ValueError("coreset_select: a row's norm2 is 2^29 or more (a norm above 1.41); the rows must be unit rows")
+    lib = _lib.load()
+    dev = q.device
+    n, start = int(n), int(start)
+    picks = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
+    radius2 = torch.empty(max(n, 0) + 1, dtype=torch.int32, device=dev)
+    min_d2 = torch.empty(N, dtype=torch.int32, device=dev)
+    ws = Workspace.get(dev, max(256, lib.aaclip_coreset_select_workspace_bytes(N, E, n)))
+    _lib.check(lib.aaclip_coreset_select(q.data_ptr(), norm2.data_ptr(), N, E, n, start, picks.data_ptr(), radius2.data_ptr(),
+                                         min_d2.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "coreset_select")
+    return picks, radius2, min_d2
+
+
+def coreset_projection(E: int, dim: int, seed: int = 0) -> torch.Tensor:
+    """the seeded Gaussian projection of support_bank_coreset as the GEMM's weight [dim, E] (host tensor)"""
+    from . import synth
+    return synth.randn("support.coreset.projection", (E, dim), dim ** -0.5, seed).t().contiguous()
+
+
+def coreset_projected_rows(rows: torch.Tensor, dim: int, seed: int = 0) -> torch.Tensor:
+    """fp32 unit rows [N, E] -> unit rows [N, dim]: the library's fp32 GEMM with the seeded projection, then
+    coreset_unit_rows.  dim must be a multiple of 128 (the GEMM's column tile)."""
+    r = _f32c(rows)
+    require_gpu(r, "coreset_projected_rows")
+    N, E = r.shape
+    if dim % 128 or dim < 128 or dim > 1024:
+        raise ValueError("support_bank_coreset: dim must be 0 or a multiple of 128 up to 1024")
+    w = coreset_projection(E, dim, seed).to(r.device)
+    out = torch.empty(N, dim, dtype=torch.float32, device=r.device)
+    gemm(_lib.F32, _lib.EPI_ACT_F32, r, w, None, out)
+    return coreset_unit_rows(out)
+
+
+def support_bank_coreset(seg_tokens_per_image_batch, form, ratio: float, dim: int = 128, seed: int = 0) -> CoresetBank:
+    """support_bank's input and concatenation order; per level the rows are (for 0 < dim < E) projected to `dim`
+    dimensions and re-normalised, quantised, and n = max(1, ceil(ratio * N)) of them are selected greedily from row 0
+    (coreset_select), truncated where the covering radius reaches 0 (every further row duplicates a pick).  The ORIGINAL
+    fp32 rows of the picks form the bank that support_nearest and support_map take."""
+    import math
+    import numpy as np
+    if not 0.0 < float(ratio) <= 1.0:
+        raise ValueError("support_bank_coreset: ratio must lie in (0, 1]")
+    dim = int(dim)
+    if dim < 0:
+        raise ValueError("support_bank_coreset: dim must not be negative")
+    form = support_form(form)
+    batches = list(seg_tokens_per_image_batch)
+    if not batches:
+        raise ValueError("support_bank: no images")
+    if torch.is_tensor(batches[0]):
+        batches = [batches]
+    levels = len(batches[0])
+    if levels < 1 or any(len(b) != levels for b in batches):
+        raise ValueError("support_bank: every batch must hold the same tap levels")
+    require_gpu(batches[0][0], "support_bank_coreset")
+    P, E = batches[0][0].shape[1:]
+    shots = sum(int(b[0].shape[0]) for b in batches)
+    N = shots * P
+    n = max(1, min(N, int(math.ceil(float(ratio) * N))))
+    used = dim if 0 < dim < E else 0
+    rows, index, radii = [], [], []
+    for l in range(levels):
+        parts = [_f32c(b[l]) for b in batches]
+        if any(p.dim() != 3 or tuple(p.shape[1:]) != (P, E) for p in parts):
+            raise ValueError("support_bank: seg tokens must be [b, P, E] with one P and E")
+        full = torch.cat(parts, dim=0).reshape(N, E)
+        q, norm2 = coreset_rows(coreset_projected_rows(full, used, seed) if used else full)
+        picks, radius2, _ = coreset_select(q, norm2, n, 0)
+        r2 = radius2.cpu().numpy().view(np.uint32)
+        zero = np.flatnonzero(r2 == 0)
+        kept = int(zero[0]) if zero.size else n
+        picks, r2 = picks[:kept].contiguous(), r2[:kept + 1].copy()
+        rows.append(support_bank_rows(torch.index_select(full, 0, picks.long()), form))
+        index.append(picks)
+        radii.append(r2)
+    return CoresetBank(rows, form, int(P), shots, index, radii, used)
+
+
 # ------------------------------------------------------------------------------- fused optimizer step (csrc/optim.hip)
 OPTIM_RECORD_FLOATS = 2          # fp32 words of aaclip_optim_record: total_norm, clip_coef
 OPTIM_MAX_GROUPS = _lib.OPTIM_MAX_GROUPS

@@ -1836,6 +1836,59 @@ int aaclip_support_map(const float* const* best_cos, int NL, const float* base, 
   return finish("support_map");
 }
 
+// ---- coreset of the support bank (coreset.hip)
+static const char* coreset_shape_check(long N, int E) {
+  if (N < 1 || N > 0x7FFFFFFFl) return "N must be 1 .. 2^31 - 1";
+  if (E < 32 || E > 1024 || E % 32 != 0) return "E must be a multiple of 32 in 32 .. 1024";
+  return nullptr;
+}
+
+int aaclip_coreset_rows(const float* rows, long N, int E, int16_t* q, int32_t* norm2, void* stream) {
+  REQUIRE(rows && q && norm2, "coreset_rows: null pointer");
+  if (const char* m = coreset_shape_check(N, E)) return fail(-1, in("coreset_rows", m));
+  REQUIRE_ALIGNED16("coreset_rows", rows, q);
+  REQUIRE(((uintptr_t)norm2 & 3) == 0, "coreset_rows: norm2 must be 4-byte aligned");
+  const size_t rb = (size_t)N * E * 4, qb = (size_t)N * E * 2, nb = (size_t)N * 4;
+  REQUIRE(!ranges_overlap(rows, rb, q, qb) && !ranges_overlap(rows, rb, norm2, nb) && !ranges_overlap(q, qb, norm2, nb),
+          "coreset_rows: rows, q and norm2 must not overlap");
+  launch_coreset_rows(rows, N, E, q, norm2, (hipStream_t)stream);
+  return finish("coreset_rows");
+}
+
+int aaclip_coreset_unit_rows(const float* rows, long N, int E, float* out, void* stream) {
+  REQUIRE(rows && out, "coreset_unit_rows: null pointer");
+  if (const char* m = coreset_shape_check(N, E)) return fail(-1, in("coreset_unit_rows", m));
+  REQUIRE_ALIGNED16("coreset_unit_rows", rows, out);
+  REQUIRE(!ranges_overlap(rows, (size_t)N * E * 4, out, (size_t)N * E * 4), "coreset_unit_rows: rows and out must not overlap");
+  launch_coreset_unit_rows(rows, N, E, out, (hipStream_t)stream);
+  return finish("coreset_unit_rows");
+}
+
+size_t aaclip_coreset_select_workspace_bytes(long N, int E, long n) {
+  return coreset_shape_check(N, E) || n < 1 || n > N ? 0 : coreset_ws_bytes(n);
+}
+
+int aaclip_coreset_select(const int16_t* q, const int32_t* norm2, long N, int E, long n, long start, int32_t* picks,
+                          uint32_t* radius2, uint32_t* min_d2, void* ws, size_t ws_bytes, void* stream) {
+  REQUIRE(q && norm2 && picks && radius2 && min_d2 && ws, "coreset_select: null pointer");
+  if (const char* m = coreset_shape_check(N, E)) return fail(-1, in("coreset_select", m));
+  REQUIRE(n >= 1 && n <= N, "coreset_select: n must be 1 .. N");
+  REQUIRE(start >= 0 && start < N, "coreset_select: start must be 0 .. N - 1");
+  REQUIRE_ALIGNED16("coreset_select", q);
+  REQUIRE((((uintptr_t)norm2 | (uintptr_t)picks | (uintptr_t)radius2 | (uintptr_t)min_d2) & 3) == 0 && ((uintptr_t)ws & 7) == 0,
+          "coreset_select: norm2 / picks / radius2 / min_d2 must be 4-byte, the workspace 8-byte aligned");
+  const size_t need = coreset_ws_bytes(n);
+  REQUIRE(ws_bytes >= need, "coreset_select: workspace too small");
+  const void* bufs[6] = {picks, radius2, min_d2, ws, q, norm2};
+  const size_t lens[6] = {(size_t)n * 4, (size_t)(n + 1) * 4, (size_t)N * 4, need, (size_t)N * E * 2, (size_t)N * 4};
+  bool clash = false;
+  for (int a = 0; a < 4; ++a)
+    for (int b = a + 1; b < 6; ++b) clash = clash || ranges_overlap(bufs[a], lens[a], bufs[b], lens[b]);
+  REQUIRE(!clash, "coreset_select: outputs and workspace must not overlap one another or the inputs");
+  launch_coreset_select(q, norm2, N, E, n, start, picks, radius2, min_d2, ws, (hipStream_t)stream);
+  return finish("coreset_select");
+}
+
 int aaclip_text_embed(const int32_t* tokens, const float* table, const float* pos, float* x, int n, int T, int D,
                       int vocab, void* stream) {
   REQUIRE(tokens && table && pos && x, "text_embed: null pointer");

@@ -309,6 +309,14 @@ void launch_support_bank_rows(const float* rows, long N, int E, int form, void* 
 void launch_support_dist(const float* cosine, float* d, long n, hipStream_t s);              // d = 1 - cosine
 void launch_support_add(const float* base, float weight, float* out, long n, hipStream_t s);   // out = base + weight * out
 
+// ---- coreset.hip : greedy k-center selection over quantised bank rows (the quantiser, the candidate word, the plan and
+// the workspace are coreset_pack.h)
+size_t coreset_ws_bytes(long n);
+void launch_coreset_rows(const float* rows, long N, int E, int16_t* q, int32_t* norm2, hipStream_t s);
+void launch_coreset_select(const int16_t* q, const int32_t* norm2, long N, int E, long n, long start, int32_t* picks,
+                           uint32_t* radius2, uint32_t* min_d2, void* ws, hipStream_t s);
+void launch_coreset_unit_rows(const float* rows, long N, int E, float* out, hipStream_t s);   // out = rows / |row|
+
 // ---- multi-tensor optimizer (optim.hip; the launch packing is optim_pack.h)
 struct OptimGroupScalars {   // one group's hyper-parameters as the kernel reads them: formed in fp64, rounded once
   float beta1, one_minus_beta1, beta2, one_minus_beta2;

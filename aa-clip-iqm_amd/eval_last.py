@@ -27,6 +27,9 @@ the same names and arguments:
                                           support={class: engine.SupportBank} adds the few-shot memory-bank term to the
                                           text-anchor map before the IQM fusion (forward_utils.support_anomaly_map;
                                           support_banks builds the banks); eval_support.py is the script with --support
+                                          (support_banks(coreset=R) reduces every bank to the greedy coreset of the
+                                          share R of its rows, an engine.CoresetBank; eval_coreset.py is the script
+                                          with --support_coreset)
   main(argv)                              the arguments and steps of test_last.main plus --device_metrics
 
 python eval_last.py --save_path ... [--device_metrics] [every argument of test_last.py]
@@ -224,12 +227,17 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
 
 def _support_nearest_pairs(nearest, bank, world):
     """per batch, per level int32 [b, P] device indices -> per level int32 [N, P, 2] host arrays of (shot, patch); under
-    torch.distributed the shards are joined in rank order"""
+    torch.distributed the shards are joined in rank order.  A bank with an `index` (engine.CoresetBank) holds a part of
+    the full bank's rows: the nearest kept row is mapped through index[l] first, so (shot, patch) stay those of the
+    full bank."""
     levels = len(bank.rows)
+    index = bank.index if "index" in getattr(bank, "_fields", ()) else None     # a plain tuple's .index is a method
     out = []
     for l in range(levels):
         parts = [b[l].cpu().numpy() for b in (nearest or [])]
         idx = np.concatenate(parts, axis=0) if parts else np.zeros((0, bank.patches), np.int32)
+        if index is not None:
+            idx = index[l].cpu().numpy()[idx]
         out.append(np.stack(np.divmod(idx, bank.patches), axis=-1).astype(np.int32))
     if world > 1:
         import torch.distributed as dist
@@ -240,12 +248,13 @@ def _support_nearest_pairs(nearest, bank, world):
 
 
 def support_banks(model, image_datasets, k: int, device, img_size: int, form=None, support_datasets=None,
-                  batch_size: int = 32):
+                  batch_size: int = 32, coreset=None, coreset_dim=128):
     """The k-shot protocol for every class: -> ({class name: engine.SupportBank}, {class name: evaluated dataset}).
     Without support_datasets the class's first k normal images feed the bank and leave the evaluated set
     (BaseSingleClassDataset.support_split); with them -- datasets of another metadata file, such as MVTec's train/good --
     their first k normal images feed it and the evaluated set stays whole.  Every process that calls this builds the same
-    banks: k images per class, no communication."""
+    banks: k images per class, no communication.  coreset: None, or the share of every bank's rows that is kept
+    (forward_utils.build_support_bank's keyword, with coreset_dim beside it): the banks are engine.CoresetBank then."""
     from forward_utils import build_support_bank
     banks, evaluated = {}, {}
     for class_name, ds in image_datasets.items():
@@ -257,8 +266,18 @@ def support_banks(model, image_datasets, k: int, device, img_size: int, form=Non
         for b in torch.utils.data.DataLoader(shots, batch_size=batch_size, shuffle=False):
             image = b["image"].to(device)
             batches.append(engine.preprocess(image, img_size) if image.dtype == torch.uint8 else image)
-        banks[class_name] = build_support_bank(model, batches, form)
+        extra = {} if coreset is None else {"coreset": coreset, "coreset_dim": coreset_dim}
+        banks[class_name] = build_support_bank(model, batches, form, **extra)
     return banks, evaluated
+
+
+def log_coreset(logger, banks):
+    """per class and level: the full bank's rows N, the rows kept and the final covering radius as a cosine distance
+    (radius2 / 2^29: d^2 = 2 - 2 cos on unit rows, in units of 2^-28)"""
+    for class_name, b in banks.items():
+        for l, (rows, r2) in enumerate(zip(b.rows, b.radius2)):
+            logger.info("coreset %s level %d: N %d, kept %d, covering radius %.6f (cosine distance, dim %d)", class_name, l,
+                        b.shots * b.patches, rows.shape[0], float(r2[-1]) / float(1 << 29), b.dim)
 
 
 def format_table(rows: List[dict]) -> str:
@@ -398,12 +417,16 @@ def run(parser: argparse.ArgumentParser, argv=None, table=None, finish=None):
             from dataset import DATA_PATH, BaseSingleClassDataset
             support_sets = {c: BaseSingleClassDataset(DATA_PATH[args.dataset], args.support_meta, args.img_size, c,
                                                       device_preprocess=args.device_preprocess) for c in image_datasets}
+        coreset = getattr(args, "support_coreset", None)
+        core = {} if coreset is None else {"coreset": coreset, "coreset_dim": getattr(args, "support_coreset_dim", 128)}
         banks, image_datasets = support_banks(model, image_datasets, shots, device, args.img_size,
                                               form=getattr(args, "support_form", None), support_datasets=support_sets,
-                                              batch_size=args.image_batch_size)
+                                              batch_size=args.image_batch_size, **core)
         bank = {"support": banks, "support_weight": getattr(args, "support_weight", SUPPORT_WEIGHT)}
         logger.info("support banks: %d shots per class, form %s, weight %s", shots,
                     "fp16" if next(iter(banks.values())).form == engine.SUPPORT_FP16 else "fp32", bank["support_weight"])
+        if coreset is not None:
+            log_coreset(logger, banks)
     where = (model, image_datasets, text_embeddings, device, args.img_size, args.dataset)
     how = dict(batch_size=args.image_batch_size, loader_kwargs={"num_workers": 4, "pin_memory": True}, logger=logger,
                use_iqm=args.iqm == "on", device_metrics=args.device_metrics)

@@ -126,11 +126,13 @@ def _map_domain(domain):
     return (1.0, 7) if domain == "Industrial" else (1.5, 9)     # sigma, ksize: calculate_anomaly_map's
 
 
-def build_support_bank(model, images, form=None) -> engine.SupportBank:
+def build_support_bank(model, images, form=None, coreset=None, coreset_dim=128):
     """The bank of the normal images `images` ([k, 3, S, S] normalised, or a sequence of such batches): the model's unit
     seg tokens of every tap level, in image order.  form: 'fp16' / 'fp32'; None picks fp32
     for a precision="fp32" model and fp16 otherwise.  Runs under no_grad with text_embeddings=None (the IQM branch has no
-    part in the bank)."""
+    part in the bank).  coreset: None for the whole bank (an engine.SupportBank), or a ratio in (0, 1]: the greedy
+    coreset of that share of the rows, selected on rows projected to coreset_dim dimensions (0: on the rows themselves)
+    -- an engine.CoresetBank (engine.support_bank_coreset)."""
     if form is None:
         code = engine.dtype_code(getattr(getattr(model, "clipmodel", model), "precision", "fp32"))
         form = "fp32" if code == _lib.F32 else "fp16"
@@ -143,6 +145,8 @@ def build_support_bank(model, images, form=None) -> engine.SupportBank:
                 raise ValueError("build_support_bank takes normalised images (engine.preprocess turns raw frames into them)")
             patch_features, _, _ = model(image.to(dev), text_embeddings=None)
             tokens.append([p.float() for p in patch_features])
+    if coreset is not None:
+        return engine.support_bank_coreset(tokens, form, coreset, dim=coreset_dim)
     return engine.support_bank(tokens, form)
 
 

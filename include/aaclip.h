@@ -650,6 +650,34 @@ int aaclip_support_bank_rows(const float* rows, long N, int E, int form, void* b
 int aaclip_support_map(const float* const* best_cos, int NL, const float* base, float weight, float* out, int B, int g,
                        int S, int ksize, float sigma, void* ws, size_t ws_bytes, void* stream);
 
+/* Coreset of the support bank (csrc/coreset.hip; the code it shares with a host program is csrc/coreset_pack.h):
+ * greedy k-center selection of n of the N bank rows, so that a bank of hundreds of images is searched at the cost of a
+ * few.  Integer arithmetic throughout, so the picks are the same on every run and equal a host definition bit for bit.
+ * The conventions are those of the support entries (checks before the first launch, *_workspace_bytes 0 for refused
+ * sizes, overlap checks, only kernels and one memset enqueued on the caller's stream).  This ABI number is unchanged:
+ * the entries are additions.
+ *   aaclip_coreset_rows: rows fp32 [N, E] -> q int16 [N, E], q_i = clamp(rint(v_i * 2^14), -32767, 32767) (the product
+ *   is exact, rint is round-half-even, -0.0 and NaN give 0), and norm2 int32 [N] = sum q_i^2, saturated at 2^31 - 1.
+ *   aaclip_coreset_select: with d2(x, c) = norm2_x + norm2_c - 2 <q_x, q_c> (the exact squared distance of the integer
+ *   rows, a uint32):
+ *       min_d2[i] = UINT32_MAX for all i;  radius2[0] = UINT32_MAX;  pick[0] = start
+ *       for t = 0 .. n-1:  min_d2[i] = min(min_d2[i], d2(i, pick[t]));  radius2[t+1] = max_i min_d2[i];
+ *                          pick[t+1] = the LOWEST i that attains it (stored while t + 1 < n)
+ *   picks int32 [n], radius2 uint32 [n + 1] (never increases; 0 from the pick after which every row duplicates a pick),
+ *   min_d2 uint32 [N] after n picks.  The first k picks of a call for n are the call for k.  PRECONDITION: norm2 came
+ *   from aaclip_coreset_rows and every value is below 2^29 (rows of norm up to 1.41), so that every dot product fits
+ *   int32; the entry does not read the device to check it (engine.coreset_select does).  N in 1 .. 2^31 - 1, n in
+ *   1 .. N, start in 0 .. N - 1, E a multiple of 32 in 32 .. 1024.  One launch per pick, chained by stream order;
+ *   launch t merges one 64-bit candidate per workgroup, min_d2 << 32 | (0xFFFFFFFF - row), into word t + 1 of the
+ *   workspace by an integer maximum.  No workgroup waits for another.  Workspace: (n + 1) * 8 bytes, rounded up.
+ *   aaclip_coreset_unit_rows: out = rows / max(|row|, 1e-12) per row of fp32 [N, E], not in place.
+ *   Alignment: rows, q and out 16 bytes; norm2, picks, radius2, min_d2 4 bytes; the workspace 8 bytes. */
+int aaclip_coreset_rows(const float* rows, long N, int E, int16_t* q, int32_t* norm2, void* stream);
+int aaclip_coreset_unit_rows(const float* rows, long N, int E, float* out, void* stream);
+size_t aaclip_coreset_select_workspace_bytes(long N, int E, long n);
+int aaclip_coreset_select(const int16_t* q, const int32_t* norm2, long N, int E, long n, long start, int32_t* picks,
+                          uint32_t* radius2, uint32_t* min_d2, void* ws, size_t ws_bytes, void* stream);
+
 /* Fused Adam / AdamW step over a list of tensors, and the gradient norm that clips it (csrc/optim.hip).  fp32
  * parameters, gradients and state only.  One launch serves up to 24 tensors and 640 chunks of 16384 elements; its table
  * travels by value in the kernel arguments, so a call copies nothing to the device, allocates nothing and waits for
