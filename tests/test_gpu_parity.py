@@ -694,7 +694,7 @@ def golden_surgery():
     return np.load(os.path.join(os.path.dirname(__file__), "golden", "surgery.npz"))
 
 
-@pytest.mark.parametrize("code", [F32, F16])
+@pytest.mark.parametrize("code", [F32, F16, BF16, F16X2])
 @pytest.mark.parametrize("B", [3, 1])
 @pytest.mark.parametrize("dpam", [2, 3])
 def test_surgery_encode_image_vs_reference_golden(dev, golden_surgery, code, B, dpam):
