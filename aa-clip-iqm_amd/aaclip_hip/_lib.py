@@ -74,6 +74,17 @@ class OptimGroup(C.Structure):
                 ("step", _l)]
 
 
+class TilePlan(C.Structure):
+    """struct aaclip_tile_plan (include/aaclip.h): the geometry of a tiled frame and the stream of the call.
+    struct_bytes is filled in on construction; the library refuses any other size."""
+    _fields_ = [("struct_bytes", _sz), ("images", _i), ("channels", _i), ("tile", _i), ("grid", _i), ("overlap", _i),
+                ("stream", _vp)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_bytes = C.sizeof(TilePlan)
+
+
 # name -> (restype, argtypes); every symbol include/aaclip.h declares
 SIGNATURES = {
     "aaclip_version": (_i, []),
@@ -158,6 +169,9 @@ SIGNATURES = {
     "aaclip_coreset_unit_rows": (_i, [_vp, _l, _i, _vp, _vp]),
     "aaclip_coreset_select_workspace_bytes": (_sz, [_l, _i, _l]),
     "aaclip_coreset_select": (_i, [_vp, _vp, _l, _i, _l, _l, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "aaclip_tile_canvas": (_i, [_i, _i, _i]),
+    "aaclip_tile_gather": (_i, [C.POINTER(TilePlan), _vp, _vp]),
+    "aaclip_tile_stitch": (_i, [C.POINTER(TilePlan), _vp, _vp]),
     "aaclip_row_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp] + [_i] * 6 + [_vp, _sz, _vp]),
     "aaclip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _l, _i, _f, _vp]),
     "aaclip_gemm": (_i, [_i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _f, _vp]),

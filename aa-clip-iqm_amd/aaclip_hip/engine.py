@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import BF16, F16, F16X2, F32, BlockWeights
+from ._lib import BF16, F16, F16X2, F32, BlockWeights, TilePlan
 
 _TORCH_DT = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F16X2: torch.float16}
 # "fp16x2": split fp16 (every matrix-product operand as an fp16 hi + lo pair, 3 MFMA products per matrix product):
@@ -2156,8 +2156,74 @@ def support_bank_coreset(seg_tokens_per_image_batch, form, ratio: float, dim: in
     return CoresetBank(rows, form, int(P), shots, index, radii, used)
 
 
+# ------------------------------------------------------------------------------- tiled inference (csrc/tiles.hip)
+def tile_canvas(S: int, G: int, O: int) -> int:
+    """The canvas side C = S + (G - 1) * (S - O) of G x G tiles of side S that overlap by O pixels (aaclip_tile_canvas);
+    ValueError for S < 1, G < 1, O outside 0 .. S // 2 or a side beyond int."""
+    c = _lib.load().aaclip_tile_canvas(int(S), int(G), int(O))
+    if c < 0:
+        raise ValueError(f"tile_canvas: tile {S}, grid {G}, overlap {O}: tile >= 1, grid >= 1 and 0 <= overlap <= tile // 2")
+    return int(c)
+
+
+def _tile_tensor(t: torch.Tensor, what: str) -> None:
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise ValueError(f"{what}: expects a tensor on the GPU (there is no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: expects fp32, got {t.dtype}")
+    if t.dim() not in (3, 4):
+        raise ValueError(f"{what}: expects [n, channels, side, side] or [n, side, side], got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: expects a contiguous tensor")
+
+
+def _tile_plan(images: int, channels: int, S: int, G: int, O: int, dev: torch.device) -> TilePlan:
+    plan = TilePlan()
+    plan.images, plan.channels, plan.tile, plan.grid, plan.overlap = images, channels, S, G, O
+    plan.stream = _stream(dev)
+    return plan
+
+
+def tile_gather(canvas: torch.Tensor, S: int, G: int, O: int) -> torch.Tensor:
+    """canvas fp32 [B, ch, C, C] (or [B, C, C]), C = tile_canvas(S, G, O) -> tiles [B * G * G, ch, S, S] (or
+    [B * G * G, S, S]): tile b * G * G + i * G + j is canvas[b, :, i * T : i * T + S, j * T : j * T + S], T = S - O, the
+    same bits (aaclip_tile_gather, one launch on the current stream)."""
+    S, G, O = int(S), int(G), int(O)
+    C_ = tile_canvas(S, G, O)
+    _tile_tensor(canvas, "tile_gather")
+    if tuple(canvas.shape[-2:]) != (C_, C_):
+        raise ValueError(f"tile_gather: tile {S}, grid {G}, overlap {O} need a canvas of side {C_}, got {tuple(canvas.shape)}")
+    B = int(canvas.shape[0])
+    lead = tuple(canvas.shape[1:-2])
+    ch = int(lead[0]) if lead else 1
+    tiles = torch.empty((B * G * G,) + lead + (S, S), dtype=torch.float32, device=canvas.device)
+    plan = _tile_plan(B, ch, S, G, O, canvas.device)
+    _lib.check(_lib.load().aaclip_tile_gather(C.byref(plan), canvas.data_ptr(), tiles.data_ptr()), "tile_gather")
+    return tiles
+
+
+def tile_stitch(tiles: torch.Tensor, G: int, O: int, images: int) -> torch.Tensor:
+    """tiles fp32 [images * G * G, ch, S, S] (or [images * G * G, S, S]) -> canvas [images, ch, C, C] (or
+    [images, C, C]): a pixel under one tile takes that tile's bits, any other the weighted mean of its 2 or 4 tiles with
+    the weights min(y + 1, S - y) * min(x + 1, S - x), in ascending tile order in fp32 (aaclip_tile_stitch, one launch on
+    the current stream; forward_utils.tile_stitch_host is the definition)."""
+    G, O, images = int(G), int(O), int(images)
+    _tile_tensor(tiles, "tile_stitch")
+    S = int(tiles.shape[-1])
+    C_ = tile_canvas(S, G, O)
+    if tiles.shape[-2] != S or images < 0 or tiles.shape[0] != images * G * G:
+        raise ValueError(f"tile_stitch: {images} images on a grid of {G} need [{images * G * G}, ..., S, S] tiles, got "
+                         f"{tuple(tiles.shape)}")
+    lead = tuple(tiles.shape[1:-2])
+    ch = int(lead[0]) if lead else 1
+    canvas = torch.empty((images,) + lead + (C_, C_), dtype=torch.float32, device=tiles.device)
+    plan = _tile_plan(images, ch, S, G, O, tiles.device)
+    _lib.check(_lib.load().aaclip_tile_stitch(C.byref(plan), tiles.data_ptr(), canvas.data_ptr()), "tile_stitch")
+    return canvas
+
+
 # ------------------------------------------------------------------------------- fused optimizer step (csrc/optim.hip)
-OPTIM_RECORD_FLOATS = 2          # fp32 words of aaclip_optim_record: total_norm, clip_coef
+OPTIM_RECORD_FLOATS = 2         # fp32 words of aaclip_optim_record: total_norm, clip_coef
 OPTIM_MAX_GROUPS = _lib.OPTIM_MAX_GROUPS
 
 

@@ -8,6 +8,7 @@
 
 #include "bf16x3.h"
 #include "kernels.h"
+#include "tile_plan.h"
 
 using namespace aaclip;
 
@@ -1887,6 +1888,52 @@ int aaclip_coreset_select(const int16_t* q, const int32_t* norm2, long N, int E,
   REQUIRE(!clash, "coreset_select: outputs and workspace must not overlap one another or the inputs");
   launch_coreset_select(q, norm2, N, E, n, start, picks, radius2, min_d2, ws, (hipStream_t)stream);
   return finish("coreset_select");
+}
+
+// ---- tiled inference (tiles.hip; the geometry and its checks: tile_plan.h)
+int aaclip_tile_canvas(int tile, int grid, int overlap) {
+  const long c = tile_canvas_side(tile, grid, overlap);
+  if (c < 0) return fail(-1, "aaclip_tile_canvas: tile >= 1, grid >= 1, 0 <= overlap <= tile / 2 and a canvas side within int");
+  return (int)c;
+}
+
+// every check of a tile entry: 0 with *launch set when there is work, 0 with *launch clear for images == 0, or the code
+static int tile_entry_check(const char* entry, const aaclip_tile_plan* plan, const void* canvas, const void* tiles,
+                            TileGeom* g, bool* launch) {
+  *launch = false;
+  if (!plan) return fail(-1, in(entry, "null plan"));
+  if (plan->struct_bytes != sizeof(aaclip_tile_plan))
+    return fail(-1, in(entry, "aaclip_tile_plan.struct_bytes does not match this library (binding generated from another "
+                              "header?)"));
+  if (const char* m = tile_plan_check(plan->images, plan->channels, plan->tile, plan->grid, plan->overlap))
+    return fail(-1, in(entry, m));
+  if (!canvas || !tiles) return fail(-1, in(entry, "null pointer"));
+  if (((uintptr_t)canvas | (uintptr_t)tiles) & 3) return fail(-1, in(entry, "canvas and tiles must be 4-byte aligned"));
+  *g = tile_geom(plan->channels, plan->tile, plan->grid, plan->overlap);
+  const size_t per_image = (size_t)plan->channels * 4;
+  const size_t canvas_bytes = (size_t)plan->images * per_image * (size_t)g->C * (size_t)g->C;
+  const size_t tiles_bytes = (size_t)plan->images * per_image * (size_t)g->G * (size_t)g->G * (size_t)g->S * (size_t)g->S;
+  if (ranges_overlap(canvas, canvas_bytes, tiles, tiles_bytes)) return fail(-1, in(entry, "canvas and tiles must not overlap"));
+  *launch = plan->images > 0;
+  return 0;
+}
+
+int aaclip_tile_gather(const aaclip_tile_plan* plan, const float* canvas, float* tiles) {
+  TileGeom g;
+  bool launch;
+  if (const int rc = tile_entry_check("aaclip_tile_gather", plan, canvas, tiles, &g, &launch)) return rc;
+  if (!launch) return 0;
+  launch_tile_gather(g, plan->images, canvas, tiles, (hipStream_t)plan->stream);
+  return finish("aaclip_tile_gather");
+}
+
+int aaclip_tile_stitch(const aaclip_tile_plan* plan, const float* tiles, float* canvas) {
+  TileGeom g;
+  bool launch;
+  if (const int rc = tile_entry_check("aaclip_tile_stitch", plan, canvas, tiles, &g, &launch)) return rc;
+  if (!launch) return 0;
+  launch_tile_stitch(g, plan->images, tiles, canvas, (hipStream_t)plan->stream);
+  return finish("aaclip_tile_stitch");
 }
 
 int aaclip_text_embed(const int32_t* tokens, const float* table, const float* pos, float* x, int n, int T, int D,

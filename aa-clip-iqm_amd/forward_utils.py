@@ -223,6 +223,50 @@ def support_anomaly_map_host(patch_features, bank_features, img_size, domain="In
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# tiled inference: a frame of side C = S + (G - 1) * (S - O) as G x G tiles of the model's side S that overlap by O pixels
+TILE_OVERLAP = 112      # derived, not tuned (no dataset was at hand): 8 grid cells of 14 px.  A tile's map is blurred over
+#                         at most 9 cells -- a radius of 4 cells = 56 px, with a reflected border -- so in an overlap of
+#                         112 px the half of the cross-fade where a tile's blur saw reflected cells carries less than
+#                         half the weight
+
+
+def tile_origins(S, G, O):
+    """-> [(row, column)] of the G * G tiles' upper left corners on the canvas, tile t = i * G + j at (i * T, j * T),
+    T = S - O; needs S >= 1, G >= 1 and 0 <= O <= S // 2 (then a canvas pixel lies in at most 2 tiles per axis)."""
+    S, G, O = int(S), int(G), int(O)
+    if S < 1 or G < 1 or not 0 <= O <= S // 2:
+        raise ValueError(f"tiles: tile {S}, grid {G}, overlap {O}: tile >= 1, grid >= 1 and 0 <= overlap <= tile // 2")
+    T = S - O
+    return [(i * T, j * T) for i in range(G) for j in range(G)]
+
+
+def tile_stitch_host(tiles, G, O):
+    """The host definition engine.tile_stitch is measured against, in numpy fp64: tiles [images * G * G, ..., S, S] ->
+    canvas [images, ..., C, C], C = S + (G - 1) * (S - O).  With w1(u) = min(u + 1, S - u) a tile weighs w1(y) * w1(x) at
+    its (y, x); a canvas pixel under exactly one tile is that tile's value, any other is
+    (sum_t w_t * v_t) / (sum_t w_t) over its covering tiles in ascending t."""
+    import numpy as np
+    v = np.asarray(tiles.detach().cpu() if torch.is_tensor(tiles) else tiles, np.float64)
+    S = v.shape[-1]
+    origins = tile_origins(S, G, O)
+    if v.ndim < 3 or v.shape[-2] != S or v.shape[0] % (G * G):
+        raise ValueError(f"tile_stitch_host: {v.shape} is not [images * {G * G}, ..., S, S]")
+    images, lead = v.shape[0] // (G * G), v.shape[1:-2]
+    C = S + (G - 1) * (S - O)
+    w1 = np.minimum(np.arange(S) + 1, S - np.arange(S)).astype(np.float64)
+    w = w1[:, None] * w1[None, :]
+    v = v.reshape((images, G * G) + lead + (S, S))
+    num, den, count = np.zeros((images,) + lead + (C, C)), np.zeros((C, C)), np.zeros((C, C), np.int64)
+    single = np.zeros_like(num)
+    for t, (r, c) in enumerate(origins):
+        num[..., r:r + S, c:c + S] += w * v[:, t]
+        den[r:r + S, c:c + S] += w
+        count[r:r + S, c:c + S] += 1
+        single[..., r:r + S, c:c + S] = v[:, t]
+    return np.where(count == 1, single, num / den)
+
+
 def image_score(det_feature: torch.Tensor, text_feature: torch.Tensor) -> torch.Tensor:
     """Per-image anomaly score (det_b . t_abnormal + 1)/2 -> [B].  Deliberate
     deviation from test_last.py:90-91, whose [B,768]@[B,768,2] broadcast yields

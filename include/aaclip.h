@@ -678,6 +678,41 @@ size_t aaclip_coreset_select_workspace_bytes(long N, int E, long n);
 int aaclip_coreset_select(const int16_t* q, const int32_t* norm2, long N, int E, long n, long start, int32_t* picks,
                           uint32_t* radius2, uint32_t* min_d2, void* ws, size_t ws_bytes, void* stream);
 
+/* Tiled inference (csrc/tiles.hip; the geometry it shares with a host program is csrc/tile_plan.h): a frame larger
+ * than the model's input is cut into overlapping tiles of the model's size and the tile maps are blended back into one
+ * map.  S = tile side, G = grid >= 1 tiles per side, O = overlap in pixels, 0 <= O <= S / 2, stride T = S - O, canvas
+ * side C = S + (G - 1) * T.  Tile t = i * G + j covers canvas rows [i * T, i * T + S) and columns [j * T, j * T + S);
+ * a canvas pixel lies in at most 2 tiles per axis.  canvas fp32 [images, channels, C, C]; tiles fp32
+ * [images * G * G, channels, S, S].
+ *   aaclip_tile_canvas: C on the host, or -1 for a refused geometry (nothing is launched).
+ *   aaclip_tile_gather: tiles[b * G * G + t, c, y, x] = canvas[b, c, i * T + y, j * T + x], a copy of bits.
+ *   aaclip_tile_stitch: with w1(u) = min(u + 1, S - u) and the weight w1(y) * w1(x) of a tile at its (y, x): a canvas
+ *   pixel under exactly one tile takes that tile's value, the same bits; any other pixel is
+ *   (sum_t w_t * v_t) / (sum_t w_t) over its covering tiles in ascending t, in fp32, every product, sum and the division
+ *   rounded on its own.  Across an overlap the two 1-D weights add up to O + 1: a linear cross-fade.  The weights and
+ *   their sums are exact in fp32 for S <= 4096.  The stitch is a gather over output pixels: no atomics, no workspace,
+ *   no memset, and a second call gives the same bytes.
+ * Each call is one launch on plan->stream (the stream travels in the plan, a hipStream_t).  Every check happens before
+ * the launch, and a failed one returns -1, leaves an error text that starts with the entry's name and writes nothing:
+ * a null plan, a struct_bytes other than sizeof, images < 0, channels < 1, tile < 1, grid < 1, overlap outside
+ * 0 .. tile / 2, a canvas side above INT_MAX, images * grid^2 * channels above 2^31 - 1, tensors of more than 2^59
+ * elements, a null or not 4-byte aligned pointer, canvas and tiles overlapping.  images == 0 returns 0 without a
+ * launch.  Vector accesses (16 or 8 bytes) are used where S and T are multiples of 4 or 2 and both pointers are aligned
+ * to that size; any other S, T and 4-byte aligned pointers take scalar accesses.  This ABI number is unchanged: the
+ * entries are additions. */
+typedef struct aaclip_tile_plan {
+  size_t struct_bytes;   /* sizeof(aaclip_tile_plan); any other value is refused */
+  int images;
+  int channels;
+  int tile;
+  int grid;
+  int overlap;
+  void* stream;          /* hipStream_t */
+} aaclip_tile_plan;
+int aaclip_tile_canvas(int tile, int grid, int overlap);
+int aaclip_tile_gather(const aaclip_tile_plan* plan, const float* canvas, float* tiles);
+int aaclip_tile_stitch(const aaclip_tile_plan* plan, const float* tiles, float* canvas);
+
 /* Fused Adam / AdamW step over a list of tensors, and the gradient norm that clips it (csrc/optim.hip).  fp32
  * parameters, gradients and state only.  One launch serves up to 24 tensors and 640 chunks of 16384 elements; its table
  * travels by value in the kernel arguments, so a call copies nothing to the device, allocates nothing and waits for
