@@ -85,6 +85,20 @@ class TilePlan(C.Structure):
         self.struct_bytes = C.sizeof(TilePlan)
 
 
+class OverlayPlan(C.Structure):
+    """struct aaclip_overlay_plan (include/aaclip.h): the sizes, panels, colours and normalisation of an overlay call and
+    its stream.  struct_bytes is filled in on construction; the library refuses any other size."""
+    _fields_ = [("struct_bytes", _sz), ("images", _i), ("height", _i), ("width", _i), ("panels", C.c_uint), ("alpha256", _i),
+                ("thickness", _i), ("pred_colour", C.c_uint8 * 3), ("truth_colour", C.c_uint8 * 3), ("mean", _f * 3),
+                ("std", _f * 3), ("stream", _vp)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_bytes = C.sizeof(OverlayPlan)
+
+
+OVERLAY_FRAME, OVERLAY_HEAT, OVERLAY_TRUTH = 1, 2, 4
+
 # name -> (restype, argtypes); every symbol include/aaclip.h declares
 SIGNATURES = {
     "aaclip_version": (_i, []),
@@ -172,6 +186,7 @@ SIGNATURES = {
     "aaclip_tile_canvas": (_i, [_i, _i, _i]),
     "aaclip_tile_gather": (_i, [C.POINTER(TilePlan), _vp, _vp]),
     "aaclip_tile_stitch": (_i, [C.POINTER(TilePlan), _vp, _vp]),
+    "aaclip_overlay_render": (_i, [C.POINTER(OverlayPlan)] + [_vp] * 7),
     "aaclip_row_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp] + [_i] * 6 + [_vp, _sz, _vp]),
     "aaclip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _l, _i, _f, _vp]),
     "aaclip_gemm": (_i, [_i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _f, _vp]),

@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import BF16, F16, F16X2, F32, BlockWeights, TilePlan
+from ._lib import BF16, F16, F16X2, F32, BlockWeights, OverlayPlan, TilePlan
 
 _TORCH_DT = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16, F16X2: torch.float16}
 # "fp16x2": split fp16 (every matrix-product operand as an fp16 hi + lo pair, 3 MFMA products per matrix product):
@@ -2220,6 +2220,116 @@ def tile_stitch(tiles: torch.Tensor, G: int, O: int, images: int) -> torch.Tenso
     plan = _tile_plan(images, ch, S, G, O, tiles.device)
     _lib.check(_lib.load().aaclip_tile_stitch(C.byref(plan), tiles.data_ptr(), canvas.data_ptr()), "tile_stitch")
     return canvas
+
+
+# ------------------------------------------------------------------------------- heat-map overlays (csrc/overlay.hip)
+OVERLAY_PANELS = ("frame", "heat", "truth")           # the order of the panels in the output; bit i selects panel i
+OVERLAY_LUTS = ("jet", "gray")
+OVERLAY_MAX_THICKNESS = 8
+_OVERLAY_LUTS: Dict[tuple, torch.Tensor] = {}
+
+
+def overlay_lut(name: str) -> torch.Tensor:
+    """The colour table `name` as a host uint8 [256, 3] tensor (RGB), defined in integers so that no rounding tie occurs:
+    "jet": lut[i][ch] = clamp(383 - |4 * i - 255 * c|, 0, 255), c = 3, 2, 1 for R, G, B -- the classic
+    clamp(1.5 - |4 v - c|) ramp at v = i / 255, rounded half up; "gray": lut[i] = (i, i, i).  Neither is claimed to equal
+    another library's bytes.  ValueError for any other name."""
+    if name == "jet":
+        i = torch.arange(256, dtype=torch.int64).view(256, 1)
+        c = torch.tensor([3, 2, 1], dtype=torch.int64).view(1, 3)
+        return (383 - (4 * i - 255 * c).abs()).clamp(0, 255).to(torch.uint8)
+    if name == "gray":
+        return torch.arange(256, dtype=torch.uint8).view(256, 1).repeat(1, 3)
+    raise ValueError(f"overlay_lut: unknown colour table {name!r} (one of {', '.join(OVERLAY_LUTS)})")
+
+
+def overlay_panels(panels, has_truth: bool) -> Tuple[str, ...]:
+    """The panels of a call in output order: None is all three, without "truth" when there is no truth mask; ValueError
+    for an empty selection, an unknown or repeated name, or "truth" without a truth mask."""
+    if panels is None:
+        return OVERLAY_PANELS if has_truth else OVERLAY_PANELS[:2]
+    panels = (panels,) if isinstance(panels, str) else tuple(panels)
+    if not panels or any(p not in OVERLAY_PANELS for p in panels) or len(set(panels)) != len(panels):
+        raise ValueError(f"overlay: panels must be a non-empty subset of {OVERLAY_PANELS}, got {panels}")
+    if "truth" in panels and not has_truth:
+        raise ValueError("overlay: the truth panel needs a truth mask")
+    return tuple(p for p in OVERLAY_PANELS if p in panels)
+
+
+def _overlay_colour(v, what: str) -> Tuple[int, int, int]:
+    v = tuple(int(c) for c in v)
+    if len(v) != 3 or any(not 0 <= c <= 255 for c in v):
+        raise ValueError(f"overlay_render: {what} must be an RGB triple of bytes, got {v}")
+    return v
+
+
+def overlay_render(frames: torch.Tensor, maps: torch.Tensor, range_record: Optional[torch.Tensor] = None,
+                   pred: Optional[torch.Tensor] = None, truth: Optional[torch.Tensor] = None, alpha: float = 0.5,
+                   lut="jet", thickness: int = 1, panels=None, pred_colour=(255, 255, 255), truth_colour=(0, 255, 0),
+                   mean=CLIP_MEAN, std=CLIP_STD) -> torch.Tensor:
+    """frames fp32 [B, 3, H, W] (the normalised model input), maps fp32 [B, H, W] (raw scores), range_record the record
+    of metrics_range or None, pred / truth uint8 [B, H, W] or None -> uint8 [B, n * H, W, 3]: the n panels of `panels`
+    (a non-empty subset of ("frame", "heat", "truth"), always in that order) stacked vertically; the default is all
+    three, without "truth" when truth is None.  alpha256 = round(alpha * 256) is the frame's weight in a blend; lut a
+    table name (overlay_lut) or a uint8 [256, 3] device tensor; thickness T in 0 .. 8 the reach of the mask contours.
+    One launch on the current stream (aaclip_overlay_render; forward_utils.render_overlays_host is the definition, byte
+    for byte).  ValueError for host tensors, wrong dtypes or shapes, non-contiguous inputs and an unknown table."""
+    what = "overlay_render"
+    for t, name, dtype, dims in ((frames, "frames", torch.float32, 4), (maps, "maps", torch.float32, 3),
+                                 (pred, "pred", torch.uint8, 3), (truth, "truth", torch.uint8, 3)):
+        if t is None and name in ("pred", "truth"):
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{what}: {name} must be a tensor on the GPU (there is no CPU fallback)")
+        if t.dtype != dtype or t.dim() != dims:
+            raise ValueError(f"{what}: {name} must be {dtype} with {dims} dimensions, got {t.dtype} {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if t.device != frames.device:
+            raise ValueError(f"{what}: {name} is on another device than frames")
+    B, ch, H, W = (int(v) for v in frames.shape)
+    if ch != 3 or H < 1 or W < 1:
+        raise ValueError(f"{what}: frames must be [B, 3, H, W] with H, W >= 1, got {tuple(frames.shape)}")
+    for t, name in ((maps, "maps"), (pred, "pred"), (truth, "truth")):
+        if t is not None and tuple(t.shape) != (B, H, W):
+            raise ValueError(f"{what}: {name} must be [{B}, {H}, {W}] like frames, got {tuple(t.shape)}")
+    dev = frames.device
+    if range_record is not None and (not torch.is_tensor(range_record) or not range_record.is_cuda
+                                     or range_record.dtype != torch.int64 or range_record.numel() != 3
+                                     or not range_record.is_contiguous() or range_record.device != dev):
+        raise ValueError(f"{what}: range_record must be the device record of metrics_range (int64 [3]) or None")
+    panels = overlay_panels(panels, truth is not None)
+    bits = sum(1 << OVERLAY_PANELS.index(p) for p in panels)
+    alpha256 = int(round(float(alpha) * 256))
+    if not 0 <= alpha256 <= 256:
+        raise ValueError(f"{what}: alpha must be in 0 .. 1, got {alpha}")
+    thickness = int(thickness)
+    if not 0 <= thickness <= OVERLAY_MAX_THICKNESS:
+        raise ValueError(f"{what}: thickness must be in 0 .. {OVERLAY_MAX_THICKNESS}, got {thickness}")
+    pred_colour, truth_colour = _overlay_colour(pred_colour, "pred_colour"), _overlay_colour(truth_colour, "truth_colour")
+    mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    if len(mean) != 3 or len(std) != 3 or any(not 0.0 < v < float("inf") for v in std):
+        raise ValueError(f"{what}: mean and std must have three entries, std positive and finite")
+    if isinstance(lut, str):
+        table = _OVERLAY_LUTS.get((dev, lut))
+        if table is None:
+            table = _OVERLAY_LUTS[(dev, lut)] = overlay_lut(lut).to(dev)
+    else:
+        table = lut
+        if (not torch.is_tensor(table) or not table.is_cuda or table.dtype != torch.uint8 or tuple(table.shape) != (256, 3)
+                or not table.is_contiguous() or table.device != dev):
+            raise ValueError(f"{what}: lut must be a table name or a contiguous uint8 [256, 3] tensor on the frames' device")
+    plan = OverlayPlan()
+    plan.images, plan.height, plan.width, plan.panels = B, H, W, bits
+    plan.alpha256, plan.thickness = alpha256, thickness
+    for c in range(3):
+        plan.pred_colour[c], plan.truth_colour[c] = pred_colour[c], truth_colour[c]
+        plan.mean[c], plan.std[c] = mean[c], std[c]
+    plan.stream = _stream(dev)
+    out = torch.empty((B, len(panels) * H, W, 3), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().aaclip_overlay_render(C.byref(plan), frames.data_ptr(), maps.data_ptr(), _ptr(range_record),
+                                                 _ptr(pred), _ptr(truth), table.data_ptr(), out.data_ptr()), what)
+    return out
 
 
 # ------------------------------------------------------------------------------- fused optimizer step (csrc/optim.hip)

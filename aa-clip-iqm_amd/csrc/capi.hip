@@ -8,6 +8,7 @@
 
 #include "bf16x3.h"
 #include "kernels.h"
+#include "overlay_plan.h"
 #include "tile_plan.h"
 
 using namespace aaclip;
@@ -1934,6 +1935,38 @@ int aaclip_tile_stitch(const aaclip_tile_plan* plan, const float* tiles, float* 
   if (!launch) return 0;
   launch_tile_stitch(g, plan->images, tiles, canvas, (hipStream_t)plan->stream);
   return finish("aaclip_tile_stitch");
+}
+
+// ---- heat-map overlays (overlay.hip; the plan checks, offsets and pixel functions: overlay_plan.h)
+int aaclip_overlay_render(const aaclip_overlay_plan* plan, const float* frames, const float* maps, const void* range_record,
+                          const uint8_t* pred, const uint8_t* truth, const uint8_t* lut, uint8_t* out) {
+  const char* entry = "aaclip_overlay_render";
+  if (!plan) return fail(-1, in(entry, "null plan"));
+  if (plan->struct_bytes != sizeof(aaclip_overlay_plan))
+    return fail(-1, in(entry, "aaclip_overlay_plan.struct_bytes does not match this library (binding generated from "
+                              "another header?)"));
+  if (const char* m = overlay_plan_check(plan->images, plan->height, plan->width, plan->panels, plan->alpha256,
+                                         plan->thickness, plan->std))
+    return fail(-1, in(entry, m));
+  if (!frames || !maps || !lut || !out) return fail(-1, in(entry, "null pointer (frames, maps, lut and out are required)"));
+  if ((plan->panels & OVERLAY_TRUTH) && !truth) return fail(-1, in(entry, "the truth panel needs a truth mask"));
+  if (((uintptr_t)frames | (uintptr_t)maps) & 3) return fail(-1, in(entry, "frames and maps must be 4-byte aligned"));
+  if (range_record && ((uintptr_t)range_record & 7)) return fail(-1, in(entry, "the range record must be 8-byte aligned"));
+  const size_t pixels = (size_t)plan->images * (size_t)plan->height * (size_t)plan->width;
+  const size_t out_bytes = pixels * 3 * (size_t)overlay_panel_count(plan->panels);
+  if (ranges_overlap(out, out_bytes, frames, pixels * 12) || ranges_overlap(out, out_bytes, maps, pixels * 4) ||
+      ranges_overlap(out, out_bytes, lut, 768) || (range_record && ranges_overlap(out, out_bytes, range_record, 24)) ||
+      (pred && ranges_overlap(out, out_bytes, pred, pixels)) || (truth && ranges_overlap(out, out_bytes, truth, pixels)))
+    return fail(-1, in(entry, "out must not overlap an input"));
+  if (plan->images == 0) return 0;
+  OverlayGeom g = overlay_geom(plan->height, plan->width, plan->panels, plan->alpha256, plan->thickness, pred != nullptr,
+                               truth != nullptr);
+  for (int c = 0; c < 3; ++c) {
+    g.pred_colour[c] = plan->pred_colour[c], g.truth_colour[c] = plan->truth_colour[c];
+    g.mean[c] = plan->mean[c], g.sd[c] = plan->std[c];
+  }
+  launch_overlay_render(g, plan->images, frames, maps, range_record, pred, truth, lut, out, (hipStream_t)plan->stream);
+  return finish("aaclip_overlay_render");
 }
 
 int aaclip_text_embed(const int32_t* tokens, const float* table, const float* pos, float* x, int n, int T, int D,

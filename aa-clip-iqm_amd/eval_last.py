@@ -141,7 +141,7 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
                   device, img_size: int, dataset: str, batch_size: int = 32, loader_kwargs=None, logger=None,
                   use_iqm: bool = True, device_metrics: bool = False, fpr_limit=None, f1_max: bool = False,
                   details: Dict[str, dict] = None, return_masks: bool = False, defects=None, support=None,
-                  support_weight: float = SUPPORT_WEIGHT) -> List[dict]:
+                  support_weight: float = SUPPORT_WEIGHT, after_class=None) -> List[dict]:
     """The per-class loop of test_last.evaluate for either metrics path.  device_metrics: the class's masks, maps and
     image scores stay on the GPU, the row comes from metrics_eval_device, and the tensors are released before the next
     class.  Under torch.distributed the shards are gathered as host arrays exactly as in test_last.evaluate (so the
@@ -157,7 +157,10 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
     under torch.distributed every rank builds the same bank itself): get_predictions_support's keyword for every class, weighted
     by support_weight.  With details and return_masks=True, details[class]["support nearest"] is then a list per tap
     level of int32 arrays [N, P, 2]: (shot, patch) = divmod(index of the nearest bank row, P) for every patch of every
-    evaluated image -- which good patch it was compared with.  support=None changes nothing."""
+    evaluated image -- which good patch it was compared with.  support=None changes nothing.
+    after_class: None, or a callable invoked as after_class(class_name, image_dataset, masks, labels, preds, preds_image,
+    file_names, details_of_class) once the class's row is computed and before its tensors are released (the dataset is
+    the one that was evaluated, details_of_class is details[class_name] or None); None changes nothing."""
     import torch.distributed as dist
     if defects is not None and not f1_max:
         raise ValueError("evaluate_rows: defects needs f1_max=True (the regions are those at the pixel F1-max threshold)")
@@ -214,6 +217,8 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
                     details[class_name]["support nearest"] = _support_nearest_pairs(nearest, support[class_name], world)
         rows.append(row_of(masks, labels, preds, preds_image, class_name, domain=DOMAINS[dataset], fpr_limit=fpr_limit,
                            **extra))
+        if after_class is not None:
+            after_class(class_name, image_dataset, masks, labels, preds, preds_image, file_names, extra.get("details"))
         del masks, preds, preds_image          # released before the next class is evaluated
         if logger:
             logger.info("%s", rows[-1])

@@ -129,10 +129,11 @@ def tiled_support_banks(model, image_datasets, k: int, device, img_size: int, ti
 def evaluate_tiled(model, image_datasets, text_embeddings, device, img_size: int, dataset: str, tiles, batch_size: int = 32,
                    loader_kwargs=None, logger=None, use_iqm: bool = True, device_metrics: bool = False, fpr_limit=None,
                    f1_max: bool = False, return_masks: bool = False, defects=None, support=None,
-                   support_weight: float = SUPPORT_WEIGHT):
+                   support_weight: float = SUPPORT_WEIGHT, after_class=None):
     """The per-class loop of eval_last.evaluate_rows over get_predictions_tiled, in one process: -> (rows, details), details
     None without f1_max.  tiles=(G, O); support: None or {class name: bank of tiled_support_banks}; the other keywords are
-    evaluate_rows'.  The maps handed to metrics_eval / metrics_eval_device are C x C."""
+    evaluate_rows', after_class included (its frames, masks and maps are C x C).  The maps handed to metrics_eval /
+    metrics_eval_device are C x C."""
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         raise ValueError("tiled evaluation runs in one process (sharded tiled evaluation is not part of it)")
@@ -161,6 +162,8 @@ def evaluate_tiled(model, image_datasets, text_embeddings, device, img_size: int
                 "image scores": [float(v) for v in scores.reshape(-1)]}
         rows.append(row_of(masks, labels, preds, preds_image, class_name, domain=DOMAINS[dataset], fpr_limit=fpr_limit,
                            **extra))
+        if after_class is not None:
+            after_class(class_name, image_dataset, masks, labels, preds, preds_image, file_names, extra.get("details"))
         del masks, preds, preds_image          # released before the next class is evaluated
         if logger:
             logger.info("%s", rows[-1])
@@ -206,9 +209,10 @@ def evaluate_details(model, image_datasets, text_embeddings, device, img_size: i
                      loader_kwargs=None, logger=None, use_iqm: bool = True, device_metrics: bool = False, aupro_limit=None,
                      f1_max: bool = False, return_masks: bool = False, defects=None, save_path=None, support=None,
                      support_weight: float = SUPPORT_WEIGHT, support_form=None, support_datasets=None, coreset=None,
-                     coreset_dim: int = 128):
-    """The tiled path of evaluate, for tiles=(G, O): the banks where support=K asks for them, evaluate_tiled, and the
-    .jsonl files of eval_defects.write_defects where defects and save_path ask for them.  -> (rows, details)."""
+                     coreset_dim: int = 128, after_class=None):
+    """The tiled path of evaluate, for tiles=(G, O): the banks where support=K asks for them, evaluate_tiled (after_class
+    is its keyword), and the .jsonl files of eval_defects.write_defects where defects and save_path ask for them.
+    -> (rows, details)."""
     S, G, O, C = tile_geometry(img_size, *tiles)
     if coreset is not None and support is None:
         raise ValueError("evaluate: coreset needs support=K")
@@ -229,7 +233,8 @@ def evaluate_details(model, image_datasets, text_embeddings, device, img_size: i
     rows, details = evaluate_tiled(model, image_datasets, text_embeddings, device, S, dataset, (G, O), batch_size=batch_size,
                                    loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm,
                                    device_metrics=device_metrics, fpr_limit=aupro_limit, f1_max=f1_max,
-                                   return_masks=return_masks, defects=defects, support=banks, support_weight=support_weight)
+                                   return_masks=return_masks, defects=defects, support=banks, support_weight=support_weight,
+                                   after_class=after_class)
     if defects is not None and save_path is not None:
         ED.write_defects(save_path, dataset, details)
     return rows, details

@@ -708,3 +708,101 @@ def visualize(*args, **kwargs):
     (reference test_last.py:17-22) resolves; calling it -- `--visualize` -- says so instead of failing on cv2."""
     raise NotImplementedError("forward_utils.visualize: visualisation is outside the MI355X hot-path build; take the "
                               "[N, S, S] maps test_last.get_predictions returns and plot them with your own tooling")
+
+
+# ------------------------------------------------------------------------------------------------
+# heat-map overlays: the definition in numpy (engine.overlay_render / csrc/overlay.hip give the same bytes)
+def _overlay_range(range_record):
+    """None, the record of engine.metrics_range (int64 [3], any device, or its numpy copy) or the dict of
+    engine.metrics_range_host -> None or (min, max) as np.float32"""
+    import numpy as np
+    if range_record is None:
+        return None
+    if isinstance(range_record, dict):
+        return np.float32(range_record["min"]), np.float32(range_record["max"])
+    r = np.ascontiguousarray(range_record.detach().cpu().numpy() if torch.is_tensor(range_record) else range_record)
+    if r.dtype != np.int64 or r.size != 3:
+        raise ValueError("overlays: range_record must be the int64 [3] record of engine.metrics_range")
+    mn, mx = r.reshape(-1)[:1].view(np.float32)
+    return mn, mx
+
+
+def overlay_contour_host(mask, thickness: int):
+    """bool [..., H, W]: mask != 0 where some pixel inside the image with |dy| <= T and |dx| <= T has mask == 0"""
+    import numpy as np
+    m = np.asarray(mask) != 0
+    T = int(thickness)
+    H, W = m.shape[-2:]
+    near_zero = np.zeros_like(m)
+    for dy in range(-T, T + 1):
+        for dx in range(-T, T + 1):
+            if abs(dy) >= H or abs(dx) >= W:          # the whole shifted copy lies outside the image
+                continue
+            ys, yd = slice(max(dy, 0), H + min(dy, 0)), slice(max(-dy, 0), H + min(-dy, 0))
+            xs, xd = slice(max(dx, 0), W + min(dx, 0)), slice(max(-dx, 0), W + min(-dx, 0))
+            near_zero[..., yd, xd] |= ~m[..., ys, xs]
+    return m & near_zero if T > 0 else np.zeros_like(m)
+
+
+def render_overlays_host(frames, maps, range_record=None, pred=None, truth=None, lut="jet", alpha256: int = 128,
+                         thickness: int = 1, pred_colour=(255, 255, 255), truth_colour=(0, 255, 0),
+                         mean=engine.CLIP_MEAN, std=engine.CLIP_STD, panels=None):
+    """The definition of the overlay panels, in numpy: -> uint8 [B, n * H, W, 3], the n panels of `panels` (a non-empty
+    subset of ("frame", "heat", "truth"), always in that order; None: all, without "truth" when truth is None) stacked
+    vertically.  frames fp32 [B, 3, H, W], the normalised model input; maps fp32 [B, H, W]; range_record what
+    engine.metrics_range gives, or None; pred / truth [B, H, W], non-zero = set, or None; lut a name of
+    engine.overlay_lut or uint8 [256, 3].  Per pixel
+      F[c]  = clamp(rint(((x[c] * std[c]) + mean[c]) * 255), 0, 255), every operation rounded to fp32, NaN -> 0;
+      q     = trunc(min(max(n, 0), 1) * 255), the product rounded toward zero, NaN -> 0, n = engine.metrics_normalise's
+              value with the record (x itself without one) -- every map is quantised, a class maximum of 1 included;
+      blend(u, v) = (alpha256 * u + (256 - alpha256) * v + 128) >> 8;
+      frame = F; heat = blend(F, lut[q]) with pred_colour on contour(pred); truth = blend(F, truth_colour) where
+      truth != 0, else F, then truth_colour on contour(truth), then pred_colour on contour(pred)
+    with contour = overlay_contour_host(mask, thickness).  Arguments may be tensors (of any device) or arrays."""
+    import numpy as np
+    host = lambda t: None if t is None else np.asarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t)
+    x, m, pred, truth = host(frames), host(maps), host(pred), host(truth)
+    if x.dtype != np.float32 or x.ndim != 4 or x.shape[1] != 3 or m.dtype != np.float32 or m.shape != x.shape[:1] + x.shape[2:]:
+        raise ValueError(f"overlays: fp32 frames [B, 3, H, W] and fp32 maps [B, H, W], got {x.shape} and {m.shape}")
+    for mask in (pred, truth):
+        if mask is not None and mask.shape != m.shape:
+            raise ValueError(f"overlays: a mask of {mask.shape} for maps of {m.shape}")
+    panels = engine.overlay_panels(panels, truth is not None)
+    a, T = int(alpha256), int(thickness)
+    if not 0 <= a <= 256 or not 0 <= T <= engine.OVERLAY_MAX_THICKNESS:
+        raise ValueError(f"overlays: alpha256 in 0 .. 256 and thickness in 0 .. 8, got {alpha256} and {thickness}")
+    table = host(engine.overlay_lut(lut) if isinstance(lut, str) else lut)
+    if table.dtype != np.uint8 or table.shape != (256, 3):
+        raise ValueError("overlays: lut must be uint8 [256, 3]")
+    blend = lambda u, v: (a * u.astype(np.int64) + (256 - a) * np.asarray(v, np.int64) + 128) >> 8
+    with np.errstate(all="ignore"):
+        sd, mu = np.asarray(std, np.float32).reshape(1, 3, 1, 1), np.asarray(mean, np.float32).reshape(1, 3, 1, 1)
+        v = np.rint(((x * sd) + mu) * np.float32(255))
+        F = np.where(np.isnan(v), np.float32(0), np.clip(v, 0, 255)).astype(np.int64).transpose(0, 2, 3, 1)     # [B, H, W, 3]
+        rng = _overlay_range(range_record)
+        n = m if rng is None or rng[1] == np.float32(1) else (m - rng[0]) / (rng[1] - rng[0])
+        q = np.where(np.isnan(n), 0.0, np.floor(np.clip(n, 0, 1).astype(np.float64) * 255.0)).astype(np.int64)
+    pc, tc = np.asarray(pred_colour, np.int64), np.asarray(truth_colour, np.int64)
+    out = []
+    for name in panels:
+        if name == "frame":
+            img = F.copy()
+        elif name == "heat":
+            img = blend(F, table[q])
+        else:
+            img = np.where((truth != 0)[..., None], blend(F, tc), F)
+            img[overlay_contour_host(truth, T)] = tc
+        if name != "frame" and pred is not None:
+            img[overlay_contour_host(pred, T)] = pc
+        out.append(img.astype(np.uint8))
+    return np.concatenate(out, axis=1)
+
+
+def render_overlays(frames, maps, range_record=None, pred=None, truth=None, lut="jet", alpha256: int = 128,
+                    thickness: int = 1, pred_colour=(255, 255, 255), truth_colour=(0, 255, 0), mean=engine.CLIP_MEAN,
+                    std=engine.CLIP_STD, panels=None):
+    """render_overlays_host's call on the GPU: device tensors in, a uint8 device tensor [B, n * H, W, 3] out, the same
+    bytes (engine.overlay_render, one launch on the current stream)."""
+    return engine.overlay_render(frames, maps, range_record=range_record, pred=pred, truth=truth, alpha=int(alpha256) / 256,
+                                 lut=lut, thickness=thickness, panels=panels, pred_colour=pred_colour,
+                                 truth_colour=truth_colour, mean=mean, std=std)

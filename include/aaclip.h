@@ -713,6 +713,52 @@ int aaclip_tile_canvas(int tile, int grid, int overlap);
 int aaclip_tile_gather(const aaclip_tile_plan* plan, const float* canvas, float* tiles);
 int aaclip_tile_stitch(const aaclip_tile_plan* plan, const float* tiles, float* canvas);
 
+/* Heat-map overlays (csrc/overlay.hip; the plan checks, offsets and pixel functions it shares with a host program are
+ * csrc/overlay_plan.h): the frame the model saw, the heat map over it and the ground truth over it as uint8 RGB panels.
+ * frames fp32 [images, 3, H, W] (the normalised model input), maps fp32 [images, H, W] (raw scores), range_record the
+ * record of aaclip_metrics_range or NULL, pred / truth uint8 [images, H, W] or NULL (non-zero = set), lut uint8
+ * [256, 3], out uint8 [images, n * H, W, 3]: the n panels that `panels` selects (bit 0 frame, bit 1 heat, bit 2 truth),
+ * in that order, stacked vertically.  Per pixel:
+ *   frame byte  F[c] = clamp(rint(((x[c] * std[c]) + mean[c]) * 255), 0, 255): every operation rounded to fp32 on its
+ *               own, rint to even, NaN -> 0.
+ *   heat byte   n = (x - min) / (max - min) in fp32 (aaclip_metrics_normalise's bits) when the record's max != 1, else
+ *               x; x itself without a record.  q = 0 for a NaN n, else the truncation of min(max(n, 0), 1) * 255 with
+ *               the fp32 product rounded toward zero.
+ *   contour(M)  true at (y, x) when M[y, x] != 0 and some pixel INSIDE the image with |dy| <= T and |dx| <= T has
+ *               M == 0, T = thickness; T = 0 draws none.
+ *   blend(u, v) = (alpha256 * u + (256 - alpha256) * v + 128) >> 8 per channel, in integers.
+ *   frame panel F.  heat panel blend(F, lut[q]), pred_colour on contour(pred).  truth panel blend(F, truth_colour) where
+ *   truth != 0, else F; then truth_colour on contour(truth); then pred_colour on contour(pred).  A NULL mask draws
+ *   nothing.
+ * One launch on plan->stream: a gather over output pixels with no workspace, no memset and no atomics, so a second call
+ * gives the same bytes; every offset is 64-bit; out may have any byte alignment (it is written in aligned 16-byte
+ * chunks, the ends of a run in narrower stores).  Every check happens before the launch, and a failed one returns -1,
+ * leaves an error text that starts with the entry's name and writes nothing: a null plan, a struct_bytes other than
+ * sizeof, images < 0, height or width < 1, no panel or an unknown panel bit, the truth panel with a NULL truth,
+ * alpha256 outside 0 .. 256, thickness outside 0 .. 8, a std that is not positive and finite, a NULL frames, maps, lut
+ * or out, frames or maps not 4-byte aligned, a record not 8-byte aligned, more than 2^56 pixels, out overlapping an
+ * input.  images == 0 checks all of that and launches nothing.  This ABI number is unchanged: the entry is an
+ * addition. */
+#define AACLIP_OVERLAY_FRAME 1u
+#define AACLIP_OVERLAY_HEAT 2u
+#define AACLIP_OVERLAY_TRUTH 4u
+typedef struct aaclip_overlay_plan {
+  size_t struct_bytes;      /* sizeof(aaclip_overlay_plan); any other value is refused */
+  int images;
+  int height;
+  int width;
+  unsigned panels;          /* AACLIP_OVERLAY_FRAME | AACLIP_OVERLAY_HEAT | AACLIP_OVERLAY_TRUTH */
+  int alpha256;             /* weight of the frame in a blend, 0 .. 256 */
+  int thickness;            /* T, 0 .. 8 */
+  uint8_t pred_colour[3];   /* RGB */
+  uint8_t truth_colour[3];
+  float mean[3];            /* the normalisation of frames, undone for the frame byte */
+  float std[3];
+  void* stream;             /* hipStream_t */
+} aaclip_overlay_plan;
+int aaclip_overlay_render(const aaclip_overlay_plan* plan, const float* frames, const float* maps, const void* range_record,
+                          const uint8_t* pred, const uint8_t* truth, const uint8_t* lut, uint8_t* out);
+
 /* Fused Adam / AdamW step over a list of tensors, and the gradient norm that clips it (csrc/optim.hip).  fp32
  * parameters, gradients and state only.  One launch serves up to 24 tensors and 640 chunks of 16384 elements; its table
  * travels by value in the kernel arguments, so a call copies nothing to the device, allocates nothing and waits for
