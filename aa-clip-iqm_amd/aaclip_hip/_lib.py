@@ -99,6 +99,17 @@ class OverlayPlan(C.Structure):
 
 OVERLAY_FRAME, OVERLAY_HEAT, OVERLAY_TRUTH = 1, 2, 4
 
+
+class PngPlan(C.Structure):
+    """struct aaclip_png_plan (include/aaclip.h): the sizes of a PNG encoding call and its stream.  struct_bytes is
+    filled in on construction; the library refuses any other size."""
+    _fields_ = [("struct_bytes", _sz), ("images", _i), ("height", _i), ("width", _i), ("channels", _i), ("stream", _vp)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_bytes = C.sizeof(PngPlan)
+
+
 # name -> (restype, argtypes); every symbol include/aaclip.h declares
 SIGNATURES = {
     "aaclip_version": (_i, []),
@@ -187,6 +198,9 @@ SIGNATURES = {
     "aaclip_tile_gather": (_i, [C.POINTER(TilePlan), _vp, _vp]),
     "aaclip_tile_stitch": (_i, [C.POINTER(TilePlan), _vp, _vp]),
     "aaclip_overlay_render": (_i, [C.POINTER(OverlayPlan)] + [_vp] * 7),
+    "aaclip_png_workspace_bytes": (_sz, [C.POINTER(PngPlan)]),
+    "aaclip_png_capacity_bytes": (_sz, [C.POINTER(PngPlan)]),
+    "aaclip_png_encode": (_i, [C.POINTER(PngPlan), _vp, _vp, _sz, _vp, _sz, _vp]),
     "aaclip_row_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp] + [_i] * 6 + [_vp, _sz, _vp]),
     "aaclip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _l, _i, _f, _vp]),
     "aaclip_gemm": (_i, [_i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _f, _vp]),

@@ -2332,6 +2332,65 @@ def overlay_render(frames: torch.Tensor, maps: torch.Tensor, range_record: Optio
     return out
 
 
+# ------------------------------------------------------------------------------- PNG encoding (csrc/png.hip)
+PNG_SEGMENT_BYTES = 32768       # csrc/png_plan.h
+
+
+def png_segments(H: int, W: int, C: int) -> Dict[str, int]:
+    """The geometry of an H x W x C image's filtered stream (csrc/png_plan.h): row_bytes = 1 + W * C, rows_per_segment =
+    max(1, 32768 // row_bytes), segments per image, stream_bytes = H * row_bytes and capacity = 8 + stream_bytes +
+    5 * segments, the largest zlib stream of one image.  ValueError for C outside {1, 3}, negative sizes and a row of
+    more than 32768 bytes."""
+    H, W, C = int(H), int(W), int(C)
+    if C not in (1, 3) or H < 0 or W < 0:
+        raise ValueError(f"png_segments: H and W must not be negative and C must be 1 or 3, got {H} x {W} x {C}")
+    row = 1 + W * C
+    if row > PNG_SEGMENT_BYTES:
+        raise ValueError(f"png_segments: a filtered row of {row} bytes exceeds {PNG_SEGMENT_BYTES}")
+    rps = max(1, PNG_SEGMENT_BYTES // row)
+    segs = -(-H // rps)
+    return {"row_bytes": row, "rows_per_segment": rps, "segments": segs, "stream_bytes": H * row,
+            "capacity": 8 + H * row + 5 * segs}
+
+
+def png_encode(pixels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """pixels uint8 [images, H, W, C] with C in {1, 3}, or [images, H, W] for C = 1, contiguous, on the GPU, at any
+    byte offset of its storage -> (payload uint8 [capacity], offsets int64 [images + 1]), both on the device: image i's
+    zlib stream (the content of its PNG's IDAT chunk) is payload[offsets[i]:offsets[i + 1]]; forward_utils.png_files
+    wraps the streams into files.  Two launches on the current stream (aaclip_png_encode; forward_utils.png_encode_host
+    is the definition, byte for byte).  ValueError for a host tensor, a wrong dtype or shape and a non-contiguous
+    input."""
+    what = "png_encode"
+    if not torch.is_tensor(pixels) or not pixels.is_cuda:
+        raise ValueError(f"{what}: pixels must be a tensor on the GPU (there is no CPU fallback)")
+    if pixels.dtype != torch.uint8 or pixels.dim() not in (3, 4):
+        raise ValueError(f"{what}: pixels must be uint8 [images, H, W, C] or [images, H, W], got {pixels.dtype} "
+                         f"{tuple(pixels.shape)}")
+    if not pixels.is_contiguous():
+        raise ValueError(f"{what}: pixels must be contiguous")
+    images, H, W = (int(v) for v in pixels.shape[:3])
+    ch = int(pixels.shape[3]) if pixels.dim() == 4 else 1
+    if ch not in (1, 3):
+        raise ValueError(f"{what}: pixels must have 1 or 3 channels, got {ch}")
+    dev = pixels.device
+    plan = _lib.PngPlan()
+    plan.images, plan.height, plan.width, plan.channels = images, H, W, ch
+    plan.stream = _stream(dev)
+    lib = _lib.load()
+    offsets = torch.zeros(images + 1, dtype=torch.int64, device=dev)
+    if images == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev), offsets
+    capacity, ws_bytes = lib.aaclip_png_capacity_bytes(C.byref(plan)), lib.aaclip_png_workspace_bytes(C.byref(plan))
+    if capacity == 0:
+        png_segments(H, W, ch)
+        raise ValueError(f"{what}: the library refuses {images} images of {H} x {W} x {ch}")
+    payload = torch.empty(capacity, dtype=torch.uint8, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.aaclip_png_encode(C.byref(plan), pixels.data_ptr(), ws.data_ptr(), ws_bytes, payload.data_ptr(), capacity,
+                                     offsets.data_ptr()), what)
+    return payload, offsets
+
+
 # ------------------------------------------------------------------------------- fused optimizer step (csrc/optim.hip)
 OPTIM_RECORD_FLOATS = 2         # fp32 words of aaclip_optim_record: total_norm, clip_coef
 OPTIM_MAX_GROUPS = _lib.OPTIM_MAX_GROUPS

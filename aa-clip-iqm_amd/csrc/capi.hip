@@ -9,6 +9,7 @@
 #include "bf16x3.h"
 #include "kernels.h"
 #include "overlay_plan.h"
+#include "png_plan.h"
 #include "tile_plan.h"
 
 using namespace aaclip;
@@ -1967,6 +1968,42 @@ int aaclip_overlay_render(const aaclip_overlay_plan* plan, const float* frames, 
   }
   launch_overlay_render(g, plan->images, frames, maps, range_record, pred, truth, lut, out, (hipStream_t)plan->stream);
   return finish("aaclip_overlay_render");
+}
+
+// ---- PNG encoding (png.hip; the format, the geometry and the plan checks: png_plan.h)
+static const char* png_plan_refusal(const aaclip_png_plan* plan) {
+  if (!plan) return "null plan";
+  if (plan->struct_bytes != sizeof(aaclip_png_plan))
+    return "aaclip_png_plan.struct_bytes does not match this library (binding generated from another header?)";
+  return png_plan_check(plan->images, plan->height, plan->width, plan->channels);
+}
+
+size_t aaclip_png_workspace_bytes(const aaclip_png_plan* plan) {
+  if (png_plan_refusal(plan)) return 0;
+  return png_workspace_bytes(png_geom(plan->images, plan->height, plan->width, plan->channels));
+}
+
+size_t aaclip_png_capacity_bytes(const aaclip_png_plan* plan) {
+  if (png_plan_refusal(plan)) return 0;
+  return png_capacity_bytes(png_geom(plan->images, plan->height, plan->width, plan->channels));
+}
+
+int aaclip_png_encode(const aaclip_png_plan* plan, const uint8_t* pixels, void* workspace, size_t ws_bytes, uint8_t* payload,
+                      size_t capacity, int64_t* offsets) {
+  const char* entry = "aaclip_png_encode";
+  if (const char* m = png_plan_refusal(plan)) return fail(-1, in(entry, m));
+  if (plan->images == 0) return 0;
+  if (!pixels || !workspace || !payload || !offsets) return fail(-1, in(entry, "null pointer"));
+  const PngGeom g = png_geom(plan->images, plan->height, plan->width, plan->channels);
+  if (ws_bytes < png_workspace_bytes(g)) return fail(-1, in(entry, "workspace too small (aaclip_png_workspace_bytes)"));
+  if (capacity < png_capacity_bytes(g)) return fail(-1, in(entry, "payload capacity too small (aaclip_png_capacity_bytes)"));
+  if ((uintptr_t)workspace & 15) return fail(-1, in(entry, "the workspace must be 16-byte aligned"));
+  if ((uintptr_t)offsets & 7) return fail(-1, in(entry, "offsets must be 8-byte aligned"));
+  const size_t pixel_bytes = (size_t)g.images * (size_t)g.H * (size_t)g.R, offsets_bytes = ((size_t)g.images + 1) * 8;
+  if (ranges_overlap(payload, capacity, pixels, pixel_bytes) || ranges_overlap(offsets, offsets_bytes, pixels, pixel_bytes))
+    return fail(-1, in(entry, "payload and offsets must not overlap pixels"));
+  launch_png_encode(g, pixels, workspace, payload, offsets, (hipStream_t)plan->stream);
+  return finish("aaclip_png_encode");
 }
 
 int aaclip_text_embed(const int32_t* tokens, const float* table, const float* pos, float* x, int n, int T, int D,

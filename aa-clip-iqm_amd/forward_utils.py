@@ -806,3 +806,285 @@ def render_overlays(frames, maps, range_record=None, pred=None, truth=None, lut=
     return engine.overlay_render(frames, maps, range_record=range_record, pred=pred, truth=truth, alpha=int(alpha256) / 256,
                                  lut=lut, thickness=thickness, panels=panels, pred_colour=pred_colour,
                                  truth_colour=truth_colour, mean=mean, std=std)
+
+
+# ------------------------------------------------------------------------------------------------ PNG encoding
+# The definition of engine.png_encode's bytes (csrc/png.hip, csrc/png_plan.h), in numpy and plain Python, with no zlib in
+# the encoding itself.  pixels uint8 [images, H, W, C], C in {1, 3}, R = W * C:
+#   filters   the filtered stream of an image is H rows of 1 + R bytes: the filter type, then the row under it; PNG's five
+#             types with bpp = C, the row above row 0 all zeros.  A row takes the type with the smallest sum of
+#             min(b, 256 - b) over its R filtered bytes, ties to the lowest type.
+#   segments  rows_per_segment = max(1, 32768 // (1 + R)) whole rows (the last segment may be shorter), each compressed on
+#             its own into one deflate block that ends on a byte; 1 + R > 32768 is refused.
+#   tokens    distance-1 matches only.  A maximal run of n equal bytes inside a segment is a literal; the other n - 1
+#             bytes follow in pieces of 258, and a last piece of 3 or more is a match, one of 1 or 2 is literals.
+#   code      png_code_lengths_host.  The leaves are the symbols with a count, in (count, symbol) order; the two smallest
+#             nodes are merged, taken from the queue of leaves and the queue of merged nodes (in the order they were made),
+#             a leaf before a merged node of the same weight.  The tree gives the NUMBER of codes of every length, a leaf
+#             deeper than the limit counted at the limit; while their Kraft sum exceeds 1, one code of the limit's length
+#             goes and the longest shorter code becomes two codes one bit longer.  The lengths are handed out in leaf
+#             order, the longest to the rarest.  Limit 15 for literals / lengths, 7 for the code-length alphabet; an
+#             alphabet with fewer than two leaves is filled up with its lowest other symbols at count 0.  The distance
+#             alphabet is one code (HDIST = 0): length 1 if the segment has a match, else 0.
+#   lengths   the HLIT literal / length lengths and the distance length, as one sequence: a non-zero length is sent as
+#             itself (symbol 16 is never used); of a zero run of z, while z >= 11 one symbol 18 takes min(z, 138), then one
+#             symbol 17 takes what is left if that is 3 or more, else it is sent as symbols 0.
+#   block     BFINAL = 0, BTYPE = 2, the header, the tokens, end-of-block, three zero bits (an empty stored block),
+#             padding to the byte, 00 00 FF FF.  Where that is not shorter than the stored block (00, LEN, NLEN, the bytes)
+#             the stored block is taken, so a segment never takes more than its length + 5 bytes.
+#   stream    78 01, the segments, 03 00 (an empty final fixed block), the Adler-32 of the filtered stream, big-endian,
+#             combined from the segments' sums s1 = sum b[i], s2 = sum (n - i) b[i] in segment order.
+PNG_SEGMENT_BYTES = engine.PNG_SEGMENT_BYTES
+_PNG_CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
+_PNG_LENGTH_BASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195,
+                    227, 258)
+_PNG_LENGTH_EXTRA = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
+
+
+def png_filter_host(image):
+    """image uint8 [H, W, C] (numpy) -> the filtered stream uint8 [H, 1 + W * C]: the chosen type and the filtered bytes
+    of every row."""
+    import numpy as np
+    image = np.asarray(image)
+    H, W, C = image.shape
+    R = W * C
+    x = image.reshape(H, R).astype(np.int32)
+    a = np.zeros_like(x)
+    a[:, C:] = x[:, :-C] if R > C else 0
+    b = np.zeros_like(x)
+    b[1:] = x[:-1]
+    c = np.zeros_like(x)
+    c[1:, C:] = x[:-1, :-C] if R > C else 0
+    p = a + b - c
+    pa, pb, pc = np.abs(p - a), np.abs(p - b), np.abs(p - c)
+    paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+    forms = np.stack([x, x - a, x - b, x - ((a + b) >> 1), x - paeth]) & 255          # [5, H, R]
+    cost = np.minimum(forms, 256 - forms).sum(axis=2)                                   # [5, H]
+    choice = np.argmin(cost, axis=0)                                                    # the first of equal minima
+    out = np.empty((H, 1 + R), dtype=np.uint8)
+    out[:, 0] = choice
+    out[:, 1:] = forms[choice, np.arange(H)]
+    return out
+
+
+def png_code_lengths_host(counts, limit):
+    """counts -> (the code length of every symbol, the number of leaves that lay deeper than the limit); see `code`"""
+    keys = {s: int(c) for s, c in enumerate(counts) if c}
+    for s in range(len(counts)):
+        if len(keys) >= 2:
+            break
+        keys.setdefault(s, 0)
+    order = sorted(keys, key=lambda s: (keys[s], s))
+    m = len(order)
+    weight = [keys[s] for s in order] + [0] * (m - 1)
+    parent = [0] * (2 * m - 1)
+    leaf, node = 0, m
+    for nxt in range(m, 2 * m - 1):
+        total = 0
+        for _ in range(2):
+            if leaf < m and (node >= nxt or weight[leaf] <= weight[node]):
+                k, leaf = leaf, leaf + 1
+            else:
+                k, node = node, node + 1
+            total += weight[k]
+            parent[k] = nxt
+        weight[nxt] = total
+    depth = [0] * (2 * m - 1)
+    for k in range(2 * m - 3, -1, -1):
+        depth[k] = depth[parent[k]] + 1
+    num = [0] * (limit + 1)
+    for d in depth[:m]:
+        num[min(d, limit)] += 1
+    total = sum(num[n] << (limit - n) for n in range(1, limit + 1))
+    while total > 1 << limit:
+        num[limit] -= 1
+        for n in range(limit - 1, 0, -1):
+            if num[n]:
+                num[n] -= 1
+                num[n + 1] += 2
+                break
+        total -= 1
+    lengths, k = [0] * len(counts), 0
+    for n in range(limit, 0, -1):
+        for _ in range(num[n]):
+            lengths[order[k]] = n
+            k += 1
+    return lengths, sum(d > limit for d in depth[:m])
+
+
+def _png_canonical(lengths):
+    """the canonical code of every symbol, bit-reversed: deflate sends a Huffman code from its most significant bit"""
+    count = [0] * 16
+    for n in lengths:
+        count[n] += 1
+    count[0] = 0
+    nxt, code = [0] * 16, 0
+    for n in range(1, 16):
+        code = (code + count[n - 1]) << 1
+        nxt[n] = code
+    out = []
+    for n in lengths:
+        if n == 0:
+            out.append(0)
+            continue
+        out.append(int(format(nxt[n], f"0{n}b")[::-1], 2))
+        nxt[n] += 1
+    return out
+
+
+def _png_length_tokens(seq):
+    """how a sequence of code lengths is sent: (symbol, extra bits, extra value) per code-length token"""
+    out, i, n = [], 0, len(seq)
+    while i < n:
+        if seq[i]:
+            out.append((seq[i], 0, 0))
+            i += 1
+            continue
+        z = 1
+        while i + z < n and seq[i + z] == 0:
+            z += 1
+        i += z
+        while z >= 11:
+            take = min(z, 138)
+            out.append((18, 7, take - 11))
+            z -= take
+        if z >= 3:
+            out.append((17, 3, z - 3))
+        else:
+            out.extend([(0, 0, 0)] * z)
+    return out
+
+
+def png_tokens_host(segment):
+    """segment uint8 [n] (numpy) -> (position, kind, length) arrays of its tokens in order: kind 1 a literal of the byte
+    at `position`, kind 2 a distance-1 match of `length` that starts there"""
+    import numpy as np
+    n = segment.size
+    starts = np.flatnonzero(np.concatenate(([True], segment[1:] != segment[:-1])))
+    runs = np.diff(np.concatenate((starts, [n])))
+    p = np.arange(n) - np.repeat(starts, runs)                     # the position in the run
+    m, q = np.repeat(runs, runs) - 1, p - 1
+    piece = np.where(q // 258 < m // 258, 258, m % 258)
+    literal = (p == 0) | (piece < 3)
+    match = ~literal & (q % 258 == 0)
+    where = np.flatnonzero(literal | match)
+    return where, np.where(literal[where], 1, 2), np.where(literal[where], 0, piece[where])
+
+
+def _png_pack(values, widths):
+    """bits, least significant first: value i takes widths[i] <= 32 bits -> (uint8 bytes, zero-padded; the bit count)"""
+    import numpy as np
+    values, widths = np.asarray(values, dtype=np.uint64), np.asarray(widths, dtype=np.int64)
+    top = int(widths.max()) if widths.size else 0
+    lanes = np.arange(top, dtype=np.uint64)
+    bits = ((values[:, None] >> lanes[None, :]) & np.uint64(1)).astype(np.uint8)
+    keep = np.arange(top)[None, :] < widths[:, None]
+    return np.packbits(bits[keep], bitorder="little"), int(widths.sum())
+
+
+def png_segment_host(segment, info=None):
+    """One segment of a filtered stream (uint8 [n], numpy) -> its deflate block as uint8 bytes.  info, a dict, collects
+    "stored", "huffman" (segment counts), "limited" and "cl_limited" (leaves that the limit moved up)."""
+    import numpy as np
+    n = segment.size
+    where, kind, length = png_tokens_host(segment)
+    base, extra = np.asarray(_PNG_LENGTH_BASE), np.asarray(_PNG_LENGTH_EXTRA)
+    slot = np.searchsorted(base, np.where(kind == 2, length, 3), side="right") - 1
+    symbol = np.where(kind == 1, segment[where].astype(np.int64), 257 + slot)
+    counts = np.bincount(symbol, minlength=286)
+    counts[256] += 1
+    has_match = int((kind == 2).any())
+    lengths, limited = png_code_lengths_host(counts, 15)
+    codes = _png_canonical(lengths)
+    hlit = 286
+    while hlit > 257 and lengths[hlit - 1] == 0:
+        hlit -= 1
+    cl_tokens = _png_length_tokens(lengths[:hlit] + [has_match])
+    cl_counts = [0] * 19
+    for s, _, _ in cl_tokens:
+        cl_counts[s] += 1
+    cl_lengths, cl_limited = png_code_lengths_host(cl_counts, 7)
+    cl_codes = _png_canonical(cl_lengths)
+    hclen = 19
+    while hclen > 4 and cl_lengths[_PNG_CL_ORDER[hclen - 1]] == 0:
+        hclen -= 1
+    head = [(0, 1), (2, 2), (hlit - 257, 5), (0, 5), (hclen - 4, 4)] + [(cl_lengths[s], 3) for s in _PNG_CL_ORDER[:hclen]]
+    for s, eb, e in cl_tokens:
+        head += [(cl_codes[s], cl_lengths[s]), (e, eb)]
+    lengths_a, codes_a = np.asarray(lengths, dtype=np.int64), np.asarray(codes, dtype=np.int64)
+    eb = np.where(kind == 2, extra[slot], 0)
+    ev = np.where(kind == 2, length - base[slot], 0)
+    value = codes_a[symbol] | (ev << lengths_a[symbol])             # a match ends in its distance code, one zero bit
+    width = lengths_a[symbol] + eb + (kind == 2)
+    values = np.concatenate(([v for v, _ in head], value, [codes[256], 0]))
+    widths = np.concatenate(([w for _, w in head], width, [lengths[256], 3]))
+    body, _ = _png_pack(values, widths)
+    block = np.concatenate((body, np.array([0, 0, 255, 255], dtype=np.uint8)))
+    stored = block.size >= n + 5
+    if stored:
+        block = np.concatenate((np.array([0, n & 255, n >> 8, ~n & 255, (~n >> 8) & 255], dtype=np.uint8), segment))
+    if info is not None:
+        info["stored" if stored else "huffman"] = info.get("stored" if stored else "huffman", 0) + 1
+        info["limited"] = info.get("limited", 0) + limited
+        info["cl_limited"] = info.get("cl_limited", 0) + cl_limited
+    return block
+
+
+def png_encode_host(pixels, info=None):
+    """pixels uint8 [images, H, W, C] or [images, H, W] (numpy or a host tensor) -> (payload uint8 numpy, offsets: a list
+    of images + 1 ints): image i's zlib stream is payload[offsets[i]:offsets[i + 1]].  The definition of
+    engine.png_encode's bytes; ValueError for C outside {1, 3} and a filtered row of more than 32768 bytes."""
+    import numpy as np
+    pixels = pixels.numpy() if torch.is_tensor(pixels) else np.asarray(pixels)
+    if pixels.ndim == 3:
+        pixels = pixels[..., None]
+    if pixels.dtype != np.uint8 or pixels.ndim != 4:
+        raise ValueError(f"png_encode_host: pixels must be uint8 [images, H, W, C], got {pixels.dtype} {pixels.shape}")
+    images, H, W, C = pixels.shape
+    geom = engine.png_segments(H, W, C)
+    step = geom["rows_per_segment"]
+    parts, offsets = [], [0]
+    for i in range(images):
+        rows = png_filter_host(pixels[i])
+        stream = [np.array([0x78, 0x01], dtype=np.uint8)]
+        a, b = 1, 0
+        for y in range(0, H, step):
+            segment = rows[y:y + step].reshape(-1)
+            stream.append(png_segment_host(segment, info))
+            n = segment.size
+            s1 = int(segment.sum(dtype=np.int64))
+            s2 = int((segment.astype(np.int64) * np.arange(n, 0, -1)).sum())
+            b = (b + n * a + s2) % 65521
+            a = (a + s1) % 65521
+        stream.append(np.array([0x03, 0x00, b >> 8, b & 255, a >> 8, a & 255], dtype=np.uint8))
+        data = np.concatenate(stream)
+        parts.append(data)
+        offsets.append(offsets[-1] + data.size)
+    return (np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)), offsets
+
+
+def png_file(stream, H, W, C) -> bytes:
+    """One image's zlib stream (bytes or a uint8 numpy array) -> its PNG file: the signature, IHDR (8 bit, colour type 2
+    for C = 3 and 0 for C = 1, no interlace), one IDAT and IEND, each chunk with its CRC-32 (zlib.crc32 on the host: the
+    compressed bytes pass through it on their way to disk anyway)."""
+    import struct
+    import zlib
+    if C not in (1, 3):
+        raise ValueError(f"png_file: C must be 1 or 3, got {C}")
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(data, zlib.crc32(tag)))
+
+    ihdr = struct.pack(">IIBBBBB", W, H, 8, 2 if C == 3 else 0, 0, 0, 0)
+    stream = stream if isinstance(stream, bytes) else bytes(memoryview(stream))
+    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", stream) + chunk(b"IEND", b"")
+
+
+def png_files(payload, offsets, H, W, C):
+    """The zlib streams of engine.png_encode / png_encode_host -> one PNG file (bytes) per image (png_file).  payload:
+    bytes, a numpy array or a host tensor; offsets: images + 1 integers (a list, an array or a host tensor)."""
+    if torch.is_tensor(payload):
+        payload = payload.numpy()
+    view = memoryview(payload).cast("B") if not isinstance(payload, (bytes, bytearray)) else memoryview(payload)
+    offsets = [int(o) for o in (offsets.tolist() if hasattr(offsets, "tolist") else offsets)]
+    return [png_file(bytes(view[lo:hi]), H, W, C) for lo, hi in zip(offsets[:-1], offsets[1:])]

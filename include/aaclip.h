@@ -759,6 +759,54 @@ typedef struct aaclip_overlay_plan {
 int aaclip_overlay_render(const aaclip_overlay_plan* plan, const float* frames, const float* maps, const void* range_record,
                           const uint8_t* pred, const uint8_t* truth, const uint8_t* lut, uint8_t* out);
 
+/* PNG encoding on the device (csrc/png.hip; the format, the code builder and the checks it shares with a host program
+ * are csrc/png_plan.h).  pixels uint8 [images, height, width, channels], channels 1 (grey) or 3 (RGB), contiguous, at
+ * any byte alignment -- aaclip_overlay_render's output is such a tensor.  The result is one zlib stream per image, the
+ * content of a PNG's IDAT chunk: image i's stream is payload[offsets[i] .. offsets[i + 1]), offsets int64
+ * [images + 1], offsets[0] = 0.  The caller wraps it in the signature, IHDR (8 bit, colour type 2 or 0, no interlace),
+ * IDAT and IEND with their CRC-32.  With R = width * channels:
+ *   filters   the filtered stream of an image is `height` rows of 1 + R bytes: the filter type and the row's bytes under
+ *             it, PNG's five types with bpp = channels, the row above row 0 all zeros.  A row takes the type with the
+ *             smallest sum of min(b, 256 - b) over its R filtered bytes, ties to the lowest type.
+ *   segments  max(1, 32768 / (1 + R)) whole rows of that stream (the last segment may be shorter), compressed on their
+ *             own into one deflate block each that ends on a byte.
+ *   tokens    distance-1 matches only.  A maximal run of n equal bytes inside a segment is a literal; the other n - 1
+ *             bytes follow in pieces of 258, and a last piece of 3 or more is a match, one of 1 or 2 literals.
+ *   code      leaves in (count, symbol) order, merged from two queues, a leaf before an internal node of the same
+ *             weight.  The tree gives the number of codes of every length, a leaf deeper than the limit (15; 7 for the
+ *             code-length alphabet) counted at the limit; while their Kraft sum exceeds 1, one code of the limit's
+ *             length goes and the longest shorter code becomes two codes one bit longer; the lengths are handed out
+ *             in leaf order, the longest to the rarest.  The distance alphabet is one code (HDIST = 0) of length 1 where
+ *             the segment has a match, else 0.  The lengths are sent as one sequence (literal / length, then distance):
+ *             a non-zero length as itself, of a zero run of z one symbol 18 of min(z, 138) while z >= 11, then one
+ *             symbol 17 if 3 or more are left, else symbols 0.  Symbol 16 is never used.
+ *   block     BFINAL = 0, BTYPE = 2, the header, the tokens, end-of-block, three zero bits (an empty stored block),
+ *             padding to the byte and 00 00 FF FF; or, where that is not shorter, the stored block 00 LEN NLEN and the
+ *             bytes.  A segment never takes more than its length + 5 bytes.
+ *   stream    78 01, the segments, 03 00 (an empty final fixed block), the Adler-32 of the filtered stream, big-endian,
+ *             combined from per-segment integer sums in segment order.
+ * Two launches on plan->stream, no global atomics, integers only: a second call gives the same bytes, and nothing past
+ * offsets[images] is written.  aaclip_png_capacity_bytes = images * (8 + height * (1 + R) + 5 * segments) is the
+ * largest payload; aaclip_png_workspace_bytes the workspace (a slot and a record per segment).  Both return 0 for a
+ * plan that is refused.  Every check happens before the first launch, and a failed one returns -1, leaves an error
+ * text that starts with the entry's name and writes nothing: a null plan, a struct_bytes other than sizeof, a negative
+ * size, height or width 0 with images > 0, channels other than 1 or 3, 1 + R above 32768, sizes whose products
+ * overflow ("too large"), a null pointer, a workspace or a capacity that is too small, a workspace not 16-byte or
+ * offsets not 8-byte aligned, payload or offsets overlapping pixels.  images == 0 checks the plan, launches nothing
+ * and returns 0.  This ABI number is unchanged: the entries are additions. */
+typedef struct aaclip_png_plan {
+  size_t struct_bytes;      /* sizeof(aaclip_png_plan); any other value is refused */
+  int images;
+  int height;
+  int width;
+  int channels;             /* 1 or 3 */
+  void* stream;             /* hipStream_t */
+} aaclip_png_plan;
+size_t aaclip_png_workspace_bytes(const aaclip_png_plan* plan);
+size_t aaclip_png_capacity_bytes(const aaclip_png_plan* plan);
+int aaclip_png_encode(const aaclip_png_plan* plan, const uint8_t* pixels, void* workspace, size_t ws_bytes,
+                      uint8_t* payload, size_t capacity, int64_t* offsets);
+
 /* Fused Adam / AdamW step over a list of tensors, and the gradient norm that clips it (csrc/optim.hip).  fp32
  * parameters, gradients and state only.  One launch serves up to 24 tensors and 640 chunks of 16384 elements; its table
  * travels by value in the kernel arguments, so a call copies nothing to the device, allocates nothing and waits for
