@@ -110,6 +110,16 @@ class PngPlan(C.Structure):
         self.struct_bytes = C.sizeof(PngPlan)
 
 
+class BootstrapPlan(C.Structure):
+    """struct aaclip_bootstrap_plan (include/aaclip.h): the sizes of a bootstrap call and its stream.  struct_bytes is
+    filled in on construction; the library refuses any other size."""
+    _fields_ = [("struct_bytes", _sz), ("n", _l), ("images", _l), ("replicates", _l), ("stream", _vp)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_bytes = C.sizeof(BootstrapPlan)
+
+
 # name -> (restype, argtypes); every symbol include/aaclip.h declares
 SIGNATURES = {
     "aaclip_version": (_i, []),
@@ -201,6 +211,9 @@ SIGNATURES = {
     "aaclip_png_workspace_bytes": (_sz, [C.POINTER(PngPlan)]),
     "aaclip_png_capacity_bytes": (_sz, [C.POINTER(PngPlan)]),
     "aaclip_png_encode": (_i, [C.POINTER(PngPlan), _vp, _vp, _sz, _vp, _sz, _vp]),
+    "aaclip_bootstrap_max_images": (_l, []),
+    "aaclip_bootstrap_workspace_bytes": (_sz, [_l, _l, _l]),
+    "aaclip_bootstrap_curves": (_i, [C.POINTER(BootstrapPlan), _vp, _vp, _vp, _vp, _vp, _sz]),
     "aaclip_row_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp] + [_i] * 6 + [_vp, _sz, _vp]),
     "aaclip_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _l, _i, _f, _vp]),
     "aaclip_gemm": (_i, [_i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _f, _vp]),

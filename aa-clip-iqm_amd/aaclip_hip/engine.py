@@ -1231,6 +1231,115 @@ def curve_metrics(scores: torch.Tensor, labels: torch.Tensor, per_image: int = 0
 
 
 # ------------------------------------------------------------------------------------------------
+# bootstrap of AUROC / AP over the images of one class (csrc/bootstrap.hip; forward_utils.bootstrap_eval_device)
+BOOTSTRAP_RECORD_WORDS = 4      # int64 words per replicate: num, P, N, ap (fp64 bits)
+BootstrapCurves = collections.namedtuple("BootstrapCurves", "num P N ap valid auroc")
+
+
+def bootstrap_max_images() -> int:
+    """The largest number of images of one bootstrap_curves call (the weight table of a replicate block lives in LDS)."""
+    return int(_lib.load().aaclip_bootstrap_max_images())
+
+
+def bootstrap_counts_tensor(counts, dev: torch.device) -> torch.Tensor:
+    """counts [R, images] (a host array or a tensor anywhere) -> a contiguous uint8 device tensor; ValueError for a
+    negative count or one above 255."""
+    c = torch.as_tensor(counts)
+    if c.dim() != 2 or c.shape[0] < 1 or c.shape[1] < 1 or c.dtype.is_floating_point or c.dtype == torch.bool:
+        raise ValueError("bootstrap counts must be an integer array [R, images]")
+    if c.dtype != torch.uint8:
+        if int(c.min()) < 0 or int(c.max()) > 255:
+            raise ValueError("bootstrap counts must lie in 0 .. 255 (they are stored as uint8)")
+        c = c.to(torch.uint8)
+    return c.to(dev).contiguous()
+
+
+def bootstrap_curves(keys: torch.Tensor, payload_sorted: torch.Tensor, counts, packed: bool = False) -> torch.Tensor:
+    """The weighted curve sums of every replicate: keys int32 [n] ascending and payload_sorted int32 [n] = image << 1 |
+    label in their order (metrics_sort_pairs of the values image << 1 | label), counts [R, images] in 0 .. 255.
+    -> records int64 [R, BOOTSTRAP_RECORD_WORDS] on the device: num, P, N, ap (fp64 bits); an invalid replicate (P == 0 or
+    N == 0) has num = 0 and ap = 0.  ValueError before any launch for more images than bootstrap_max_images(), for a
+    payload that names an image outside the counts, and for a replicate whose weighted size reaches 2^31.
+    packed: must be False -- the pair sort's keys are unpacked, the label rides in the payload."""
+    require_gpu(keys, "bootstrap_curves")
+    require_gpu(payload_sorted, "bootstrap_curves")
+    if packed:
+        raise ValueError("bootstrap_curves takes the unpacked keys of metrics_sort_pairs")
+    n, dev = keys.numel(), keys.device
+    if keys.dtype != torch.int32 or keys.dim() != 1 or not keys.is_contiguous() or not 1 <= n <= METRICS_MAX_N:
+        raise ValueError("bootstrap_curves expects the int32 [n] keys of metrics_sort_pairs")
+    if (payload_sorted.dtype != torch.int32 or payload_sorted.shape != keys.shape or not payload_sorted.is_contiguous()
+            or payload_sorted.device != dev):
+        raise ValueError("bootstrap_curves expects the int32 [n] sorted payload of metrics_sort_pairs")
+    counts = bootstrap_counts_tensor(counts, dev)
+    R, images = (int(v) for v in counts.shape)
+    lib = _lib.load()
+    if images > lib.aaclip_bootstrap_max_images():
+        raise ValueError(f"bootstrap_curves: {images} images, this build supports {lib.aaclip_bootstrap_max_images()} "
+                         "per call")
+    image = payload_sorted >> 1
+    if int(image.min()) < 0 or int(image.max()) >= images:
+        raise ValueError(f"bootstrap_curves: the payload names an image outside 0 .. {images - 1}")
+    elements = torch.bincount(image, minlength=images)
+    heaviest = int((counts.to(torch.int64) * elements[None, :]).sum(dim=1).max())
+    if heaviest >= 2 ** 31:
+        raise ValueError(f"bootstrap_curves: a replicate weighs {heaviest} elements; the sums need less than 2^31")
+    records = torch.empty(R, BOOTSTRAP_RECORD_WORDS, dtype=torch.int64, device=dev)
+    ws = Workspace.get(dev, lib.aaclip_bootstrap_workspace_bytes(n, images, R))
+    plan = _lib.BootstrapPlan(n=n, images=images, replicates=R, stream=_stream(dev))
+    _lib.check(lib.aaclip_bootstrap_curves(C.byref(plan), keys.data_ptr(), payload_sorted.data_ptr(), counts.data_ptr(),
+                                           records.data_ptr(), ws.data_ptr(), ws.numel()), "bootstrap_curves")
+    return records
+
+
+def bootstrap_records_host(records: torch.Tensor) -> BootstrapCurves:
+    """The records of bootstrap_curves on the host (one synchronising copy): numpy arrays over the replicates; auroc =
+    num / (2 P N) in fp64, 0 where the replicate is invalid."""
+    h = records.cpu()
+    num, P, N = (h[:, k].numpy().copy() for k in range(3))
+    ap = h[:, 3].contiguous().view(torch.float64).numpy().copy()
+    valid = (P > 0) & (N > 0)
+    auroc = num.astype("float64") / (2.0 * P * N).clip(min=1.0)
+    auroc[~valid] = 0.0
+    return BootstrapCurves(num, P, N, ap, valid, auroc)
+
+
+def bootstrap_metrics(scores: torch.Tensor, labels: torch.Tensor, per_image: int, counts,
+                      normalise: bool = True) -> BootstrapCurves:
+    """AUROC / AP of every bootstrap replicate over images: scores fp32 and labels uint8 of images * per_image elements,
+    image i owning the elements [i * per_image, (i + 1) * per_image); counts [R, images].  The scores are those
+    curve_metrics sorts (min-max normalised over the whole class when normalise: the range is NOT recomputed per
+    replicate), sorted ONCE with the payload image << 1 | label; bootstrap_curves does the rest.  per_image = 1 serves
+    the image scores.  -> BootstrapCurves(num, P, N, ap, valid, auroc) of numpy arrays [R].
+    Raises ValueError where curve_metrics does (non-finite scores, max == min under normalise, one class only)."""
+    scores, labels = _metrics_inputs(scores, labels, "bootstrap_metrics")
+    if labels is None:
+        raise ValueError("bootstrap_metrics needs labels")
+    n, dev = scores.numel(), scores.device
+    if per_image < 1 or n % per_image:
+        raise ValueError(f"bootstrap_metrics: {n} scores are no multiple of per_image = {per_image}")
+    images = n // per_image
+    counts = bootstrap_counts_tensor(counts, dev)
+    if counts.shape[1] != images:
+        raise ValueError(f"bootstrap_metrics: counts of {counts.shape[1]} images for {images} images")
+    if images > bootstrap_max_images():
+        raise ValueError(f"bootstrap_metrics: {images} images, this build supports {bootstrap_max_images()} per call")
+    rng, _ = metrics_range(scores, labels)
+    r = metrics_range_host(rng)
+    if r["nonfinite"]:
+        raise ValueError(f"bootstrap_metrics: {r['nonfinite']} of {n} scores are not finite")
+    if normalise and r["max"] == r["min"]:
+        raise ValueError("bootstrap_metrics: all scores are equal (max == min): the min-max normalisation divides by zero")
+    if r["positives"] == 0 or r["positives"] == n:
+        raise ValueError("bootstrap_metrics: only one class present in the labels; AUROC and AP are not defined")
+    norm = metrics_normalise(scores, rng) if normalise else scores
+    payload = (torch.arange(n, dtype=torch.int32, device=dev).div_(per_image, rounding_mode="floor") << 1) | (labels != 0)
+    keys, payload_sorted = metrics_sort_pairs(norm, payload.to(torch.int32))
+    del norm, payload
+    return bootstrap_records_host(bootstrap_curves(keys, payload_sorted, counts))
+
+
+# ------------------------------------------------------------------------------------------------
 # exact F1-max and its operating point (csrc/metrics.hip; forward_utils.f1max_eval_device), masks at a threshold
 F1MAX_RECORD_WORDS = 7          # int64 words: tp, fp, P, N, groups, start index, key (low half) | fp32 threshold bits (high)
 THRESHOLD_RECORD_WORDS = 4      # int64 words: tp, fp, fn, tn

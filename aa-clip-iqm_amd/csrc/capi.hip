@@ -1516,6 +1516,39 @@ int aaclip_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, lon
   return finish("metrics_curve");
 }
 
+// ---- bootstrap of AUROC / AP over images (bootstrap.hip)
+static inline bool bootstrap_shape_ok(long n, long images, long R) {
+  return n >= 1 && n <= 2147483647L && images >= 1 && images <= bootstrap_max_images() && R >= 1 && R <= (1L << 20);
+}
+
+long aaclip_bootstrap_max_images(void) { return bootstrap_max_images(); }
+
+size_t aaclip_bootstrap_workspace_bytes(long n, long images, long R) {
+  return bootstrap_shape_ok(n, images, R) ? up256(bootstrap_ws_bytes(n, R)) : 0;
+}
+
+int aaclip_bootstrap_curves(const aaclip_bootstrap_plan* plan, const uint32_t* keys, const uint32_t* payload,
+                            const uint8_t* counts, void* records, void* ws, size_t ws_bytes) {
+  REQUIRE(plan && keys && payload && counts && records && ws, "bootstrap_curves: null pointer");
+  REQUIRE(plan->struct_bytes == sizeof(aaclip_bootstrap_plan), "bootstrap_curves: plan->struct_bytes is not sizeof(aaclip_bootstrap_plan)");
+  const long n = plan->n, images = plan->images, R = plan->replicates;
+  REQUIRE(n >= 1 && n <= 2147483647L, "bootstrap_curves: n must be 1 .. 2^31 - 1");
+  REQUIRE(images >= 1 && images <= bootstrap_max_images(), "bootstrap_curves: images must be 1 .. 1024 (the weight table of a replicate block fills 64 KiB of LDS)");
+  REQUIRE(R >= 1 && R <= (1L << 20), "bootstrap_curves: R must be 1 .. 2^20");
+  REQUIRE((((uintptr_t)keys | (uintptr_t)payload) & 3) == 0 && (((uintptr_t)records | (uintptr_t)ws) & 7) == 0,
+          "bootstrap_curves: keys / payload must be 4-byte, records / workspace 8-byte aligned");
+  const size_t need = aaclip_bootstrap_workspace_bytes(n, images, R), n4 = (size_t)n * 4, nc = (size_t)R * images,
+               nr = (size_t)R * 32;
+  REQUIRE(!ranges_overlap(ws, need, keys, n4) && !ranges_overlap(ws, need, payload, n4) &&
+              !ranges_overlap(ws, need, counts, nc) && !ranges_overlap(ws, need, records, nr) &&
+              !ranges_overlap(records, nr, keys, n4) && !ranges_overlap(records, nr, payload, n4) &&
+              !ranges_overlap(records, nr, counts, nc),
+          "bootstrap_curves: inputs, records and workspace must not overlap one another");
+  REQUIRE(ws_bytes >= need, "bootstrap_curves: workspace too small");
+  launch_bootstrap_curves(keys, payload, n, counts, images, R, records, ws, (hipStream_t)plan->stream);
+  return finish("bootstrap_curves");
+}
+
 // ---- exact F1-max and the masks at a threshold (metrics.hip)
 size_t aaclip_metrics_f1max_workspace_bytes(long n) { return metrics_n_ok(n) ? up256(metrics_f1max_ws_bytes(n)) : 0; }
 

@@ -317,6 +317,13 @@ void launch_coreset_select(const int16_t* q, const int32_t* norm2, long N, int E
                            uint32_t* radius2, uint32_t* min_d2, void* ws, hipStream_t s);
 void launch_coreset_unit_rows(const float* rows, long N, int E, float* out, hipStream_t s);   // out = rows / |row|
 
+// ---- bootstrap.hip : bootstrap of AUROC / AP over images, a weighted curve pass over ONE sort (the records, the group
+// term and the workspace layout are bootstrap_plan.h)
+size_t bootstrap_ws_bytes(long n, long R);
+long bootstrap_max_images();
+void launch_bootstrap_curves(const uint32_t* keys, const uint32_t* payload, long n, const uint8_t* counts, long images,
+                             long R, void* records, void* ws, hipStream_t s);
+
 // ---- multi-tensor optimizer (optim.hip; the launch packing is optim_pack.h)
 struct OptimGroupScalars {   // one group's hyper-parameters as the kernel reads them: formed in fp64, rounded once
   float beta1, one_minus_beta1, beta2, one_minus_beta2;

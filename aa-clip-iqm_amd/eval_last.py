@@ -141,7 +141,7 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
                   device, img_size: int, dataset: str, batch_size: int = 32, loader_kwargs=None, logger=None,
                   use_iqm: bool = True, device_metrics: bool = False, fpr_limit=None, f1_max: bool = False,
                   details: Dict[str, dict] = None, return_masks: bool = False, defects=None, support=None,
-                  support_weight: float = SUPPORT_WEIGHT, after_class=None) -> List[dict]:
+                  support_weight: float = SUPPORT_WEIGHT, bootstrap=None, after_class=None) -> List[dict]:
     """The per-class loop of test_last.evaluate for either metrics path.  device_metrics: the class's masks, maps and
     image scores stay on the GPU, the row comes from metrics_eval_device, and the tensors are released before the next
     class.  Under torch.distributed the shards are gathered as host arrays exactly as in test_last.evaluate (so the
@@ -160,8 +160,16 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
     evaluated image -- which good patch it was compared with.  support=None changes nothing.
     after_class: None, or a callable invoked as after_class(class_name, image_dataset, masks, labels, preds, preds_image,
     file_names, details_of_class) once the class's row is computed and before its tensors are released (the dataset is
-    the one that was evaluated, details_of_class is details[class_name] or None); None changes nothing."""
+    the one that was evaluated, details_of_class is details[class_name] or None); None changes nothing.
+    bootstrap: None, or dict(R=, seed=0, level=0.95, stratified=False): metrics_eval's keyword for every class, with the
+    class's position in image_datasets as class_index -- the interval columns of forward_utils.bootstrap_interval_cols
+    in every row and, by bootstrap_average, in the average; details[class]["bootstrap"] holds the replicates.  One
+    process only.  None changes nothing."""
     import torch.distributed as dist
+    if bootstrap is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise ValueError("evaluate_rows: bootstrap runs in one process (the replicates of a sharded class are not gathered)")
+    if bootstrap is not None and details is None:
+        details = {}
     if defects is not None and not f1_max:
         raise ValueError("evaluate_rows: defects needs f1_max=True (the regions are those at the pixel F1-max threshold)")
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -215,6 +223,9 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
                     "image scores": [float(v) for v in scores.reshape(len(file_names), -1)[:, 0]] if file_names else []}
                 if support is not None and return_masks:
                     details[class_name]["support nearest"] = _support_nearest_pairs(nearest, support[class_name], world)
+        if bootstrap is not None:
+            extra["bootstrap"] = dict(bootstrap, class_index=len(rows))
+            extra.setdefault("details", details.setdefault(class_name, {}))
         rows.append(row_of(masks, labels, preds, preds_image, class_name, domain=DOMAINS[dataset], fpr_limit=fpr_limit,
                            **extra))
         if after_class is not None:
@@ -226,8 +237,25 @@ def evaluate_rows(model, image_datasets: Dict[str, torch.utils.data.Dataset], te
             (DEFECT_COLS if defects is not None else []))
     avg = {c: float(np.mean([r[c] for r in rows])) for c in cols}
     avg["class name"] = "Average"
+    if bootstrap is not None:
+        bootstrap_average(avg, [details[r["class name"]]["bootstrap"] for r in rows])
     rows.append(avg)
     return rows
+
+
+def bootstrap_average(avg: dict, per_class: List[dict]) -> dict:
+    """The Average row's intervals: per replicate the mean over the classes of that replicate's values -- every class
+    draws with the same seed and R, so replicate r of the average is replicate r of every class -- invalid where any
+    class's replicate is; the interval is that of the means, in percent, unrounded like the row's other entries.
+    per_class: the details[class]["bootstrap"] dicts.  -> {"valid": mask, column: means} (avg gets the columns)."""
+    from forward_utils import BOOTSTRAP_COLS, bootstrap_interval
+    valid = np.logical_and.reduce([b["valid"] for b in per_class])
+    out = {"valid": valid}
+    for col in BOOTSTRAP_COLS:
+        out[col] = np.mean([b[col] for b in per_class], axis=0)
+        lo, hi = bootstrap_interval(out[col], valid, per_class[0]["level"])
+        avg[col + " lo"], avg[col + " hi"] = lo * 100, hi * 100
+    return out
 
 
 def _support_nearest_pairs(nearest, bank, world):
@@ -286,9 +314,11 @@ def log_coreset(logger, banks):
 
 
 def format_table(rows: List[dict]) -> str:
-    """test_last.format_table, with the AUPRO column and the two F1-max columns behind it where the rows carry them"""
+    """test_last.format_table, with the AUPRO column, the two F1-max columns and the bootstrap interval columns behind it
+    where the rows carry them"""
+    from forward_utils import bootstrap_interval_cols
     table = TL.format_table(rows)
-    for col in [AUPRO_COL] + F1_COLS:
+    for col in [AUPRO_COL] + F1_COLS + bootstrap_interval_cols():
         if rows and col in rows[0]:
             extra = [f"{col:>14s}"] + [f"{r[col]:>14.2f}" for r in rows]
             table = "\n".join(line + "  " + cell for line, cell in zip(table.split("\n"), extra))

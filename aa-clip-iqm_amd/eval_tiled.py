@@ -129,9 +129,9 @@ def tiled_support_banks(model, image_datasets, k: int, device, img_size: int, ti
 def evaluate_tiled(model, image_datasets, text_embeddings, device, img_size: int, dataset: str, tiles, batch_size: int = 32,
                    loader_kwargs=None, logger=None, use_iqm: bool = True, device_metrics: bool = False, fpr_limit=None,
                    f1_max: bool = False, return_masks: bool = False, defects=None, support=None,
-                   support_weight: float = SUPPORT_WEIGHT, after_class=None):
+                   support_weight: float = SUPPORT_WEIGHT, bootstrap=None, after_class=None):
     """The per-class loop of eval_last.evaluate_rows over get_predictions_tiled, in one process: -> (rows, details), details
-    None without f1_max.  tiles=(G, O); support: None or {class name: bank of tiled_support_banks}; the other keywords are
+    None without f1_max and without bootstrap (evaluate_rows' keyword, passed to every class and to the average).  tiles=(G, O); support: None or {class name: bank of tiled_support_banks}; the other keywords are
     evaluate_rows', after_class included (its frames, masks and maps are C x C).  The maps handed to metrics_eval /
     metrics_eval_device are C x C."""
     import torch.distributed as dist
@@ -141,7 +141,7 @@ def evaluate_tiled(model, image_datasets, text_embeddings, device, img_size: int
         raise ValueError("evaluate_tiled: defects needs f1_max=True (the regions are those at the pixel F1-max threshold)")
     G, O = tiles
     S, G, O, C = tile_geometry(img_size, G, O)
-    rows, details = [], {} if f1_max else None
+    rows, details = [], {} if f1_max or bootstrap is not None else None
     row_of = metrics_eval_device if device_metrics else metrics_eval
     for class_name, image_dataset in image_datasets.items():
         loader = torch.utils.data.DataLoader(image_dataset, batch_size=max(1, batch_size // (G * G)), shuffle=False,
@@ -160,6 +160,9 @@ def evaluate_tiled(model, image_datasets, text_embeddings, device, img_size: int
                 "masks": bool(return_masks), "file_names": list(file_names),
                 "labels": [int(v) for v in np.asarray(labels).reshape(-1)],
                 "image scores": [float(v) for v in scores.reshape(-1)]}
+        if bootstrap is not None:
+            extra["bootstrap"] = dict(bootstrap, class_index=len(rows))
+            extra.setdefault("details", details.setdefault(class_name, {}))
         rows.append(row_of(masks, labels, preds, preds_image, class_name, domain=DOMAINS[dataset], fpr_limit=fpr_limit,
                            **extra))
         if after_class is not None:
@@ -171,6 +174,8 @@ def evaluate_tiled(model, image_datasets, text_embeddings, device, img_size: int
             (DEFECT_COLS if defects is not None else []))
     avg = {c: float(np.mean([r[c] for r in rows])) for c in cols}
     avg["class name"] = "Average"
+    if bootstrap is not None:
+        EL.bootstrap_average(avg, [details[r["class name"]]["bootstrap"] for r in rows])
     rows.append(avg)
     return rows, details
 
@@ -209,9 +214,9 @@ def evaluate_details(model, image_datasets, text_embeddings, device, img_size: i
                      loader_kwargs=None, logger=None, use_iqm: bool = True, device_metrics: bool = False, aupro_limit=None,
                      f1_max: bool = False, return_masks: bool = False, defects=None, save_path=None, support=None,
                      support_weight: float = SUPPORT_WEIGHT, support_form=None, support_datasets=None, coreset=None,
-                     coreset_dim: int = 128, after_class=None):
+                     coreset_dim: int = 128, bootstrap=None, after_class=None):
     """The tiled path of evaluate, for tiles=(G, O): the banks where support=K asks for them, evaluate_tiled (after_class
-    is its keyword), and the .jsonl files of eval_defects.write_defects where defects and save_path ask for them.
+    and bootstrap are its keywords), and the .jsonl files of eval_defects.write_defects where defects and save_path ask for them.
     -> (rows, details)."""
     S, G, O, C = tile_geometry(img_size, *tiles)
     if coreset is not None and support is None:
@@ -234,7 +239,7 @@ def evaluate_details(model, image_datasets, text_embeddings, device, img_size: i
                                    loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm,
                                    device_metrics=device_metrics, fpr_limit=aupro_limit, f1_max=f1_max,
                                    return_masks=return_masks, defects=defects, support=banks, support_weight=support_weight,
-                                   after_class=after_class)
+                                   after_class=after_class, bootstrap=bootstrap)
     if defects is not None and save_path is not None:
         ED.write_defects(save_path, dataset, details)
     return rows, details

@@ -554,8 +554,170 @@ def _defect_columns(row, details, d, want_masks):
             details["kept masks"] = d["kept mask"]
 
 
+# ------------------------------------------------------------------------------------------------
+# bootstrap intervals of AUROC / AP over the images of one class ("Bootstrap intervals on the device")
+BOOTSTRAP_COLS = ["pixel AUC", "pixel AP", "image AUC", "image AP"]
+BOOTSTRAP_MAX_INVALID = 0.05    # share of a class's replicates that may lack a label before the class is refused
+Bootstrap = collections.namedtuple("Bootstrap", "num P N ap valid auroc")
+
+
+def bootstrap_interval_cols(cols=BOOTSTRAP_COLS):
+    """the columns that metrics_eval(bootstrap=...) adds: "<column> lo", "<column> hi" for every bootstrapped column"""
+    return [f"{c} {end}" for c in cols for end in ("lo", "hi")]
+
+
+def bootstrap_counts(images: int, R: int, seed: int, class_index: int, image_label=None):
+    """-> uint8 [R, images]: how often replicate r draws image i, `images` draws with replacement per replicate, from
+    numpy's default_rng([seed, class_index]) -- the same seed, class index and image count give the same counts.
+    image_label given (the stratified form): the label-0 images and the label-1 images are drawn separately, in that
+    order from the one generator, each group keeping its size.  ValueError for a count above 255."""
+    import numpy as np
+    images, R = int(images), int(R)
+    if images < 1 or R < 1:
+        raise ValueError(f"bootstrap_counts: {images} images and {R} replicates; both must be at least 1")
+    rng = np.random.default_rng([int(seed), int(class_index)])
+    counts = np.zeros((R, images), np.int64)
+    if image_label is None:
+        groups = [np.arange(images)]
+    else:
+        lab = np.asarray(image_label).reshape(-1) != 0
+        if lab.size != images:
+            raise ValueError(f"bootstrap_counts: {lab.size} image labels for {images} images")
+        groups = [np.nonzero(~lab)[0], np.nonzero(lab)[0]]
+    rows = np.arange(R)[:, None]
+    for members in groups:
+        if members.size:
+            draw = rng.integers(0, members.size, size=(R, members.size))
+            np.add.at(counts, (rows, members[draw]), 1)
+    if counts.max() > 255:
+        raise ValueError(f"bootstrap_counts: an image was drawn {counts.max()} times; the counts are stored as uint8")
+    return counts.astype(np.uint8)
+
+
+def _bootstrap_check(valid, class_name, what):
+    """logs the invalid replicates of a class and refuses it above BOOTSTRAP_MAX_INVALID"""
+    import logging
+    bad, R = int((~valid).sum()), int(valid.size)
+    logging.getLogger(__name__).info("bootstrap %s (%s): %d of %d replicates invalid (one label only)", class_name, what,
+                                     bad, R)
+    if bad > BOOTSTRAP_MAX_INVALID * R:
+        raise ValueError(f"bootstrap: {bad} of {R} replicates of class {class_name!r} ({what}) hold one label only, more "
+                         f"than {BOOTSTRAP_MAX_INVALID:.0%}; draw the two labels separately (--bootstrap_stratified)")
+
+
+def bootstrap_eval(labels, scores, image_of, counts, class_name=None, what="scores") -> Bootstrap:
+    """The definition of the bootstrap records, in numpy: labels, scores and image_of (the image of every element) of
+    one size, counts [R, images].  The elements are sorted ONCE by score, ascending and stable; replicate r gives element
+    e the weight counts[r, image_of[e]].  With E(i) / M(i) the weighted positives / elements before sorted index i,
+    P = E(n), Mtot = M(n), a tie group [i, i2) has tp = P - E(i), fp = (Mtot - M(i)) - tp, tp0 = P - E(i2),
+    fp0 = (Mtot - M(i2)) - tp0 and adds (fp - fp0)(tp + tp0) to num (integers) and ((tp - tp0) / P)(tp / (tp + fp)) to ap
+    (fp64), EXACTLY 0 where tp == tp0.  N = Mtot - P; P == 0 or N == 0 makes the replicate invalid: num = ap = 0.
+    These are sklearn's roc_auc_score (num / (2 P N)) and average_precision_score of the literally repeated images.
+    -> Bootstrap(num, P, N, ap, valid, auroc) of arrays [R]; num is int64: the weighted size of every replicate is
+    checked to lie below 2^31, so num < 2^61.
+    class_name: given, the invalid replicates are logged and more than 5 % of them raise ValueError."""
+    import numpy as np
+    labels = np.asarray(labels).reshape(-1) != 0
+    scores = np.asarray(scores).reshape(-1)
+    image_of = np.asarray(image_of).reshape(-1).astype(np.int64)
+    counts = np.asarray(counts)
+    if counts.ndim != 2 or counts.min() < 0 or counts.max() > 255:
+        raise ValueError("bootstrap_eval: counts must be [R, images] in 0 .. 255")
+    n, (R, images) = scores.size, counts.shape
+    if labels.size != n or image_of.size != n or n < 1 or image_of.min() < 0 or image_of.max() >= images:
+        raise ValueError("bootstrap_eval: labels, scores and image_of must have one size and name images of the counts")
+    counts = counts.astype(np.int64)
+    if int((counts * np.bincount(image_of, minlength=images)[None, :]).sum(axis=1).max()) >= 2 ** 31:
+        raise ValueError("bootstrap_eval: a replicate weighs 2^31 elements or more")
+    order = np.argsort(scores, kind="stable")
+    s, lab, img = scores[order], labels[order].astype(np.int64), image_of[order]
+    start = np.nonzero(np.concatenate([[True], s[1:] != s[:-1]]))[0]
+    stop = np.concatenate([start[1:], [n]])
+    num, P, N, ap = np.zeros(R, np.int64), np.zeros(R, np.int64), np.zeros(R, np.int64), np.zeros(R, np.float64)
+    block = max(1, (1 << 22) // n)
+    for r0 in range(0, R, block):
+        w = counts[r0:r0 + block][:, img]                                        # [b, n]
+        zero = np.zeros((w.shape[0], 1), np.int64)
+        M = np.concatenate([zero, np.cumsum(w, axis=1)], axis=1)
+        E = np.concatenate([zero, np.cumsum(w * lab[None, :], axis=1)], axis=1)
+        Pb, Mt = E[:, -1:], M[:, -1:]
+        tp, tp0 = Pb - E[:, start], Pb - E[:, stop]
+        fp, fp0 = (Mt - M[:, start]) - tp, (Mt - M[:, stop]) - tp0
+        nb = ((fp - fp0) * (tp + tp0)).sum(axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            terms = ((tp - tp0) / Pb.astype(np.float64)) * (tp / (tp + fp).astype(np.float64))
+        terms[tp == tp0] = 0.0
+        ok = (Pb[:, 0] > 0) & (Mt[:, 0] - Pb[:, 0] > 0)
+        P[r0:r0 + block], N[r0:r0 + block] = Pb[:, 0], Mt[:, 0] - Pb[:, 0]
+        num[r0:r0 + block] = np.where(ok, nb, 0)
+        ap[r0:r0 + block] = np.where(ok, terms.sum(axis=1), 0.0)
+    return _bootstrap_result(num, P, N, ap, class_name, what)
+
+
+def _bootstrap_result(num, P, N, ap, class_name, what) -> Bootstrap:
+    import numpy as np
+    valid = (P > 0) & (N > 0)
+    auroc = np.where(valid, num.astype(np.float64) / np.maximum(2.0 * P * N, 1.0), 0.0)
+    if class_name is not None:
+        _bootstrap_check(valid, class_name, what)
+    return Bootstrap(num, P, N, ap, valid, auroc)
+
+
+def bootstrap_eval_device(labels, scores, per_image, counts, normalise=False, class_name=None, what="scores") -> Bootstrap:
+    """bootstrap_eval on the GPU (engine.bootstrap_metrics: one sort, then csrc/bootstrap.hip) for device tensors whose
+    image i owns the elements [i * per_image, (i + 1) * per_image): the same integers, ap within rounding of the order
+    of its fp64 sum."""
+    b = engine.bootstrap_metrics(scores, labels, per_image, counts, normalise=normalise)
+    return _bootstrap_result(b.num, b.P, b.N, b.ap, class_name, what)
+
+
+def bootstrap_interval(values, valid, level=0.95):
+    """-> (lo, hi): numpy's default quantiles (1 - level) / 2 and (1 + level) / 2 of the valid replicates' values"""
+    import numpy as np
+    values, valid = np.asarray(values, np.float64), np.asarray(valid, bool)
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError(f"bootstrap_interval: level must lie in (0, 1), got {level}")
+    if not valid.any():
+        raise ValueError("bootstrap_interval: no valid replicate")
+    lo, hi = np.quantile(values[valid], [(1.0 - level) / 2.0, (1.0 + level) / 2.0])
+    return float(lo), float(hi)
+
+
+def _bootstrap_settings(bootstrap):
+    known = {"R", "seed", "level", "stratified", "class_index"}
+    if not isinstance(bootstrap, dict) or "R" not in bootstrap or set(bootstrap) - known:
+        raise ValueError(f"bootstrap must be a dict with R and any of {sorted(known - {'R'})}")
+    R, level = int(bootstrap["R"]), float(bootstrap.get("level", 0.95))
+    if R < 1 or not 0.0 < level < 1.0:
+        raise ValueError("bootstrap: R must be at least 1 and level must lie in (0, 1)")
+    return R, int(bootstrap.get("seed", 0)), level, bool(bootstrap.get("stratified", False)), int(bootstrap.get("class_index", 0))
+
+
+def _bootstrap_columns(row, details, bootstrap, class_name, image_label, replicates):
+    """The interval columns of one class.  replicates(counts) -> (pixel Bootstrap, image Bootstrap or None).  A replicate
+    counts where it is valid for the pixels AND for the images; the columns of a point estimate that is the fixed 0 of a
+    one-label class are 0.  details (a dict or None) receives "bootstrap"."""
+    import numpy as np
+    R, seed, level, stratified, class_index = _bootstrap_settings(bootstrap)
+    image_label = np.asarray(image_label).reshape(-1)
+    counts = bootstrap_counts(image_label.size, R, seed, class_index, image_label if stratified else None)
+    pixel, image = replicates(counts)
+    valid = pixel.valid if image is None else pixel.valid & image.valid
+    zeros = np.zeros(R, np.float64)
+    arrays = {"pixel AUC": pixel.auroc, "pixel AP": pixel.ap,
+              "image AUC": zeros if image is None else image.auroc, "image AP": zeros if image is None else image.ap}
+    for col in BOOTSTRAP_COLS:
+        fixed = image is None and col.startswith("image")
+        lo, hi = (0.0, 0.0) if fixed else bootstrap_interval(arrays[col], valid, level)
+        row[col + " lo"], row[col + " hi"] = round(lo, 4) * 100, round(hi, 4) * 100
+    if details is not None:
+        details["bootstrap"] = dict({c: np.where(valid, arrays[c], 0.0) for c in BOOTSTRAP_COLS}, valid=valid, seed=seed,
+                                    R=R, level=level, stratified=stratified, class_index=class_index,
+                                    images=int(image_label.size), point={c: row[c] for c in BOOTSTRAP_COLS})
+
+
 def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, fpr_limit=None,
-                 f1_max=False, details=None, defects=None):
+                 f1_max=False, details=None, defects=None, bootstrap=None):
     """Pixel / image AUROC and AP of one class, reference forward_utils.py:233-308:
     global min-max normalisation of maps and image scores (:246-253), per-image maximum of
     the normalised map (:277), Industrial score = 0.5*max_pixel + 0.5*image score, Medical =
@@ -570,7 +732,12 @@ def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names
     uint8 predicted masks `normalised map >= pixel threshold` under "masks".
     defects: None, or a min_area >= 1 (needs f1_max=True): adds DEFECT_COLS -- "region recall", "region precision", "false
     regions / image" of defects_eval at the pixel threshold -- and puts the per-image lists of the kept predicted regions
-    under details["defects"] and, where "masks" was asked for, the filtered masks under details["kept masks"]."""
+    under details["defects"] and, where "masks" was asked for, the filtered masks under details["kept masks"].
+    bootstrap: None, or dict(R=, seed=0, level=0.95, stratified=False, class_index=0): R replicates of the class's images
+    (bootstrap_counts) through bootstrap_eval -- slow on the host, meant for small classes -- add "<column> lo" and
+    "<column> hi" for the four columns above (bootstrap_interval_cols), in percent with the table's rounding, 0 where
+    the point estimate is the fixed 0; the scores are the normalised pixels and the combined image scores of the WHOLE
+    class, not re-normalised per replicate.  details["bootstrap"] receives the replicate arrays and the valid mask."""
     import numpy as np
     from sklearn.metrics import average_precision_score, roc_auc_score
 
@@ -621,6 +788,15 @@ def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names
             details["masks"] = (pixel_preds >= pixel_preds.dtype.type(pixel_f1.threshold)).astype(np.uint8)
         if defects is not None:
             _defect_columns(row, details, defects_eval(pixel_label, pixel_preds, pixel_f1.threshold, defects), want_masks)
+    if bootstrap is not None:
+        def replicates(counts):
+            image_of = np.repeat(np.arange(pixel_preds.shape[0]), pp.size // pixel_preds.shape[0])
+            pixel = bootstrap_eval(pl, pp, image_of, counts, class_names, "pixels")
+            if image_label.max() == image_label.min():
+                return pixel, None
+            return pixel, bootstrap_eval(image_label.reshape(-1), image_preds.reshape(-1), np.arange(image_label.size),
+                                         counts, class_names, "images")
+        _bootstrap_columns(row, details, bootstrap, class_names, image_label, replicates)
     return row
 
 
@@ -633,7 +809,7 @@ def _f1_columns(row, details, pixel_f1, image_f1):
 
 
 def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, fpr_limit=None,
-                        f1_max=False, details=None, defects=None):
+                        f1_max=False, details=None, defects=None, bootstrap=None):
     """metrics_eval with the sort and the curve sums on the GPU (csrc/metrics.hip through engine.curve_metrics): the same
     arguments, shape handling, domain rule, `image_label.max() != image_label.min()` rule, result dict and rounding, and
     the same numbers -- sklearn's tie groups and definitions, an integer AUROC numerator, an fp64 AP sum.
@@ -645,7 +821,9 @@ def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, clas
     serves AUROC / AP already, and details["masks"] is a device tensor from engine.metrics_threshold, which normalises
     the raw maps on the fly and reads the threshold from the device record.
     defects: as in metrics_eval, through engine.defects_at_threshold: the threshold and the range stay on the device, the
-    lists come from the region tables and details["kept masks"] is a device tensor."""
+    lists come from the region tables and details["kept masks"] is a device tensor.
+    bootstrap: as in metrics_eval, through engine.bootstrap_metrics: one more sort per level (pixels, images) with the
+    image index as payload, then the weighted curve pass of csrc/bootstrap.hip over all R replicates."""
     import numpy as np
 
     if defects is not None and not f1_max:
@@ -699,6 +877,13 @@ def metrics_eval_device(pixel_label, image_label, pixel_preds, image_preds, clas
                     shaped = shaped.reshape(shaped.shape[0], side, side)
             _defect_columns(row, details, defects_eval_device(pl, shaped, records["f1max"], defects,
                                                               range_record=records["range"]), want_masks)
+    if bootstrap is not None:
+        def replicates(counts):
+            pixel = bootstrap_eval_device(pl, pp, pp.numel() // n_img, counts, True, class_names, "pixels")
+            if image_label.max() == image_label.min():
+                return pixel, None
+            return pixel, bootstrap_eval_device(il, score, 1, counts, False, class_names, "images")
+        _bootstrap_columns(row, details, bootstrap, class_names, image_label, replicates)
     return row
 
 

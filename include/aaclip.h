@@ -807,6 +807,38 @@ size_t aaclip_png_capacity_bytes(const aaclip_png_plan* plan);
 int aaclip_png_encode(const aaclip_png_plan* plan, const uint8_t* pixels, void* workspace, size_t ws_bytes,
                       uint8_t* payload, size_t capacity, int64_t* offsets);
 
+/* Bootstrap of AUROC / AP over the IMAGES of one class (csrc/bootstrap.hip; the definition is
+ * forward_utils.bootstrap_eval, DESIGN.md section 6 "Bootstrap intervals on the device").  This ABI number is unchanged:
+ * the entries are additions.  The conventions are those of the metrics entries (checks before the first launch, the
+ * workspace size last, *_workspace_bytes 0 for refused sizes, no atomics, the fp64 sum in an order fixed by n alone:
+ * two calls give the same bytes).
+ *   keys [n] ascending and payload [n] = image << 1 | label in their order: what aaclip_metrics_sort_pairs gives for the
+ *   values image << 1 | label.  n in 1 .. 2^31 - 1, images in 1 .. aaclip_bootstrap_max_images(); a payload whose
+ *   image is not below `images` is read as the last image.  counts u8 [R][images]: replicate r gives every element of
+ *   image i the weight counts[r][i].  R in 1 .. 2^20.  The CALLER guarantees sum_i counts[r][i] * (elements of image i)
+ *   < 2^31 for every r (the counts live on the device; aaclip_hip.engine checks it on the host).
+ *   records [R] <- {num, P, N, ap}: P / N the weighted positives / negatives, num the integer AUROC numerator
+ *   (AUROC = num / (2 P N)), ap the fp64 average-precision sum over the tie groups, a group without a weighted positive
+ *   adding exactly 0.  P == 0 or N == 0 marks an INVALID replicate: num = 0, ap = 0.
+ *   The workspace does not grow with R beyond 512: the entry walks the replicates in chunks of 8 blocks of 64.
+ *   The sizes and the stream travel in a plan, as in aaclip_png_plan; every launch goes to plan->stream and the call
+ *   only enqueues work on it (it may be captured into a graph). */
+typedef struct aaclip_bootstrap_record {   /* 32 bytes */
+  unsigned long long num, P, N;
+  double ap;
+} aaclip_bootstrap_record;
+typedef struct aaclip_bootstrap_plan {
+  size_t struct_bytes;      /* sizeof(aaclip_bootstrap_plan); any other value is refused */
+  long n;                   /* sorted elements */
+  long images;
+  long replicates;          /* R */
+  void* stream;             /* hipStream_t */
+} aaclip_bootstrap_plan;
+long aaclip_bootstrap_max_images(void);
+size_t aaclip_bootstrap_workspace_bytes(long n, long images, long R);
+int aaclip_bootstrap_curves(const aaclip_bootstrap_plan* plan, const uint32_t* keys, const uint32_t* payload,
+                            const uint8_t* counts, void* records, void* ws, size_t ws_bytes);
+
 /* Fused Adam / AdamW step over a list of tensors, and the gradient norm that clips it (csrc/optim.hip).  fp32
  * parameters, gradients and state only.  One launch serves up to 24 tensors and 640 chunks of 16384 elements; its table
  * travels by value in the kernel arguments, so a call copies nothing to the device, allocates nothing and waits for
