@@ -26,18 +26,15 @@ python eval_bootstrap.py --save_path ... --device_metrics --bootstrap 1000 [--bo
 from __future__ import annotations
 
 import argparse
-import logging
 import os
 
 import numpy as np
-import torch
 
 import eval_defects as ED
 import eval_last as EL
+import eval_overlay as EO
 import eval_png as EP
 import eval_tiled as ET
-import test_last as TL
-from aaclip_hip import engine
 from forward_utils import BOOTSTRAP_COLS, SUPPORT_WEIGHT, TILE_OVERLAP
 
 NPZ_KEYS = {"pixel AUC": "pixel_auc", "pixel AP": "pixel_ap", "image AUC": "image_auc", "image AP": "image_ap"}
@@ -88,77 +85,35 @@ def evaluate(model, image_datasets, text_embeddings, device, img_size: int, data
     None or a list that receives the paths).  The files of overlay / masks_png are written as eval_png.evaluate writes
     them.  -> rows, or (rows, details) with return_masks.  One process only."""
     where = (model, image_datasets, text_embeddings, device, img_size, dataset)
+    below = dict(batch_size=batch_size, loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm,
+                 device_metrics=device_metrics, aupro_limit=aupro_limit, f1_max=f1_max, return_masks=return_masks,
+                 defects=defects, save_path=save_path, support=support, support_weight=support_weight,
+                 support_form=support_form, support_datasets=support_datasets, coreset=coreset, coreset_dim=coreset_dim)
+    files = dict(overlay=overlay, overlay_limit=overlay_limit, overlay_thickness=overlay_thickness,
+                 overlay_colormap=overlay_colormap, overlay_written=overlay_written, overlay_encoder=overlay_encoder,
+                 masks_png=masks_png, masks_written=masks_written)
     if bootstrap is None:
-        return EP.evaluate(*where, batch_size=batch_size, loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm,
-                           device_metrics=device_metrics, aupro_limit=aupro_limit, f1_max=f1_max, return_masks=return_masks,
-                           defects=defects, save_path=save_path, support=support, support_weight=support_weight,
-                           support_form=support_form, support_datasets=support_datasets, coreset=coreset,
-                           coreset_dim=coreset_dim, tiles=tiles, tile_overlap=tile_overlap, overlay=overlay,
-                           overlay_limit=overlay_limit, overlay_thickness=overlay_thickness,
-                           overlay_colormap=overlay_colormap, overlay_written=overlay_written,
-                           overlay_encoder=overlay_encoder, masks_png=masks_png, masks_written=masks_written)
+        return EP.evaluate(*where, **below, tiles=tiles, tile_overlap=tile_overlap, **files)
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         raise ValueError("bootstrap runs in one process (the replicates of a sharded class are not gathered)")
     bootstrap = bootstrap_settings(**bootstrap)
-    files = masks_png or overlay is not None
-    if overlay_encoder not in EP.ENCODERS:
-        raise ValueError(f"evaluate: overlay_encoder must be one of {EP.ENCODERS}, got {overlay_encoder!r}")
-    if files and save_path is None:
-        raise ValueError("evaluate: overlay and masks_png need save_path (the files go to <save_path>/overlays and /masks)")
-    if overlay is not None and (not 0.0 <= float(overlay) <= 1.0
-                                or not 0 <= int(overlay_thickness) <= engine.OVERLAY_MAX_THICKNESS):
-        raise ValueError("evaluate: overlay takes an alpha in 0 .. 1 and overlay_thickness 0 .. 8")
-    if coreset is not None and support is None:
-        raise ValueError("evaluate: coreset needs support=K")
-    f1 = f1_max or defects is not None or files
+    EP.check_encoder(overlay_encoder)
+    with_files = masks_png or overlay is not None
+    after = None
+    if with_files:
+        after = EP.files_callback(save_path, dataset, device, batch_size, loader_kwargs, defects, tiles, **files)
+    f1 = f1_max or defects is not None or with_files
     if return_masks and not f1:
         raise ValueError("evaluate: return_masks needs f1_max=True (the masks are those of its threshold)")
-    after = None
-    if files:
-        engine.overlay_lut(overlay_colormap)
-        after = EP.png_callback(save_path, dataset, device, overlay=None if overlay is None else float(overlay),
-                                encoder=overlay_encoder, masks_png=masks_png, limit=overlay_limit,
-                                thickness=int(overlay_thickness), colormap=overlay_colormap,
-                                batch_size=batch_size if tiles is None else max(1, batch_size // (int(tiles) ** 2)),
-                                loader_kwargs=loader_kwargs, defects=defects, written=overlay_written,
-                                masks_written=masks_written)
-    masks = return_masks or files
-    if tiles is not None:
-        rows, details = ET.evaluate_details(*where, (tiles, tile_overlap), batch_size=batch_size, loader_kwargs=loader_kwargs,
-                                            logger=logger, use_iqm=use_iqm, device_metrics=device_metrics,
-                                            aupro_limit=aupro_limit, f1_max=f1, return_masks=masks, defects=defects,
-                                            save_path=save_path, support=support, support_weight=support_weight,
-                                            support_form=support_form, support_datasets=support_datasets, coreset=coreset,
-                                            coreset_dim=coreset_dim, after_class=after, bootstrap=bootstrap)
-    else:
-        banks = None
-        if support is not None:
-            core = {} if coreset is None else {"coreset": coreset, "coreset_dim": coreset_dim}
-            banks, image_datasets = EL.support_banks(model, image_datasets, support, device, img_size, form=support_form,
-                                                     support_datasets=support_datasets, batch_size=batch_size, **core)
-            if logger and coreset is not None:
-                EL.log_coreset(logger, banks)
-        details = {}
-        extra = {} if defects is None else {"defects": defects}
-        if banks is not None:
-            extra.update(support=banks, support_weight=support_weight)
-        rows = EL.evaluate_rows(model, image_datasets, text_embeddings, device, img_size, dataset, batch_size=batch_size,
-                                loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm, device_metrics=device_metrics,
-                                fpr_limit=aupro_limit, f1_max=f1, details=details, return_masks=masks, after_class=after,
-                                bootstrap=bootstrap, **extra)
-        if defects is not None and save_path is not None:
-            ED.write_defects(save_path, dataset, details)
+    rows, details = ET.evaluate_details(*where, None if tiles is None else (tiles, tile_overlap),
+                                        **dict(below, f1_max=f1, return_masks=return_masks or with_files),
+                                        after_class=after, bootstrap=bootstrap)
     if save_path is not None:
         paths = write_bootstrap(save_path, dataset, rows, details)
         if bootstrap_written is not None:
             bootstrap_written.extend(paths)
-    if return_masks:
-        return rows, details
-    for d in details.values():               # the masks were asked for on the files' behalf only
-        for key in ("masks", "kept masks", "support nearest"):
-            d.pop(key, None)
-    return rows
+    return EO.own_masks_only(rows, details, return_masks)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -181,65 +136,25 @@ def _check_arguments(parser: argparse.ArgumentParser, args) -> None:
         parser.error("--bootstrap_level takes a level in (0, 1)")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         parser.error("--bootstrap runs in one process: the replicates of a sharded class are not gathered")
-    EP._check_arguments(parser, args)
+    EO._check_arguments(parser, args)
 
 
 def run(parser: argparse.ArgumentParser, argv=None):
-    """Without --bootstrap: eval_png.run.  With it: the steps of eval_png.run and this module's evaluate."""
+    """Without --bootstrap: eval_png.run.  With it: the session of eval_png.run and this module's evaluate."""
     args = parser.parse_args(argv)
     if args.bootstrap is None:
         return EP.run(parser, argv)
     _check_arguments(parser, args)
-    from dataset import DATA_PATH, BaseSingleClassDataset, get_dataset
-    from forward_utils import get_adapted_text_embedding
-    from model.adapter import AdaptedCLIP
-    from model.clip import create_model
-    S = args.img_size
-    C = S if args.tiles is None else ET.tile_geometry(S, args.tiles, args.tile_overlap)[3]
-    TL.setup_seed(args.seed)
-    os.makedirs(args.save_path, exist_ok=True)
-    logger = logging.getLogger(__name__)
-    logging.basicConfig(filename=os.path.join(args.save_path, "test.log"), encoding="utf-8", level=logging.INFO)
-    logger.info("args: %s", vars(args))
-    if not torch.cuda.is_available():
-        raise RuntimeError("the AA-CLIP HIP path needs an MI355X; there is no CPU fallback")
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
-    torch.cuda.set_device(device)
-    clip_model = create_model(model_name=args.model_name, img_size=S, device=device, pretrained="openai",
-                              require_pretrained=True, precision=args.precision)
-    clip_model.eval()
-    model = AdaptedCLIP(clip_model=clip_model, text_adapt_weight=args.text_adapt_weight,
-                        image_adapt_weight=args.image_adapt_weight, text_adapt_until=args.text_adapt_until,
-                        image_adapt_until=args.image_adapt_until, relu=args.relu,
-                        iqm_hidden_size=args.iqm_hidden_size, iqm_num_layers=args.iqm_num_layers,
-                        iqm_num_heads=args.iqm_num_heads).to(device)
-    model.eval()
-    adapt_text = EL.load_adapters(model, args.save_path, logger)
-    image_datasets = get_dataset(args.dataset, C, None, args.shot, "test", logger=logger,
-                                 device_preprocess=args.device_preprocess)
-    with torch.no_grad():
-        text_embeddings = get_adapted_text_embedding(model if adapt_text else clip_model, args.dataset, device)
-    support_sets = None
-    if args.support is not None and args.support_meta:
-        support_sets = {c: BaseSingleClassDataset(DATA_PATH[args.dataset], args.support_meta, C, c,
-                                                  device_preprocess=args.device_preprocess) for c in image_datasets}
+    session, where = EO.open_session(args, __name__)
     f1 = bool(args.f1max) or args.defects is not None or args.masks_png or args.overlay is not None
     written = []
-    rows = evaluate(model, image_datasets, text_embeddings, device, S, args.dataset, batch_size=args.image_batch_size,
-                    loader_kwargs={"num_workers": 4, "pin_memory": True}, logger=logger, use_iqm=args.iqm == "on",
-                    device_metrics=args.device_metrics, aupro_limit=args.aupro, f1_max=f1, defects=args.defects,
-                    save_path=args.save_path, support=args.support, support_weight=args.support_weight,
-                    support_form=args.support_form, support_datasets=support_sets, coreset=args.support_coreset,
-                    coreset_dim=args.support_coreset_dim, tiles=args.tiles, tile_overlap=args.tile_overlap,
-                    overlay=args.overlay, overlay_limit=args.overlay_limit, overlay_thickness=args.overlay_thickness,
-                    overlay_colormap=args.overlay_colormap, overlay_encoder=args.overlay_encoder, masks_png=args.masks_png,
+    rows = evaluate(*where, f1_max=f1, **ET.session_keywords(args, session), **EO.overlay_keywords(args),
+                    overlay_encoder=args.overlay_encoder, masks_png=args.masks_png,
                     bootstrap=bootstrap_settings(args.bootstrap, args.bootstrap_seed, args.bootstrap_level,
                                                  args.bootstrap_stratified), bootstrap_written=written)
-    logger.info("bootstrap: %d replicates, seed %d, level %s, %s; %d files", args.bootstrap, args.bootstrap_seed,
-                args.bootstrap_level, "stratified" if args.bootstrap_stratified else "plain", len(written))
-    table = ED.format_table(rows)
-    logger.info("final results:\n%s", table)
-    print(table)
+    session.logger.info("bootstrap: %d replicates, seed %d, level %s, %s; %d files", args.bootstrap, args.bootstrap_seed,
+                        args.bootstrap_level, "stratified" if args.bootstrap_stratified else "plain", len(written))
+    ED.log_table(session.logger, rows)
     return rows
 
 

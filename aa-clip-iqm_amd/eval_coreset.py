@@ -19,10 +19,8 @@ python eval_coreset.py --save_path ... --support K [--support_meta FILE] [--supp
 from __future__ import annotations
 
 import argparse
-import os
 
 import eval_defects as ED
-import eval_last as EL
 import eval_support as ES
 from forward_utils import SUPPORT_WEIGHT
 
@@ -42,22 +40,10 @@ def evaluate(model, image_datasets, text_embeddings, device, img_size: int, data
     if coreset is None:
         return ES.evaluate(*where, **how, support=support, support_weight=support_weight, support_form=support_form,
                            support_datasets=support_datasets)
-    if support is None:
-        raise ValueError("evaluate: coreset needs support=K")
-    banks, evaluated = EL.support_banks(model, image_datasets, support, device, img_size, form=support_form,
-                                        support_datasets=support_datasets, batch_size=batch_size, coreset=coreset,
-                                        coreset_dim=coreset_dim)
-    if logger:
-        EL.log_coreset(logger, banks)
-    where = (model, evaluated, text_embeddings, device, img_size, dataset)
     f1 = f1_max or defects is not None
-    details = {} if f1 else None
-    extra = {} if defects is None else {"defects": defects}
-    rows = EL.evaluate_rows(*where, batch_size=batch_size, loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm,
-                            device_metrics=device_metrics, fpr_limit=aupro_limit, f1_max=f1, details=details,
-                            return_masks=return_masks, support=banks, support_weight=support_weight, **extra)
-    if defects is not None and save_path is not None and int(os.environ.get("RANK", "0")) == 0:
-        ED.write_defects(save_path, dataset, details)
+    rows, details = ED.evaluate_details(*where, **dict(how, f1_max=f1), support=support, support_weight=support_weight,
+                                        support_form=support_form, support_datasets=support_datasets, coreset=coreset,
+                                        coreset_dim=coreset_dim)
     return (rows, details) if return_masks and f1 else rows
 
 
@@ -70,17 +56,21 @@ def build_parser() -> argparse.ArgumentParser:
     return parser
 
 
-def run(parser: argparse.ArgumentParser, argv=None):
-    """Without --support_coreset: eval_support.run.  With it: the same steps, the banks reduced to their coresets
-    (eval_last.run reads the coreset arguments)."""
-    args = parser.parse_args(argv)
+def check_arguments(parser: argparse.ArgumentParser, args) -> None:
     if args.support_coreset is not None:
-        if args.support is None:
-            parser.error("--support_coreset needs --support K")
         if not 0.0 < args.support_coreset <= 1.0:
             parser.error("--support_coreset takes a share in (0, 1]")
         if args.support_coreset_dim < 0 or args.support_coreset_dim % 128:
             parser.error("--support_coreset_dim takes 0 or a multiple of 128")
+
+
+def run(parser: argparse.ArgumentParser, argv=None):
+    """Without --support_coreset: eval_support.run.  With it: the same steps, the banks reduced to their coresets
+    (eval_last.run reads the coreset arguments)."""
+    args = parser.parse_args(argv)
+    if args.support_coreset is not None and args.support is None:
+        parser.error("--support_coreset needs --support K")
+    check_arguments(parser, args)
     return ES.run(parser, argv)
 
 

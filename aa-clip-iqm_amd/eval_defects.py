@@ -14,6 +14,7 @@
                          peak in the normalised units of the thresholds.  Rank 0 writes.
 
 Without --defects it prints exactly what eval_metrics.py prints.  evaluate(..., defects=MIN_AREA) is the function form.
+evaluate_details is the evaluation that the scripts from eval_support.py up share: banks, evaluate_rows, these files.
 
 python eval_defects.py --save_path ... [--device_metrics] [--aupro [LIMIT]] [--f1max] [--defects [MIN_AREA]] [...]
 """
@@ -26,7 +27,7 @@ from typing import Dict, List
 
 import eval_last as EL
 import eval_metrics as EM
-from forward_utils import DEFECT_COLS
+from forward_utils import DEFECT_COLS, SUPPORT_WEIGHT
 
 DEFECTS_DEFAULT_MIN_AREA = 1
 
@@ -67,12 +68,44 @@ def evaluate(model, image_datasets, text_embeddings, device, img_size: int, data
     where = (model, image_datasets, text_embeddings, device, img_size, dataset)
     if defects is None:
         return EM.evaluate(*where, **how, aupro_limit=aupro_limit, f1_max=f1_max, return_masks=return_masks)
-    details = {}
-    rows = EL.evaluate_rows(*where, **how, fpr_limit=aupro_limit, f1_max=True, details=details,
-                            return_masks=return_masks, defects=defects)
-    if save_path is not None and int(os.environ.get("RANK", "0")) == 0:
-        write_defects(save_path, dataset, details)
+    rows, details = evaluate_details(*where, **how, aupro_limit=aupro_limit, f1_max=True, return_masks=return_masks,
+                                     defects=defects, save_path=save_path)
     return (rows, details) if return_masks else rows
+
+
+def evaluate_details(model, image_datasets, text_embeddings, device, img_size: int, dataset: str, batch_size: int = 32,
+                     loader_kwargs=None, logger=None, use_iqm: bool = True, device_metrics: bool = False, aupro_limit=None,
+                     f1_max: bool = False, return_masks: bool = False, defects=None, save_path=None, support=None,
+                     support_weight: float = SUPPORT_WEIGHT, support_form=None, support_datasets=None, coreset=None,
+                     coreset_dim: int = 128, bootstrap=None, after_class=None):
+    """The evaluation behind every script from this one up, at the model's own size (eval_tiled.evaluate_details is its
+    twin over tiles): the banks where support=K asks for them (eval_last.support_banks, reduced by coreset, which is
+    logged), eval_last.evaluate_rows -- defects needs f1_max=True; bootstrap and after_class are its keywords -- and the
+    .jsonl files of write_defects where defects and save_path ask for them, written by rank 0.  -> (rows, details),
+    details None without f1_max and without bootstrap."""
+    if coreset is not None and support is None:
+        raise ValueError("evaluate: coreset needs support=K")
+    banks = None
+    if support is not None:
+        core = {} if coreset is None else {"coreset": coreset, "coreset_dim": coreset_dim}
+        banks, image_datasets = EL.support_banks(model, image_datasets, support, device, img_size, form=support_form,
+                                                 support_datasets=support_datasets, batch_size=batch_size, **core)
+        if logger and coreset is not None:
+            EL.log_coreset(logger, banks)
+    details = {} if f1_max or bootstrap is not None else None
+    rows = EL.evaluate_rows(model, image_datasets, text_embeddings, device, img_size, dataset, batch_size=batch_size,
+                            loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm, device_metrics=device_metrics,
+                            fpr_limit=aupro_limit, f1_max=f1_max, details=details, return_masks=return_masks,
+                            defects=defects, support=banks, support_weight=support_weight, bootstrap=bootstrap,
+                            after_class=after_class)
+    write_defects_of(defects, save_path, dataset, details)
+    return rows, details
+
+
+def write_defects_of(defects, save_path, dataset: str, details) -> None:
+    """write_defects where the evaluation asked for defects and has a save_path, in the process of rank 0"""
+    if defects is not None and save_path is not None and int(os.environ.get("RANK", "0")) == 0:
+        write_defects(save_path, dataset, details)
 
 
 def format_table(rows: List[dict]) -> str:
@@ -95,20 +128,27 @@ def build_parser() -> argparse.ArgumentParser:
     return parser
 
 
+def check_arguments(parser: argparse.ArgumentParser, args) -> None:
+    if args.defects is not None and args.defects < 1:
+        parser.error("--defects takes a minimum area of at least 1 pixel")
+
+
+def log_table(logger, rows) -> None:
+    """this module's table into the log and onto the terminal: how the scripts above this one end"""
+    table = format_table(rows)
+    logger.info("final results:\n%s", table)
+    print(table)
+
+
 def run(parser: argparse.ArgumentParser, argv=None):
     """Without --defects: eval_last.run, which is what eval_metrics.py runs.  With it: the same steps with the regions
     asked for, this module's table, and the .jsonl files written by rank 0."""
     args = parser.parse_args(argv)
     if args.defects is None:
         return EL.run(parser, argv)
-    if args.defects < 1:
-        parser.error("--defects takes a minimum area of at least 1 pixel")
-
-    def finish(args, rows, details):
-        if int(os.environ.get("RANK", "0")) == 0:
-            write_defects(args.save_path, args.dataset, details)
-
-    return EL.run(parser, argv, table=format_table, finish=finish)
+    check_arguments(parser, args)
+    return EL.run(parser, argv, table=format_table,
+                  finish=lambda args, rows, details: write_defects_of(args.defects, args.save_path, args.dataset, details))
 
 
 def main(argv=None):

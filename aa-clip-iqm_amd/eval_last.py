@@ -30,6 +30,8 @@ the same names and arguments:
                                           (support_banks(coreset=R) reduces every bank to the greedy coreset of the
                                           share R of its rows, an engine.CoresetBank; eval_coreset.py is the script
                                           with --support_coreset)
+  open_session(args, name, canvas)        the set-up of every script of the tower, once: seed, test.log, device, model,
+                                          adapters, datasets, text embeddings, --support_meta datasets
   main(argv)                              the arguments and steps of test_last.main plus --device_metrics
 
 python eval_last.py --save_path ... [--device_metrics] [every argument of test_last.py]
@@ -37,6 +39,7 @@ python eval_last.py --save_path ... [--device_metrics] [every argument of test_l
 from __future__ import annotations
 
 import argparse
+import collections
 import logging
 import os
 from glob import glob
@@ -397,37 +400,44 @@ def main(argv=None):
     return run(build_parser(), argv)
 
 
-def run(parser: argparse.ArgumentParser, argv=None, table=None, finish=None):
-    """main() for a parser that may carry further arguments: `aupro` (eval_aupro.py), a false-positive rate or None,
-    `f1max` (eval_metrics.py), which adds the F1-max columns and logs every class's thresholds, and `defects`
-    (eval_defects.py), a minimum area or None, which implies f1max and adds the region-level columns, and `support`
-    (eval_support.py), a number of shots or None, with `support_weight`, `support_form` and `support_meta` beside it: the
-    banks of support_banks are built after the text embeddings and every class is evaluated with its bank.  table: the
-    function that formats the rows (format_table); finish(args, rows, details): called after the evaluation when the
-    F1-max path ran."""
-    from dataset import get_dataset
-    from forward_utils import get_adapted_text_embedding
-    from model.adapter import AdaptedCLIP
-    from model.clip import create_model
-    args = parser.parse_args(argv)
-    defects = getattr(args, "defects", None)
-    aupro, f1_max = getattr(args, "aupro", None), bool(getattr(args, "f1max", False)) or defects is not None
+def check_arguments(parser: argparse.ArgumentParser, args) -> None:
+    """what this script and eval_aupro.py refuse"""
+    aupro = getattr(args, "aupro", None)
     if args.iqm_hidden_size != 768:
         parser.error("--iqm_hidden_size must be 768 (the visual features' width; see test_last.py)")
     if aupro is not None and not 0.0 < aupro <= 1.0:
         parser.error("--aupro takes a false-positive rate in (0, 1]")
+
+
+Session = collections.namedtuple("Session", "logger device clip_model model adapt_text image_datasets text_embeddings "
+                                            "support_datasets")
+
+
+def open_session(args, name: str, canvas=None, log_lines=()) -> Session:
+    """What every script of the tower sets up before it evaluates, once: the seed, <save_path>/test.log with a logger
+    called `name` (the `args:` line, then log_lines), the device (and, under WORLD_SIZE > 1, the process group), the CLIP
+    model and the AdaptedCLIP around it at --img_size with the adapters of load_adapters, the datasets at `canvas` pixels
+    (None: --img_size; eval_tiled.py's frames are larger than the model's side), the text embeddings -- of the adapted
+    model where a text adapter was loaded -- and, for --support K with --support_meta, that file's datasets at the canvas
+    size (else None).  Arguments that the lower parsers lack count as absent."""
+    from dataset import DATA_PATH, BaseSingleClassDataset, get_dataset
+    from forward_utils import get_adapted_text_embedding
+    from model.adapter import AdaptedCLIP
+    from model.clip import create_model
+    canvas = args.img_size if canvas is None else canvas
     TL.setup_seed(args.seed)
     os.makedirs(args.save_path, exist_ok=True)
-    logger = logging.getLogger(__name__)
+    logger = logging.getLogger(name)
     logging.basicConfig(filename=os.path.join(args.save_path, "test.log"), encoding="utf-8", level=logging.INFO)
     logger.info("args: %s", vars(args))
+    for line in log_lines:
+        logger.info("%s", line)
     if not torch.cuda.is_available():
         raise RuntimeError("the AA-CLIP HIP path needs an MI355X; there is no CPU fallback")
-    world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
-    if world > 1:
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(os.environ.get("AACLIP_BENCH_BACKEND", "nccl"))
@@ -441,28 +451,45 @@ def run(parser: argparse.ArgumentParser, argv=None, table=None, finish=None):
                         iqm_num_heads=args.iqm_num_heads).to(device)
     model.eval()
     adapt_text = load_adapters(model, args.save_path, logger)
-    image_datasets = get_dataset(args.dataset, args.img_size, None, args.shot, "test", logger=logger,
+    image_datasets = get_dataset(args.dataset, canvas, None, args.shot, "test", logger=logger,
                                  device_preprocess=args.device_preprocess)
     with torch.no_grad():
         text_embeddings = get_adapted_text_embedding(model if adapt_text else clip_model, args.dataset, device)
+    support_datasets = None
+    if getattr(args, "support", None) is not None and getattr(args, "support_meta", None):
+        support_datasets = {c: BaseSingleClassDataset(DATA_PATH[args.dataset], args.support_meta, canvas, c,
+                                                      device_preprocess=args.device_preprocess) for c in image_datasets}
+    return Session(logger, device, clip_model, model, adapt_text, image_datasets, text_embeddings, support_datasets)
+
+
+def run(parser: argparse.ArgumentParser, argv=None, table=None, finish=None):
+    """main() for a parser that may carry further arguments: `aupro` (eval_aupro.py), a false-positive rate or None,
+    `f1max` (eval_metrics.py), which adds the F1-max columns and logs every class's thresholds, and `defects`
+    (eval_defects.py), a minimum area or None, which implies f1max and adds the region-level columns, and `support`
+    (eval_support.py), a number of shots or None, with `support_weight`, `support_form` and `support_meta` beside it: the
+    banks of support_banks are built after the text embeddings and every class is evaluated with its bank.  table: the
+    function that formats the rows (format_table); finish(args, rows, details): called after the evaluation when the
+    F1-max path ran."""
+    args = parser.parse_args(argv)
+    defects = getattr(args, "defects", None)
+    aupro, f1_max = getattr(args, "aupro", None), bool(getattr(args, "f1max", False)) or defects is not None
+    check_arguments(parser, args)
+    session = open_session(args, __name__)
+    logger, device, model, image_datasets = session.logger, session.device, session.model, session.image_datasets
     shots, bank = getattr(args, "support", None), {}
     if shots is not None:
-        support_sets = None
-        if getattr(args, "support_meta", None):
-            from dataset import DATA_PATH, BaseSingleClassDataset
-            support_sets = {c: BaseSingleClassDataset(DATA_PATH[args.dataset], args.support_meta, args.img_size, c,
-                                                      device_preprocess=args.device_preprocess) for c in image_datasets}
         coreset = getattr(args, "support_coreset", None)
         core = {} if coreset is None else {"coreset": coreset, "coreset_dim": getattr(args, "support_coreset_dim", 128)}
         banks, image_datasets = support_banks(model, image_datasets, shots, device, args.img_size,
-                                              form=getattr(args, "support_form", None), support_datasets=support_sets,
+                                              form=getattr(args, "support_form", None),
+                                              support_datasets=session.support_datasets,
                                               batch_size=args.image_batch_size, **core)
         bank = {"support": banks, "support_weight": getattr(args, "support_weight", SUPPORT_WEIGHT)}
         logger.info("support banks: %d shots per class, form %s, weight %s", shots,
                     "fp16" if next(iter(banks.values())).form == engine.SUPPORT_FP16 else "fp32", bank["support_weight"])
         if coreset is not None:
             log_coreset(logger, banks)
-    where = (model, image_datasets, text_embeddings, device, args.img_size, args.dataset)
+    where = (model, image_datasets, session.text_embeddings, device, args.img_size, args.dataset)
     how = dict(batch_size=args.image_batch_size, loader_kwargs={"num_workers": 4, "pin_memory": True}, logger=logger,
                use_iqm=args.iqm == "on", device_metrics=args.device_metrics)
     if f1_max:
@@ -481,7 +508,7 @@ def run(parser: argparse.ArgumentParser, argv=None, table=None, finish=None):
     logger.info("final results:\n%s", table)
     if int(os.environ.get("RANK", "0")) == 0:
         print(table)
-    if world > 1:
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         torch.distributed.destroy_process_group()
     return rows
 

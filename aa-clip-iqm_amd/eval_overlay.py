@@ -25,7 +25,6 @@ from __future__ import annotations
 
 import argparse
 import concurrent.futures
-import logging
 import os
 
 import numpy as np
@@ -34,7 +33,6 @@ import torch
 import eval_defects as ED
 import eval_last as EL
 import eval_tiled as ET
-import test_last as TL
 from aaclip_hip import engine
 from forward_utils import SUPPORT_WEIGHT, TILE_OVERLAP, render_overlays
 
@@ -74,6 +72,12 @@ def _range_record(preds, device) -> torch.Tensor:
     return torch.from_numpy(record).to(device)
 
 
+def _submit_pillow(pool, panels: torch.Tensor, paths) -> list:
+    """one batch of rendered panels -> the futures of its files: the panels come to the host, the pool's threads encode"""
+    host = panels.cpu().numpy()
+    return [pool.submit(_save_png, path, host[i]) for i, path in enumerate(paths)]
+
+
 def write_overlays(folder: str, image_dataset, masks, preds, file_names, pred_masks, device, alpha: float = OVERLAY_ALPHA,
                    limit=None, thickness: int = 1, colormap: str = "jet", batch_size: int = 32, loader_kwargs=None) -> list:
     """The overlay pass over one evaluated class: `image_dataset` is walked again in file order, every batch of frames is
@@ -83,6 +87,13 @@ def write_overlays(folder: str, image_dataset, masks, preds, file_names, pred_ma
     [N, H, W], pred_masks [N, H, W] or None: device tensors (the device metrics path) or host arrays, which are uploaded
     batch by batch.  limit: None or the number of leading images.  One batch of panels is held at a time.
     -> the paths written, in file order."""
+    return _overlay_pass(_submit_pillow, folder, image_dataset, masks, preds, file_names, pred_masks, device, alpha, limit,
+                         thickness, colormap, batch_size, loader_kwargs)
+
+
+def _overlay_pass(submit, folder: str, image_dataset, masks, preds, file_names, pred_masks, device, alpha, limit, thickness,
+                  colormap, batch_size, loader_kwargs) -> list:
+    """write_overlays, with submit(pool, panels, paths) -> futures as the step that turns a rendered batch into files"""
     n = len(file_names) if limit is None else max(0, min(int(limit), len(file_names)))
     if len(image_dataset) != len(file_names) or len(preds) != len(file_names):
         raise ValueError(f"overlays: {len(image_dataset)} images, {len(preds)} maps and {len(file_names)} file names")
@@ -116,8 +127,7 @@ def write_overlays(folder: str, image_dataset, masks, preds, file_names, pred_ma
                                      pred, truth, lut=colormap, alpha256=int(round(float(alpha) * 256)), thickness=thickness)
             for f in pending:                                    # the batch before this one is on disk: one batch is held
                 f.result()
-            host = panels.cpu().numpy()
-            pending = [pool.submit(_save_png, paths[done + i], host[i]) for i in range(b)]
+            pending = submit(pool, panels, paths[done:done + b])
             done += b
         for f in pending:
             f.result()
@@ -126,21 +136,53 @@ def write_overlays(folder: str, image_dataset, masks, preds, file_names, pred_ma
     return paths
 
 
-def overlay_callback(save_path: str, dataset: str, device, alpha: float, limit=None, thickness: int = 1, colormap: str = "jet",
-                     batch_size: int = 32, loader_kwargs=None, defects=None, written=None):
-    """-> the after_class callable of eval_last.evaluate_rows / eval_tiled.evaluate_tiled that runs write_overlays for the
-    class: the predicted masks are details["kept masks"] with defects, else details["masks"].  written: None or a dict
-    that receives {class name: paths}."""
+def mask_callback(what: str, defects, *passes):
+    """-> the after_class callable of eval_last.evaluate_rows / eval_tiled.evaluate_tiled that hands the class's predicted
+    masks -- details["kept masks"] with defects, else details["masks"] -- to every pass, called as
+    pass(class_name, image_dataset, masks, preds, file_names, pred_masks).  what: the files' name in the error."""
     def after_class(class_name, image_dataset, masks, labels, preds, preds_image, file_names, details):
         if details is None or "masks" not in details:
-            raise ValueError("overlays need the masks at the pixel F1-max threshold (f1_max=True, return_masks=True)")
+            raise ValueError(f"{what} need the masks at the pixel F1-max threshold (f1_max=True, return_masks=True)")
         pred_masks = details["kept masks"] if defects is not None else details["masks"]
+        for write in passes:
+            write(class_name, image_dataset, masks, preds, file_names, pred_masks)
+    return after_class
+
+
+def overlay_callback(save_path: str, dataset: str, device, alpha: float, limit=None, thickness: int = 1, colormap: str = "jet",
+                     batch_size: int = 32, loader_kwargs=None, defects=None, written=None):
+    """-> the after_class callable that runs write_overlays for the class (mask_callback picks the predicted masks).
+    written: None or a dict that receives {class name: paths}."""
+    def overlays(class_name, image_dataset, masks, preds, file_names, pred_masks):
         folder = os.path.join(save_path, "overlays", dataset, class_name)
         paths = write_overlays(folder, image_dataset, masks, preds, file_names, pred_masks, device, alpha=alpha, limit=limit,
                                thickness=thickness, colormap=colormap, batch_size=batch_size, loader_kwargs=loader_kwargs)
         if written is not None:
             written[class_name] = paths
-    return after_class
+    return mask_callback("overlays", defects, overlays)
+
+
+def check_files(one_process: str, needs_save_path: str, save_path, overlay, overlay_thickness, overlay_colormap) -> None:
+    """what evaluate refuses before it writes overlays or masks; the two messages are the caller's"""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise ValueError(one_process)
+    if save_path is None:
+        raise ValueError(needs_save_path)
+    if overlay is not None and (not 0.0 <= float(overlay) <= 1.0
+                                or not 0 <= int(overlay_thickness) <= engine.OVERLAY_MAX_THICKNESS):
+        raise ValueError("evaluate: overlay takes an alpha in 0 .. 1 and overlay_thickness 0 .. 8")
+    engine.overlay_lut(overlay_colormap)
+
+
+def own_masks_only(rows, details, return_masks: bool):
+    """-> (rows, details) with return_masks; else rows, and the masks that were asked for on the files' behalf are dropped"""
+    if return_masks:
+        return rows, details
+    for d in details.values():
+        for key in ("masks", "kept masks", "support nearest"):
+            d.pop(key, None)
+    return rows
 
 
 def evaluate(model, image_datasets, text_embeddings, device, img_size: int, dataset: str, batch_size: int = 32,
@@ -155,57 +197,21 @@ def evaluate(model, image_datasets, text_embeddings, device, img_size: int, data
     a dict that receives {class name: paths}).  overlay implies f1_max and needs save_path; the rows and the return
     value are those of eval_tiled.evaluate with f1_max=True.  One process only."""
     where = (model, image_datasets, text_embeddings, device, img_size, dataset)
+    below = dict(batch_size=batch_size, loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm,
+                 device_metrics=device_metrics, aupro_limit=aupro_limit, f1_max=f1_max, return_masks=return_masks,
+                 defects=defects, save_path=save_path, support=support, support_weight=support_weight,
+                 support_form=support_form, support_datasets=support_datasets, coreset=coreset, coreset_dim=coreset_dim)
     if overlay is None:
-        return ET.evaluate(*where, batch_size=batch_size, loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm,
-                           device_metrics=device_metrics, aupro_limit=aupro_limit, f1_max=f1_max, return_masks=return_masks,
-                           defects=defects, save_path=save_path, support=support, support_weight=support_weight,
-                           support_form=support_form, support_datasets=support_datasets, coreset=coreset,
-                           coreset_dim=coreset_dim, tiles=tiles, tile_overlap=tile_overlap)
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise ValueError("overlays are written by one process (sharded evaluation with overlays is not part of it)")
-    if save_path is None:
-        raise ValueError("evaluate: overlay needs save_path (the overlays go to <save_path>/overlays)")
-    if not 0.0 <= float(overlay) <= 1.0 or not 0 <= int(overlay_thickness) <= engine.OVERLAY_MAX_THICKNESS:
-        raise ValueError("evaluate: overlay takes an alpha in 0 .. 1 and overlay_thickness 0 .. 8")
-    engine.overlay_lut(overlay_colormap)
-    if coreset is not None and support is None:
-        raise ValueError("evaluate: coreset needs support=K")
+        return ET.evaluate(*where, **below, tiles=tiles, tile_overlap=tile_overlap)
+    check_files("overlays are written by one process (sharded evaluation with overlays is not part of it)",
+                "evaluate: overlay needs save_path (the overlays go to <save_path>/overlays)", save_path, overlay,
+                overlay_thickness, overlay_colormap)
     after = overlay_callback(save_path, dataset, device, float(overlay), limit=overlay_limit, thickness=int(overlay_thickness),
-                             colormap=overlay_colormap, batch_size=batch_size if tiles is None else
-                             max(1, batch_size // (int(tiles) ** 2)), loader_kwargs=loader_kwargs, defects=defects,
-                             written=overlay_written)
-    if tiles is not None:
-        rows, details = ET.evaluate_details(*where, (tiles, tile_overlap), batch_size=batch_size, loader_kwargs=loader_kwargs,
-                                            logger=logger, use_iqm=use_iqm, device_metrics=device_metrics,
-                                            aupro_limit=aupro_limit, f1_max=True, return_masks=True, defects=defects,
-                                            save_path=save_path, support=support, support_weight=support_weight,
-                                            support_form=support_form, support_datasets=support_datasets, coreset=coreset,
-                                            coreset_dim=coreset_dim, after_class=after)
-    else:
-        banks = None
-        if support is not None:
-            core = {} if coreset is None else {"coreset": coreset, "coreset_dim": coreset_dim}
-            banks, image_datasets = EL.support_banks(model, image_datasets, support, device, img_size, form=support_form,
-                                                     support_datasets=support_datasets, batch_size=batch_size, **core)
-            if logger and coreset is not None:
-                EL.log_coreset(logger, banks)
-        details = {}
-        extra = {} if defects is None else {"defects": defects}
-        if banks is not None:
-            extra.update(support=banks, support_weight=support_weight)
-        rows = EL.evaluate_rows(model, image_datasets, text_embeddings, device, img_size, dataset, batch_size=batch_size,
-                                loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm, device_metrics=device_metrics,
-                                fpr_limit=aupro_limit, f1_max=True, details=details, return_masks=True, after_class=after,
-                                **extra)
-        if defects is not None:
-            ED.write_defects(save_path, dataset, details)
-    if return_masks:
-        return rows, details
-    for d in details.values():               # the masks were asked for on the overlays' behalf only
-        for key in ("masks", "kept masks", "support nearest"):
-            d.pop(key, None)
-    return rows
+                             colormap=overlay_colormap, batch_size=ET.frames_per_batch(batch_size, tiles),
+                             loader_kwargs=loader_kwargs, defects=defects, written=overlay_written)
+    rows, details = ET.evaluate_details(*where, None if tiles is None else (tiles, tile_overlap),
+                                        **dict(below, f1_max=True, return_masks=True), after_class=after)
+    return own_masks_only(rows, details, return_masks)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -223,7 +229,8 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def _check_arguments(parser: argparse.ArgumentParser, args) -> None:
-    if not 0.0 <= args.overlay <= 1.0:
+    """this script's checks (the alpha where --overlay is given: eval_png.py writes masks without it), then eval_tiled's"""
+    if args.overlay is not None and not 0.0 <= args.overlay <= 1.0:
         parser.error("--overlay takes the frame's weight in 0 .. 1")
     if args.overlay_limit is not None and args.overlay_limit < 0:
         parser.error("--overlay_limit takes a number of images")
@@ -231,82 +238,39 @@ def _check_arguments(parser: argparse.ArgumentParser, args) -> None:
         parser.error("--overlay_thickness takes 0 .. 8 pixels")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         parser.error("--overlay runs in one process: sharded evaluation with overlays is not part of this script")
-    if args.tiles is not None:
-        ET._check_arguments(parser, args)
-        return
-    if args.iqm_hidden_size != 768:
-        parser.error("--iqm_hidden_size must be 768 (the visual features' width; see test_last.py)")
-    if args.aupro is not None and not 0.0 < args.aupro <= 1.0:
-        parser.error("--aupro takes a false-positive rate in (0, 1]")
-    if args.defects is not None and args.defects < 1:
-        parser.error("--defects takes a minimum area of at least 1 pixel")
-    if args.support is None and (args.support_meta is not None or args.support_coreset is not None):
-        parser.error("--support_meta and --support_coreset need --support K")
-    if args.support is not None and args.support < 1:
-        parser.error("--support takes at least 1 shot")
-    if args.support_coreset is not None:
-        if not 0.0 < args.support_coreset <= 1.0:
-            parser.error("--support_coreset takes a share in (0, 1]")
-        if args.support_coreset_dim < 0 or args.support_coreset_dim % 128:
-            parser.error("--support_coreset_dim takes 0 or a multiple of 128")
+    ET._check_arguments(parser, args)
+
+
+def open_session(args, name: str):
+    """eval_last.open_session with the datasets at the canvas size of --tiles: -> (session, where), where = the six
+    leading arguments of evaluate"""
+    canvas = args.img_size if args.tiles is None else ET.tile_geometry(args.img_size, args.tiles, args.tile_overlap)[3]
+    session = EL.open_session(args, name, canvas)
+    return session, (session.model, session.image_datasets, session.text_embeddings, session.device, args.img_size,
+                     args.dataset)
+
+
+def overlay_keywords(args) -> dict:
+    """the keywords of evaluate that --tiles and the --overlay flags set"""
+    return dict(tiles=args.tiles, tile_overlap=args.tile_overlap, overlay=args.overlay, overlay_limit=args.overlay_limit,
+                overlay_thickness=args.overlay_thickness, overlay_colormap=args.overlay_colormap)
 
 
 def run(parser: argparse.ArgumentParser, argv=None):
-    """Without --overlay: eval_tiled.run.  With it: the steps of eval_tiled.run (the datasets built at the canvas size
-    with --tiles, at --img_size without) and this module's evaluate."""
+    """Without --overlay: eval_tiled.run.  With it: the session (the datasets built at the canvas size with --tiles, at
+    --img_size without) and this module's evaluate."""
     args = parser.parse_args(argv)
     if args.overlay is None:
         return ET.run(parser, argv)
     _check_arguments(parser, args)
-    from dataset import DATA_PATH, BaseSingleClassDataset, get_dataset
-    from forward_utils import get_adapted_text_embedding
-    from model.adapter import AdaptedCLIP
-    from model.clip import create_model
-    S = args.img_size
-    C = S if args.tiles is None else ET.tile_geometry(S, args.tiles, args.tile_overlap)[3]
-    TL.setup_seed(args.seed)
-    os.makedirs(args.save_path, exist_ok=True)
-    logger = logging.getLogger(__name__)
-    logging.basicConfig(filename=os.path.join(args.save_path, "test.log"), encoding="utf-8", level=logging.INFO)
-    logger.info("args: %s", vars(args))
-    if not torch.cuda.is_available():
-        raise RuntimeError("the AA-CLIP HIP path needs an MI355X; there is no CPU fallback")
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
-    torch.cuda.set_device(device)
-    clip_model = create_model(model_name=args.model_name, img_size=S, device=device, pretrained="openai",
-                              require_pretrained=True, precision=args.precision)
-    clip_model.eval()
-    model = AdaptedCLIP(clip_model=clip_model, text_adapt_weight=args.text_adapt_weight,
-                        image_adapt_weight=args.image_adapt_weight, text_adapt_until=args.text_adapt_until,
-                        image_adapt_until=args.image_adapt_until, relu=args.relu,
-                        iqm_hidden_size=args.iqm_hidden_size, iqm_num_layers=args.iqm_num_layers,
-                        iqm_num_heads=args.iqm_num_heads).to(device)
-    model.eval()
-    adapt_text = EL.load_adapters(model, args.save_path, logger)
-    image_datasets = get_dataset(args.dataset, C, None, args.shot, "test", logger=logger,
-                                 device_preprocess=args.device_preprocess)
-    with torch.no_grad():
-        text_embeddings = get_adapted_text_embedding(model if adapt_text else clip_model, args.dataset, device)
-    support_sets = None
-    if args.support is not None and args.support_meta:
-        support_sets = {c: BaseSingleClassDataset(DATA_PATH[args.dataset], args.support_meta, C, c,
-                                                  device_preprocess=args.device_preprocess) for c in image_datasets}
+    session, where = open_session(args, __name__)
     written = {}
-    rows, details = evaluate(model, image_datasets, text_embeddings, device, S, args.dataset, batch_size=args.image_batch_size,
-                             loader_kwargs={"num_workers": 4, "pin_memory": True}, logger=logger, use_iqm=args.iqm == "on",
-                             device_metrics=args.device_metrics, aupro_limit=args.aupro, f1_max=True, return_masks=True,
-                             defects=args.defects, save_path=args.save_path, support=args.support,
-                             support_weight=args.support_weight, support_form=args.support_form,
-                             support_datasets=support_sets, coreset=args.support_coreset,
-                             coreset_dim=args.support_coreset_dim, tiles=args.tiles, tile_overlap=args.tile_overlap,
-                             overlay=args.overlay, overlay_limit=args.overlay_limit, overlay_thickness=args.overlay_thickness,
-                             overlay_colormap=args.overlay_colormap, overlay_written=written)
+    rows, details = evaluate(*where, f1_max=True, return_masks=True, **ET.session_keywords(args, session),
+                             **overlay_keywords(args), overlay_written=written)
     for name, d in details.items():
-        logger.info("%s: pixel threshold %.9g, image threshold %s (normalised units); %d overlays", name,
-                    d["pixel threshold"], d["image threshold"], len(written.get(name, ())))
-    table = ED.format_table(rows)
-    logger.info("final results:\n%s", table)
-    print(table)
+        session.logger.info("%s: pixel threshold %.9g, image threshold %s (normalised units); %d overlays", name,
+                            d["pixel threshold"], d["image threshold"], len(written.get(name, ())))
+    ED.log_table(session.logger, rows)
     return rows
 
 

@@ -23,19 +23,16 @@ from __future__ import annotations
 
 import argparse
 import concurrent.futures
-import logging
 import os
 
 import numpy as np
 import torch
 
 import eval_defects as ED
-import eval_last as EL
 import eval_overlay as EO
 import eval_tiled as ET
-import test_last as TL
 from aaclip_hip import engine
-from forward_utils import SUPPORT_WEIGHT, TILE_OVERLAP, png_file, render_overlays
+from forward_utils import SUPPORT_WEIGHT, TILE_OVERLAP, png_file
 
 ENCODERS = ("device", "pillow")
 
@@ -69,49 +66,9 @@ def write_overlays(folder: str, image_dataset, masks, preds, file_names, pred_ma
     of panels compressed on the GPU (submit_device_pngs).  The files decode to the same pixels.  -> the paths written."""
     if encoder not in ENCODERS:
         raise ValueError(f"overlays: encoder must be one of {ENCODERS}, got {encoder!r}")
-    if encoder == "pillow":
-        return EO.write_overlays(folder, image_dataset, masks, preds, file_names, pred_masks, device, alpha=alpha, limit=limit,
-                                 thickness=thickness, colormap=colormap, batch_size=batch_size, loader_kwargs=loader_kwargs)
-    n = len(file_names) if limit is None else max(0, min(int(limit), len(file_names)))
-    if len(image_dataset) != len(file_names) or len(preds) != len(file_names):
-        raise ValueError(f"overlays: {len(image_dataset)} images, {len(preds)} maps and {len(file_names)} file names")
-    paths = EO.overlay_paths(folder, list(file_names)[:n])       # before anything is written
-    if n == 0:
-        return paths
-    H, W = (int(v) for v in preds.shape[-2:])
-    record = EO._range_record(preds, device)
-    to_device = lambda a, dtype: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device).to(dtype)
-    os.makedirs(folder, exist_ok=True)
-    loader = torch.utils.data.DataLoader(image_dataset, batch_size=batch_size, shuffle=False, **(loader_kwargs or {}))
-    done, pending = 0, []
-    with concurrent.futures.ThreadPoolExecutor(max_workers=EO.OVERLAY_WRITERS) as pool:
-        for batch in loader:
-            if done >= n:
-                break
-            if list(batch["file_name"]) != list(file_names[done:done + len(batch["file_name"])]):
-                raise ValueError("overlays: the dataset's second walk does not give the file order of the maps")
-            b = min(len(batch["file_name"]), n - done)
-            image = batch["image"][:b].to(device, non_blocking=True)
-            if image.dtype == torch.uint8:                       # raw HWC frames: resize to the maps' side + normalise
-                if H != W:
-                    raise ValueError(f"overlays: raw frames need square maps, got {H} x {W}")
-                image = engine.preprocess(image, H)
-            if tuple(image.shape[-2:]) != (H, W):
-                raise ValueError(f"overlays: frames of {tuple(image.shape[-2:])} px for maps of {H} x {W} px")
-            rows = slice(done, done + b)
-            truth = (to_device(masks[rows], torch.float32).reshape(b, H, W) != 0).to(torch.uint8).contiguous()
-            pred = None if pred_masks is None else to_device(pred_masks[rows], torch.uint8).reshape(b, H, W).contiguous()
-            panels = render_overlays(image.float().contiguous(), to_device(preds[rows], torch.float32).contiguous(), record,
-                                     pred, truth, lut=colormap, alpha256=int(round(float(alpha) * 256)), thickness=thickness)
-            for f in pending:                                    # the batch before this one is on disk: one batch is held
-                f.result()
-            pending = submit_device_pngs(pool, panels, paths[done:done + b])
-            done += b
-        for f in pending:
-            f.result()
-    if done != n:
-        raise ValueError(f"overlays: the dataset gave {done} of {n} images")
-    return paths
+    submit = submit_device_pngs if encoder == "device" else EO._submit_pillow
+    return EO._overlay_pass(submit, folder, image_dataset, masks, preds, file_names, pred_masks, device, alpha, limit,
+                            thickness, colormap, batch_size, loader_kwargs)
 
 
 def write_masks(folder: str, file_names, pred_masks, device, encoder: str = "pillow", batch_size: int = 32) -> list:
@@ -151,25 +108,41 @@ def write_masks(folder: str, file_names, pred_masks, device, encoder: str = "pil
 def png_callback(save_path: str, dataset: str, device, overlay=None, encoder: str = "pillow", masks_png: bool = False,
                  limit=None, thickness: int = 1, colormap: str = "jet", batch_size: int = 32, loader_kwargs=None,
                  defects=None, written=None, masks_written=None):
-    """-> the after_class callable that writes a class's overlays (overlay: None or ALPHA) and its masks (masks_png); the
-    predicted masks are details["kept masks"] with defects, else details["masks"].  written / masks_written: None or
-    dicts that receive {class name: paths}."""
-    def after_class(class_name, image_dataset, masks, labels, preds, preds_image, file_names, details):
-        if details is None or "masks" not in details:
-            raise ValueError("overlays and masks need the masks at the pixel F1-max threshold (f1_max=True, return_masks=True)")
-        pred_masks = details["kept masks"] if defects is not None else details["masks"]
-        if overlay is not None:
-            paths = write_overlays(os.path.join(save_path, "overlays", dataset, class_name), image_dataset, masks, preds,
-                                   file_names, pred_masks, device, alpha=overlay, limit=limit, thickness=thickness,
-                                   colormap=colormap, batch_size=batch_size, loader_kwargs=loader_kwargs, encoder=encoder)
-            if written is not None:
-                written[class_name] = paths
-        if masks_png:
-            paths = write_masks(os.path.join(save_path, "masks", dataset, class_name), file_names, pred_masks, device,
-                                encoder=encoder, batch_size=batch_size)
-            if masks_written is not None:
-                masks_written[class_name] = paths
-    return after_class
+    """-> the after_class callable that writes a class's overlays (overlay: None or ALPHA) and its masks (masks_png) from
+    the predicted masks that eval_overlay.mask_callback picks.  written / masks_written: None or dicts that receive
+    {class name: paths}."""
+    def overlays(class_name, image_dataset, masks, preds, file_names, pred_masks):
+        paths = write_overlays(os.path.join(save_path, "overlays", dataset, class_name), image_dataset, masks, preds,
+                               file_names, pred_masks, device, alpha=overlay, limit=limit, thickness=thickness,
+                               colormap=colormap, batch_size=batch_size, loader_kwargs=loader_kwargs, encoder=encoder)
+        if written is not None:
+            written[class_name] = paths
+
+    def mask_files(class_name, image_dataset, masks, preds, file_names, pred_masks):
+        paths = write_masks(os.path.join(save_path, "masks", dataset, class_name), file_names, pred_masks, device,
+                            encoder=encoder, batch_size=batch_size)
+        if masks_written is not None:
+            masks_written[class_name] = paths
+
+    passes = ([overlays] if overlay is not None else []) + ([mask_files] if masks_png else [])
+    return EO.mask_callback("overlays and masks", defects, *passes)
+
+
+def check_encoder(overlay_encoder) -> None:
+    if overlay_encoder not in ENCODERS:
+        raise ValueError(f"evaluate: overlay_encoder must be one of {ENCODERS}, got {overlay_encoder!r}")
+
+
+def files_callback(save_path, dataset: str, device, batch_size: int, loader_kwargs, defects, tiles, *, overlay, overlay_limit,
+                   overlay_thickness, overlay_colormap, overlay_written, overlay_encoder, masks_png, masks_written):
+    """evaluate's keywords -> what it refuses before it writes files (eval_overlay.check_files), then its png_callback"""
+    EO.check_files("overlays and masks are written by one process (sharded evaluation with them is not part of it)",
+                   "evaluate: overlay and masks_png need save_path (the files go to <save_path>/overlays and /masks)",
+                   save_path, overlay, overlay_thickness, overlay_colormap)
+    return png_callback(save_path, dataset, device, overlay=None if overlay is None else float(overlay),
+                        encoder=overlay_encoder, masks_png=masks_png, limit=overlay_limit, thickness=int(overlay_thickness),
+                        colormap=overlay_colormap, batch_size=ET.frames_per_batch(batch_size, tiles),
+                        loader_kwargs=loader_kwargs, defects=defects, written=overlay_written, masks_written=masks_written)
 
 
 def evaluate(model, image_datasets, text_embeddings, device, img_size: int, dataset: str, batch_size: int = 32,
@@ -185,63 +158,22 @@ def evaluate(model, image_datasets, text_embeddings, device, img_size: int, data
     overlay.  Either implies f1_max and needs save_path; the rows and the return value are those of eval_overlay.evaluate
     with f1_max=True.  One process only."""
     where = (model, image_datasets, text_embeddings, device, img_size, dataset)
-    if overlay_encoder not in ENCODERS:
-        raise ValueError(f"evaluate: overlay_encoder must be one of {ENCODERS}, got {overlay_encoder!r}")
+    below = dict(batch_size=batch_size, loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm,
+                 device_metrics=device_metrics, aupro_limit=aupro_limit, f1_max=f1_max, return_masks=return_masks,
+                 defects=defects, save_path=save_path, support=support, support_weight=support_weight,
+                 support_form=support_form, support_datasets=support_datasets, coreset=coreset, coreset_dim=coreset_dim)
+    check_encoder(overlay_encoder)
     if not masks_png and (overlay is None or overlay_encoder == "pillow"):
-        return EO.evaluate(*where, batch_size=batch_size, loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm,
-                           device_metrics=device_metrics, aupro_limit=aupro_limit, f1_max=f1_max, return_masks=return_masks,
-                           defects=defects, save_path=save_path, support=support, support_weight=support_weight,
-                           support_form=support_form, support_datasets=support_datasets, coreset=coreset,
-                           coreset_dim=coreset_dim, tiles=tiles, tile_overlap=tile_overlap, overlay=overlay,
+        return EO.evaluate(*where, **below, tiles=tiles, tile_overlap=tile_overlap, overlay=overlay,
                            overlay_limit=overlay_limit, overlay_thickness=overlay_thickness,
                            overlay_colormap=overlay_colormap, overlay_written=overlay_written)
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise ValueError("overlays and masks are written by one process (sharded evaluation with them is not part of it)")
-    if save_path is None:
-        raise ValueError("evaluate: overlay and masks_png need save_path (the files go to <save_path>/overlays and /masks)")
-    if overlay is not None and (not 0.0 <= float(overlay) <= 1.0
-                                or not 0 <= int(overlay_thickness) <= engine.OVERLAY_MAX_THICKNESS):
-        raise ValueError("evaluate: overlay takes an alpha in 0 .. 1 and overlay_thickness 0 .. 8")
-    engine.overlay_lut(overlay_colormap)
-    if coreset is not None and support is None:
-        raise ValueError("evaluate: coreset needs support=K")
-    after = png_callback(save_path, dataset, device, overlay=None if overlay is None else float(overlay),
-                         encoder=overlay_encoder, masks_png=masks_png, limit=overlay_limit, thickness=int(overlay_thickness),
-                         colormap=overlay_colormap, batch_size=batch_size if tiles is None else
-                         max(1, batch_size // (int(tiles) ** 2)), loader_kwargs=loader_kwargs, defects=defects,
-                         written=overlay_written, masks_written=masks_written)
-    if tiles is not None:
-        rows, details = ET.evaluate_details(*where, (tiles, tile_overlap), batch_size=batch_size, loader_kwargs=loader_kwargs,
-                                            logger=logger, use_iqm=use_iqm, device_metrics=device_metrics,
-                                            aupro_limit=aupro_limit, f1_max=True, return_masks=True, defects=defects,
-                                            save_path=save_path, support=support, support_weight=support_weight,
-                                            support_form=support_form, support_datasets=support_datasets, coreset=coreset,
-                                            coreset_dim=coreset_dim, after_class=after)
-    else:
-        banks = None
-        if support is not None:
-            core = {} if coreset is None else {"coreset": coreset, "coreset_dim": coreset_dim}
-            banks, image_datasets = EL.support_banks(model, image_datasets, support, device, img_size, form=support_form,
-                                                     support_datasets=support_datasets, batch_size=batch_size, **core)
-            if logger and coreset is not None:
-                EL.log_coreset(logger, banks)
-        details = {}
-        extra = {} if defects is None else {"defects": defects}
-        if banks is not None:
-            extra.update(support=banks, support_weight=support_weight)
-        rows = EL.evaluate_rows(model, image_datasets, text_embeddings, device, img_size, dataset, batch_size=batch_size,
-                                loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm, device_metrics=device_metrics,
-                                fpr_limit=aupro_limit, f1_max=True, details=details, return_masks=True, after_class=after,
-                                **extra)
-        if defects is not None:
-            ED.write_defects(save_path, dataset, details)
-    if return_masks:
-        return rows, details
-    for d in details.values():               # the masks were asked for on the files' behalf only
-        for key in ("masks", "kept masks", "support nearest"):
-            d.pop(key, None)
-    return rows
+    after = files_callback(save_path, dataset, device, batch_size, loader_kwargs, defects, tiles, overlay=overlay,
+                           overlay_limit=overlay_limit, overlay_thickness=overlay_thickness,
+                           overlay_colormap=overlay_colormap, overlay_written=overlay_written,
+                           overlay_encoder=overlay_encoder, masks_png=masks_png, masks_written=masks_written)
+    rows, details = ET.evaluate_details(*where, None if tiles is None else (tiles, tile_overlap),
+                                        **dict(below, f1_max=True, return_masks=True), after_class=after)
+    return EO.own_masks_only(rows, details, return_masks)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -255,70 +187,23 @@ def build_parser() -> argparse.ArgumentParser:
     return parser
 
 
-def _check_arguments(parser: argparse.ArgumentParser, args) -> None:
-    """eval_overlay's checks; without --overlay they run against its default alpha, which passes"""
-    probe = args if args.overlay is not None else argparse.Namespace(**dict(vars(args), overlay=EO.OVERLAY_ALPHA))
-    EO._check_arguments(parser, probe)
-
-
 def run(parser: argparse.ArgumentParser, argv=None):
-    """Without --masks_png and without --overlay with --overlay_encoder device: eval_overlay.run.  Else its steps and this
-    module's evaluate."""
+    """Without --masks_png and without --overlay with --overlay_encoder device: eval_overlay.run.  Else its checks and
+    session and this module's evaluate."""
     args = parser.parse_args(argv)
     if not args.masks_png and (args.overlay is None or args.overlay_encoder == "pillow"):
         return EO.run(parser, argv)
-    _check_arguments(parser, args)
-    from dataset import DATA_PATH, BaseSingleClassDataset, get_dataset
-    from forward_utils import get_adapted_text_embedding
-    from model.adapter import AdaptedCLIP
-    from model.clip import create_model
-    S = args.img_size
-    C = S if args.tiles is None else ET.tile_geometry(S, args.tiles, args.tile_overlap)[3]
-    TL.setup_seed(args.seed)
-    os.makedirs(args.save_path, exist_ok=True)
-    logger = logging.getLogger(__name__)
-    logging.basicConfig(filename=os.path.join(args.save_path, "test.log"), encoding="utf-8", level=logging.INFO)
-    logger.info("args: %s", vars(args))
-    if not torch.cuda.is_available():
-        raise RuntimeError("the AA-CLIP HIP path needs an MI355X; there is no CPU fallback")
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
-    torch.cuda.set_device(device)
-    clip_model = create_model(model_name=args.model_name, img_size=S, device=device, pretrained="openai",
-                              require_pretrained=True, precision=args.precision)
-    clip_model.eval()
-    model = AdaptedCLIP(clip_model=clip_model, text_adapt_weight=args.text_adapt_weight,
-                        image_adapt_weight=args.image_adapt_weight, text_adapt_until=args.text_adapt_until,
-                        image_adapt_until=args.image_adapt_until, relu=args.relu,
-                        iqm_hidden_size=args.iqm_hidden_size, iqm_num_layers=args.iqm_num_layers,
-                        iqm_num_heads=args.iqm_num_heads).to(device)
-    model.eval()
-    adapt_text = EL.load_adapters(model, args.save_path, logger)
-    image_datasets = get_dataset(args.dataset, C, None, args.shot, "test", logger=logger,
-                                 device_preprocess=args.device_preprocess)
-    with torch.no_grad():
-        text_embeddings = get_adapted_text_embedding(model if adapt_text else clip_model, args.dataset, device)
-    support_sets = None
-    if args.support is not None and args.support_meta:
-        support_sets = {c: BaseSingleClassDataset(DATA_PATH[args.dataset], args.support_meta, C, c,
-                                                  device_preprocess=args.device_preprocess) for c in image_datasets}
+    EO._check_arguments(parser, args)
+    session, where = EO.open_session(args, __name__)
     written, masks_written = {}, {}
-    rows, details = evaluate(model, image_datasets, text_embeddings, device, S, args.dataset, batch_size=args.image_batch_size,
-                             loader_kwargs={"num_workers": 4, "pin_memory": True}, logger=logger, use_iqm=args.iqm == "on",
-                             device_metrics=args.device_metrics, aupro_limit=args.aupro, f1_max=True, return_masks=True,
-                             defects=args.defects, save_path=args.save_path, support=args.support,
-                             support_weight=args.support_weight, support_form=args.support_form,
-                             support_datasets=support_sets, coreset=args.support_coreset,
-                             coreset_dim=args.support_coreset_dim, tiles=args.tiles, tile_overlap=args.tile_overlap,
-                             overlay=args.overlay, overlay_limit=args.overlay_limit, overlay_thickness=args.overlay_thickness,
-                             overlay_colormap=args.overlay_colormap, overlay_written=written,
-                             overlay_encoder=args.overlay_encoder, masks_png=args.masks_png, masks_written=masks_written)
+    rows, details = evaluate(*where, f1_max=True, return_masks=True, **ET.session_keywords(args, session),
+                             **EO.overlay_keywords(args), overlay_written=written, overlay_encoder=args.overlay_encoder,
+                             masks_png=args.masks_png, masks_written=masks_written)
     for name, d in details.items():
-        logger.info("%s: pixel threshold %.9g, image threshold %s (normalised units); %d overlays, %d masks (%s)", name,
-                    d["pixel threshold"], d["image threshold"], len(written.get(name, ())),
-                    len(masks_written.get(name, ())), args.overlay_encoder)
-    table = ED.format_table(rows)
-    logger.info("final results:\n%s", table)
-    print(table)
+        session.logger.info("%s: pixel threshold %.9g, image threshold %s (normalised units); %d overlays, %d masks (%s)",
+                            name, d["pixel threshold"], d["image threshold"], len(written.get(name, ())),
+                            len(masks_written.get(name, ())), args.overlay_encoder)
+    ED.log_table(session.logger, rows)
     return rows
 
 

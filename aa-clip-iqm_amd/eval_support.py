@@ -21,10 +21,8 @@ python eval_support.py --save_path ... [--device_metrics] [--support K] [--suppo
 from __future__ import annotations
 
 import argparse
-import os
 
 import eval_defects as ED
-import eval_last as EL
 from forward_utils import SUPPORT_WEIGHT
 
 
@@ -42,16 +40,11 @@ def evaluate(model, image_datasets, text_embeddings, device, img_size: int, data
     if support is None:
         return ED.evaluate(*where, **how, aupro_limit=aupro_limit, f1_max=f1_max, return_masks=return_masks, defects=defects,
                            save_path=save_path)
-    banks, evaluated = EL.support_banks(model, image_datasets, support, device, img_size, form=support_form,
-                                        support_datasets=support_datasets, batch_size=batch_size)
-    where = (model, evaluated, text_embeddings, device, img_size, dataset)
     f1 = f1_max or defects is not None
-    details = {} if f1 else None
-    extra = {} if defects is None else {"defects": defects}
-    rows = EL.evaluate_rows(*where, **how, fpr_limit=aupro_limit, f1_max=f1, details=details, return_masks=return_masks,
-                            support=banks, support_weight=support_weight, **extra)
-    if defects is not None and save_path is not None and int(os.environ.get("RANK", "0")) == 0:
-        ED.write_defects(save_path, dataset, details)
+    rows, details = ED.evaluate_details(*where, **how, aupro_limit=aupro_limit, f1_max=f1, return_masks=return_masks,
+                                        defects=defects, save_path=save_path, support=support,
+                                        support_weight=support_weight, support_form=support_form,
+                                        support_datasets=support_datasets)
     return (rows, details) if return_masks and f1 else rows
 
 
@@ -68,16 +61,18 @@ def build_parser() -> argparse.ArgumentParser:
     return parser
 
 
+def check_arguments(parser: argparse.ArgumentParser, args) -> None:
+    if args.support is not None and args.support < 1:
+        parser.error("--support takes at least 1 shot")
+
+
 def run(parser: argparse.ArgumentParser, argv=None):
     """Without --support: eval_defects.run.  With it: the same steps with the banks built after the text embeddings
     (eval_last.run reads the support arguments)."""
     args = parser.parse_args(argv)
-    if args.support is None:
-        if args.support_meta is not None:
-            parser.error("--support_meta needs --support K")
-        return ED.run(parser, argv)
-    if args.support < 1:
-        parser.error("--support takes at least 1 shot")
+    if args.support is None and args.support_meta is not None:
+        parser.error("--support_meta needs --support K")
+    check_arguments(parser, args)
     return ED.run(parser, argv)
 
 

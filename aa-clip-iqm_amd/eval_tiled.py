@@ -25,7 +25,6 @@ python eval_tiled.py --save_path ... [--tiles G] [--tile_overlap O] [every argum
 from __future__ import annotations
 
 import argparse
-import logging
 import os
 
 import numpy as np
@@ -34,6 +33,7 @@ import torch
 import eval_coreset as EC
 import eval_defects as ED
 import eval_last as EL
+import eval_support as ES
 import test_last as TL
 from aaclip_hip import engine
 from dataset import DOMAINS
@@ -47,6 +47,11 @@ def tile_geometry(img_size: int, tiles: int, tile_overlap: int):
     S, G, O = int(img_size), int(tiles), int(tile_overlap)
     tile_origins(S, G, O)
     return S, G, O, S + (G - 1) * (S - O)
+
+
+def frames_per_batch(batch_size: int, tiles) -> int:
+    """the frames in a loader batch: batch_size, or with tiles=G as many as give about batch_size tiles"""
+    return batch_size if tiles is None else max(1, batch_size // (int(tiles) ** 2))
 
 
 def _canvas_batch(input_data, device, S, G, O, C):
@@ -119,7 +124,7 @@ def tiled_support_banks(model, image_datasets, k: int, device, img_size: int, ti
         else:
             shots, evaluated[class_name] = support_datasets[class_name].support_split(k)[0], ds
         batches = []
-        for b in torch.utils.data.DataLoader(shots, batch_size=max(1, batch_size // (G * G)), shuffle=False):
+        for b in torch.utils.data.DataLoader(shots, batch_size=frames_per_batch(batch_size, G), shuffle=False):
             batches.append(engine.tile_gather(_canvas_batch(b, device, S, G, O, C), S, G, O))
         extra = {} if coreset is None else {"coreset": coreset, "coreset_dim": coreset_dim}
         banks[class_name] = build_support_bank(model, batches, form, **extra)
@@ -144,7 +149,7 @@ def evaluate_tiled(model, image_datasets, text_embeddings, device, img_size: int
     rows, details = [], {} if f1_max or bootstrap is not None else None
     row_of = metrics_eval_device if device_metrics else metrics_eval
     for class_name, image_dataset in image_datasets.items():
-        loader = torch.utils.data.DataLoader(image_dataset, batch_size=max(1, batch_size // (G * G)), shuffle=False,
+        loader = torch.utils.data.DataLoader(image_dataset, batch_size=frames_per_batch(batch_size, G), shuffle=False,
                                              **(loader_kwargs or {}))
         with torch.no_grad():
             masks, labels, preds, preds_image, file_names = get_predictions_tiled(
@@ -193,20 +198,16 @@ def evaluate(model, image_datasets, text_embeddings, device, img_size: int, data
     coreset as in eval_coreset).  With tiles, details[class]["support nearest"] is NOT produced; the other entries of
     details, the rows and the return value are eval_coreset.evaluate's."""
     where = (model, image_datasets, text_embeddings, device, img_size, dataset)
+    below = dict(batch_size=batch_size, loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm,
+                 device_metrics=device_metrics, aupro_limit=aupro_limit, f1_max=f1_max, return_masks=return_masks,
+                 defects=defects, save_path=save_path, support=support, support_weight=support_weight,
+                 support_form=support_form, support_datasets=support_datasets, coreset=coreset, coreset_dim=coreset_dim)
     if tiles is None:
-        return EC.evaluate(*where, batch_size=batch_size, loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm,
-                           device_metrics=device_metrics, aupro_limit=aupro_limit, f1_max=f1_max, return_masks=return_masks,
-                           defects=defects, save_path=save_path, support=support, support_weight=support_weight,
-                           support_form=support_form, support_datasets=support_datasets, coreset=coreset,
-                           coreset_dim=coreset_dim)
+        return EC.evaluate(*where, **below)
     f1 = f1_max or defects is not None
     if return_masks and not f1:
         raise ValueError("evaluate: return_masks needs f1_max=True (the masks are those of its threshold)")
-    rows, details = evaluate_details(*where, (tiles, tile_overlap), batch_size=batch_size, loader_kwargs=loader_kwargs,
-                                     logger=logger, use_iqm=use_iqm, device_metrics=device_metrics, aupro_limit=aupro_limit,
-                                     f1_max=f1, return_masks=return_masks, defects=defects, save_path=save_path,
-                                     support=support, support_weight=support_weight, support_form=support_form,
-                                     support_datasets=support_datasets, coreset=coreset, coreset_dim=coreset_dim)
+    rows, details = evaluate_details(*where, (tiles, tile_overlap), **dict(below, f1_max=f1))
     return (rows, details) if return_masks and f1 else rows
 
 
@@ -215,9 +216,18 @@ def evaluate_details(model, image_datasets, text_embeddings, device, img_size: i
                      f1_max: bool = False, return_masks: bool = False, defects=None, save_path=None, support=None,
                      support_weight: float = SUPPORT_WEIGHT, support_form=None, support_datasets=None, coreset=None,
                      coreset_dim: int = 128, bootstrap=None, after_class=None):
-    """The tiled path of evaluate, for tiles=(G, O): the banks where support=K asks for them, evaluate_tiled (after_class
-    and bootstrap are its keywords), and the .jsonl files of eval_defects.write_defects where defects and save_path ask for them.
-    -> (rows, details)."""
+    """The evaluation behind evaluate and the scripts above this one.  tiles=None: eval_defects.evaluate_details, the path
+    at the model's own size.  tiles=(G, O), its tiled twin: the banks where support=K asks for them, evaluate_tiled
+    (after_class and bootstrap are its keywords), and the .jsonl files of eval_defects.write_defects where defects and
+    save_path ask for them.  -> (rows, details)."""
+    if tiles is None:
+        return ED.evaluate_details(model, image_datasets, text_embeddings, device, img_size, dataset, batch_size=batch_size,
+                                   loader_kwargs=loader_kwargs, logger=logger, use_iqm=use_iqm,
+                                   device_metrics=device_metrics, aupro_limit=aupro_limit, f1_max=f1_max,
+                                   return_masks=return_masks, defects=defects, save_path=save_path, support=support,
+                                   support_weight=support_weight, support_form=support_form,
+                                   support_datasets=support_datasets, coreset=coreset, coreset_dim=coreset_dim,
+                                   bootstrap=bootstrap, after_class=after_class)
     S, G, O, C = tile_geometry(img_size, *tiles)
     if coreset is not None and support is None:
         raise ValueError("evaluate: coreset needs support=K")
@@ -240,8 +250,7 @@ def evaluate_details(model, image_datasets, text_embeddings, device, img_size: i
                                    device_metrics=device_metrics, fpr_limit=aupro_limit, f1_max=f1_max,
                                    return_masks=return_masks, defects=defects, support=banks, support_weight=support_weight,
                                    after_class=after_class, bootstrap=bootstrap)
-    if defects is not None and save_path is not None:
-        ED.write_defects(save_path, dataset, details)
+    ED.write_defects_of(defects, save_path, dataset, details)
     return rows, details
 
 
@@ -255,85 +264,51 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def _check_arguments(parser: argparse.ArgumentParser, args) -> None:
-    """what the scripts below this one refuse, for the path that does not go through their run()"""
-    if args.tiles < 1:
-        parser.error("--tiles takes at least 1 tile per side")
-    if not 0 <= args.tile_overlap <= args.img_size // 2:
-        parser.error("--tile_overlap takes 0 .. img_size // 2 pixels")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        parser.error("--tiles runs in one process: sharded tiled evaluation is not part of this script")
-    if args.iqm_hidden_size != 768:
-        parser.error("--iqm_hidden_size must be 768 (the visual features' width; see test_last.py)")
-    if args.aupro is not None and not 0.0 < args.aupro <= 1.0:
-        parser.error("--aupro takes a false-positive rate in (0, 1]")
-    if args.defects is not None and args.defects < 1:
-        parser.error("--defects takes a minimum area of at least 1 pixel")
+    """this script's checks where --tiles is given, then those of every script below it, for the scripts whose run()
+    does not go through theirs"""
+    if args.tiles is not None:
+        if args.tiles < 1:
+            parser.error("--tiles takes at least 1 tile per side")
+        if not 0 <= args.tile_overlap <= args.img_size // 2:
+            parser.error("--tile_overlap takes 0 .. img_size // 2 pixels")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            parser.error("--tiles runs in one process: sharded tiled evaluation is not part of this script")
+    EL.check_arguments(parser, args)
+    ED.check_arguments(parser, args)
     if args.support is None and (args.support_meta is not None or args.support_coreset is not None):
         parser.error("--support_meta and --support_coreset need --support K")
-    if args.support is not None and args.support < 1:
-        parser.error("--support takes at least 1 shot")
-    if args.support_coreset is not None:
-        if not 0.0 < args.support_coreset <= 1.0:
-            parser.error("--support_coreset takes a share in (0, 1]")
-        if args.support_coreset_dim < 0 or args.support_coreset_dim % 128:
-            parser.error("--support_coreset_dim takes 0 or a multiple of 128")
+    ES.check_arguments(parser, args)
+    EC.check_arguments(parser, args)
+
+
+def session_keywords(args, session) -> dict:
+    """the keywords of eval_coreset.evaluate that the command line and the session set: all but f1_max and return_masks"""
+    return dict(batch_size=args.image_batch_size, loader_kwargs={"num_workers": 4, "pin_memory": True},
+                logger=session.logger, use_iqm=args.iqm == "on", device_metrics=args.device_metrics,
+                aupro_limit=args.aupro, defects=args.defects, save_path=args.save_path, support=args.support,
+                support_weight=args.support_weight, support_form=args.support_form,
+                support_datasets=session.support_datasets, coreset=args.support_coreset,
+                coreset_dim=args.support_coreset_dim)
 
 
 def run(parser: argparse.ArgumentParser, argv=None):
-    """Without --tiles: eval_coreset.run.  With it: the steps of eval_last.run with the model built at --img_size, the
-    datasets built at the canvas size and this module's evaluate."""
+    """Without --tiles: eval_coreset.run.  With it: eval_last.open_session with the datasets built at the canvas size (the
+    model stays at --img_size) and evaluate_details."""
     args = parser.parse_args(argv)
     if args.tiles is None:
         return EC.run(parser, argv)
     _check_arguments(parser, args)
-    from dataset import DATA_PATH, BaseSingleClassDataset, get_dataset
-    from forward_utils import get_adapted_text_embedding
-    from model.adapter import AdaptedCLIP
-    from model.clip import create_model
     S, G, O, C = tile_geometry(args.img_size, args.tiles, args.tile_overlap)
-    TL.setup_seed(args.seed)
-    os.makedirs(args.save_path, exist_ok=True)
-    logger = logging.getLogger(__name__)
-    logging.basicConfig(filename=os.path.join(args.save_path, "test.log"), encoding="utf-8", level=logging.INFO)
-    logger.info("args: %s", vars(args))
-    logger.info("tiled inference: S %d, G %d, O %d, C %d (%d tiles per frame)", S, G, O, C, G * G)
-    if not torch.cuda.is_available():
-        raise RuntimeError("the AA-CLIP HIP path needs an MI355X; there is no CPU fallback")
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
-    torch.cuda.set_device(device)
-    clip_model = create_model(model_name=args.model_name, img_size=S, device=device, pretrained="openai",
-                              require_pretrained=True, precision=args.precision)
-    clip_model.eval()
-    model = AdaptedCLIP(clip_model=clip_model, text_adapt_weight=args.text_adapt_weight,
-                        image_adapt_weight=args.image_adapt_weight, text_adapt_until=args.text_adapt_until,
-                        image_adapt_until=args.image_adapt_until, relu=args.relu,
-                        iqm_hidden_size=args.iqm_hidden_size, iqm_num_layers=args.iqm_num_layers,
-                        iqm_num_heads=args.iqm_num_heads).to(device)
-    model.eval()
-    adapt_text = EL.load_adapters(model, args.save_path, logger)
-    image_datasets = get_dataset(args.dataset, C, None, args.shot, "test", logger=logger,
-                                 device_preprocess=args.device_preprocess)
-    with torch.no_grad():
-        text_embeddings = get_adapted_text_embedding(model if adapt_text else clip_model, args.dataset, device)
-    support_sets = None
-    if args.support is not None and args.support_meta:
-        support_sets = {c: BaseSingleClassDataset(DATA_PATH[args.dataset], args.support_meta, C, c,
-                                                  device_preprocess=args.device_preprocess) for c in image_datasets}
+    session = EL.open_session(args, __name__, C, ["tiled inference: S %d, G %d, O %d, C %d (%d tiles per frame)"
+                                                  % (S, G, O, C, G * G)])
     f1 = bool(args.f1max) or args.defects is not None
-    rows, details = evaluate_details(model, image_datasets, text_embeddings, device, S, args.dataset, (G, O),
-                                     batch_size=args.image_batch_size, loader_kwargs={"num_workers": 4, "pin_memory": True},
-                                     logger=logger, use_iqm=args.iqm == "on", device_metrics=args.device_metrics,
-                                     aupro_limit=args.aupro, f1_max=f1, defects=args.defects, save_path=args.save_path,
-                                     support=args.support, support_weight=args.support_weight,
-                                     support_form=args.support_form, support_datasets=support_sets,
-                                     coreset=args.support_coreset, coreset_dim=args.support_coreset_dim)
+    rows, details = evaluate_details(session.model, session.image_datasets, session.text_embeddings, session.device, S,
+                                     args.dataset, (G, O), f1_max=f1, **session_keywords(args, session))
     if f1:
         for name, d in details.items():
-            logger.info("%s: pixel threshold %.9g, image threshold %s (normalised units)", name, d["pixel threshold"],
-                        d["image threshold"])
-    table = ED.format_table(rows)
-    logger.info("final results:\n%s", table)
-    print(table)
+            session.logger.info("%s: pixel threshold %.9g, image threshold %s (normalised units)", name,
+                                d["pixel threshold"], d["image threshold"])
+    ED.log_table(session.logger, rows)
     return rows
 
 
