@@ -86,6 +86,12 @@ static inline int split_w(int dtype) { return dtype == AACLIP_F16X2 ? 2 : 1; }  
 static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 static inline bool dtype_ok(int d) { return d == AACLIP_F32 || d == AACLIP_F16 || d == AACLIP_BF16 || d == AACLIP_F16X2; }
 static inline bool plain_dtype_ok(int d) { return d == AACLIP_F32 || d == AACLIP_F16 || d == AACLIP_BF16; }
+// A launch takes its grid in work-items: workgroups * 256 threads must stay below 2^32.  Measured on gfx950 with
+// head_expand: 2^24 - 1 workgroups run, exactly 2^24 is a launch error, and 2^24 + k silently runs k of them.  The
+// entries whose kernels take one workgroup per row (group) therefore refuse a row count that needs 2^24 or more.
+static inline bool grid_fits(long workgroups) { return workgroups < (1L << 24); }
+static inline bool rows4_fit(long rows) { return grid_fits((rows + 3) / 4); }   // four rows per workgroup
+#define TOO_MANY_ROWS4(entry) entry ": too many rows (one workgroup per 4 rows, below 2^24 workgroups: rows <= 2^26 - 4)"
 // shape limits shared by the map entry points (anomaly_map.hip, iqm.hip, train_loss.hip)
 static inline bool map_shape_ok(int B, int g, int S) { return B > 0 && B <= 65535 && g >= 1 && g <= 40 && S >= 1; }
 
@@ -176,6 +182,7 @@ int aaclip_layernorm(const float* x, const float* w, const float* b, void* out, 
   REQUIRE(x && w && b && out, "layernorm: null pointer");
   REQUIRE(dtype_ok(out_dtype), "layernorm: bad dtype");
   REQUIRE(rows > 0, "layernorm: rows must be positive");
+  REQUIRE(rows4_fit(rows), TOO_MANY_ROWS4("layernorm"));
   REQUIRE_ROW_WIDTH(D);
   launch_layernorm(out_dtype, x, w, b, out, rows, D, eps, (hipStream_t)stream);
   return finish("layernorm");
@@ -217,6 +224,7 @@ int aaclip_attention_log2q(int dtype, const void* qkv, void* ctx, int B, int L, 
 
 int aaclip_adapter_mix(float* x, const float* a, long rows, int D, float weight, void* stream) {
   REQUIRE(x && a && rows > 0, "adapter_mix: bad arguments");
+  REQUIRE(rows4_fit(rows), TOO_MANY_ROWS4("adapter_mix"));
   REQUIRE_ROW_WIDTH(D);
   launch_adapter_mix(x, a, rows, D, weight, (hipStream_t)stream);
   return finish("adapter_mix");
@@ -282,6 +290,7 @@ int aaclip_adapter_mix_fold(int dtype, float* x, const float* a, long rows, int 
                             float* row_ab, void* stream) {
   REQUIRE(dtype == AACLIP_F16 || dtype == AACLIP_BF16, "adapter_mix_fold: fp16 or bf16 rows only");
   REQUIRE(x && a && out16 && row_ab && rows > 0, "adapter_mix_fold: bad arguments");
+  REQUIRE(rows4_fit(rows), TOO_MANY_ROWS4("adapter_mix_fold"));
   REQUIRE(!(((uintptr_t)x | (uintptr_t)a) & 15) && !(((uintptr_t)out16 | (uintptr_t)row_ab) & 7),
           "adapter_mix_fold: x and a must be 16-byte, out16 and row_ab 8-byte aligned");
   REQUIRE_ROW_WIDTH(D);
@@ -306,6 +315,7 @@ int aaclip_layernorm_split(const float* x, const float* w, const float* b, void*
                            int hi8, void* stream) {
   REQUIRE(x && w && b && out, "layernorm_split: null pointer");
   REQUIRE(rows > 0, "layernorm_split: rows must be positive");
+  REQUIRE(rows4_fit(rows), TOO_MANY_ROWS4("layernorm_split"));
   REQUIRE_ROW_WIDTH(D);
   launch_layernorm(AACLIP_F16X2, x, w, b, out, rows, D, eps, (hipStream_t)stream, hi8 != 0);
   return finish("layernorm_split");
@@ -416,13 +426,14 @@ int aaclip_cross_rows_levels_backward(int x_dtype, const float* qt, const void* 
 int aaclip_head_expand(int dtype, const float* q, void* qm, long rows, int H, int D, float scale, void* stream) {
   REQUIRE(plain_dtype_ok(dtype), "head_expand: bad dtype (fp32, fp16 or bf16)");
   REQUIRE(q && qm && rows > 0 && H > 0 && D > 0 && D % H == 0, "head_expand: bad arguments");
-  REQUIRE(rows * H < (1L << 31), "head_expand: too many rows");
+  REQUIRE(rows < (1L << 24) && grid_fits(rows * H), "head_expand: too many rows (one workgroup per expanded row: rows * H < 2^24)");
   launch_head_expand(dtype, q, qm, rows, H, D, scale, (hipStream_t)stream);
   return finish("head_expand");
 }
 
 int aaclip_head_diag(const float* full, float* ctx, long rows, int H, int D, void* stream) {
-  REQUIRE(full && ctx && rows > 0 && rows < (1L << 31) && H > 0 && D > 0 && D % H == 0, "head_diag: bad arguments");
+  REQUIRE(full && ctx && rows > 0 && H > 0 && D > 0 && D % H == 0, "head_diag: bad arguments");
+  REQUIRE(grid_fits(rows), "head_diag: too many rows (one workgroup per row: rows < 2^24)");
   launch_head_diag(full, ctx, rows, H, D, (hipStream_t)stream);
   return finish("head_diag");
 }
@@ -431,6 +442,7 @@ int aaclip_residual_layernorm(const float* a, const float* b, const float* w, co
                               int D, float eps, void* stream) {
   REQUIRE(a && w && bias && out, "residual_layernorm: null pointer");
   REQUIRE(rows > 0 && D > 0 && D % 64 == 0 && D <= 4096, "residual_layernorm: D must be a multiple of 64, <= 4096");
+  REQUIRE(rows4_fit(rows), TOO_MANY_ROWS4("residual_layernorm"));
   launch_residual_layernorm(a, b, w, bias, out, rows, D, eps, (hipStream_t)stream);
   return finish("residual_layernorm");
 }
@@ -467,7 +479,9 @@ int aaclip_small_attention_backward(const float* q, const float* k, const float*
   return finish("small_attention_backward");
 }
 
-size_t aaclip_layernorm_param_grad_workspace_bytes(long rows, int D) { return layernorm_param_grad_ws_bytes(rows, D); }
+size_t aaclip_layernorm_param_grad_workspace_bytes(long rows, int D) {
+  return rows4_fit(rows) ? layernorm_param_grad_ws_bytes(rows, D) : 0;
+}
 
 int aaclip_layernorm_param_grad(const float* x, const float* d_y, float* d_w, float* d_b, long rows, int D, float eps,
                                 void* ws, size_t ws_bytes, void* stream) {
@@ -475,7 +489,7 @@ int aaclip_layernorm_param_grad(const float* x, const float* d_y, float* d_w, fl
   REQUIRE(d_w || d_b, "layernorm_param_grad: nothing to compute (d_w and d_b are both NULL)");
   REQUIRE(rows > 0 && D > 0, "layernorm_param_grad: empty problem");
   REQUIRE(D % 64 == 0 && D <= 4096, "layernorm_param_grad: D must be a multiple of 64, <= 4096");
-  REQUIRE(rows < (1L << 31), "layernorm_param_grad: too many rows");
+  REQUIRE(rows4_fit(rows), TOO_MANY_ROWS4("layernorm_param_grad"));
   REQUIRE_ALIGNED16("layernorm_param_grad", x, d_y, d_w, d_b, ws);
   REQUIRE(ws_bytes >= layernorm_param_grad_ws_bytes(rows, D), "layernorm_param_grad: workspace too small");
   launch_layernorm_param_grad(x, d_y, d_w, d_b, rows, D, eps, ws, (hipStream_t)stream);
@@ -737,7 +751,7 @@ static int blocks_core(const float* x_in, float* const* x_out, float* x_all, con
   REQUIRE(F % 128 == 0, "block: F must be a multiple of 128");
   REQUIRE_ROW_WIDTH(D);   // every accepted width is a multiple of 128, which the 128-tile GEMMs need
   const long rows = (long)B * L;
-  REQUIRE(rows < (1L << 31) / 4, "block: too many rows");
+  REQUIRE(rows4_fit(rows), "block: too many rows");   // the row kernels: one workgroup per 4 rows, below 2^24
   const WsLayout l = ws_layout(dtype, rows, D, F, 0);
   REQUIRE(ws_bytes >= l.total, "block: workspace too small");
   if (x_out)
@@ -1036,6 +1050,7 @@ int aaclip_layernorm_backward(const float* x, const float* w, const float* d_y, 
                               long rows, int D, float eps, void* stream) {
   REQUIRE(x && w && d_y && d_x, "layernorm_backward: null pointer");
   REQUIRE(rows > 0, "layernorm_backward: rows must be positive");
+  REQUIRE(rows4_fit(rows), TOO_MANY_ROWS4("layernorm_backward"));
   REQUIRE_ROW_WIDTH(D);
   REQUIRE_ALIGNED16("layernorm_backward", x, w, d_y, d_resid, d_x);
   launch_layernorm_backward(x, w, d_y, d_resid, d_x, nullptr, rows, D, eps, (hipStream_t)stream);
@@ -1046,6 +1061,7 @@ int aaclip_adapter_mix_backward(const float* u, const float* z, const float* d_y
                                 int D, float weight, void* stream) {
   REQUIRE(u && z && d_y && d_z && d_u, "adapter_mix_backward: null pointer");
   REQUIRE(rows > 0, "adapter_mix_backward: rows must be positive");
+  REQUIRE(rows4_fit(rows), TOO_MANY_ROWS4("adapter_mix_backward"));
   REQUIRE_ROW_WIDTH(D);
   REQUIRE_ALIGNED16("adapter_mix_backward", u, z, d_y, d_z, d_u);
   launch_adapter_mix_backward(u, z, d_y, d_z, d_u, rows, D, weight, (hipStream_t)stream);
@@ -1084,7 +1100,7 @@ static int block_backward_body(int route, const char* name, const float* x_in, c
   if (const char* m = route == BLOCK_BWD_SHORT ? attention_backward_check(B, L, H) : attention_backward_long_check(B, L, H))
     return fail(-1, m);
   const long rows = (long)B * L;
-  REQUIRE(rows < (1L << 31) / 4, in(name, "too many rows"));
+  REQUIRE(rows4_fit(rows), in(name, "too many rows"));
   REQUIRE(w->ln1_w && w->ln1_b && w->out_b && w->ln2_w && w->ln2_b && w->fc_b && w->proj_b,
           in(name, "null weight pointer"));
   REQUIRE(wp->qkv_w && wp->qkv_b && wp->out_w && wp->fc_w && wp->proj_w,
@@ -1189,7 +1205,8 @@ int aaclip_block_backward_long(const float* x_in, const aaclip_block_weights* w,
 int aaclip_split3_rows(const float* src, void* dst, long rows, int K, void* stream) {
   REQUIRE(src && dst, "split3_rows: null pointer");
   REQUIRE(rows > 0 && K > 0 && K % 64 == 0, "split3_rows: rows must be positive and K a positive multiple of 64");
-  REQUIRE(rows < (1L << 40) / K, "split3_rows: problem too large");
+  REQUIRE(rows <= (1L << 35) / K && grid_fits((rows * (K / 8) + 255) / 256),
+          "split3_rows: too many rows (one thread per 8 elements, below 2^24 workgroups: rows * K <= 2^35 - 2048)");
   REQUIRE_ALIGNED16("split3_rows", src, dst);
   launch_split3_rows(src, dst, rows, K, (hipStream_t)stream);
   return finish("split3_rows");
@@ -1301,7 +1318,7 @@ int aaclip_tap_head_backward(const float* x, const float* ln_post_w, const float
   REQUIRE(E % 128 == 0, "tap_head_backward: E must be a multiple of 128");
   REQUIRE(act >= AACLIP_ACT_NONE && act <= AACLIP_ACT_RELU, "tap_head_backward: bad activation");
   const long rows = (long)B * L;
-  REQUIRE(rows < (1L << 31) / 4, "tap_head_backward: too many rows");
+  REQUIRE(rows4_fit(rows), "tap_head_backward: too many rows");
   REQUIRE_ALIGNED16("tap_head_backward", x, ln_post_w, ln_post_b, proj_w, proj_wt, d_seg, det_w, det_wt, d_det, d_x,
                     d_proj_w, d_det_w, ws);
   const ThLayout l = th_layout(rows, D, E);
@@ -1433,6 +1450,7 @@ static inline bool metrics_n_ok(long n) { return n >= 2 && n <= 2147483647L; }
 
 size_t aaclip_metrics_range_workspace_bytes(long n, long per_image) {
   if (!metrics_n_ok(n) || per_image < 0 || (per_image > 0 && n % per_image != 0)) return 0;
+  if (!grid_fits(metrics_range_partials(n, per_image))) return 0;
   return up256(metrics_range_ws_bytes(n, per_image));
 }
 
@@ -1441,6 +1459,8 @@ int aaclip_metrics_range(const float* scores, const uint8_t* labels, long n, lon
   REQUIRE(scores && record && ws, "metrics_range: null pointer");
   REQUIRE(metrics_n_ok(n), "metrics_range: n must be 2 .. 2^31 - 1");
   REQUIRE(per_image >= 0 && (per_image == 0 || n % per_image == 0), "metrics_range: n must be a multiple of per_image");
+  REQUIRE(grid_fits(metrics_range_partials(n, per_image)),
+          "metrics_range: too many workgroups (one or more per image: n / per_image must stay below 2^24)");
   REQUIRE(!image_max || per_image > 0, "metrics_range: image maxima need per_image > 0");
   REQUIRE((((uintptr_t)scores | (uintptr_t)image_max) & 3) == 0 && (((uintptr_t)record | (uintptr_t)ws) & 7) == 0,
           "metrics_range: scores / image_max must be 4-byte, record / workspace 8-byte aligned");
@@ -1573,6 +1593,7 @@ int aaclip_metrics_f1max(const uint32_t* keys, const uint8_t* labels_sorted, lon
 
 size_t aaclip_metrics_threshold_workspace_bytes(long n, long per_image) {
   if (!metrics_n_ok(n) || per_image < 0 || (per_image > 0 && n % per_image != 0)) return 0;
+  if (!grid_fits(metrics_range_partials(n, per_image))) return 0;
   return up256(metrics_threshold_ws_bytes(n, per_image));
 }
 
@@ -1584,6 +1605,8 @@ int aaclip_metrics_threshold(const float* scores, const uint8_t* labels, long n,
   REQUIRE(metrics_n_ok(n), "metrics_threshold: n must be 2 .. 2^31 - 1");
   REQUIRE(per_image >= 0 && (per_image == 0 || n % per_image == 0),
           "metrics_threshold: n must be a multiple of per_image");
+  REQUIRE(grid_fits(metrics_range_partials(n, per_image)),
+          "metrics_threshold: too many workgroups (one or more per image: n / per_image must stay below 2^24)");
   REQUIRE(!image_counts || (labels && per_image > 0), "metrics_threshold: per-image counts need labels and per_image > 0");
   REQUIRE((((uintptr_t)scores | (uintptr_t)image_counts) & 3) == 0 &&
               (((uintptr_t)range_record | (uintptr_t)f1max_record | (uintptr_t)totals | (uintptr_t)ws) & 7) == 0,

@@ -394,7 +394,7 @@ int aaclip_row_head_backward(const float* x, const int32_t* tokens, const float*
  * d_proj_w (out) [E, D] and d_det_w (out) [E, D] are overwritten.  d_x (out) [B*L, D], overwritten, CLS rows exactly
  * zero; may be NULL when only the projections train -- then proj_wt / det_wt may be NULL too and no input-gradient
  * product runs.  Otherwise the transpose of every part that is present is required.
- * D, E supported row widths (256, 512, 768, 1024), L > 1, B*L < 2^29, act one of AACLIP_ACT_*.
+ * D, E supported row widths (256, 512, 768, 1024), L > 1, B*L <= 2^26 - 4, act one of AACLIP_ACT_*.
  * ws_bytes >= aaclip_tap_head_backward_workspace_bytes(B, L, D, E): 0 for an empty problem, monotonic in each
  * argument.  Errors carry the "tap_head_backward:" prefix.
  * The IQM branch's backward: its key / value side in the projected form, from the gradient of the cross-attention's
@@ -925,7 +925,18 @@ int aaclip_profile_end(float* ms, int* tags, int max_n);
  * unchanged. */
 int aaclip_set_gemm_variant(int v);
 
-/* Building blocks, exported for unit parity tests and for callers that fuse differently. */
+/* Building blocks, exported for unit parity tests and for callers that fuse differently.
+ * Row limits.  A launch covers its grid only below 2^24 workgroups of 256 threads, so the entries whose kernels take
+ * one workgroup per row (group) refuse more (rc < 0, nothing launched): rows <= 2^26 - 4 for aaclip_layernorm,
+ * aaclip_layernorm_split, aaclip_adapter_mix, aaclip_adapter_mix_fold, aaclip_residual_layernorm,
+ * aaclip_layernorm_backward, aaclip_adapter_mix_backward and aaclip_layernorm_param_grad (4 rows per workgroup);
+ * rows * H < 2^24 for aaclip_head_expand and rows < 2^24 for aaclip_head_diag (one workgroup per row);
+ * rows * K <= 2^35 - 2048 for aaclip_split3_rows; n / per_image < 2^24 images for aaclip_metrics_range and
+ * aaclip_metrics_threshold (their *_workspace_bytes, and aaclip_layernorm_param_grad's, are 0 beyond).  The block
+ * entries run the same row kernels: aaclip_block(s), aaclip_blocks_to / _taps, aaclip_block_backward(_long, _bf16x3) and
+ * aaclip_tap_head_backward take B * L <= 2^26 - 4 rows.  aaclip_ln_stats_finalize takes rows < 2^27.  The
+ * other row and element entries (aaclip_split_rows, aaclip_combine3, aaclip_linear_smallk, aaclip_act_backward,
+ * aaclip_bias_grad, aaclip_drop_cls_rows) walk any count with a bounded grid. */
 int aaclip_layernorm(const float* x, const float* w, const float* b, void* out, int out_dtype, long rows, int D,
                      float eps, void* stream);
 int aaclip_gemm(int dtype, int epi, const void* A, long lda, const void* W, const float* bias, void* out, long ldc,
