@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "bf16x3.h"
+#include "buffers.h"
 #include "kernels.h"
 #include "overlay_plan.h"
 #include "png_plan.h"
@@ -26,6 +27,10 @@ static const char* in(const char* entry, const char* msg) {
   static thread_local char text[256];
   snprintf(text, sizeof(text), "%s: %s", entry, msg);
   return text;
+}
+// nullptr, or why a plan struct is refused before any of its fields is read; mismatch names the struct
+template <class Plan> static const char* plan_refusal(const Plan* plan, const char* mismatch) {
+  return !plan ? "null plan" : plan->struct_bytes == sizeof(Plan) ? nullptr : mismatch;
 }
 #define REQUIRE(cond, msg) \
   do {                     \
@@ -367,11 +372,7 @@ int aaclip_cross_rows_backward(int x_dtype, const float* qt, const void* x, cons
   REQUIRE(act >= AACLIP_ACT_NONE && act <= AACLIP_ACT_RELU, "cross_rows_backward: bad activation");
   REQUIRE(B > 0 && R > 0 && Lk > 0 && Dk > 0, "cross_rows_backward: empty problem");
   REQUIRE(B <= 65535, "cross_rows_backward: grid limit (B <= 65535)");
-  if (const char* m = cross_rows_check(R, Lk, Dk)) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), "cross_rows_backward: %s", m);
-    return fail(-1, buf);
-  }
+  if (const char* m = cross_rows_check(R, Lk, Dk)) return fail(-1, in("cross_rows_backward", m));
   REQUIRE_ALIGNED16("cross_rows_backward", qt, x, d_out, d_qt, d_x, ws);
   REQUIRE(ws_bytes >= cross_rows_backward_ws_bytes(B, R, Lk, Dk), "cross_rows_backward: workspace too small");
   launch_cross_rows_backward(x_dtype, qt, x, d_out, d_qt, d_x, act, accumulate, B, R, Lk, Dk, ws, (hipStream_t)stream);
@@ -1388,10 +1389,6 @@ int aaclip_preprocess(const uint8_t* src, int B, int Hs, int Ws, int S, const in
 }
 
 // ---- train-time input work (augment.hip)
-static inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
 
 size_t aaclip_color_jitter_workspace_bytes(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
@@ -1404,10 +1401,13 @@ int aaclip_color_jitter(const uint8_t* src, uint8_t* dst, int B, int H, int W, c
   REQUIRE(B > 0 && B <= 65535 && H >= 1 && W >= 1 && H <= (1 << 16) && W <= (1 << 16), "color_jitter: bad frame shape");
   const size_t bytes = (size_t)B * H * W * 3;
   REQUIRE(bytes <= ((size_t)1 << 36), "color_jitter: more than 64 GiB of frames in one call");
-  REQUIRE(src == dst || !ranges_overlap(src, bytes, dst, bytes),
-          "color_jitter: dst must be src itself (in place) or not overlap it");
-  REQUIRE(((uintptr_t)ws & 7) == 0, "color_jitter: workspace must be 8-byte aligned");
-  REQUIRE(ws_bytes >= aaclip_color_jitter_workspace_bytes(B, H, W), "color_jitter: workspace too small");
+  const size_t need = aaclip_color_jitter_workspace_bytes(B, H, W);
+  const Buf b[] = {wr(dst, bytes), rd(src == dst ? nullptr : src, bytes), wr(ws, need, 8), rd(factors, (size_t)B * 12),
+                   rd(apply, (size_t)B * 4)};   // in place: dst stands for both
+  REQUIRE(!bufs_overlap(b[0], b[1]), "color_jitter: dst must be src itself (in place) or not overlap it");
+  REQUIRE(bufs_misaligned(b) < 0, "color_jitter: workspace must be 8-byte aligned");
+  REQUIRE(ws_bytes >= need, "color_jitter: workspace too small");
+  REQUIRE(!bufs_clash(b), "color_jitter: dst and the workspace must not overlap each other or the inputs");
   launch_color_jitter(src, dst, B, H, W, factors, apply, ws, (hipStream_t)stream);
   return finish("color_jitter");
 }
@@ -1437,9 +1437,9 @@ int aaclip_augment_geometric(const float* image, const float* mask, int B, int S
   REQUIRE(B > 0 && B <= 65535, "augment_geometric: batch must be 1..65535");
   REQUIRE(S >= 1 && S <= 4096, "augment_geometric: size must be 1..4096");
   const size_t plane = (size_t)S * S * 4, ni = (size_t)B * 3 * plane, nm = (size_t)B * plane;
-  REQUIRE(!ranges_overlap(image_out, ni, image, ni) && !ranges_overlap(image_out, ni, mask, nm) &&
-              !ranges_overlap(mask_out, nm, image, ni) && !ranges_overlap(mask_out, nm, mask, nm) &&
-              !ranges_overlap(image_out, ni, mask_out, nm),
+  const Buf b[] = {wr(image_out, ni), wr(mask_out, nm), rd(image, ni), rd(mask, nm), rd(angle_deg, (size_t)B * 4),
+                   rd(shift, (size_t)B * 8), rd(flags, (size_t)B * 4)};
+  REQUIRE(!bufs_clash(b),
           "augment_geometric: the outputs must not overlap the inputs or each other (every pixel is a gather)");
   launch_augment_geometric(image, mask, B, S, angle_deg, shift, flags, image_out, mask_out, (hipStream_t)stream);
   return finish("augment_geometric");
@@ -1462,15 +1462,11 @@ int aaclip_metrics_range(const float* scores, const uint8_t* labels, long n, lon
   REQUIRE(grid_fits(metrics_range_partials(n, per_image)),
           "metrics_range: too many workgroups (one or more per image: n / per_image must stay below 2^24)");
   REQUIRE(!image_max || per_image > 0, "metrics_range: image maxima need per_image > 0");
-  REQUIRE((((uintptr_t)scores | (uintptr_t)image_max) & 3) == 0 && (((uintptr_t)record | (uintptr_t)ws) & 7) == 0,
-          "metrics_range: scores / image_max must be 4-byte, record / workspace 8-byte aligned");
   const size_t range_need = aaclip_metrics_range_workspace_bytes(n, per_image);
-  REQUIRE(!ranges_overlap(ws, range_need, scores, (size_t)n * 4) && !ranges_overlap(ws, range_need, record, 24) &&
-              !ranges_overlap(record, 24, scores, (size_t)n * 4) && !(labels && ranges_overlap(ws, range_need, labels, (size_t)n)) &&
-              !(image_max && (ranges_overlap(ws, range_need, image_max, (size_t)(n / per_image) * 4) ||
-                              ranges_overlap(image_max, (size_t)(n / per_image) * 4, scores, (size_t)n * 4) ||
-                              ranges_overlap(image_max, (size_t)(n / per_image) * 4, record, 24))),
-          "metrics_range: scores, labels, outputs and workspace must not overlap one another");
+  const Buf b[] = {rd(scores, (size_t)n * 4, 4), rd(labels, (size_t)n), wr(record, 24, 8), wr(ws, range_need, 8),
+                   wr(image_max, image_max ? (size_t)(n / per_image) * 4 : 0, 4)};
+  REQUIRE(bufs_misaligned(b) < 0, "metrics_range: scores / image_max must be 4-byte, record / workspace 8-byte aligned");
+  REQUIRE(!bufs_clash(b), "metrics_range: scores, labels, outputs and workspace must not overlap one another");
   REQUIRE(ws_bytes >= range_need, "metrics_range: workspace too small");
   launch_metrics_range(scores, labels, n, per_image, image_max, record, ws, (hipStream_t)stream);
   return finish("metrics_range");
@@ -1479,10 +1475,11 @@ int aaclip_metrics_range(const float* scores, const uint8_t* labels, long n, lon
 int aaclip_metrics_normalise(const float* scores, float* out, long n, const void* range_record, void* stream) {
   REQUIRE(scores && out && range_record, "metrics_normalise: null pointer");
   REQUIRE(n >= 1 && n <= 2147483647L, "metrics_normalise: n must be 1 .. 2^31 - 1");
-  REQUIRE((((uintptr_t)scores | (uintptr_t)out) & 3) == 0 && ((uintptr_t)range_record & 7) == 0,
-          "metrics_normalise: scores / out must be 4-byte, the record 8-byte aligned");
-  REQUIRE(scores == out || !ranges_overlap(scores, (size_t)n * 4, out, (size_t)n * 4),
-          "metrics_normalise: out must be scores itself (in place) or not overlap it");
+  const Buf b[] = {wr(out, (size_t)n * 4, 4), rd(scores == out ? nullptr : scores, (size_t)n * 4, 4),
+                   rd(range_record, 24, 8)};   // in place: out stands for both
+  REQUIRE(bufs_misaligned(b) < 0, "metrics_normalise: scores / out must be 4-byte, the record 8-byte aligned");
+  REQUIRE(!bufs_overlap(b[0], b[1]), "metrics_normalise: out must be scores itself (in place) or not overlap it");
+  REQUIRE(!bufs_clash(b), "metrics_normalise: out must not overlap the range record");
   launch_metrics_normalise(scores, out, n, range_record, (hipStream_t)stream);
   return finish("metrics_normalise");
 }
@@ -1497,19 +1494,12 @@ int aaclip_metrics_sort(const float* scores, const uint8_t* labels, long n, int 
   REQUIRE(packed == 0 || packed == 1, "metrics_sort: packed must be 0 or 1");
   REQUIRE(packed || labels_sorted, "metrics_sort: labels_sorted is required when the label is not packed into the key");
   REQUIRE(metrics_n_ok(n), "metrics_sort: n must be 2 .. 2^31 - 1");
-  REQUIRE((((uintptr_t)scores | (uintptr_t)keys) & 3) == 0 && (((uintptr_t)out_of_range | (uintptr_t)ws) & 7) == 0,
-          "metrics_sort: scores / keys must be 4-byte, out_of_range / workspace 8-byte aligned");
-  REQUIRE(!ranges_overlap(keys, (size_t)n * 4, scores, (size_t)n * 4) &&
-              !(labels_sorted && ranges_overlap(labels_sorted, (size_t)n, labels, (size_t)n)),
-          "metrics_sort: the outputs must not overlap the inputs");
   const size_t sort_need = aaclip_metrics_sort_workspace_bytes(n);   // the workspace holds the other half of the ping-pong
-  REQUIRE(!ranges_overlap(ws, sort_need, scores, (size_t)n * 4) && !ranges_overlap(ws, sort_need, labels, (size_t)n) &&
-              !ranges_overlap(ws, sort_need, keys, (size_t)n * 4) && !ranges_overlap(ws, sort_need, out_of_range, 8) &&
-              !(labels_sorted && ranges_overlap(ws, sort_need, labels_sorted, (size_t)n)) &&
-              !ranges_overlap(out_of_range, 8, keys, (size_t)n * 4) &&
-              !(labels_sorted && (ranges_overlap(out_of_range, 8, labels_sorted, (size_t)n) ||
-                                  ranges_overlap(keys, (size_t)n * 4, labels_sorted, (size_t)n))),
-          "metrics_sort: inputs, outputs and workspace must not overlap one another");
+  const Buf b[] = {rd(scores, (size_t)n * 4, 4), rd(labels, (size_t)n), wr(keys, (size_t)n * 4, 4),
+                   wr(labels_sorted, (size_t)n), wr(out_of_range, 8, 8), wr(ws, sort_need, 8)};
+  REQUIRE(bufs_misaligned(b) < 0, "metrics_sort: scores / keys must be 4-byte, out_of_range / workspace 8-byte aligned");
+  REQUIRE(!bufs_overlap(b[2], b[0]) && !bufs_overlap(b[3], b[1]), "metrics_sort: the outputs must not overlap the inputs");
+  REQUIRE(!bufs_clash(b), "metrics_sort: inputs, outputs and workspace must not overlap one another");
   REQUIRE(ws_bytes >= sort_need, "metrics_sort: workspace too small");
   launch_metrics_sort(scores, labels, n, packed, keys, labels_sorted, out_of_range, ws, (hipStream_t)stream);
   return finish("metrics_sort");
@@ -1523,14 +1513,10 @@ int aaclip_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, lon
   REQUIRE(packed == 0 || packed == 1, "metrics_curve: packed must be 0 or 1");
   REQUIRE(packed || labels_sorted, "metrics_curve: labels_sorted is required when the label is not packed into the key");
   REQUIRE(metrics_n_ok(n), "metrics_curve: n must be 2 .. 2^31 - 1");
-  REQUIRE(((uintptr_t)keys & 3) == 0 && (((uintptr_t)record | (uintptr_t)ws) & 7) == 0,
-          "metrics_curve: keys must be 4-byte, record / workspace 8-byte aligned");
   const size_t curve_need = aaclip_metrics_curve_workspace_bytes(n);
-  REQUIRE(!ranges_overlap(ws, curve_need, keys, (size_t)n * 4) && !ranges_overlap(ws, curve_need, record, 40) &&
-              !ranges_overlap(record, 40, keys, (size_t)n * 4) &&
-              !(labels_sorted && (ranges_overlap(ws, curve_need, labels_sorted, (size_t)n) ||
-                                  ranges_overlap(record, 40, labels_sorted, (size_t)n))),
-          "metrics_curve: keys, labels, record and workspace must not overlap one another");
+  const Buf b[] = {rd(keys, (size_t)n * 4, 4), rd(labels_sorted, (size_t)n), wr(record, 40, 8), wr(ws, curve_need, 8)};
+  REQUIRE(bufs_misaligned(b) < 0, "metrics_curve: keys must be 4-byte, record / workspace 8-byte aligned");
+  REQUIRE(!bufs_clash(b), "metrics_curve: keys, labels, record and workspace must not overlap one another");
   REQUIRE(ws_bytes >= curve_need, "metrics_curve: workspace too small");
   launch_metrics_curve(keys, labels_sorted, n, packed, record, ws, (hipStream_t)stream);
   return finish("metrics_curve");
@@ -1555,15 +1541,11 @@ int aaclip_bootstrap_curves(const aaclip_bootstrap_plan* plan, const uint32_t* k
   REQUIRE(n >= 1 && n <= 2147483647L, "bootstrap_curves: n must be 1 .. 2^31 - 1");
   REQUIRE(images >= 1 && images <= bootstrap_max_images(), "bootstrap_curves: images must be 1 .. 1024 (the weight table of a replicate block fills 64 KiB of LDS)");
   REQUIRE(R >= 1 && R <= (1L << 20), "bootstrap_curves: R must be 1 .. 2^20");
-  REQUIRE((((uintptr_t)keys | (uintptr_t)payload) & 3) == 0 && (((uintptr_t)records | (uintptr_t)ws) & 7) == 0,
-          "bootstrap_curves: keys / payload must be 4-byte, records / workspace 8-byte aligned");
-  const size_t need = aaclip_bootstrap_workspace_bytes(n, images, R), n4 = (size_t)n * 4, nc = (size_t)R * images,
-               nr = (size_t)R * 32;
-  REQUIRE(!ranges_overlap(ws, need, keys, n4) && !ranges_overlap(ws, need, payload, n4) &&
-              !ranges_overlap(ws, need, counts, nc) && !ranges_overlap(ws, need, records, nr) &&
-              !ranges_overlap(records, nr, keys, n4) && !ranges_overlap(records, nr, payload, n4) &&
-              !ranges_overlap(records, nr, counts, nc),
-          "bootstrap_curves: inputs, records and workspace must not overlap one another");
+  const size_t need = aaclip_bootstrap_workspace_bytes(n, images, R), n4 = (size_t)n * 4;
+  const Buf b[] = {rd(keys, n4, 4), rd(payload, n4, 4), rd(counts, (size_t)R * images), wr(records, (size_t)R * 32, 8),
+                   wr(ws, need, 8)};
+  REQUIRE(bufs_misaligned(b) < 0, "bootstrap_curves: keys / payload must be 4-byte, records / workspace 8-byte aligned");
+  REQUIRE(!bufs_clash(b), "bootstrap_curves: inputs, records and workspace must not overlap one another");
   REQUIRE(ws_bytes >= need, "bootstrap_curves: workspace too small");
   launch_bootstrap_curves(keys, payload, n, counts, images, R, records, ws, (hipStream_t)plan->stream);
   return finish("bootstrap_curves");
@@ -1578,14 +1560,11 @@ int aaclip_metrics_f1max(const uint32_t* keys, const uint8_t* labels_sorted, lon
   REQUIRE(packed == 0 || packed == 1, "metrics_f1max: packed must be 0 or 1");
   REQUIRE(packed || labels_sorted, "metrics_f1max: labels_sorted is required when the label is not packed into the key");
   REQUIRE(metrics_n_ok(n), "metrics_f1max: n must be 2 .. 2^31 - 1");
-  REQUIRE(((uintptr_t)keys & 3) == 0 && (((uintptr_t)record | (uintptr_t)ws) & 7) == 0,
-          "metrics_f1max: keys must be 4-byte, record / workspace 8-byte aligned");
-  const size_t need = aaclip_metrics_f1max_workspace_bytes(n), rec = sizeof(aaclip_metrics_f1max_record);
-  REQUIRE(!ranges_overlap(ws, need, keys, (size_t)n * 4) && !ranges_overlap(ws, need, record, rec) &&
-              !ranges_overlap(record, rec, keys, (size_t)n * 4) &&
-              !(labels_sorted && (ranges_overlap(ws, need, labels_sorted, (size_t)n) ||
-                                  ranges_overlap(record, rec, labels_sorted, (size_t)n))),
-          "metrics_f1max: keys, labels, record and workspace must not overlap one another");
+  const size_t need = aaclip_metrics_f1max_workspace_bytes(n);
+  const Buf b[] = {rd(keys, (size_t)n * 4, 4), rd(labels_sorted, (size_t)n),
+                   wr(record, sizeof(aaclip_metrics_f1max_record), 8), wr(ws, need, 8)};
+  REQUIRE(bufs_misaligned(b) < 0, "metrics_f1max: keys must be 4-byte, record / workspace 8-byte aligned");
+  REQUIRE(!bufs_clash(b), "metrics_f1max: keys, labels, record and workspace must not overlap one another");
   REQUIRE(ws_bytes >= need, "metrics_f1max: workspace too small");
   launch_metrics_f1max(keys, labels_sorted, n, packed, record, ws, (hipStream_t)stream);
   return finish("metrics_f1max");
@@ -1608,20 +1587,13 @@ int aaclip_metrics_threshold(const float* scores, const uint8_t* labels, long n,
   REQUIRE(grid_fits(metrics_range_partials(n, per_image)),
           "metrics_threshold: too many workgroups (one or more per image: n / per_image must stay below 2^24)");
   REQUIRE(!image_counts || (labels && per_image > 0), "metrics_threshold: per-image counts need labels and per_image > 0");
-  REQUIRE((((uintptr_t)scores | (uintptr_t)image_counts) & 3) == 0 &&
-              (((uintptr_t)range_record | (uintptr_t)f1max_record | (uintptr_t)totals | (uintptr_t)ws) & 7) == 0,
+  const size_t need = aaclip_metrics_threshold_workspace_bytes(n, per_image);
+  const Buf b[] = {wr(mask, (size_t)n), wr(image_counts, image_counts ? (size_t)(n / per_image) * 16 : 0, 4),
+                   wr(totals, sizeof(aaclip_metrics_threshold_record), 8), wr(ws, need, 8), rd(scores, (size_t)n * 4, 4),
+                   rd(labels, (size_t)n), rd(range_record, 24, 8), rd(f1max_record, sizeof(aaclip_metrics_f1max_record), 8)};
+  REQUIRE(bufs_misaligned(b) < 0,
           "metrics_threshold: scores / image_counts must be 4-byte, records / totals / workspace 8-byte aligned");
-  const size_t need = aaclip_metrics_threshold_workspace_bytes(n, per_image), n4 = (size_t)n * 4;
-  const size_t f1 = sizeof(aaclip_metrics_f1max_record), tot = sizeof(aaclip_metrics_threshold_record);
-  const size_t cnt = image_counts ? (size_t)(n / per_image) * 16 : 0;
-  // every written buffer (mask, image_counts, totals, workspace) against every other buffer of the call
-  const void* bufs[8] = {mask, image_counts, totals, ws, scores, labels, range_record, f1max_record};
-  const size_t lens[8] = {(size_t)n, cnt, tot, need, n4, (size_t)n, 24, f1};
-  bool clash = false;
-  for (int a = 0; a < 4; ++a)
-    for (int b = a + 1; b < 8; ++b)
-      clash = clash || (bufs[a] && bufs[b] && ranges_overlap(bufs[a], lens[a], bufs[b], lens[b]));
-  REQUIRE(!clash, "metrics_threshold: scores, labels, records, outputs and workspace must not overlap one another");
+  REQUIRE(!bufs_clash(b), "metrics_threshold: scores, labels, records, outputs and workspace must not overlap one another");
   REQUIRE(ws_bytes >= need, "metrics_threshold: workspace too small");
   launch_metrics_threshold(scores, labels, n, per_image, range_record, f1max_record, mask, image_counts, totals, ws,
                            (hipStream_t)stream);
@@ -1669,12 +1641,15 @@ int aaclip_optim_grad_norm(const aaclip_optim_tensors* tensors, float max_norm, 
   if (const char* m = optim_tensors_check(tensors, 1, 0)) return fail(-1, in("optim_grad_norm", m));
   REQUIRE(max_norm > 0.0f, "optim_grad_norm: max_norm must be above 0");
   REQUIRE(record && workspace, "optim_grad_norm: null pointer");
-  REQUIRE((((uintptr_t)record | (uintptr_t)workspace) & 7) == 0,
-          "optim_grad_norm: record and workspace must be 8-byte aligned");
   const size_t need = aaclip_optim_grad_norm_workspace_bytes(tensors);
+  const Buf b[] = {wr(record, sizeof(aaclip_optim_record), 8), wr(workspace, need, 8)};
+  REQUIRE(bufs_misaligned(b) < 0, "optim_grad_norm: record and workspace must be 8-byte aligned");
   REQUIRE(workspace_bytes >= need, "optim_grad_norm: workspace too small");
-  REQUIRE(!ranges_overlap(workspace, need, record, sizeof(aaclip_optim_record)),
-          "optim_grad_norm: record and workspace must not overlap");
+  REQUIRE(!bufs_clash(b), "optim_grad_norm: record and workspace must not overlap");
+  for (long i = 0; i < tensors->count; ++i) {   // the table's read-only rows: one gradient per tensor
+    const Buf g = rd(tensors->items[i].g, (size_t)tensors->items[i].n * 4, 4);
+    REQUIRE(!bufs_overlap(b[0], g) && !bufs_overlap(b[1], g), "optim_grad_norm: record and workspace must not overlap a gradient");
+  }
   long* counts = optim_counts(tensors);
   if (!counts) return fail(-3, "optim_grad_norm: out of memory");
   launch_optim_grad_norm(tensors->items, counts, tensors->count, max_norm, record, workspace, (hipStream_t)stream);
@@ -1736,15 +1711,10 @@ int aaclip_metrics_regions(const uint8_t* mask, long images, long H, long W, int
   REQUIRE(connectivity == 4 || connectivity == 8, "metrics_regions: connectivity must be 4 or 8");
   const long n = regions_pixels(images, H, W);
   REQUIRE(n != 0, "metrics_regions: images, H, W must be positive with 2 .. 2^31 - 1 pixels in all");
-  REQUIRE((((uintptr_t)region | (uintptr_t)area) & 3) == 0 && (((uintptr_t)record | (uintptr_t)ws) & 7) == 0,
-          "metrics_regions: region / area must be 4-byte, record / workspace 8-byte aligned");
   const size_t need = aaclip_metrics_regions_workspace_bytes(images, H, W), n4 = (size_t)n * 4;
-  REQUIRE(!ranges_overlap(ws, need, mask, (size_t)n) && !ranges_overlap(ws, need, region, n4) &&
-              !ranges_overlap(ws, need, area, n4) && !ranges_overlap(ws, need, record, 24) &&
-              !ranges_overlap(region, n4, mask, (size_t)n) && !ranges_overlap(area, n4, mask, (size_t)n) &&
-              !ranges_overlap(region, n4, area, n4) && !ranges_overlap(record, 24, mask, (size_t)n) &&
-              !ranges_overlap(record, 24, region, n4) && !ranges_overlap(record, 24, area, n4),
-          "metrics_regions: mask, outputs, record and workspace must not overlap one another");
+  const Buf b[] = {rd(mask, (size_t)n), wr(region, n4, 4), wr(area, n4, 4), wr(record, 24, 8), wr(ws, need, 8)};
+  REQUIRE(bufs_misaligned(b) < 0, "metrics_regions: region / area must be 4-byte, record / workspace 8-byte aligned");
+  REQUIRE(!bufs_clash(b), "metrics_regions: mask, outputs, record and workspace must not overlap one another");
   REQUIRE(ws_bytes >= need, "metrics_regions: workspace too small");
   launch_metrics_regions(mask, n, (int)H, (int)W, connectivity, region, area, record, ws, (hipStream_t)stream);
   return finish("metrics_regions");
@@ -1758,17 +1728,13 @@ int aaclip_metrics_sort_pairs(const float* scores, const uint32_t* values, long 
                               uint32_t* values_sorted, void* ws, size_t ws_bytes, void* stream) {
   REQUIRE(scores && values && keys && values_sorted && ws, "metrics_sort_pairs: null pointer");
   REQUIRE(metrics_n_ok(n), "metrics_sort_pairs: n must be 2 .. 2^31 - 1");
-  REQUIRE((((uintptr_t)scores | (uintptr_t)values | (uintptr_t)keys | (uintptr_t)values_sorted) & 3) == 0 &&
-              ((uintptr_t)ws & 7) == 0,
-          "metrics_sort_pairs: scores / values / keys must be 4-byte, the workspace 8-byte aligned");
   const size_t need = aaclip_metrics_sort_pairs_workspace_bytes(n), n4 = (size_t)n * 4;
-  REQUIRE(!ranges_overlap(keys, n4, scores, n4) && !ranges_overlap(keys, n4, values, n4) &&
-              !ranges_overlap(values_sorted, n4, scores, n4) && !ranges_overlap(values_sorted, n4, values, n4),
+  const Buf b[] = {rd(scores, n4, 4), rd(values, n4, 4), wr(keys, n4, 4), wr(values_sorted, n4, 4), wr(ws, need, 8)};
+  REQUIRE(bufs_misaligned(b) < 0,
+          "metrics_sort_pairs: scores / values / keys must be 4-byte, the workspace 8-byte aligned");
+  REQUIRE(!bufs_overlap(b[2], b[0]) && !bufs_overlap(b[2], b[1]) && !bufs_overlap(b[3], b[0]) && !bufs_overlap(b[3], b[1]),
           "metrics_sort_pairs: the outputs must not overlap the inputs");
-  REQUIRE(!ranges_overlap(ws, need, scores, n4) && !ranges_overlap(ws, need, values, n4) &&
-              !ranges_overlap(ws, need, keys, n4) && !ranges_overlap(ws, need, values_sorted, n4) &&
-              !ranges_overlap(keys, n4, values_sorted, n4),
-          "metrics_sort_pairs: inputs, outputs and workspace must not overlap one another");
+  REQUIRE(!bufs_clash(b), "metrics_sort_pairs: inputs, outputs and workspace must not overlap one another");
   REQUIRE(ws_bytes >= need, "metrics_sort_pairs: workspace too small");
   launch_metrics_sort_pairs(scores, values, n, keys, values_sorted, ws, (hipStream_t)stream);
   return finish("metrics_sort_pairs");
@@ -1783,15 +1749,10 @@ int aaclip_metrics_pro_curve(const uint32_t* keys, const uint32_t* areas_sorted,
   REQUIRE(keys && areas_sorted && regions_record && record && ws, "metrics_pro_curve: null pointer");
   REQUIRE(metrics_n_ok(n), "metrics_pro_curve: n must be 2 .. 2^31 - 1");
   REQUIRE(fpr_limit > 0.0 && fpr_limit <= 1.0, "metrics_pro_curve: fpr_limit must lie in (0, 1]");
-  REQUIRE((((uintptr_t)keys | (uintptr_t)areas_sorted) & 3) == 0 &&
-              (((uintptr_t)regions_record | (uintptr_t)record | (uintptr_t)ws) & 7) == 0,
-          "metrics_pro_curve: keys / areas must be 4-byte, records / workspace 8-byte aligned");
   const size_t need = aaclip_metrics_pro_curve_workspace_bytes(n), n4 = (size_t)n * 4;
-  REQUIRE(!ranges_overlap(ws, need, keys, n4) && !ranges_overlap(ws, need, areas_sorted, n4) &&
-              !ranges_overlap(ws, need, record, 40) && !ranges_overlap(ws, need, regions_record, 24) &&
-              !ranges_overlap(record, 40, keys, n4) && !ranges_overlap(record, 40, areas_sorted, n4) &&
-              !ranges_overlap(record, 40, regions_record, 24),
-          "metrics_pro_curve: keys, areas, records and workspace must not overlap one another");
+  const Buf b[] = {rd(keys, n4, 4), rd(areas_sorted, n4, 4), rd(regions_record, 24, 8), wr(record, 40, 8), wr(ws, need, 8)};
+  REQUIRE(bufs_misaligned(b) < 0, "metrics_pro_curve: keys / areas must be 4-byte, records / workspace 8-byte aligned");
+  REQUIRE(!bufs_clash(b), "metrics_pro_curve: keys, areas, records and workspace must not overlap one another");
   REQUIRE(ws_bytes >= need, "metrics_pro_curve: workspace too small");
   launch_metrics_pro_curve(keys, areas_sorted, n, regions_record, fpr_limit, record, ws, (hipStream_t)stream);
   return finish("metrics_pro_curve");
@@ -1813,20 +1774,14 @@ int aaclip_region_table(const uint32_t* region, const uint32_t* area, const floa
   REQUIRE(min_area >= 1, "region_table: min_area must be at least 1");
   REQUIRE(capacity >= 0, "region_table: capacity must not be negative");
   REQUIRE(capacity == 0 || rows, "region_table: rows is null with capacity > 0");
-  REQUIRE((((uintptr_t)region | (uintptr_t)area | (uintptr_t)scores | (uintptr_t)image_offsets) & 3) == 0 &&
-              (((uintptr_t)range_record | (uintptr_t)rows | (uintptr_t)record | (uintptr_t)ws) & 7) == 0,
-          "region_table: region / area / scores / image_offsets must be 4-byte, rows / records / workspace 8-byte aligned");
   const size_t need = aaclip_region_table_workspace_bytes(images, H, W), n4 = (size_t)n * 4;
-  const size_t row_bytes = rows ? (size_t)(capacity < n ? capacity : n) * sizeof(aaclip_region_row) : 0;
-  // every written buffer (rows, image_offsets, kept_mask, record, workspace) against every other buffer of the call
-  const void* bufs[10] = {rows, image_offsets, kept_mask, record, ws, region, area, scores, range_record, other};
-  const size_t lens[10] = {row_bytes, (size_t)(images + 1) * 4, (size_t)n, sizeof(aaclip_region_table_record), need,
-                           n4, n4, n4, 24, (size_t)n};
-  bool clash = false;
-  for (int a = 0; a < 5; ++a)
-    for (int b = a + 1; b < 10; ++b)
-      clash = clash || (bufs[a] && bufs[b] && lens[a] && lens[b] && ranges_overlap(bufs[a], lens[a], bufs[b], lens[b]));
-  REQUIRE(!clash, "region_table: inputs, outputs, records and workspace must not overlap one another");
+  const Buf b[] = {wr(rows, (size_t)(capacity < n ? capacity : n) * sizeof(aaclip_region_row), 8),
+                   wr(image_offsets, (size_t)(images + 1) * 4, 4), wr(kept_mask, (size_t)n),
+                   wr(record, sizeof(aaclip_region_table_record), 8), wr(ws, need, 8), rd(region, n4, 4), rd(area, n4, 4),
+                   rd(scores, n4, 4), rd(range_record, 24, 8), rd(other, (size_t)n)};
+  REQUIRE(bufs_misaligned(b) < 0,
+          "region_table: region / area / scores / image_offsets must be 4-byte, rows / records / workspace 8-byte aligned");
+  REQUIRE(!bufs_clash(b), "region_table: inputs, outputs, records and workspace must not overlap one another");
   REQUIRE(ws_bytes >= need, "region_table: workspace too small");
   launch_region_table(region, area, scores, range_record, other, images, (int)H, (int)W, min_area, capacity, rows,
                       image_offsets, kept_mask, record, ws, (hipStream_t)stream);
@@ -1849,18 +1804,14 @@ int aaclip_support_nearest(const float* q, long M, const void* bank, long N, int
                            int* best_idx, void* ws, size_t ws_bytes, void* stream) {
   REQUIRE(q && bank && best_cos && ws, "support_nearest: null pointer");
   if (const char* m = support_shape_check(M, N, E, form)) return fail(-1, in("support_nearest", m));
-  REQUIRE_ALIGNED16("support_nearest", q, bank);
-  REQUIRE((((uintptr_t)best_cos | (uintptr_t)best_idx) & 3) == 0 && ((uintptr_t)ws & 7) == 0,
-          "support_nearest: best_cos / best_idx must be 4-byte, the workspace 8-byte aligned");
   const size_t need = support_ws_bytes(M);
+  const Buf b[] = {rd(q, (size_t)M * E * 4, 16), rd(bank, (size_t)N * E * (form == AACLIP_SUPPORT_FP16 ? 2 : 4), 16),
+                   wr(best_cos, (size_t)M * 4, 4), wr(best_idx, (size_t)M * 4, 4), wr(ws, need, 8)};
+  const int bad = bufs_misaligned(b);
+  REQUIRE(bad < 0 || bad >= 2, in("support_nearest", "pointers must be 16-byte aligned"));
+  REQUIRE(bad < 0, "support_nearest: best_cos / best_idx must be 4-byte, the workspace 8-byte aligned");
   REQUIRE(ws_bytes >= need, "support_nearest: workspace too small");
-  const size_t qb = (size_t)M * E * 4, bb = (size_t)N * E * (form == AACLIP_SUPPORT_FP16 ? 2 : 4), ob = (size_t)M * 4;
-  const void* bufs[5] = {best_cos, best_idx, ws, q, bank};
-  const size_t lens[5] = {ob, ob, need, qb, bb};
-  bool clash = false;
-  for (int a = 0; a < 3; ++a)
-    for (int b = a + 1; b < 5; ++b) clash = clash || (bufs[a] && bufs[b] && ranges_overlap(bufs[a], lens[a], bufs[b], lens[b]));
-  REQUIRE(!clash, "support_nearest: outputs and workspace must not overlap one another or the inputs");
+  REQUIRE(!bufs_clash(b), "support_nearest: outputs and workspace must not overlap one another or the inputs");
   launch_support_nearest(q, M, bank, N, E, form, best_cos, best_idx, ws, (hipStream_t)stream);
   return finish("support_nearest");
 }
@@ -1868,9 +1819,9 @@ int aaclip_support_nearest(const float* q, long M, const void* bank, long N, int
 int aaclip_support_bank_rows(const float* rows, long N, int E, int form, void* bank, void* stream) {
   REQUIRE(rows && bank, "support_bank_rows: null pointer");
   if (const char* m = support_shape_check(1, N, E, form)) return fail(-1, in("support_bank_rows", m));
-  REQUIRE_ALIGNED16("support_bank_rows", rows, bank);
-  const size_t rb = (size_t)N * E * 4, bb = (size_t)N * E * (form == AACLIP_SUPPORT_FP16 ? 2 : 4);
-  REQUIRE(!ranges_overlap(rows, rb, bank, bb), "support_bank_rows: rows and bank must not overlap");
+  const Buf b[] = {rd(rows, (size_t)N * E * 4, 16), wr(bank, (size_t)N * E * (form == AACLIP_SUPPORT_FP16 ? 2 : 4), 16)};
+  REQUIRE(bufs_misaligned(b) < 0, in("support_bank_rows", "pointers must be 16-byte aligned"));
+  REQUIRE(!bufs_clash(b), "support_bank_rows: rows and bank must not overlap");
   launch_support_bank_rows(rows, N, E, form, bank, (hipStream_t)stream);
   return finish("support_bank_rows");
 }
@@ -1884,9 +1835,13 @@ int aaclip_support_map(const float* const* best_cos, int NL, const float* base, 
   REQUIRE(sigma > 0.f, "support_map: sigma must be positive");
   const long BP = (long)B * g * g, n = (long)B * S * S;
   REQUIRE(ws_bytes >= (size_t)NL * BP * 4, "support_map: workspace too small");
-  REQUIRE(base == nullptr || !ranges_overlap(base, (size_t)n * 4, out, (size_t)n * 4),
-          "support_map: base must not overlap out");
+  const size_t lb = (size_t)BP * 4;
+  const Buf b[] = {wr(out, (size_t)n * 4), rd(base, (size_t)n * 4), wr(ws, (size_t)NL * lb), rd(best_cos[0], lb),
+                   rd(NL > 1 ? best_cos[1] : nullptr, lb), rd(NL > 2 ? best_cos[2] : nullptr, lb),
+                   rd(NL > 3 ? best_cos[3] : nullptr, lb)};
+  REQUIRE(!bufs_overlap(b[0], b[1]), "support_map: base must not overlap out");
   for (int l = 0; l < NL; ++l) REQUIRE(best_cos[l], "support_map: null level pointer");
+  REQUIRE(!bufs_clash(b), "support_map: out and the workspace must not overlap each other or the inputs");
   hipStream_t s = (hipStream_t)stream;
   float* pre = (float*)ws;
   for (int l = 0; l < NL; ++l) launch_support_dist(best_cos[l], pre + (size_t)l * BP, BP, s);
@@ -1905,10 +1860,11 @@ static const char* coreset_shape_check(long N, int E) {
 int aaclip_coreset_rows(const float* rows, long N, int E, int16_t* q, int32_t* norm2, void* stream) {
   REQUIRE(rows && q && norm2, "coreset_rows: null pointer");
   if (const char* m = coreset_shape_check(N, E)) return fail(-1, in("coreset_rows", m));
-  REQUIRE_ALIGNED16("coreset_rows", rows, q);
-  REQUIRE(((uintptr_t)norm2 & 3) == 0, "coreset_rows: norm2 must be 4-byte aligned");
-  const size_t rb = (size_t)N * E * 4, qb = (size_t)N * E * 2, nb = (size_t)N * 4;
-  REQUIRE(!ranges_overlap(rows, rb, q, qb) && !ranges_overlap(rows, rb, norm2, nb) && !ranges_overlap(q, qb, norm2, nb),
+  const Buf b[] = {rd(rows, (size_t)N * E * 4, 16), wr(q, (size_t)N * E * 2, 16), wr(norm2, (size_t)N * 4, 4)};
+  const int bad = bufs_misaligned(b);
+  REQUIRE(bad < 0 || bad == 2, in("coreset_rows", "pointers must be 16-byte aligned"));
+  REQUIRE(bad < 0, "coreset_rows: norm2 must be 4-byte aligned");
+  REQUIRE(!bufs_clash(b),
           "coreset_rows: rows, q and norm2 must not overlap");
   launch_coreset_rows(rows, N, E, q, norm2, (hipStream_t)stream);
   return finish("coreset_rows");
@@ -1917,8 +1873,9 @@ int aaclip_coreset_rows(const float* rows, long N, int E, int16_t* q, int32_t* n
 int aaclip_coreset_unit_rows(const float* rows, long N, int E, float* out, void* stream) {
   REQUIRE(rows && out, "coreset_unit_rows: null pointer");
   if (const char* m = coreset_shape_check(N, E)) return fail(-1, in("coreset_unit_rows", m));
-  REQUIRE_ALIGNED16("coreset_unit_rows", rows, out);
-  REQUIRE(!ranges_overlap(rows, (size_t)N * E * 4, out, (size_t)N * E * 4), "coreset_unit_rows: rows and out must not overlap");
+  const Buf b[] = {rd(rows, (size_t)N * E * 4, 16), wr(out, (size_t)N * E * 4, 16)};
+  REQUIRE(bufs_misaligned(b) < 0, in("coreset_unit_rows", "pointers must be 16-byte aligned"));
+  REQUIRE(!bufs_clash(b), "coreset_unit_rows: rows and out must not overlap");
   launch_coreset_unit_rows(rows, N, E, out, (hipStream_t)stream);
   return finish("coreset_unit_rows");
 }
@@ -1933,17 +1890,14 @@ int aaclip_coreset_select(const int16_t* q, const int32_t* norm2, long N, int E,
   if (const char* m = coreset_shape_check(N, E)) return fail(-1, in("coreset_select", m));
   REQUIRE(n >= 1 && n <= N, "coreset_select: n must be 1 .. N");
   REQUIRE(start >= 0 && start < N, "coreset_select: start must be 0 .. N - 1");
-  REQUIRE_ALIGNED16("coreset_select", q);
-  REQUIRE((((uintptr_t)norm2 | (uintptr_t)picks | (uintptr_t)radius2 | (uintptr_t)min_d2) & 3) == 0 && ((uintptr_t)ws & 7) == 0,
-          "coreset_select: norm2 / picks / radius2 / min_d2 must be 4-byte, the workspace 8-byte aligned");
   const size_t need = coreset_ws_bytes(n);
+  const Buf b[] = {rd(q, (size_t)N * E * 2, 16), rd(norm2, (size_t)N * 4, 4), wr(picks, (size_t)n * 4, 4),
+                   wr(radius2, (size_t)(n + 1) * 4, 4), wr(min_d2, (size_t)N * 4, 4), wr(ws, need, 8)};
+  const int bad = bufs_misaligned(b);
+  REQUIRE(bad != 0, in("coreset_select", "pointers must be 16-byte aligned"));
+  REQUIRE(bad < 0, "coreset_select: norm2 / picks / radius2 / min_d2 must be 4-byte, the workspace 8-byte aligned");
   REQUIRE(ws_bytes >= need, "coreset_select: workspace too small");
-  const void* bufs[6] = {picks, radius2, min_d2, ws, q, norm2};
-  const size_t lens[6] = {(size_t)n * 4, (size_t)(n + 1) * 4, (size_t)N * 4, need, (size_t)N * E * 2, (size_t)N * 4};
-  bool clash = false;
-  for (int a = 0; a < 4; ++a)
-    for (int b = a + 1; b < 6; ++b) clash = clash || ranges_overlap(bufs[a], lens[a], bufs[b], lens[b]);
-  REQUIRE(!clash, "coreset_select: outputs and workspace must not overlap one another or the inputs");
+  REQUIRE(!bufs_clash(b), "coreset_select: outputs and workspace must not overlap one another or the inputs");
   launch_coreset_select(q, norm2, N, E, n, start, picks, radius2, min_d2, ws, (hipStream_t)stream);
   return finish("coreset_select");
 }
@@ -1959,19 +1913,19 @@ int aaclip_tile_canvas(int tile, int grid, int overlap) {
 static int tile_entry_check(const char* entry, const aaclip_tile_plan* plan, const void* canvas, const void* tiles,
                             TileGeom* g, bool* launch) {
   *launch = false;
-  if (!plan) return fail(-1, in(entry, "null plan"));
-  if (plan->struct_bytes != sizeof(aaclip_tile_plan))
-    return fail(-1, in(entry, "aaclip_tile_plan.struct_bytes does not match this library (binding generated from another "
-                              "header?)"));
+  if (const char* m = plan_refusal(plan, "aaclip_tile_plan.struct_bytes does not match this library (binding generated "
+                                         "from another header?)"))
+    return fail(-1, in(entry, m));
   if (const char* m = tile_plan_check(plan->images, plan->channels, plan->tile, plan->grid, plan->overlap))
     return fail(-1, in(entry, m));
   if (!canvas || !tiles) return fail(-1, in(entry, "null pointer"));
-  if (((uintptr_t)canvas | (uintptr_t)tiles) & 3) return fail(-1, in(entry, "canvas and tiles must be 4-byte aligned"));
   *g = tile_geom(plan->channels, plan->tile, plan->grid, plan->overlap);
-  const size_t per_image = (size_t)plan->channels * 4;
-  const size_t canvas_bytes = (size_t)plan->images * per_image * (size_t)g->C * (size_t)g->C;
-  const size_t tiles_bytes = (size_t)plan->images * per_image * (size_t)g->G * (size_t)g->G * (size_t)g->S * (size_t)g->S;
-  if (ranges_overlap(canvas, canvas_bytes, tiles, tiles_bytes)) return fail(-1, in(entry, "canvas and tiles must not overlap"));
+  const size_t per_image = (size_t)plan->images * (size_t)plan->channels * 4;
+  // one of the two is the entry's output: with two buffers the pair is checked whichever it is
+  const Buf b[] = {wr(canvas, per_image * (size_t)g->C * (size_t)g->C, 4),
+                   wr(tiles, per_image * (size_t)g->G * (size_t)g->G * (size_t)g->S * (size_t)g->S, 4)};
+  if (bufs_misaligned(b) >= 0) return fail(-1, in(entry, "canvas and tiles must be 4-byte aligned"));
+  if (bufs_clash(b)) return fail(-1, in(entry, "canvas and tiles must not overlap"));
   *launch = plan->images > 0;
   return 0;
 }
@@ -1998,23 +1952,21 @@ int aaclip_tile_stitch(const aaclip_tile_plan* plan, const float* tiles, float* 
 int aaclip_overlay_render(const aaclip_overlay_plan* plan, const float* frames, const float* maps, const void* range_record,
                           const uint8_t* pred, const uint8_t* truth, const uint8_t* lut, uint8_t* out) {
   const char* entry = "aaclip_overlay_render";
-  if (!plan) return fail(-1, in(entry, "null plan"));
-  if (plan->struct_bytes != sizeof(aaclip_overlay_plan))
-    return fail(-1, in(entry, "aaclip_overlay_plan.struct_bytes does not match this library (binding generated from "
-                              "another header?)"));
+  if (const char* m = plan_refusal(plan, "aaclip_overlay_plan.struct_bytes does not match this library (binding "
+                                         "generated from another header?)"))
+    return fail(-1, in(entry, m));
   if (const char* m = overlay_plan_check(plan->images, plan->height, plan->width, plan->panels, plan->alpha256,
                                          plan->thickness, plan->std))
     return fail(-1, in(entry, m));
   if (!frames || !maps || !lut || !out) return fail(-1, in(entry, "null pointer (frames, maps, lut and out are required)"));
   if ((plan->panels & OVERLAY_TRUTH) && !truth) return fail(-1, in(entry, "the truth panel needs a truth mask"));
-  if (((uintptr_t)frames | (uintptr_t)maps) & 3) return fail(-1, in(entry, "frames and maps must be 4-byte aligned"));
-  if (range_record && ((uintptr_t)range_record & 7)) return fail(-1, in(entry, "the range record must be 8-byte aligned"));
   const size_t pixels = (size_t)plan->images * (size_t)plan->height * (size_t)plan->width;
-  const size_t out_bytes = pixels * 3 * (size_t)overlay_panel_count(plan->panels);
-  if (ranges_overlap(out, out_bytes, frames, pixels * 12) || ranges_overlap(out, out_bytes, maps, pixels * 4) ||
-      ranges_overlap(out, out_bytes, lut, 768) || (range_record && ranges_overlap(out, out_bytes, range_record, 24)) ||
-      (pred && ranges_overlap(out, out_bytes, pred, pixels)) || (truth && ranges_overlap(out, out_bytes, truth, pixels)))
-    return fail(-1, in(entry, "out must not overlap an input"));
+  const Buf b[] = {rd(frames, pixels * 12, 4), rd(maps, pixels * 4, 4), rd(range_record, 24, 8), rd(pred, pixels),
+                   rd(truth, pixels), rd(lut, 768), wr(out, pixels * 3 * (size_t)overlay_panel_count(plan->panels))};
+  const int bad = bufs_misaligned(b);
+  if (bad == 0 || bad == 1) return fail(-1, in(entry, "frames and maps must be 4-byte aligned"));
+  if (bad >= 0) return fail(-1, in(entry, "the range record must be 8-byte aligned"));
+  if (bufs_clash(b)) return fail(-1, in(entry, "out must not overlap an input"));
   if (plan->images == 0) return 0;
   OverlayGeom g = overlay_geom(plan->height, plan->width, plan->panels, plan->alpha256, plan->thickness, pred != nullptr,
                                truth != nullptr);
@@ -2028,9 +1980,9 @@ int aaclip_overlay_render(const aaclip_overlay_plan* plan, const float* frames, 
 
 // ---- PNG encoding (png.hip; the format, the geometry and the plan checks: png_plan.h)
 static const char* png_plan_refusal(const aaclip_png_plan* plan) {
-  if (!plan) return "null plan";
-  if (plan->struct_bytes != sizeof(aaclip_png_plan))
-    return "aaclip_png_plan.struct_bytes does not match this library (binding generated from another header?)";
+  if (const char* m = plan_refusal(plan, "aaclip_png_plan.struct_bytes does not match this library (binding generated "
+                                         "from another header?)"))
+    return m;
   return png_plan_check(plan->images, plan->height, plan->width, plan->channels);
 }
 
@@ -2053,11 +2005,14 @@ int aaclip_png_encode(const aaclip_png_plan* plan, const uint8_t* pixels, void* 
   const PngGeom g = png_geom(plan->images, plan->height, plan->width, plan->channels);
   if (ws_bytes < png_workspace_bytes(g)) return fail(-1, in(entry, "workspace too small (aaclip_png_workspace_bytes)"));
   if (capacity < png_capacity_bytes(g)) return fail(-1, in(entry, "payload capacity too small (aaclip_png_capacity_bytes)"));
-  if ((uintptr_t)workspace & 15) return fail(-1, in(entry, "the workspace must be 16-byte aligned"));
-  if ((uintptr_t)offsets & 7) return fail(-1, in(entry, "offsets must be 8-byte aligned"));
-  const size_t pixel_bytes = (size_t)g.images * (size_t)g.H * (size_t)g.R, offsets_bytes = ((size_t)g.images + 1) * 8;
-  if (ranges_overlap(payload, capacity, pixels, pixel_bytes) || ranges_overlap(offsets, offsets_bytes, pixels, pixel_bytes))
+  const Buf b[] = {rd(pixels, (size_t)g.images * (size_t)g.H * (size_t)g.R), wr(workspace, png_workspace_bytes(g), 16),
+                   wr(payload, capacity), wr(offsets, ((size_t)g.images + 1) * 8, 8)};
+  const int bad = bufs_misaligned(b);
+  if (bad == 1) return fail(-1, in(entry, "the workspace must be 16-byte aligned"));
+  if (bad >= 0) return fail(-1, in(entry, "offsets must be 8-byte aligned"));
+  if (bufs_overlap(b[2], b[0]) || bufs_overlap(b[3], b[0]))
     return fail(-1, in(entry, "payload and offsets must not overlap pixels"));
+  if (bufs_clash(b)) return fail(-1, in(entry, "the workspace, payload and offsets must not overlap one another or pixels"));
   launch_png_encode(g, pixels, workspace, payload, offsets, (hipStream_t)plan->stream);
   return finish("aaclip_png_encode");
 }

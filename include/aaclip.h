@@ -424,10 +424,28 @@ int aaclip_resample_table(int in_size, int out_size, int32_t* bounds, int32_t* c
 int aaclip_preprocess(const uint8_t* src, int B, int Hs, int Ws, int S, const int32_t* hbounds, const int32_t* hcoefs,
                       const int32_t* vbounds, const int32_t* vcoefs, const float* lut, float* out, void* stream);
 
+/* Buffers of a call.  For the data-side entries below -- the input work, the metrics and their bootstrap, the optimiser's
+ * gradient norm, the support bank, the coreset, tiles, overlays and PNG encoding -- one rule holds, checked before the
+ * first launch: every buffer the call WRITES (outputs, records, the workspace, over the lengths stated at the entry, the
+ * workspace over its *_workspace_bytes) shares no byte with any other buffer of the call; buffers the call only reads may
+ * alias one another.  A NULL or empty buffer overlaps nothing, and a range may end on the last byte of the address space.
+ * A refusal carries the entry's name and the word "overlap".  Two entries take an in-place form, named where they are
+ * described: aaclip_color_jitter with dst == src and aaclip_metrics_normalise with out == scores; a partial overlap of
+ * the two is refused.  The rule covers these pairs, which earlier revisions of the library let through:
+ *   aaclip_metrics_sort        keys x labels, labels_sorted x scores, out_of_range x scores, out_of_range x labels
+ *   aaclip_metrics_range       image_max x labels, record x labels
+ *   aaclip_metrics_normalise   out x range_record
+ *   aaclip_color_jitter        ws x src, dst, factors, apply; dst x factors, apply
+ *   aaclip_augment_geometric   image_out, mask_out x angle_deg, shift, flags
+ *   aaclip_optim_grad_norm     record, workspace x every tensor's gradient
+ *   aaclip_support_map         ws x out, base, the level pointers; out x the level pointers
+ *   aaclip_png_encode          workspace x pixels, payload, offsets; payload x offsets
+ * Alignment is checked on every pointer that is given, from the same table (csrc/buffers.h). */
+
 /* Train-time input work on raw frames (reference dataset/__init__.py:37-102).  The reference draws its random numbers
  * inside DataLoader workers; here every drawn number is an argument, so a call is a pure function of its inputs and two
  * calls give the same bits.  All checks run before the first launch.  Errors carry the entry point's name as prefix.
- *   aaclip_color_jitter: src / dst uint8 [B,H,W,3] (device; dst == src is allowed, a partial overlap is not).  Per
+ *   aaclip_color_jitter: src / dst uint8 [B,H,W,3] (device; dst == src is allowed, a partial overlap is not: "Buffers of a call").  Per
  *   frame b: factors[3b .. 3b+2] = brightness, contrast, saturation factor (fp32, device), apply[b] bit 0 / 1 / 2 =
  *   run that step (int32, device); a clear bit skips the step.  Each step is Pillow's ImageEnhance: blend(degenerate,
  *   image, factor) = fp32 d + f * (s - d), clipped to [0, 255], truncated; degenerate = 0 (brightness), the constant
@@ -462,7 +480,7 @@ int aaclip_augment_geometric(const float* image, const float* mask, int B, int S
  * No floating-point atomics, every floating-point sum in an order fixed by n and the number of tie groups: two calls
  * give the same bits.  All checks precede the first launch, the workspace size last; errors carry the entry's name.
  * Every *_workspace_bytes is 0 for a refused n and monotonic in n.  scores / keys 4-byte, records and workspaces 8-byte
- * aligned; scores, labels, outputs, records and the workspace of a call must not overlap one another (checked).
+ * aligned; what a call writes overlaps no other buffer of it ("Buffers of a call" above).
  *   aaclip_metrics_range: record <- {min, max, number of non-finite scores (left out of min and max), number of
  *   non-zero labels (0 when labels is NULL)} in two stages (per-workgroup partials, one workgroup folds them in index
  *   order).  per_image > 0 (n a multiple of it): image_max[n / per_image] <- the maximum of every image; 0: none.
@@ -639,7 +657,8 @@ int aaclip_region_table(const uint32_t* region, const uint32_t* area, const floa
  *   (FP32, N * E * 4 bytes).
  *   aaclip_support_map: out [B, S, S] = base + weight * sum over levels of upsample(blur(1 - best_cos[l])), with
  *   aaclip_anomaly_map's blur, align-corners upsample and level order; best_cos[l] fp32 [B * g * g]; base [B, S, S] or
- *   NULL (= 0), not overlapping out; the distance is not clamped.  Workspace: NL * B * g * g * 4 bytes.
+ *   NULL (= 0); the distance is not clamped.  Workspace: NL * B * g * g * 4 bytes.  out and the workspace overlap neither
+ *   each other nor base or a level ("Buffers of a call").
  *   Alignment: q, rows and bank 16 bytes; best_cos, best_idx 4 bytes; the workspace 8 bytes. */
 #define AACLIP_SUPPORT_FP32 0
 #define AACLIP_SUPPORT_FP16 1
@@ -792,7 +811,8 @@ int aaclip_overlay_render(const aaclip_overlay_plan* plan, const float* frames, 
  * text that starts with the entry's name and writes nothing: a null plan, a struct_bytes other than sizeof, a negative
  * size, height or width 0 with images > 0, channels other than 1 or 3, 1 + R above 32768, sizes whose products
  * overflow ("too large"), a null pointer, a workspace or a capacity that is too small, a workspace not 16-byte or
- * offsets not 8-byte aligned, payload or offsets overlapping pixels.  images == 0 checks the plan, launches nothing
+ * offsets not 8-byte aligned, the workspace, payload or offsets overlapping one another or pixels ("Buffers of a call").
+ * images == 0 checks the plan, launches nothing
  * and returns 0.  This ABI number is unchanged: the entries are additions. */
 typedef struct aaclip_png_plan {
   size_t struct_bytes;      /* sizeof(aaclip_png_plan); any other value is refused */
