@@ -251,6 +251,9 @@ SIGNATURES = {
     "aaclip_drop_cls_rows": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "aaclip_iqm_map": (_i, [C.POINTER(_vp), _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _sz, _vp]),
     "aaclip_set_gemm_variant": (_i, [_i]),
+    "aaclip_set_tail_overlap": (_i, [_i]),
+    "aaclip_set_plan_cus": (_i, [_i]),
+    "aaclip_tail_overlap_count": (_l, []),
     "aaclip_profile_begin": (_i, [C.c_uint, _i]),
     "aaclip_profile_end": (_i, [C.POINTER(C.c_float), C.POINTER(C.c_int), _i]),
 }

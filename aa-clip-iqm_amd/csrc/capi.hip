@@ -16,6 +16,8 @@
 using namespace aaclip;
 
 static thread_local char g_err[512] = "";
+// Tail overlap (tail_plan.h), decided per product from the pricing in profiles/ln_tail_overlap_pricing.txt
+static constexpr bool TAIL_LN_OUT_PROJ = true, TAIL_LN_C_PROJ = true;
 static int g_ln_fold = 1;   // aaclip_set_gemm_variant bit 17 turns the LayerNorm folding off (A/B measurements)
 
 static int fail(int code, const char* msg) {
@@ -153,6 +155,19 @@ int aaclip_set_gemm_variant(int v) {
   g_ln_fold = ((v >> 17) & 1) ? 0 : 1;
   return 0;
 }
+
+int aaclip_set_tail_overlap(int on) {
+  set_tail_overlap(on != 0);
+  return 0;
+}
+
+int aaclip_set_plan_cus(int cus) {
+  REQUIRE(cus == 0 || (cus >= 8 && cus % 8 == 0 && cus <= 1024), "set_plan_cus: 0 (the device's count) or a multiple of 8, 8 .. 1024");
+  set_plan_cus(cus);
+  return 0;
+}
+
+long aaclip_tail_overlap_count(void) { return tail_launch_count(); }
 
 int aaclip_version(void) { return AACLIP_ABI_VERSION; }
 const char* aaclip_last_error(void) { return g_err; }
@@ -591,10 +606,15 @@ int aaclip_patch_embed(const float* img, const void* conv_w, const float* cls, c
 // mix when the block has an adapter).  *aux_out tells the caller whether they were produced.
 // x_in != x: the block READS the stream from x_in (left untouched) and continues it in x -- the first residual
 // update (out_proj) takes its residual from x_in and writes x.
+// Split fp16, FULL / CAUSAL attention: where a residual product leaves a partial last round, the LayerNorm after it runs
+// beside that round (tail_plan.h; launch_gemm_resid_ln) and only its last rows as a pass.  ln_2 belongs to this block.
+// ln_1 of the NEXT block (`next`, null: none) is produced by this block's c_proj: *ln1_out tells the caller that `narrow`
+// holds those rows, and it hands that to the next block as ln1_in, which then skips its own ln_1 pass.
 static int block_impl(const float* x_in, float* x, const aaclip_block_weights* w, float mix, int B, int L, int D, int H,
                       int F, int attn_mode, int dtype, void* ws, const WsLayout& l, hipStream_t s, bool aux_in,
-                      bool want_out, bool* aux_out) {
+                      bool want_out, bool* aux_out, bool ln1_in, const aaclip_block_weights* next, bool* ln1_out) {
   *aux_out = false;
+  *ln1_out = false;
   REQUIRE(w->ln1_w && w->ln1_b && w->qkv_w && w->qkv_b && w->out_w && w->out_b && w->ln2_w && w->ln2_b && w->fc_w &&
               w->fc_b && w->proj_w && w->proj_b,
           "block: null weight pointer");
@@ -640,7 +660,7 @@ static int block_impl(const float* x_in, float* x, const aaclip_block_weights* w
     if (aux_in && folding && w->qkv_w_fold && w->qkv_fold_s && w->qkv_fold_b && gemm_routes_to_256t(dtype, p)) {
       // ln_1 folded into the QKV product (include/aaclip.h, aaclip_block_weights)
       p.A = x16; p.W = w->qkv_w_fold; p.bias = w->qkv_fold_b; p.row_ab = rowab; p.col_s = w->qkv_fold_s;
-    } else {
+    } else if (!ln1_in) {
       ProfScope ps(0, s);
       launch_layernorm(dtype, x_in, w->ln1_w, w->ln1_b, narrow, rows, D, 1e-5f, s, !qkv_exact);
     }
@@ -669,7 +689,18 @@ static int block_impl(const float* x_in, float* x, const aaclip_block_weights* w
     p.out16 = x16;
     p.stats_out = partials;
   }
-  { ProfScope ps(3, s); launch_gemm(dtype, EPI_BIAS_RESID, p, s); }
+  // rows of `narrow` (split8 rows: 4 * D bytes) whose LayerNorm a residual product's tail launch has produced
+  const bool tail_ln = dtype == AACLIP_F16X2 && attn_mode != AACLIP_ATTN_VV_BATCH;
+  long ln_done = 0;
+  {
+    ProfScope ps(3, s);
+    if (tail_ln && TAIL_LN_OUT_PROJ) {
+      const LnRows ln2 = {w->ln2_w, w->ln2_b, narrow, 1e-5f, !(ex & AACLIP_EXACT16_FC)};
+      ln_done = launch_gemm_resid_ln(dtype, p, ln2, s);
+    } else {
+      launch_gemm(dtype, EPI_BIAS_RESID, p, s);
+    }
+  }
   // ---- x += c_proj(gelu(c_fc(ln_2 x)))
   if (fold2) {
     ProfScope ps(0, s);
@@ -677,7 +708,8 @@ static int block_impl(const float* x_in, float* x, const aaclip_block_weights* w
     fc.A = x16; fc.W = w->fc_w_fold; fc.bias = w->fc_fold_b; fc.row_ab = rowab; fc.col_s = w->fc_fold_s;
   } else {
     ProfScope ps(0, s);
-    launch_layernorm(dtype, x, w->ln2_w, w->ln2_b, narrow, rows, D, 1e-5f, s, !(ex & AACLIP_EXACT16_FC));
+    launch_layernorm(dtype, x + ln_done * D, w->ln2_w, w->ln2_b, narrow + ln_done * 4 * D, rows - ln_done, D, 1e-5f, s,
+                     !(ex & AACLIP_EXACT16_FC));
   }
   { ProfScope ps(4, s); launch_gemm(dtype, EPI_BIAS_GELU, fc, s); }
   p = gemm_params(big, sw * F, w->proj_w, w->proj_b, x, D, M, D, F);
@@ -689,7 +721,24 @@ static int block_impl(const float* x_in, float* x, const aaclip_block_weights* w
     p.out16 = x16;
     p.stats_out = partials;
   }
-  { ProfScope ps(5, s); launch_gemm(dtype, EPI_BIAS_RESID, p, s); }
+  // the next block's ln_1 beside c_proj's tail: not where an adapter still changes the rows
+  const bool ln1_next = tail_ln && TAIL_LN_C_PROJ && next && next->ln1_w && next->ln1_b && !w->adapter_w;
+  ln_done = 0;
+  {
+    ProfScope ps(5, s);
+    if (ln1_next) {
+      const LnRows ln1 = {next->ln1_w, next->ln1_b, narrow, 1e-5f, !(next->exact16 & AACLIP_EXACT16_QKV)};
+      ln_done = launch_gemm_resid_ln(dtype, p, ln1, s);
+    } else {
+      launch_gemm(dtype, EPI_BIAS_RESID, p, s);
+    }
+  }
+  if (ln_done > 0) {
+    ProfScope ps(0, s);
+    launch_layernorm(dtype, x + ln_done * D, next->ln1_w, next->ln1_b, narrow + ln_done * 4 * D, rows - ln_done, D, 1e-5f,
+                     s, !(next->exact16 & AACLIP_EXACT16_QKV));
+    *ln1_out = true;
+  }
   if (emit && !w->adapter_w) {
     ProfScope ps(0, s);
     launch_ln_stats_finalize(partials, rowab, rows, D / 64, D, 1e-5f, s);
@@ -757,15 +806,16 @@ static int blocks_core(const float* x_in, float* const* x_out, float* x_all, con
   REQUIRE(ws_bytes >= l.total, "block: workspace too small");
   if (x_out)
     for (int i = 0; i < n_blocks; ++i) REQUIRE(x_out[i], "block: null output buffer");
-  bool aux = false;
+  bool aux = false, ln1 = false;   // ln1: `narrow` already holds ln_1 of the block about to run
   const float* src = x_in;
   for (int i = 0; i < n_blocks; ++i) {
-    bool produced = false;
+    bool produced = false, ln1_produced = false;
     float* dst = x_out ? x_out[i] : x_all;
     int rc = block_impl(src, dst, w + i, mix, B, L, D, H, F, attn_mode, dtype, ws, l, (hipStream_t)stream, aux,
-                        i + 1 < n_blocks, &produced);
+                        i + 1 < n_blocks, &produced, ln1, i + 1 < n_blocks ? w + i + 1 : nullptr, &ln1_produced);
     if (rc) return rc;
     aux = produced;
+    ln1 = ln1_produced;
     src = dst;
   }
   return finish("block");

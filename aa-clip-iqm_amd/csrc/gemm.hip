@@ -480,4 +480,17 @@ void launch_gemm(int dtype, int epi, const GemmParams& p, hipStream_t s) {
   }
 }
 
+static bool g_tail_overlap = true;
+void set_tail_overlap(bool on) { g_tail_overlap = on; }
+
+long launch_gemm_resid_ln(int dtype, const GemmParams& p, const LnRows& ln, hipStream_t s) {
+  if (g_tail_overlap && dtype == AACLIP_F16X2 && !p.out_qk8 && gemm_split_routes_to_256t(p) &&
+      big_kernel_form(dtype) == GEMM256_WALK) {
+    const long done = launch_resid_ln_tail(p, ln, s);
+    if (done > 0) return done;
+  }
+  launch_gemm(dtype, EPI_BIAS_RESID, p, s);
+  return 0;
+}
+
 }  // namespace aaclip

@@ -11,8 +11,12 @@
 // Operand roles are swapped (W rows = MFMA A operand), so a lane holds output
 // column m = lane&15 and rows n = 4*(lane>>4) + j of each 16x16 tile.
 #include "common.h"
+#include <assert.h>
+
 #include "kernels.h"
+#include "ln_row.h"
 #include "mma16.h"
+#include "tail_plan.h"
 
 namespace aaclip {
 
@@ -538,9 +542,14 @@ template <int KIND, typename T> AACLIP_DEV f32x4 mma_e4m3k(const FragPair<T, fal
 // the epilogue of the current one, which then stages its rows in the other stage alone (epilogue256t<..., COMPACT>): the
 // prologue of a tile (argument loads, first DMA round trip, 32-64 KiB of LDS fill: ~5 us with the matrix pipe idle) runs
 // under the previous tile's stores.  `vgrid` is the size of that virtual grid (unused without WALK).
-template <typename T, int EPI, int NP = 0, bool QK8 = false, bool WALK = false>   // QK8: GemmParams::out_qk8 (EPI_BIAS, split operands only)
-__global__ __launch_bounds__(512, 2) void gemm16_256x_kernel(GemmParams p, int PN, int patches_n, int total_patches, int PM, int vgrid) {
+// The kernel's body is a device function that two kernels share: gemm16_256x_kernel below, and (LNT, split operands, WALK)
+// the tail launch of a residual product (tail_plan.h, gemm16_256x_ln_tail_kernel), where p describes the rows PAST the
+// full rounds and the workgroup runs the ONE tile (slot_tm, slot_tn) as a one-tile walk.
+template <typename T, int EPI, int NP, bool QK8, bool WALK, bool LNT>
+AACLIP_DEV void gemm16_256x_body(const GemmParams& p, int PN, int patches_n, int total_patches, int PM, int vgrid, int slot_tm,
+                                 int slot_tn) {
   static_assert(!WALK || NP != 0, "the walking form exists for split operands (tile-independent per-lane DMA offsets)");
+  static_assert(!LNT || (WALK && EPI == EPI_BIAS_RESID), "the tail launch is the walking kernel of a residual product");
   typedef typename Elem<T>::vec8 vec8;
   __shared__ __attribute__((aligned(16))) char smem[131072];
 
@@ -562,7 +571,11 @@ __global__ __launch_bounds__(512, 2) void gemm16_256x_kernel(GemmParams p, int P
   };
   int tm = 0, tn = 0;
   int vb = blockIdx.x;
-  if constexpr (WALK) {
+  if constexpr (LNT) {
+    tm = slot_tm;
+    tn = slot_tn;
+    vb = vgrid;   // no further tile: the walk below ends after this one
+  } else if constexpr (WALK) {
     while (vb < vgrid && !map_tile(vb, tm, tn)) vb += gridDim.x;
     if (vb >= vgrid) return;   // whole workgroup, before any barrier
   } else {
@@ -770,6 +783,35 @@ __global__ __launch_bounds__(512, 2) void gemm16_256x_kernel(GemmParams p, int P
 #undef LD_N
 #undef QUADX
 #undef KTILE
+}
+
+template <typename T, int EPI, int NP = 0, bool QK8 = false, bool WALK = false>   // QK8: GemmParams::out_qk8 (EPI_BIAS, split operands only)
+__global__ __launch_bounds__(512, 2) void gemm16_256x_kernel(GemmParams p, int PN, int patches_n, int total_patches, int PM, int vgrid) {
+  gemm16_256x_body<T, EPI, NP, QK8, WALK, false>(p, PN, patches_n, total_patches, PM, vgrid, 0, 0);
+}
+
+// Launch B of a split fp16 residual product (tail_plan.h): the workgroups of the tile slots run one tail tile each, exactly
+// as the walking kernel does; every other workgroup runs LayerNorm rows of the rows launch A completed (lt).  The two kinds
+// of workgroup touch disjoint rows (launch_resid_ln_tail asserts it) and never wait for one another.
+template <int NP>
+__global__ __launch_bounds__(512, 2) void gemm16_256x_ln_tail_kernel(GemmParams p, LnTail lt) {
+  const int w = blockIdx.x;
+  int slot_tm = 0, slot_tn = 0;
+  if (w >= lt.slots.span || !tail_slot_tile(lt.slots, w, slot_tm, slot_tn)) {
+    // (the GEMM body sets fp8_saturate_mode(); these waves convert in the default mode, as the LayerNorm pass does)
+    const long waves = 8L * (lt.slots.grid - lt.slots.span + lt.slots.holes);
+    const long first = 8L * tail_ln_worker(lt.slots, w) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const bool hi8 = lt.hi8 != 0;
+    switch (lt.nch) {
+      case 1: layernorm_split_rows_strided<1>(lt.x, lt.w, lt.b, lt.out, first, waves, lt.rows, lane, lt.eps, hi8); break;
+      case 2: layernorm_split_rows_strided<2>(lt.x, lt.w, lt.b, lt.out, first, waves, lt.rows, lane, lt.eps, hi8); break;
+      case 3: layernorm_split_rows_strided<3>(lt.x, lt.w, lt.b, lt.out, first, waves, lt.rows, lane, lt.eps, hi8); break;
+      case 4: layernorm_split_rows_strided<4>(lt.x, lt.w, lt.b, lt.out, first, waves, lt.rows, lane, lt.eps, hi8); break;
+    }
+    return;   // whole workgroup, before any barrier
+  }
+  gemm16_256x_body<f16, EPI_BIAS_RESID, NP, false, true, true>(p, 0, 0, 0, 0, 0, slot_tm, slot_tn);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1052,6 +1094,42 @@ static void launch_split(int epi, const GemmParams& p, hipStream_t s) {
     if constexpr (EPI == EPI_BIAS) dispatch_bool(p.out_qk8 != 0, run);
     else run(std::false_type{});
   });
+}
+
+// The grid the row split is PLANNED with, which is also launch B's: the walking grid, or what set_plan_cus() names so that
+// tests meet a tail at small shapes (launch A walks its rows on the device's grid either way).
+static int g_plan_cus = 0;
+static long g_tail_launches = 0;
+void set_plan_cus(int cus) { g_plan_cus = cus; }
+long tail_launch_count() { return g_tail_launches; }
+template <int NP>
+static void launch_tail_b(const GemmParams& pb, const LnTail& lt, hipStream_t s) {
+  hipLaunchKernelGGL((gemm16_256x_ln_tail_kernel<NP>), dim3(lt.slots.grid), dim3(512), 0, s, pb, lt);
+}
+// A split fp16 residual product on the walking kernel with the LayerNorm that follows it (tail_plan.h): launch A = the
+// rows of the full rounds, launch B = the tail tiles beside LayerNorm rows [0, r0).  Returns r0, the rows whose LayerNorm
+// is done, or 0 where the plan does not engage: then nothing was launched.
+long launch_resid_ln_tail(const GemmParams& p, const LnRows& ln, hipStream_t s) {
+  const TailPlan t = tail_plan(p.M, p.N, g_plan_cus > 0 ? g_plan_cus : walk_grid());
+  if (!t.engaged || p.ldc != p.N || p.out16 || p.stats_out) return 0;
+  // launch B's LayerNorm workers and tiles touch disjoint rows, and the LayerNorm reads the rows launch A wrote
+  assert(tail_rows_disjoint(p.M, t.r0, p.N, (uintptr_t)p.A, p.lda, (uintptr_t)p.out, p.ldc, (uintptr_t)p.resid, (uintptr_t)ln.out));
+  GemmParams pa = p;
+  pa.M = (int)t.r0;
+  if (p.w_exact16) launch_split<3, true>(EPI_BIAS_RESID, pa, s);
+  else launch_split<4, true>(EPI_BIAS_RESID, pa, s);
+  GemmParams pb = p;   // rows [r0, M) as a problem of its own
+  pb.M = p.M - (int)t.r0;
+  pb.A = (const f16*)p.A + t.r0 * p.lda;
+  pb.out = (float*)p.out + t.r0 * p.ldc;
+  if (p.resid) pb.resid = p.resid + t.r0 * p.ldc;
+  LnTail lt;
+  lt.x = (const float*)p.out; lt.w = ln.w; lt.b = ln.b; lt.out = (f16*)ln.out; lt.rows = t.r0; lt.eps = ln.eps;
+  lt.nch = p.N / 256; lt.hi8 = ln.hi8 ? 1 : 0; lt.slots = tail_slots(t);
+  if (p.w_exact16) launch_tail_b<3>(pb, lt, s);
+  else launch_tail_b<4>(pb, lt, s);
+  ++g_tail_launches;
+  return t.r0;
 }
 
 // plain 16-bit operands: the 8-wave kernel with two N-side fragment sets, which takes K tiles in pairs; an odd K-tile

@@ -7,6 +7,7 @@
 
 #include "../../include/aaclip.h"
 #include "optim_pack.h"
+#include "tail_plan.h"
 
 namespace aaclip {
 
@@ -49,6 +50,26 @@ bool gemm256_applicable(int dtype, const GemmParams& p);
 // 256 x 256 form).  Plain operands with an odd K-tile count run the one-set 8-wave kernel whatever form is asked for.
 enum Gemm256Form { GEMM256_TILE, GEMM256_HALF_TILE, GEMM256_WALK };
 void launch_gemm256t(int dtype, int epi, const GemmParams& p, hipStream_t s, Gemm256Form form);
+// The LayerNorm that follows a split fp16 residual product, run beside the product's partial last round (tail_plan.h).
+// LnRows: its weights, its split8 output rows and the hi8 flag of launch_layernorm; it reads the product's output.
+struct LnRows { const float* w; const float* b; void* out; float eps; bool hi8; };
+// kernel argument of the tail launch (gemm256t.hip); all zero for every other launch of the kernel
+struct LnTail {
+  const float* x; const float* w; const float* b;
+  _Float16* out;
+  long rows;
+  float eps;
+  int nch, hi8;
+  TailSlots slots;
+};
+// gemm256t.hip: launches A and B, returns the rows whose LayerNorm is done (0: plan not engaged, nothing launched)
+long launch_resid_ln_tail(const GemmParams& p, const LnRows& ln, hipStream_t s);
+// gemm.hip: the residual product p, and where the tail overlap applies (split fp16 on the walking kernel, switch on, plan
+// engaged) the LayerNorm `ln` of its first rows with it; returns how many rows of `ln` are done (0: none, plain launch)
+long launch_gemm_resid_ln(int dtype, const GemmParams& p, const LnRows& ln, hipStream_t s);
+void set_tail_overlap(bool on);
+void set_plan_cus(int cus);   // CU count the row split is planned with; 0 = the device's (tests: a tail at small shapes)
+long tail_launch_count();     // tail launches (launch B) issued so far
 // Kernel selection, for the tests that compare the forms with one another: GEMM variants 0 (automatic), 1 (128-tile
 // kernel) and 80 / 81 / 82 (the 256-tile forms, gemm.hip), attention variants 0 and 1 (128-query kernel).  Both return
 // false for anything else and leave the selection alone.

@@ -4,6 +4,7 @@
 // chunks per lane).
 #include "common.h"
 #include "kernels.h"
+#include "ln_row.h"
 
 namespace aaclip {
 
@@ -12,43 +13,8 @@ const char* row_width_check(int D) {
   return "row width must be 256, 512, 768 or 1024";
 }
 
-template <int NCH>
-AACLIP_DEV void load_row(const float* p, int lane, f32x4 (&v)[NCH]) {
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) v[c] = *(const f32x4*)(p + (c * 64 + lane) * 4);
-}
-
-template <typename T>
-AACLIP_DEV void store4(T* p, f32x4 v);
-template <>
-AACLIP_DEV void store4<float>(float* p, f32x4 v) { *(f32x4*)p = v; }
-template <>
-AACLIP_DEV void store4<f16>(f16* p, f32x4 v) {
-  f16x4 o = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
-  *(f16x4*)p = o;
-}
-template <>
-AACLIP_DEV void store4<bf16>(bf16* p, f32x4 v) {
-  bf16x4 o = {(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-  *(bf16x4*)p = o;
-}
-
-// LayerNorm over the last dim, reference model/transformer.py:37-43 (eps 1e-5),
-// two-pass statistics in registers; out may alias x when T == float.
-// split8 row (AACLIP_F16X2, common.h): 4 values at column `col` of a row of logical width `width` starting at `row`:
-// hi plane (fp16), then the lo8 and hi8 planes (e4m3, one byte per element)
-// hi8 = false: the hi8 plane is not written (its only reader is the Ah8 . Wl8 correction tile, which a product whose
-// weight is exact in fp16 skips)
-AACLIP_DEV void store4_split(f16* row, int col, f32x4 v, int width, bool hi8 = true) {
-  const float vv[4] = {v[0], v[1], v[2], v[3]};
-  f16x4 hi;
-  uint32_t l8, h8;
-  split8x4(vv, hi, l8, h8);
-  *(f16x4*)(row + col) = hi;
-  uint8_t* p8 = (uint8_t*)(row + width);
-  *(uint32_t*)(p8 + col) = l8;
-  if (hi8) *(uint32_t*)(p8 + width + col) = h8;
-}
+// load_row, store4, store4_split and the LayerNorm of one row (layernorm_row) live in ln_row.h: the residual products'
+// tail launch (gemm256t.hip) runs the same row code
 
 template <typename T, int NCH, bool SPLIT = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, const float* __restrict__ w,
@@ -58,30 +24,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, const fl
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  f32x4 v[NCH];
+  f32x4 v[NCH], g[NCH], bb[NCH];
   load_row<NCH>(x + row * D, lane, v);
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) s += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
-  const float mean = wave_sum(s) * (1.0f / D);
-  float q = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float d = v[c][e] - mean;
-      q = fmaf(d, d, q);
-    }
-  const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int col = (c * 64 + lane) * 4;
-    f32x4 g = *(const f32x4*)(w + col), bb = *(const f32x4*)(b + col), y;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] = (v[c][e] - mean) * rstd * g[e] + bb[e];
-    if constexpr (SPLIT) store4_split(out + row * 2 * D, col, y, D, hi8);
-    else store4<T>(out + row * D + col, y);
-  }
+  load_row<NCH>(w, lane, g);
+  load_row<NCH>(b, lane, bb);
+  layernorm_row<T, NCH, SPLIT>(v, g, bb, out + row * (SPLIT ? 2 : 1) * D, lane, eps, hi8);
 }
 
 template <typename T>

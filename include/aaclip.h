@@ -945,6 +945,20 @@ int aaclip_profile_end(float* ms, int* tags, int max_n);
  * unchanged. */
 int aaclip_set_gemm_variant(int v);
 
+/* Split fp16 blocks (aaclip_block(s), FULL / CAUSAL attention): where the 256x256 tiles of a residual product (out_proj,
+ * c_proj) leave the last round of the walking kernel partly empty (at least two full rounds, a tail of at most half the
+ * CUs), the product runs as two launches on the caller's stream -- the rows of the full rounds, then ONE launch whose
+ * workgroups run the tail tiles or the LayerNorm that follows the product on the rows already complete -- and only the
+ * LayerNorm of the last rows remains a pass.  Results are bit-identical either way.  on = 0 keeps the single launch and
+ * the whole pass.  Default: on. */
+int aaclip_set_tail_overlap(int on);
+/* For tests: the CU count the row split above is planned with, so that a tail exists at small shapes.
+ * cus = 0 (default): the device's count; otherwise a multiple of 8, 8 .. 1024 (anything else: rc < 0, no change). */
+int aaclip_set_plan_cus(int cus);
+/* How many tail launches (the second launch above) this process has issued so far: tests tell an engaged split from a
+ * single launch by it. */
+long aaclip_tail_overlap_count(void);
+
 /* Building blocks, exported for unit parity tests and for callers that fuse differently.
  * Row limits.  A launch covers its grid only below 2^24 workgroups of 256 threads, so the entries whose kernels take
  * one workgroup per row (group) refuse more (rc < 0, nothing launched): rows <= 2^26 - 4 for aaclip_layernorm,
