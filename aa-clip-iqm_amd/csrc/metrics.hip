@@ -11,28 +11,19 @@
 // No floating-point atomics; every floating-point sum runs in an order fixed by n alone, so two calls give the same bits.
 #include "common.h"
 #include "kernels.h"
+#include "metrics_records.h"
+#include "tile_scan.h"
 #include <math.h>
 
 namespace aaclip {
 
-static constexpr int MT = 256;   // threads of every workgroup in this file (4 waves)
-typedef unsigned long long u64;
-static inline size_t up256_bytes(size_t v) { return (v + 255) & ~(size_t)255; }
+static constexpr int MT = TILE_THREADS;   // threads of every workgroup in this file (4 waves)
 
 // ---------------------------------------------------------------------------------------------------- range
 // A SEGMENT is one image (per_image elements), or the whole array when per_image is 0.  Stage 1: blocks_per_segment
 // workgroups per segment, each a strided share; stage 2: one workgroup folds the partials in index order.
 static constexpr int RANGE_ITEMS = 4096;        // elements of a segment per workgroup before another one is added
 static constexpr int RANGE_MAX_BLOCKS = 1024;   // workgroups per segment at the most
-
-struct RangePartial {
-  float mn, mx;
-  u64 bad, pos;
-};
-struct RangeRecord {   // include/aaclip.h aaclip_metrics_range_record
-  float mn, mx;
-  u64 bad, pos;
-};
 
 long metrics_range_blocks(long seg_len) {
   const long b = (seg_len + RANGE_ITEMS - 1) / RANGE_ITEMS;
@@ -43,73 +34,47 @@ long metrics_range_partials(long n, long per_image) {
   return (n / seg_len) * metrics_range_blocks(seg_len);
 }
 size_t metrics_range_ws_bytes(long n, long per_image) {
-  return (size_t)metrics_range_partials(n, per_image) * sizeof(RangePartial);
+  return (size_t)metrics_range_partials(n, per_image) * sizeof(RangeRecord);
+}
+
+// min / max of the finite scores and the two counts of a and b; the per-workgroup partial is a RangeRecord itself
+AACLIP_DEV RangeRecord range_merge(const RangeRecord& a, const RangeRecord& b) {
+  return RangeRecord{fminf(a.mn, b.mn), fmaxf(a.mx, b.mx), a.bad + b.bad, a.pos + b.pos};
 }
 
 __global__ __launch_bounds__(MT) void metrics_range_partial_kernel(const float* __restrict__ scores,
                                                                    const uint8_t* __restrict__ labels, long seg_len,
-                                                                   int blocks, RangePartial* __restrict__ partial) {
-  __shared__ float s_mn[MT], s_mx[MT];
-  __shared__ u64 s_bad[MT], s_pos[MT];
+                                                                   int blocks, RangeRecord* __restrict__ partial) {
+  __shared__ RangeRecord s_r[MT];
   const long seg = blockIdx.x / blocks;
   const int blk = blockIdx.x % blocks;
   const long base = seg * seg_len;
-  float mn = INFINITY, mx = -INFINITY;
-  u64 bad = 0, pos = 0;
+  RangeRecord r{INFINITY, -INFINITY, 0, 0};
   for (long i = (long)blk * MT + threadIdx.x; i < seg_len; i += (long)blocks * MT) {
     const float x = scores[base + i];
     if (isfinite(x)) {
-      mn = fminf(mn, x);
-      mx = fmaxf(mx, x);
+      r.mn = fminf(r.mn, x);
+      r.mx = fmaxf(r.mx, x);
     } else {
-      ++bad;
+      ++r.bad;
     }
-    if (labels) pos += labels[base + i] != 0;
+    if (labels) r.pos += labels[base + i] != 0;
   }
-  const int t = threadIdx.x;
-  s_mn[t] = mn, s_mx[t] = mx, s_bad[t] = bad, s_pos[t] = pos;
-  __syncthreads();
-  for (int o = MT / 2; o > 0; o >>= 1) {
-    if (t < o) {
-      s_mn[t] = fminf(s_mn[t], s_mn[t + o]);
-      s_mx[t] = fmaxf(s_mx[t], s_mx[t + o]);
-      s_bad[t] += s_bad[t + o];
-      s_pos[t] += s_pos[t + o];
-    }
-    __syncthreads();
-  }
-  if (t == 0) partial[blockIdx.x] = RangePartial{s_mn[0], s_mx[0], s_bad[0], s_pos[0]};
+  r = block_fold(r, s_r, range_merge);
+  if (threadIdx.x == 0) partial[blockIdx.x] = r;
 }
 
 // one workgroup: the record over all partials, then the maximum of every segment
-__global__ __launch_bounds__(MT) void metrics_range_fold_kernel(const RangePartial* __restrict__ partial, long segs,
+__global__ __launch_bounds__(MT) void metrics_range_fold_kernel(const RangeRecord* __restrict__ partial, long segs,
                                                                 int blocks, RangeRecord* __restrict__ rec,
                                                                 float* __restrict__ image_max) {
-  __shared__ float s_mn[MT], s_mx[MT];
-  __shared__ u64 s_bad[MT], s_pos[MT];
+  __shared__ RangeRecord s_r[MT];
   const int t = threadIdx.x;
   const long total = segs * blocks;
-  float mn = INFINITY, mx = -INFINITY;
-  u64 bad = 0, pos = 0;
-  for (long i = t; i < total; i += MT) {
-    const RangePartial p = partial[i];
-    mn = fminf(mn, p.mn);
-    mx = fmaxf(mx, p.mx);
-    bad += p.bad;
-    pos += p.pos;
-  }
-  s_mn[t] = mn, s_mx[t] = mx, s_bad[t] = bad, s_pos[t] = pos;
-  __syncthreads();
-  for (int o = MT / 2; o > 0; o >>= 1) {
-    if (t < o) {
-      s_mn[t] = fminf(s_mn[t], s_mn[t + o]);
-      s_mx[t] = fmaxf(s_mx[t], s_mx[t + o]);
-      s_bad[t] += s_bad[t + o];
-      s_pos[t] += s_pos[t + o];
-    }
-    __syncthreads();
-  }
-  if (t == 0) *rec = RangeRecord{s_mn[0], s_mx[0], s_bad[0], s_pos[0]};
+  RangeRecord r{INFINITY, -INFINITY, 0, 0};
+  for (long i = t; i < total; i += MT) r = range_merge(r, partial[i]);
+  r = block_fold(r, s_r, range_merge);
+  if (t == 0) *rec = r;
   if (image_max)
     for (long s = t; s < segs; s += MT) {
       float m = -INFINITY;
@@ -123,7 +88,7 @@ void launch_metrics_range(const float* scores, const uint8_t* labels, long n, lo
   const long seg_len = per_image > 0 ? per_image : n;
   const long segs = n / seg_len;
   const int blocks = (int)metrics_range_blocks(seg_len);
-  RangePartial* partial = (RangePartial*)ws;
+  RangeRecord* partial = (RangeRecord*)ws;
   hipLaunchKernelGGL(metrics_range_partial_kernel, dim3((unsigned)(segs * blocks)), dim3(MT), 0, s, scores, labels,
                      seg_len, blocks, partial);
   hipLaunchKernelGGL(metrics_range_fold_kernel, dim3(1), dim3(MT), 0, s, partial, segs, blocks, (RangeRecord*)record,
@@ -131,15 +96,12 @@ void launch_metrics_range(const float* scores, const uint8_t* labels, long n, lo
 }
 
 // ------------------------------------------------------------------------------------------------ normalise
-// numpy's float32 (x - min) / (max - min): an IEEE subtraction and a correctly rounded division (the file is built
-// with -ffp-contract=off).  The decision is the reference's `if preds.max() != 1`, read from the device record.
+// metrics_records.h range_normalised, the decision read from the device record
 __global__ __launch_bounds__(MT) void metrics_normalise_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                                long n, const RangeRecord* __restrict__ rec) {
   const long i = (long)blockIdx.x * MT + threadIdx.x;
   if (i >= n) return;
-  const float mn = rec->mn, mx = rec->mx;
-  const float x = in[i];
-  out[i] = mx != 1.0f ? __fdiv_rn(x - mn, mx - mn) : x;
+  out[i] = range_normalised(in[i], range_norm(rec));
 }
 
 void launch_metrics_normalise(const float* in, float* out, long n, const void* record, hipStream_t s) {
@@ -179,12 +141,8 @@ __global__ __launch_bounds__(MT) void metrics_keys_kernel(const float* __restric
 //   scatter     a wave walks its chunk in index order; in a round, the lanes that hold the same digit find each other
 //               with eight ballots, rank themselves by lane number, and the lowest of them advances the chunk's
 //               counter of that digit: equal digits keep their input order, which makes the sort stable
-static constexpr int SORT_ROUNDS = 32;
-static constexpr int SORT_CHUNK = 64 * SORT_ROUNDS;
-static constexpr int SORT_WAVES = MT / 64;
-static constexpr int SCAN_SEGMENTS = 256;   // row segments of the table scan at the most
+static constexpr int SORT_WAVES = MT / 64;   // SORT_ROUNDS, SORT_CHUNK, SCAN_SEGMENTS: metrics_records.h
 
-long metrics_sort_chunks(long n) { return (n + SORT_CHUNK - 1) / SORT_CHUNK; }
 long metrics_sort_group_items() { return (long)SORT_CHUNK * SORT_WAVES; }
 
 __global__ __launch_bounds__(MT) void sort_hist_kernel(const uint32_t* __restrict__ keys, long n, int shift,
@@ -307,8 +265,7 @@ __global__ __launch_bounds__(MT) void sort_scatter_kernel(const uint32_t* __rest
 // (nothing when v_in is null) starts in v_in, ping-pongs between v_b and v_out and ends in v_out.
 template <typename V>
 static void sort_passes(uint32_t* keys, uint32_t* keys_b, const V* v_in, V* v_out, V* v_b, uint32_t* table,
-                        uint32_t* seg_sum, long n, hipStream_t s) {
-  const long chunks = metrics_sort_chunks(n);
+                        uint32_t* seg_sum, long n, long chunks, hipStream_t s) {
   const long seg_len = (chunks + SCAN_SEGMENTS - 1) / SCAN_SEGMENTS;
   const int segments = (int)((chunks + seg_len - 1) / seg_len);
   const unsigned groups = (unsigned)((chunks + SORT_WAVES - 1) / SORT_WAVES);
@@ -326,49 +283,31 @@ static void sort_passes(uint32_t* keys, uint32_t* keys_b, const V* v_in, V* v_ou
   }
 }
 
-size_t metrics_sort_ws_bytes(long n) {
-  const long chunks = metrics_sort_chunks(n);
-  return up256_bytes((size_t)n * 4) + up256_bytes((size_t)n) + (size_t)chunks * 1024 + (size_t)SCAN_SEGMENTS * 1024;
-}
+size_t metrics_sort_ws_bytes(long n) { return sort_layout(n, 1).bytes; }
 
-// ws: [keys B: n uint32] [labels B: n bytes] [table: chunks x 256 uint32] [segment sums: 256 x 256 uint32]
 // The keys start in `keys` and are back there after the fourth pass; so are the labels in `labels_sorted`.
 void launch_metrics_sort(const float* scores, const uint8_t* labels, long n, int packed, uint32_t* keys,
                          uint8_t* labels_sorted, unsigned long long* out_of_range, void* ws, hipStream_t s) {
+  const SortLayout l = sort_layout(n, 1);
   char* p = (char*)ws;
-  uint32_t* keys_b = (uint32_t*)p;
-  p += up256_bytes((size_t)n * 4);
-  uint8_t* lab_b = (uint8_t*)p;
-  p += up256_bytes((size_t)n);
-  uint32_t* table = (uint32_t*)p;
-  p += (size_t)metrics_sort_chunks(n) * 1024;
-  uint32_t* seg_sum = (uint32_t*)p;
   (void)hipMemsetAsync(out_of_range, 0, sizeof(u64), s);
   hipLaunchKernelGGL(metrics_keys_kernel, dim3((unsigned)((n + MT - 1) / MT)), dim3(MT), 0, s, scores, labels, n, packed,
                      keys, out_of_range);
-  sort_passes<uint8_t>(keys, keys_b, packed ? nullptr : labels, labels_sorted, lab_b, table, seg_sum, n, s);
+  sort_passes<uint8_t>(keys, (uint32_t*)(p + l.keys_b), packed ? nullptr : labels, labels_sorted,
+                       (uint8_t*)(p + l.values_b), (uint32_t*)(p + l.table), (uint32_t*)(p + l.seg_sum), n, l.chunks, s);
 }
 
-size_t metrics_sort_pairs_ws_bytes(long n) {
-  const long chunks = metrics_sort_chunks(n);
-  return 2 * up256_bytes((size_t)n * 4) + (size_t)chunks * 1024 + (size_t)SCAN_SEGMENTS * 1024;
-}
+size_t metrics_sort_pairs_ws_bytes(long n) { return sort_layout(n, 4).bytes; }
 
 // The same four passes with a 32-bit value beside the unpacked key.
-// ws: [keys B: n uint32] [values B: n uint32] [table: chunks x 256 uint32] [segment sums: 256 x 256 uint32]
 void launch_metrics_sort_pairs(const float* scores, const uint32_t* values, long n, uint32_t* keys,
                                uint32_t* values_sorted, void* ws, hipStream_t s) {
+  const SortLayout l = sort_layout(n, 4);
   char* p = (char*)ws;
-  uint32_t* keys_b = (uint32_t*)p;
-  p += up256_bytes((size_t)n * 4);
-  uint32_t* val_b = (uint32_t*)p;
-  p += up256_bytes((size_t)n * 4);
-  uint32_t* table = (uint32_t*)p;
-  p += (size_t)metrics_sort_chunks(n) * 1024;
-  uint32_t* seg_sum = (uint32_t*)p;
   hipLaunchKernelGGL(metrics_keys_kernel, dim3((unsigned)((n + MT - 1) / MT)), dim3(MT), 0, s, scores,
                      (const uint8_t*)nullptr, n, 0, keys, (u64*)nullptr);
-  sort_passes<uint32_t>(keys, keys_b, values, values_sorted, val_b, table, seg_sum, n, s);
+  sort_passes<uint32_t>(keys, (uint32_t*)(p + l.keys_b), values, values_sorted, (uint32_t*)(p + l.values_b),
+                        (uint32_t*)(p + l.table), (uint32_t*)(p + l.seg_sum), n, l.chunks, s);
 }
 
 // ---------------------------------------------------------------------------------------------------- curve
@@ -381,20 +320,7 @@ void launch_metrics_sort_pairs(const float* scores, const uint32_t* values, long
 //   tp = P - E, fp = (n - i) - tp at its mark; tp0 = P - E2, fp0 = (n - i2) - tp0 at the mark before it (0, 0 for the
 //   top group).  num += (fp - fp0)(tp + tp0) in uint64 (at most n^2 / 2 < 2^61);
 //   AP += ((tp - tp0) / P) (tp / (tp + fp)) in fp64.
-static constexpr int CURVE_ITEMS = 16;
-static constexpr int CURVE_TILE = MT * CURVE_ITEMS;
-static constexpr int CURVE_MAX_BLOCKS = 1024;   // workgroups of the group sums = partials the last kernel folds
-
-struct CurveRecord {   // include/aaclip.h aaclip_metrics_curve_record (its sixth word is written by the sort)
-  u64 num, P, N, groups;
-  double ap;
-};
-
-long metrics_curve_tiles(long n) { return (n + CURVE_TILE - 1) / CURVE_TILE; }
-long metrics_curve_blocks(long n) {
-  const long b = (n + MT - 1) / MT;
-  return b < CURVE_MAX_BLOCKS ? b : CURVE_MAX_BLOCKS;
-}
+static constexpr int CURVE_ITEMS = METRICS_SCAN_ITEMS;
 
 AACLIP_DEV u64 curve_word(const uint32_t* __restrict__ keys, const uint8_t* __restrict__ lab, long i, int packed) {
   const uint32_t k = keys[i];
@@ -408,94 +334,47 @@ AACLIP_DEV u64 curve_word(const uint32_t* __restrict__ keys, const uint8_t* __re
   return ((u64)start << 32) | label;
 }
 
-AACLIP_DEV u64 curve_thread_sum(const uint32_t* __restrict__ keys, const uint8_t* __restrict__ lab, long n, int packed,
-                                long first) {
-  u64 acc = 0;
-#pragma unroll 4
-  for (int j = 0; j < CURVE_ITEMS; ++j)
-    if (first + j < n) acc += curve_word(keys, lab, first + j, packed);
-  return acc;
-}
-
+// the three levels of tile_scan.h on the words
 __global__ __launch_bounds__(MT) void curve_tile_sum_kernel(const uint32_t* __restrict__ keys,
                                                             const uint8_t* __restrict__ lab, long n, int packed,
                                                             u64* __restrict__ tile_sum) {
-  __shared__ u64 red[MT];
-  const int t = threadIdx.x;
-  red[t] = curve_thread_sum(keys, lab, n, packed, (long)blockIdx.x * CURVE_TILE + (long)t * CURVE_ITEMS);
-  __syncthreads();
-  for (int o = MT / 2; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  if (t == 0) tile_sum[blockIdx.x] = red[0];
-}
-
-// exclusive prefix of `mine` over the workgroup's threads, in thread order (integers: any order gives the same sum)
-AACLIP_DEV u64 block_exclusive_scan(u64 mine, u64* lds) {
-  const int t = threadIdx.x;
-  lds[t] = mine;
-  __syncthreads();
-  for (int o = 1; o < MT; o <<= 1) {
-    const u64 add = t >= o ? lds[t - o] : 0;
-    __syncthreads();
-    lds[t] += add;
-    __syncthreads();
-  }
-  return lds[t] - mine;
+  tile_sum_body<CURVE_ITEMS, u64>(n, tile_sum, [=](long i) { return curve_word(keys, lab, i, packed); });
 }
 
 // one workgroup: tile_sum <- its exclusive prefix, *total <- the sum of all (groups << 32 | positives)
 __global__ __launch_bounds__(MT) void curve_tile_scan_kernel(u64* __restrict__ tile_sum, long tiles,
                                                              u64* __restrict__ total) {
-  __shared__ u64 lds[MT];
-  const int t = threadIdx.x;
-  const long per = (tiles + MT - 1) / MT;
-  const long j0 = t * per < tiles ? t * per : tiles, j1 = j0 + per < tiles ? j0 + per : tiles;
-  u64 acc = 0;
-  for (long j = j0; j < j1; ++j) acc += tile_sum[j];
-  u64 run = block_exclusive_scan(acc, lds);
-  if (t == MT - 1) *total = run + acc;
-  for (long j = j0; j < j1; ++j) {
-    const u64 c = tile_sum[j];
-    tile_sum[j] = run;
-    run += c;
-  }
+  const u64 all = tile_scan_body(tile_sum, tiles);
+  if (threadIdx.x == 0) *total = all;
 }
 
 __global__ __launch_bounds__(MT) void curve_mark_kernel(const uint32_t* __restrict__ keys,
                                                         const uint8_t* __restrict__ lab, long n, int packed,
                                                         const u64* __restrict__ tile_prefix, u64* __restrict__ marks) {
-  __shared__ u64 lds[MT];
-  const long first = (long)blockIdx.x * CURVE_TILE + (long)threadIdx.x * CURVE_ITEMS;
-  const u64 mine = curve_thread_sum(keys, lab, n, packed, first);
-  u64 run = tile_prefix[blockIdx.x] + block_exclusive_scan(mine, lds);
-#pragma unroll 4
-  for (int j = 0; j < CURVE_ITEMS; ++j) {
-    const long i = first + j;
-    if (i >= n) break;
-    const u64 word = curve_word(keys, lab, i, packed);
-    const u64 g = run >> 32;
-    if ((word >> 32) && g < (u64)n) marks[g] = ((u64)i << 32) | (run & 0xFFFFFFFFull);   // g < groups <= n
-    run += word;
-  }
+  tile_walk_body<CURVE_ITEMS, u64>(
+      n, tile_prefix, [=](long i) { return curve_word(keys, lab, i, packed); },
+      [=](long i, u64 word, u64 run) {
+        const u64 g = run >> 32;
+        if ((word >> 32) && g < (u64)n) marks[g] = ((u64)i << 32) | (run & 0xFFFFFFFFull);   // g < groups <= n
+      });
 }
 
 // Workgroup b sums a contiguous share of the groups, counted from the top; a thread takes every 256th of them, the
-// threads are folded by a tree: the order depends on n and the number of groups alone.
+// threads are folded by block_fold: the order depends on n and the number of groups alone.
+struct CurveSums {
+  u64 num;
+  double ap;
+};
 __global__ __launch_bounds__(MT) void curve_group_kernel(const u64* __restrict__ marks, const u64* __restrict__ total,
                                                          long n, u64* __restrict__ part_num,
                                                          double* __restrict__ part_ap) {
-  __shared__ u64 s_num[MT];
-  __shared__ double s_ap[MT];
-  const int t = threadIdx.x;
+  __shared__ CurveSums s_sum[MT];
   const u64 tot = *total;
   const long G = (long)(tot >> 32), P = (long)(tot & 0xFFFFFFFFull);
-  const long per = (G + gridDim.x - 1) / gridDim.x;
-  const long k0 = (long)blockIdx.x * per, k1 = k0 + per < G ? k0 + per : G;
+  const GroupShare share = group_share(G);
   u64 num = 0;
   double ap = 0.0;
-  for (long k = k0 + t; k < k1; k += MT) {
+  for (long k = share.k0 + threadIdx.x; k < share.k1; k += MT) {
     const long g = G - 1 - k;
     const u64 a = marks[g];
     const long i = (long)(a >> 32), E = (long)(a & 0xFFFFFFFFull);
@@ -508,16 +387,10 @@ __global__ __launch_bounds__(MT) void curve_group_kernel(const u64* __restrict__
     num += (u64)(fp - fp0) * (u64)(tp + tp0);
     ap += ((double)(tp - tp0) / (double)P) * ((double)tp / (double)(tp + fp));
   }
-  s_num[t] = num, s_ap[t] = ap;
-  __syncthreads();
-  for (int o = MT / 2; o > 0; o >>= 1) {
-    if (t < o) {
-      s_num[t] += s_num[t + o];
-      s_ap[t] += s_ap[t + o];
-    }
-    __syncthreads();
-  }
-  if (t == 0) part_num[blockIdx.x] = s_num[0], part_ap[blockIdx.x] = s_ap[0];
+  const CurveSums all = block_fold(CurveSums{num, ap}, s_sum, [](const CurveSums& a, const CurveSums& b) {
+    return CurveSums{a.num + b.num, a.ap + b.ap};
+  });
+  if (threadIdx.x == 0) part_num[blockIdx.x] = all.num, part_ap[blockIdx.x] = all.ap;
 }
 
 // the partials in index order, by one thread
@@ -535,47 +408,31 @@ __global__ void curve_final_kernel(const u64* __restrict__ part_num, const doubl
   rec->num = num, rec->P = P, rec->N = (u64)n - P, rec->groups = tot >> 32, rec->ap = ap;
 }
 
-// The phases that aaclip_metrics_curve and aaclip_metrics_f1max share: tile sums, their scan, the mark list.
-// ws: [tile sums: tiles x 8] [total: 8] [marks: n x 8] [rest: what the entry's own reduction needs]
-struct CurveMarks {
-  const u64* total;   // groups << 32 | positives
-  const u64* marks;   // marks[g] = i << 32 | E, ascending
-  char* rest;
-};
-static size_t curve_marks_ws_bytes(long n) {
-  return up256_bytes((size_t)metrics_curve_tiles(n) * 8) + 256 + up256_bytes((size_t)n * 8);
-}
-static CurveMarks launch_curve_marks(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* ws,
-                                     hipStream_t s) {
-  const long tiles = metrics_curve_tiles(n);
-  char* p = (char*)ws;
-  u64* tile_sum = (u64*)p;
-  p += up256_bytes((size_t)tiles * 8);
-  u64* total = (u64*)p;
-  p += 256;
-  u64* marks = (u64*)p;
-  p += up256_bytes((size_t)n * 8);
+// The phases that aaclip_metrics_curve and aaclip_metrics_f1max share: tile sums, their scan, the mark list
+// (total: groups << 32 | positives; marks[g] = i << 32 | E, ascending).
+static void launch_curve_marks(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed,
+                               const CurveMarksLayout& m, char* p, hipStream_t s) {
+  u64 *tile_sum = (u64*)(p + m.tile_sum), *total = (u64*)(p + m.total), *marks = (u64*)(p + m.marks);
+  const long tiles = m.tiles;
   hipLaunchKernelGGL(curve_tile_sum_kernel, dim3((unsigned)tiles), dim3(MT), 0, s, keys, labels_sorted, n, packed,
                      tile_sum);
   hipLaunchKernelGGL(curve_tile_scan_kernel, dim3(1), dim3(MT), 0, s, tile_sum, tiles, total);
   hipLaunchKernelGGL(curve_mark_kernel, dim3((unsigned)tiles), dim3(MT), 0, s, keys, labels_sorted, n, packed, tile_sum,
                      marks);
-  return CurveMarks{total, marks, p};
 }
 
-size_t metrics_curve_ws_bytes(long n) {
-  return curve_marks_ws_bytes(n) + 2 * up256_bytes((size_t)metrics_curve_blocks(n) * 8);
-}
+size_t metrics_curve_ws_bytes(long n) { return curve_layout(n).bytes; }
 
-// rest: [partial numerators] [partial AP sums]
 void launch_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
                           hipStream_t s) {
-  const int parts = (int)metrics_curve_blocks(n);
-  const CurveMarks m = launch_curve_marks(keys, labels_sorted, n, packed, ws, s);
-  u64* part_num = (u64*)m.rest;
-  double* part_ap = (double*)(m.rest + up256_bytes((size_t)parts * 8));
-  hipLaunchKernelGGL(curve_group_kernel, dim3(parts), dim3(MT), 0, s, m.marks, m.total, n, part_num, part_ap);
-  hipLaunchKernelGGL(curve_final_kernel, dim3(1), dim3(64), 0, s, part_num, part_ap, parts, m.total, n,
+  const CurveLayout l = curve_layout(n);
+  char* p = (char*)ws;
+  const int parts = l.front.parts;
+  u64 *total = (u64*)(p + l.front.total), *marks = (u64*)(p + l.front.marks), *part_num = (u64*)(p + l.part_num);
+  double* part_ap = (double*)(p + l.part_ap);
+  launch_curve_marks(keys, labels_sorted, n, packed, l.front, p, s);
+  hipLaunchKernelGGL(curve_group_kernel, dim3(parts), dim3(MT), 0, s, marks, total, n, part_num, part_ap);
+  hipLaunchKernelGGL(curve_final_kernel, dim3(1), dim3(64), 0, s, part_num, part_ap, parts, total, n,
                      (CurveRecord*)record);
 }
 
@@ -588,11 +445,7 @@ void launch_metrics_curve(const uint32_t* keys, const uint8_t* labels_sorted, lo
 struct F1Candidate {
   u64 tp, d, i;
 };
-struct F1MaxRecord {   // include/aaclip.h aaclip_metrics_f1max_record
-  u64 tp, fp, P, N, groups, start;
-  uint32_t key;
-  float threshold;
-};
+static_assert(sizeof(F1Candidate) == F1_CANDIDATE_BYTES, "f1max_layout sizes the partials");
 
 AACLIP_DEV bool f1_beats(const F1Candidate& a, const F1Candidate& b) {
   if (a.d == 0) return false;
@@ -601,38 +454,28 @@ AACLIP_DEV bool f1_beats(const F1Candidate& a, const F1Candidate& b) {
   return l > r || (l == r && a.i > b.i);
 }
 
-// the workgroup's best candidate, valid in thread 0
-AACLIP_DEV F1Candidate f1_block_best(F1Candidate best, u64* s_tp, u64* s_d, u64* s_i) {
-  const int t = threadIdx.x;
-  s_tp[t] = best.tp, s_d[t] = best.d, s_i[t] = best.i;
-  __syncthreads();
-  for (int o = MT / 2; o > 0; o >>= 1) {
-    if (t < o) {
-      const F1Candidate mine{s_tp[t], s_d[t], s_i[t]}, other{s_tp[t + o], s_d[t + o], s_i[t + o]};
-      if (f1_beats(other, mine)) s_tp[t] = other.tp, s_d[t] = other.d, s_i[t] = other.i;
-    }
-    __syncthreads();
-  }
-  return F1Candidate{s_tp[0], s_d[0], s_i[0]};
+// the workgroup's best candidate
+AACLIP_DEV F1Candidate f1_block_best(F1Candidate best, F1Candidate* lds) {
+  return block_fold(best, lds, [](const F1Candidate& mine, const F1Candidate& other) {
+    return f1_beats(other, mine) ? other : mine;
+  });
 }
 
 // Workgroup b takes a contiguous share of the groups, a thread every 256th of them.
 __global__ __launch_bounds__(MT) void f1max_group_kernel(const u64* __restrict__ marks, const u64* __restrict__ total,
                                                          long n, F1Candidate* __restrict__ partial) {
-  __shared__ u64 s_tp[MT], s_d[MT], s_i[MT];
+  __shared__ F1Candidate lds[MT];
   const u64 tot = *total;
-  const long G = (long)(tot >> 32);
   const u64 P = tot & 0xFFFFFFFFull;
-  const long per = (G + gridDim.x - 1) / gridDim.x;
-  const long g0 = (long)blockIdx.x * per, g1 = g0 + per < G ? g0 + per : G;
+  const GroupShare share = group_share((long)(tot >> 32));
   F1Candidate best{0, 0, 0};
-  for (long g = g0 + threadIdx.x; g < g1; g += MT) {
+  for (long g = share.k0 + threadIdx.x; g < share.k1; g += MT) {
     const u64 a = marks[g];
     const u64 i = a >> 32, E = a & 0xFFFFFFFFull;
     const F1Candidate c{P - E, ((u64)n - i) + P, i};
     if (f1_beats(c, best)) best = c;
   }
-  best = f1_block_best(best, s_tp, s_d, s_i);
+  best = f1_block_best(best, lds);
   if (threadIdx.x == 0) partial[blockIdx.x] = best;
 }
 
@@ -641,13 +484,13 @@ __global__ __launch_bounds__(MT) void f1max_final_kernel(const F1Candidate* __re
                                                          const u64* __restrict__ total, long n,
                                                          const uint32_t* __restrict__ keys, int packed,
                                                          F1MaxRecord* __restrict__ rec) {
-  __shared__ u64 s_tp[MT], s_d[MT], s_i[MT];
+  __shared__ F1Candidate lds[MT];
   F1Candidate best{0, 0, 0};
   for (int j = threadIdx.x; j < parts; j += MT) {
     const F1Candidate c = partial[j];
     if (f1_beats(c, best)) best = c;
   }
-  best = f1_block_best(best, s_tp, s_d, s_i);
+  best = f1_block_best(best, lds);
   if (threadIdx.x != 0) return;
   const u64 tot = *total;
   const u64 P = tot & 0xFFFFFFFFull;
@@ -659,34 +502,28 @@ __global__ __launch_bounds__(MT) void f1max_final_kernel(const F1Candidate* __re
   rec->start = start, rec->key = score, rec->threshold = __uint_as_float(bits);
 }
 
-size_t metrics_f1max_ws_bytes(long n) {
-  return curve_marks_ws_bytes(n) + up256_bytes((size_t)metrics_curve_blocks(n) * sizeof(F1Candidate));
-}
+size_t metrics_f1max_ws_bytes(long n) { return f1max_layout(n).bytes; }
 
-// rest: [partial candidates]
 void launch_metrics_f1max(const uint32_t* keys, const uint8_t* labels_sorted, long n, int packed, void* record, void* ws,
                           hipStream_t s) {
-  const int parts = (int)metrics_curve_blocks(n);
-  const CurveMarks m = launch_curve_marks(keys, labels_sorted, n, packed, ws, s);
-  F1Candidate* partial = (F1Candidate*)m.rest;
-  hipLaunchKernelGGL(f1max_group_kernel, dim3(parts), dim3(MT), 0, s, m.marks, m.total, n, partial);
-  hipLaunchKernelGGL(f1max_final_kernel, dim3(1), dim3(MT), 0, s, partial, parts, m.total, n, keys, packed,
+  const F1MaxLayout l = f1max_layout(n);
+  char* p = (char*)ws;
+  const int parts = l.front.parts;
+  u64 *total = (u64*)(p + l.front.total), *marks = (u64*)(p + l.front.marks);
+  F1Candidate* partial = (F1Candidate*)(p + l.partial);
+  launch_curve_marks(keys, labels_sorted, n, packed, l.front, p, s);
+  hipLaunchKernelGGL(f1max_group_kernel, dim3(parts), dim3(MT), 0, s, marks, total, n, partial);
+  hipLaunchKernelGGL(f1max_final_kernel, dim3(1), dim3(MT), 0, s, partial, parts, total, n, keys, packed,
                      (F1MaxRecord*)record);
 }
 
 // ------------------------------------------------------------------------------------------------- threshold
-// flagged = (v >= threshold), v the raw score or the score normalised as metrics_normalise_kernel does it.  Segments and
+// flagged = (v >= threshold), v the raw score or, with a range record, range_normalised's.  Segments and
 // workgroups per segment are those of the range kernels.  Within a segment the elements in front of the first 16-byte
 // aligned score (at most 3) and behind the last whole quad (at most 3) are taken one by one by the segment's first
 // workgroup; the quads in between are read with one 128-bit load each, their four mask bytes stored as one word where
 // the mask's address at the quad is 4-byte aligned (the same for every quad of a segment), byte by byte otherwise; the
 // labels likewise.  Counts are integers: stage 1 leaves {tp, fp, fn, tn} per workgroup, stage 2 folds them.
-struct ThresholdRecord {   // include/aaclip.h aaclip_metrics_threshold_record
-  u64 tp, fp, fn, tn;
-};
-
-AACLIP_DEV float threshold_value(float x, bool norm, float mn, float mx) { return norm ? __fdiv_rn(x - mn, mx - mn) : x; }
-
 AACLIP_DEV void threshold_count(bool flag, bool pos, uint32_t& tp, uint32_t& fp, uint32_t& fn, uint32_t& tn) {
   tp += flag && pos, fp += flag && !pos, fn += !flag && pos, tn += !flag && !pos;
 }
@@ -696,14 +533,12 @@ __global__ __launch_bounds__(MT) void metrics_threshold_kernel(const float* __re
                                                                int blocks, const RangeRecord* __restrict__ range,
                                                                const F1MaxRecord* __restrict__ f1,
                                                                uint8_t* __restrict__ mask, uint4* __restrict__ partial) {
-  __shared__ uint32_t s_c[4][MT];
+  __shared__ uint4 s_c[MT];
   const long seg = blockIdx.x / blocks;
   const int blk = blockIdx.x % blocks, t = threadIdx.x;
   const long base = seg * seg_len;
   const float thr = f1->threshold;
-  float mn = 0.0f, mx = 1.0f;
-  if (range) mn = range->mn, mx = range->mx;
-  const bool norm = range && mx != 1.0f;
+  const RangeNorm norm = range_norm(range);
   // head: elements in front of the first 16-byte aligned score of the segment
   long head = (long)(((16 - ((uintptr_t)(scores + base) & 15)) & 15) >> 2);
   if (head > seg_len) head = seg_len;
@@ -715,7 +550,7 @@ __global__ __launch_bounds__(MT) void metrics_threshold_kernel(const float* __re
     if (t < head) i = t;
     else if (t - head < seg_len - tail0) i = tail0 + (t - head);
     if (i >= 0) {
-      const bool flag = threshold_value(scores[base + i], norm, mn, mx) >= thr;
+      const bool flag = range_normalised(scores[base + i], norm) >= thr;
       if (mask) mask[base + i] = flag ? 1 : 0;
       threshold_count(flag, labels && labels[base + i] != 0, tp, fp, fn, tn);
     }
@@ -733,8 +568,8 @@ __global__ __launch_bounds__(MT) void metrics_threshold_kernel(const float* __re
       lab = (uint32_t)labels[e] | ((uint32_t)labels[e + 1] << 8) | ((uint32_t)labels[e + 2] << 16) |
             ((uint32_t)labels[e + 3] << 24);
     }
-    const bool f0 = threshold_value(x.x, norm, mn, mx) >= thr, f1b = threshold_value(x.y, norm, mn, mx) >= thr;
-    const bool f2 = threshold_value(x.z, norm, mn, mx) >= thr, f3 = threshold_value(x.w, norm, mn, mx) >= thr;
+    const bool f0 = range_normalised(x.x, norm) >= thr, f1b = range_normalised(x.y, norm) >= thr;
+    const bool f2 = range_normalised(x.z, norm) >= thr, f3 = range_normalised(x.w, norm) >= thr;
     if (mask_word) {
       *reinterpret_cast<uint32_t*>(mask + e) =
           (uint32_t)f0 | ((uint32_t)f1b << 8) | ((uint32_t)f2 << 16) | ((uint32_t)f3 << 24);
@@ -746,23 +581,17 @@ __global__ __launch_bounds__(MT) void metrics_threshold_kernel(const float* __re
     threshold_count(f2, (lab & 0xFF0000u) != 0, tp, fp, fn, tn);
     threshold_count(f3, (lab & 0xFF000000u) != 0, tp, fp, fn, tn);
   }
-  s_c[0][t] = tp, s_c[1][t] = fp, s_c[2][t] = fn, s_c[3][t] = tn;
-  __syncthreads();
-  for (int o = MT / 2; o > 0; o >>= 1) {
-    if (t < o) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) s_c[c][t] += s_c[c][t + o];
-    }
-    __syncthreads();
-  }
-  if (t == 0) partial[blockIdx.x] = make_uint4(s_c[0][0], s_c[1][0], s_c[2][0], s_c[3][0]);
+  const uint4 all = block_fold(make_uint4(tp, fp, fn, tn), s_c, [](const uint4& a, const uint4& b) {
+    return make_uint4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+  });
+  if (t == 0) partial[blockIdx.x] = all;
 }
 
 // one workgroup: every image's counts from its workgroups in index order, and the totals over all partials
 __global__ __launch_bounds__(MT) void metrics_threshold_fold_kernel(const uint4* __restrict__ partial, long segs,
                                                                     int blocks, uint32_t* __restrict__ image_counts,
                                                                     ThresholdRecord* __restrict__ totals) {
-  __shared__ u64 s_c[4][MT];
+  __shared__ ThresholdRecord s_c[MT];
   const int t = threadIdx.x;
   if (image_counts)
     for (long s = t; s < segs; s += MT) {
@@ -781,16 +610,11 @@ __global__ __launch_bounds__(MT) void metrics_threshold_fold_kernel(const uint4*
     const uint4 p = partial[j];
     tp += p.x, fp += p.y, fn += p.z, tn += p.w;
   }
-  s_c[0][t] = tp, s_c[1][t] = fp, s_c[2][t] = fn, s_c[3][t] = tn;
-  __syncthreads();
-  for (int o = MT / 2; o > 0; o >>= 1) {
-    if (t < o) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) s_c[c][t] += s_c[c][t + o];
-    }
-    __syncthreads();
-  }
-  if (t == 0) *totals = ThresholdRecord{s_c[0][0], s_c[1][0], s_c[2][0], s_c[3][0]};
+  const ThresholdRecord sum =
+      block_fold(ThresholdRecord{tp, fp, fn, tn}, s_c, [](const ThresholdRecord& a, const ThresholdRecord& b) {
+        return ThresholdRecord{a.tp + b.tp, a.fp + b.fp, a.fn + b.fn, a.tn + b.tn};
+      });
+  if (t == 0) *totals = sum;
 }
 
 size_t metrics_threshold_ws_bytes(long n, long per_image) {

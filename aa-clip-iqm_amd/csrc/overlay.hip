@@ -18,16 +18,12 @@
 // The fp32 steps are separately rounded operations (-ffp-contract=off, and the intrinsics say so again).
 #include "common.h"
 #include "kernels.h"
+#include "metrics_records.h"
 #include "overlay_plan.h"
 
 namespace aaclip {
 
 namespace {
-
-struct RangeRecord {   // include/aaclip.h aaclip_metrics_range_record
-  float mn, mx;
-  unsigned long long bad, pos;
-};
 
 AACLIP_DEV int frame_byte(float x, float sd, float mean) {
   return overlay_clamp_byte(rintf(__fmul_rn(__fadd_rn(__fmul_rn(x, sd), mean), 255.0f)));
@@ -36,8 +32,8 @@ AACLIP_DEV int frame_byte(float x, float sd, float mean) {
 // q = trunc(clamp(n, 0, 1) * 255) with the product rounded toward zero: the product of an fp32 and 255 is exact in
 // fp64, and truncating the exact product equals truncating its fp32 value rounded toward zero (integers up to 255 are
 // fp32 values, so the rounding never crosses one)
-AACLIP_DEV int heat_byte(float x, bool norm, float mn, float span) {
-  const float n = norm ? __fdiv_rn(__fsub_rn(x, mn), span) : x;
+AACLIP_DEV int heat_byte(float x, const RangeNorm& norm) {
+  const float n = range_normalised(x, norm);
   if (n != n) return 0;
   const float c = n < 0.0f ? 0.0f : (n > 1.0f ? 1.0f : n);
   return (int)((double)c * 255.0);
@@ -80,13 +76,7 @@ __global__ __launch_bounds__(OVERLAY_THREADS) void overlay_kernel(
   const int tid = threadIdx.x;
   for (int e = tid; e < 256; e += OVERLAY_THREADS)
     s_lut[e] = (uint32_t)lut[3 * e] | ((uint32_t)lut[3 * e + 1] << 8) | ((uint32_t)lut[3 * e + 2] << 16);
-  bool norm = false;
-  float mn = 0.0f, span = 1.0f;
-  if (rec) {
-    mn = rec->mn;
-    norm = rec->mx != 1.0f;
-    span = __fsub_rn(rec->mx, mn);
-  }
+  const RangeNorm norm = range_norm(rec);
   const int H = g.H, W = g.W, T = g.T, n = g.n_panels, a = g.alpha256;
   const int slot_heat = (int)(g.panels & OVERLAY_FRAME), slot_truth = slot_heat + (int)((g.panels >> 1) & 1u);
   const long long tiles = (long long)g.tiles_x * g.tiles_y;
@@ -127,7 +117,7 @@ __global__ __launch_bounds__(OVERLAY_THREADS) void overlay_kernel(
           if (cp) {
             put3(d, g.pred_colour[0], g.pred_colour[1], g.pred_colour[2]);
           } else {
-            const uint32_t colour = s_lut[heat_byte(maps[overlay_map_offset(H, W, image, y, x)], norm, mn, span)];
+            const uint32_t colour = s_lut[heat_byte(maps[overlay_map_offset(H, W, image, y, x)], norm)];
             put3(d, overlay_blend(a, F[0], (int)(colour & 255)), overlay_blend(a, F[1], (int)((colour >> 8) & 255)),
                  overlay_blend(a, F[2], (int)((colour >> 16) & 255)));
           }

@@ -16,6 +16,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "metrics_records.h"
+
 #if defined(__HIPCC__)
 #define AACLIP_RT_HD __host__ __device__ inline
 #else
@@ -53,14 +55,9 @@ AACLIP_RT_HD unsigned long long region_peak_pack(uint32_t key, uint32_t index_in
 AACLIP_RT_HD uint32_t region_peak_key(unsigned long long word) { return (uint32_t)(word >> 32); }
 AACLIP_RT_HD uint32_t region_peak_index(unsigned long long word) { return 0xFFFFFFFFu - (uint32_t)(word & 0xFFFFFFFFull); }
 
-// the compared score: the raw one, or aaclip_metrics_normalise's (x - min) / (max - min), one IEEE subtraction and one
-// correctly rounded division (both files are built without contraction)
+// the compared score: metrics_records.h range_normalised
 AACLIP_RT_HD float region_compared(float x, bool norm, float mn, float mx) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return norm ? __fdiv_rn(x - mn, mx - mn) : x;
-#else
-  return norm ? (x - mn) / (mx - mn) : x;
-#endif
+  return range_normalised(x, RangeNorm{norm, mn, mx});
 }
 
 AACLIP_RT_HD RegionRow region_row_start(uint32_t image, uint32_t root_number, uint32_t first, uint32_t area, int H, int W) {
@@ -90,13 +87,12 @@ struct RegionTableLayout {
   long tiles;
 };
 inline RegionTableLayout region_table_layout(long n, long images) {
-  const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   RegionTableLayout l;
   l.tiles = (n + REGION_TABLE_TILE - 1) / REGION_TABLE_TILE;
   l.rowof = 0;
-  l.tile_word = l.rowof + up((size_t)n * 4);
-  l.roots_before = l.tile_word + up((size_t)l.tiles * 8);
-  l.total = l.roots_before + up((size_t)(images + 1) * 4);
+  l.tile_word = l.rowof + up256_bytes((size_t)n * 4);
+  l.roots_before = l.tile_word + up256_bytes((size_t)l.tiles * 8);
+  l.total = l.roots_before + up256_bytes((size_t)(images + 1) * 4);
   l.bytes = l.total + 256;
   return l;
 }

@@ -17,17 +17,13 @@
 #include "common.h"
 #include "kernels.h"
 #include "region_table.h"
+#include "tile_scan.h"
 
 namespace aaclip {
 
 static constexpr int TT = REGION_TABLE_THREADS, TI = REGION_TABLE_ITEMS, TILE = REGION_TABLE_TILE;
 static constexpr int TW = TT / 64;   // waves of a workgroup
-typedef unsigned long long u64;
-
-struct TableRange {   // metrics.hip RangeRecord
-  float mn, mx;
-  u64 bad, pos;
-};
+static_assert(TT == TILE_THREADS, "the tile scan is tile_scan.h's");
 
 AACLIP_DEV void table_flags(const uint32_t* __restrict__ region, const uint32_t* __restrict__ area, long n, long p,
                             uint32_t min_area, bool& root, bool& kept) {
@@ -66,28 +62,9 @@ __global__ __launch_bounds__(TT) void table_tile_scan_kernel(u64* __restrict__ t
                                                              long images, int32_t* __restrict__ image_offsets,
                                                              uint32_t* __restrict__ roots_before,
                                                              RegionTableRecord* __restrict__ rec) {
-  __shared__ u64 lds[TT];
-  const int t = threadIdx.x;
-  const long per = (tiles + TT - 1) / TT;
-  const long j0 = t * per < tiles ? t * per : tiles, j1 = j0 + per < tiles ? j0 + per : tiles;
-  u64 acc = 0;
-  for (long j = j0; j < j1; ++j) acc += tile_word[j];
-  lds[t] = acc;
-  __syncthreads();
-  for (int o = 1; o < TT; o <<= 1) {
-    const u64 add = t >= o ? lds[t - o] : 0;
-    __syncthreads();
-    lds[t] += add;
-    __syncthreads();
-  }
-  u64 run = t > 0 ? lds[t - 1] : 0;
-  for (long j = j0; j < j1; ++j) {
-    const u64 c = tile_word[j];
-    tile_word[j] = run;
-    run += c;
-  }
-  if (t == 0) {
-    const u64 kept = lds[TT - 1] & 0xFFFFFFFFull, roots = lds[TT - 1] >> 32;
+  const u64 all = tile_scan_body(tile_word, tiles);
+  if (threadIdx.x == 0) {
+    const u64 kept = all & 0xFFFFFFFFull, roots = all >> 32;
     *rec = RegionTableRecord{kept, roots, 0, kept > (u64)capacity ? kept - (u64)capacity : 0};
     image_offsets[images] = (int32_t)kept;
     roots_before[images] = (uint32_t)roots;
@@ -168,7 +145,7 @@ AACLIP_DEV void table_fold_row(RegionRow* row, u64 word, uint32_t x0, uint32_t y
 __global__ __launch_bounds__(TT) void table_accumulate_kernel(const uint32_t* __restrict__ region,
                                                               const uint32_t* __restrict__ area,
                                                               const float* __restrict__ scores,
-                                                              const TableRange* __restrict__ range,
+                                                              const RangeRecord* __restrict__ range,
                                                               const uint8_t* __restrict__ other, long n, uint32_t per,
                                                               int W, uint32_t min_area, uint32_t capacity,
                                                               RegionRow* rows, uint32_t* rowof,
@@ -182,9 +159,7 @@ __global__ __launch_bounds__(TT) void table_accumulate_kernel(const uint32_t* __
     s_x1[t] = s_y1[t] = s_ov[t] = 0;
   }
   __syncthreads();
-  float mn = 0.0f, mx = 1.0f;
-  if (range) mn = range->mn, mx = range->mx;
-  const bool norm = range && mx != 1.0f;
+  const RangeNorm norm = range_norm(range);
   const long tile0 = (long)blockIdx.x * TILE;
   const u64 le = (2ull << lane) - 1, ge = ~0ull << lane;   // the lanes up to and from this one
   uint32_t regions[TI], areas[TI];   // every round's loads are issued before the first round is folded
@@ -208,7 +183,7 @@ __global__ __launch_bounds__(TT) void table_accumulate_kernel(const uint32_t* __
       rem = (uint32_t)p % per;
       y = rem / (uint32_t)W;
       x = rem - y * (uint32_t)W;
-      key = region_score_key(region_score_bits(region_compared(scores[p], norm, mn, mx)));
+      key = region_score_key(region_score_bits(range_normalised(scores[p], norm)));
       set = other && other[p] != 0;
     }
     // a run: consecutive lanes of one region in one image row; lanes that are not kept carry id 0 and belong to none
@@ -297,7 +272,7 @@ void launch_region_table(const uint32_t* region, const uint32_t* area, const flo
   hipLaunchKernelGGL(table_rows_kernel, grid, dim3(TT), 0, s, region, area, n, (uint32_t)per, H, W, ma, (uint32_t)cap,
                      tile_word, (RegionRow*)rows, image_offsets, rowof, roots_before);
   hipLaunchKernelGGL(table_accumulate_kernel, grid, dim3(TT), 0, s, region, area, scores,
-                     (const TableRange*)range_record, other, n, (uint32_t)per, W, ma, (uint32_t)cap, (RegionRow*)rows,
+                     (const RangeRecord*)range_record, other, n, (uint32_t)per, W, ma, (uint32_t)cap, (RegionRow*)rows,
                      rowof, kept_mask, rec);
   if (cap > 0)
     hipLaunchKernelGGL(table_finish_kernel, dim3((unsigned)((cap + TT - 1) / TT)), dim3(TT), 0, s, (RegionRow*)rows, cap,
